@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — ICP iterations/sec on the BASELINE.json workload, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -26,6 +26,11 @@ launch stream inside the timed region), `phases` (from the coarse pose = `value`
 and, at N = 1, `cpu_baseline` (the C oracle, a scalar single-thread port of the PCL path, on a bounded sample of the same
 workload).  A timed window during which an overlapped update launch gave up its bounded wait (ope.h: ope_icp_update_fallbacks)
 has timed launches that did nothing: it is detected and measured again (`config.update_launch` says how).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step handed its caller as DIR/<name>.npy: the pose
+(`transform`, float32 4x4, ope_icp_current_transform) and the run's state (`iterations`, `mse`, `n_corr`, `align_strength`,
+float64, ope_icp_poll).  The inputs are generated from fixed seeds, so two builds run with the same arguments can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -72,6 +77,8 @@ def main() -> int:
                                                           "estimateFinePose really installs), reported beside `value` at N = 1")
     ap.add_argument("--no-coarse", action="store_true", help="skip the FPFH + SAC-IA initial alignment (identity start)")
     ap.add_argument("--cpu-iters", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (pose and run state) as DIR/<name>.npy")
     ap.add_argument("--steady", type=int, default=100, help="iterations timed in the converged regime, after the run has been taken to --settle iterations (reported, not `value`)")
     ap.add_argument("--settle", type=int, default=150, help="iterations from the coarse pose after which the run counts as settled (the steady-state phase starts there)")
     ap.add_argument("--full-run", type=int, default=100, help="a second run from the coarse pose, this many iterations timed as a whole (reported as phases.full_run; 0: skip)")
@@ -306,6 +313,7 @@ def main() -> int:
         kernels_timed = ctx.icp_kernel_launches()
         overlapped_updates = ctx.icp_overlapped_updates()
         T_timed = ctx.icp_current_transform()      # (polls: a fallback is noticed here at the latest)
+        res_timed = ctx.icp_poll() if args.dump_outputs else None
         if ctx.icp_update_fallbacks() == fallbacks0:
             break
         assert attempt < 2, "the run fell back to in-line update launches in every attempt"
@@ -498,6 +506,13 @@ def main() -> int:
             ctypes.CDLL(None).fflush(None)     # C stdio buffers (still pointing at fd 1 = stderr now)
         except Exception:
             pass
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            dump = {"transform": np.asarray(T_timed, np.float32), "iterations": np.float64(res_timed.iterations),
+                    "mse": np.float64(res_timed.last_mse), "n_corr": np.float64(res_timed.n_corr),
+                    "align_strength": np.float64(res_timed.align_strength)}
+            for name, a in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a))
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(line) + "\n").encode())
         if not ok:
