@@ -368,6 +368,15 @@ def transform_points(xyz, T):
     return out
 
 
+def transform_normals(nrm, T):
+    """The rotation part of T applied to normals (orc_transform_normals: the order of orc_transform_points, no translation)."""
+    nrm = _f32(nrm, 3)
+    out = np.empty_like(nrm)
+    t = colmajor(T)
+    lib().orc_transform_normals(_p(nrm, _fp), len(nrm), _p(t, _fp), _p(out, _fp))
+    return out
+
+
 def normals_knn(xyz, k: int = 30, vp=(0.0, 0.0, 0.0)):
     xyz = _f32(xyz, 3)
     v = np.asarray(vp, np.float32)

@@ -346,7 +346,8 @@ def test_icp_empty_target_and_missing_target_error_codes(ctx):
 @pytest.mark.parametrize("k", [20, 10, 7])
 def test_icp_normal_shooting_and_rejectors_match_oracle(ctx, k):
     """The configuration estimateFinePose actually runs (poseestimator.cpp:242-246,331-337): k = 20; k = 10 is the
-    class default (register lists for both), any other k takes the LDS list."""
+    class default; k = 7 takes the KR = 8 register list (every k has one: launch_icp_accumulate).  The whole trajectory
+    only; test_gpu_normal_shooting.py compares every launch exactly."""
     ope = load_pkg()
     rng = np.random.default_rng(3)
     u = rng.normal(size=(6000, 3)); u /= np.linalg.norm(u, axis=1, keepdims=True)
