@@ -295,6 +295,32 @@ int ope_icp_certificate_stats(ope_ctx *ctx, int64_t out[4]);
 int ope_icp_run(ope_ctx *ctx, const ope_cloud *src, const ope_index *tgt, const float *guess,
                 const ope_icp_params *params, float out_T[16], ope_icp_result *result);
 
+/* Batched ICP: n independent registrations in ONE launch, one workgroup per problem running its whole loop (search,
+ * rejectors, sums, the update step and PCL's convergence rule of ope_icp_run) with no host round trip between iterations.
+ * For many small problems, e.g. checking candidate clusters in order (rosinterface.cpp:243-262) or refining several
+ * hypotheses.  Problem i registers src[i] to the target of tgt[i] from guesses[16*i .. 16*i+15] (column-major; guesses NULL =
+ * identity for all).  One params for all problems; every run starts from the state ope_icp_begin would give it.
+ * fitness_max_range >= 0: getFitnessScore(fitness_max_range) of each final transform (registration_mod.hpp:131-165; what
+ * ope_fitness computes) in the same launch; < 0: no fitness pass (fitness = DBL_MAX, fitness_n = -1).  Synchronous, on the
+ * context's stream; the state of the context's single run (ope_icp_correspondences, ope_icp_current_transform, the step-wise
+ * calls) is left as it was.
+ * Each problem's sums are added in a fixed order inside its workgroup: its result is bit-reproducible and does not depend on
+ * the other problems of the batch or its position among them.  deterministic_sums, tree_walk, update_launch,
+ * skip_certificates and check_every are ignored.
+ * OPE_EINVAL, nothing launched: reciprocal correspondences, OPE_EST_POINT_TO_PLANE_LM, normal shooting or a rejector without
+ * source normals, point-to-plane or the surface-normal rejector without target normals, k_normal_shooting outside 1..32 (normal
+ * shooting), a source of more than 65536 valid points (use ope_icp_run), fixed correspondences set for one of the source
+ * clouds, a context with a communicator.  OPE_EEMPTY: a NULL target.  n = 0 does nothing.  An empty or all-non-finite source,
+ * or fewer than min_correspondences pairs, ends that problem with OPE_CONV_NO_CORRESPONDENCES; the others are unaffected. */
+typedef struct {
+  ope_icp_result result; /* as ope_icp_run reports it (align_strength from the problem's own cloud sizes) */
+  float T[16];           /* final transformation, column-major */
+  double fitness;        /* getFitnessScore(fitness_max_range) of T; DBL_MAX if no point is in range */
+  int64_t fitness_n;     /* points that entered it */
+} ope_icp_batch_result;
+int ope_icp_run_batch(ope_ctx *ctx, size_t n, const ope_cloud *const *src, const ope_index *const *tgt, const float *guesses,
+                      const ope_icp_params *params, double fitness_max_range, ope_icp_batch_result *out);
+
 /* Step-wise form of the same loop, for one-process-per-GPU drivers that put a
  * collective between the local reduction and the transform update:
  *   begin -> { accumulate -> [all-reduce 17 doubles at ope_icp_sums_device()] -> update } * -> end

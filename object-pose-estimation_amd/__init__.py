@@ -85,6 +85,15 @@ class IcpResult(C.Structure):
     ]
 
 
+class IcpBatchResult(C.Structure):
+    _fields_ = [
+        ("result", IcpResult),
+        ("T", C.c_float * 16),
+        ("fitness", C.c_double),
+        ("fitness_n", C.c_int64),
+    ]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("launches", C.c_int), ("algorithmic_bytes", C.c_double)]
 
@@ -136,6 +145,8 @@ ABI = [
     ("ope_radius_search", C.c_int, [_vp, _vp, _vp, C.c_float, C.c_int, _ip, _ip, _fp]),
     ("ope_icp_default_params", None, [C.POINTER(IcpParams)]),
     ("ope_icp_run", C.c_int, [_vp, _vp, _vp, _fp, C.POINTER(IcpParams), _fp, C.POINTER(IcpResult)]),
+    ("ope_icp_run_batch", C.c_int, [_vp, C.c_size_t, C.POINTER(_vp), C.POINTER(_vp), _fp, C.POINTER(IcpParams), C.c_double,
+                                     C.POINTER(IcpBatchResult)]),
     ("ope_icp_begin", C.c_int, [_vp, _vp, _vp, _fp, C.POINTER(IcpParams)]),
     ("ope_icp_accumulate", C.c_int, [_vp]),
     ("ope_icp_sums_device", _vp, [_vp]),
@@ -249,6 +260,12 @@ class IcpOut:
     last_mse: float
     n_corr: int
     align_strength: float
+
+
+@dataclass
+class IcpBatchOut(IcpOut):
+    fitness: float | None    # getFitnessScore(fitness_max_range) of T (DBL_MAX: no point in range)
+    fitness_n: int | None    # points that entered it
 
 
 class Context:
@@ -411,6 +428,32 @@ class Context:
         self._chk(lib().ope_icp_run(self.h, src.h, tgt.h if tgt is not None else None, _p(g, _fp), C.byref(p),
                                     _p(T, _fp), C.byref(r)))
         return IcpOut(from_colmajor(T), r.iterations, bool(r.converged), r.state, r.last_mse, r.n_corr, r.align_strength)
+
+    def icp_batch(self, srcs, indexes, params: IcpParams | None = None, guesses=None, fitness_max_range: float | None = None) -> list:
+        """ope_icp_run_batch: problem i registers srcs[i] to indexes[i] (guesses[i] a (4,4) or None), all in one launch.
+        One IcpBatchOut per problem; fitness / fitness_n are None without fitness_max_range."""
+        n = len(srcs)
+        if len(indexes) != n:
+            raise ValueError("one index per source cloud")
+        p = params or default_icp_params()
+        hs = (_vp * max(n, 1))(*[s.h for s in srcs])
+        ht = (_vp * max(n, 1))(*[t.h if t is not None else None for t in indexes])
+        g = None
+        if guesses is not None:
+            if len(guesses) != n:
+                raise ValueError("one guess per problem")
+            g = np.concatenate([colmajor(np.eye(4) if x is None else x) for x in guesses]) if n else np.zeros(16, np.float32)
+        out = (IcpBatchResult * max(n, 1))()
+        rng = -1.0 if fitness_max_range is None else float(fitness_max_range)
+        self._chk(lib().ope_icp_run_batch(self.h, n, hs, ht, _p(g, _fp), C.byref(p), rng, out))
+        res = []
+        for i in range(n):
+            o = out[i]
+            r = o.result
+            res.append(IcpBatchOut(from_colmajor(np.frombuffer(o.T, np.float32)), r.iterations, bool(r.converged), r.state, r.last_mse,
+                                   r.n_corr, r.align_strength, o.fitness if fitness_max_range is not None else None,
+                                   o.fitness_n if fitness_max_range is not None else None))
+        return res
 
     def icp_begin(self, src: "Cloud", tgt: "Index", params: IcpParams | None = None, guess=None):
         p = params or default_icp_params()

@@ -1038,6 +1038,84 @@ int ope_icp_begin(ope_ctx *ctx, const ope_cloud *src, const ope_index *tgt, cons
   return rc;
 }
 
+}  // extern "C"
+
+// The state a run starts from (ope_internal.hpp): ope_icp_begin and every problem of ope_icp_run_batch (icp_batch.hip).
+void ope::icp_state_init(IcpState *h, const ope_cloud *src, const ope_index *tgt, const float *guess, const ope_icp_params &p, bool cert_run,
+                         bool cluttered) {
+  std::memset(h, 0, sizeof *h);
+  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const float *g = guess ? guess : I4;
+  for (int i = 0; i < 16; ++i) { h->F[i] = g[i]; h->Tk[i] = I4[i]; }
+  colmajor_to_rows(g, h->Ff);
+  for (int d = 0; d < 3; ++d) h->pivot[d] = tgt->pivot[d];
+  h->prev_mse = h->cur_mse = std::numeric_limits<double>::max();
+  // thresholds wired as at icp_mod.hpp:164-168 (quirk Q1: rotation threshold = 1 - transformation_epsilon)
+  h->rotation_threshold = 1.0 - p.transformation_epsilon;
+  h->translation_threshold = p.transformation_epsilon;
+  h->mse_threshold_relative = p.euclidean_fitness_epsilon;
+  h->mse_threshold_absolute = p.mse_threshold_absolute;
+  h->max_corr_dist = p.max_corr_dist;
+  h->max_d2 = p.max_corr_dist * p.max_corr_dist;
+  h->surface_normal_thr = p.surface_normal_thr;
+  h->self_occluded_thr = p.self_occluded_thr;
+  h->max_iterations = p.max_iterations;
+  h->failure_after_max_iter = p.failure_after_max_iter;
+  h->min_correspondences = p.min_correspondences;
+  h->corr_mode = p.corr_mode;
+  h->k_normal_shooting = p.k_normal_shooting;
+  h->use_surface_normal_rej = p.use_surface_normal_rej;
+  h->use_self_occluded_rej = p.use_self_occluded_rej;
+  h->use_reciprocal = p.use_reciprocal;
+  h->estimator = p.estimator;
+  {
+    // Skip certificates (ope.h: skip_certificates): plain 1-NN runs.  Automatic: kept once an update moves no scene point by
+    // more than a quarter of the target's point spacing, estimated from the surface of its bounding box over its size (a
+    // closed surface sampled by n points inside that box: spacing ~ sqrt(area / n); the factor matters little — a run that starts keeping them
+    // early pays a few percent per launch for walks that report their bounds, one that starts late walks a little longer).
+    const double ex = (double)tgt->bb_hi[0] - tgt->bb_lo[0], ey = (double)tgt->bb_hi[1] - tgt->bb_lo[1], ez = (double)tgt->bb_hi[2] - tgt->bb_lo[2];
+    const double spacing = std::sqrt(2.0 * (ex * ey + ey * ez + ez * ex) / (double)std::max<size_t>(tgt->n, 1));
+    // When launches start keeping certificates (automatic mode).  A run on a clean source — every query near the surface: the
+    // grid kernel's case, or an index without a grid — profits as soon as surface points can hold one: the update that moves the
+    // scene by less than spacing / 24.  A run that starts on the tree kernel BECAUSE the device counted more than 3 % of its
+    // queries far outside the target (clutter) does not: its launches last as long as the walks of the far queries, whose
+    // neighbours lie within microns of each other in distance, whatever the surface points save (DESIGN 4.1d: C3's first
+    // hundred iterations got 6 % slower with the early threshold) — it waits until the scene moves by less than spacing / 512,
+    // shortly before those queries can hold certificates too.
+    h->cert_thr = !cert_run ? -1.0f : p.skip_certificates == OPE_CERT_ALWAYS ? std::numeric_limits<float>::infinity()
+                                 : (float)(spacing / (cluttered ? 512.0 : (double)kCertWorth));
+    if (const char *e = dev_env("OPE_CERT_THR")) h->cert_thr = (float)atof(e);   // developer sweep (metres)
+    h->cert_mode = (cert_run && p.skip_certificates == OPE_CERT_ALWAYS) ? 1 : 0;
+    // what a certificate is worth (icp_accumulate_kernel): the (kCertCand + 1)-th neighbour of a query D from a surface sampled at
+    // `spacing` lies ~ kCertCand spacing^2 / (2 pi D) further out than the nearest one, never more than about the spacing itself
+    h->cert_cap = (float)spacing;
+    h->cert_k = (float)((double)kCertCand * spacing * spacing / (2.0 * 3.14159265358979323846));
+    if (const char *e = dev_env("OPE_CERT_CAP")) h->cert_cap = (float)atof(e);   // developer sweep (metres)
+    double r2 = 0;
+    for (int d = 0; d < 3; ++d) {
+      h->src_c[d] = 0.5f * (src->bb_lo[d] + src->bb_hi[d]);
+      const double hd = 0.5 * ((double)src->bb_hi[d] - (double)src->bb_lo[d]);
+      r2 += hd * hd;
+    }
+    h->src_r = (float)std::sqrt(r2);
+  }
+  {
+    // inverse of the guess (adjugate), rows layout
+    const double a = g[0], b = g[4], c = g[8], d = g[1], e = g[5], f = g[9], gg = g[2], hh = g[6], ii = g[10];
+    const double det = a * (e * ii - f * hh) - b * (d * ii - f * gg) + c * (d * hh - e * gg);
+    const double id = det != 0 ? 1.0 / det : 0.0;
+    const double M[9] = {(e * ii - f * hh) * id, (c * hh - b * ii) * id, (b * f - c * e) * id,
+                         (f * gg - d * ii) * id, (a * ii - c * gg) * id, (c * d - a * f) * id,
+                         (d * hh - e * gg) * id, (b * gg - a * hh) * id, (a * e - b * d) * id};
+    for (int r = 0; r < 3; ++r) {
+      h->Finv[4 * r + 0] = (float)M[3 * r]; h->Finv[4 * r + 1] = (float)M[3 * r + 1]; h->Finv[4 * r + 2] = (float)M[3 * r + 2];
+      h->Finv[4 * r + 3] = (float)(-(M[3 * r] * g[12] + M[3 * r + 1] * g[13] + M[3 * r + 2] * g[14]));
+    }
+  }
+}
+
+extern "C" {
+
 static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *tgt, const float *guess, const ope_icp_params *params) {
   if (!ctx || !src) return set_err(ctx, OPE_EINVAL, "ope_icp_begin: bad argument");
   // Registration::initCompute: "No input target dataset was given!" (registration_mod.hpp:73-77)
@@ -1208,86 +1286,18 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
   // no start hints yet: the first iteration walks top-down (hints belong to one (src, tgt) pairing)
   OPE_HIP(ctx, hipMemsetAsync(ctx->d_hint, 0, sizeof(uint32_t) * std::max<size_t>(src->n, 1), ctx->stream));
 
+  // Skip certificates (ope.h: skip_certificates): plain 1-NN runs.
+  ctx->cert_run = p.corr_mode == OPE_CORR_NEAREST && !p.use_reciprocal && p.deterministic_sums == 0 && p.skip_certificates != OPE_CERT_OFF &&
+                  !dev_env("OPE_NO_CERT");
   IcpState *h = ctx->h_state;
-  std::memset(h, 0, sizeof *h);
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  const float *g = guess ? guess : I4;
-  for (int i = 0; i < 16; ++i) { h->F[i] = g[i]; h->Tk[i] = I4[i]; }
-  colmajor_to_rows(g, h->Ff);
-  for (int d = 0; d < 3; ++d) h->pivot[d] = tgt->pivot[d];
-  h->prev_mse = h->cur_mse = std::numeric_limits<double>::max();
-  // thresholds wired as at icp_mod.hpp:164-168 (quirk Q1: rotation threshold = 1 - transformation_epsilon)
-  h->rotation_threshold = 1.0 - p.transformation_epsilon;
-  h->translation_threshold = p.transformation_epsilon;
-  h->mse_threshold_relative = p.euclidean_fitness_epsilon;
-  h->mse_threshold_absolute = p.mse_threshold_absolute;
-  h->max_corr_dist = p.max_corr_dist;
-  h->max_d2 = p.max_corr_dist * p.max_corr_dist;
-  h->surface_normal_thr = p.surface_normal_thr;
-  h->self_occluded_thr = p.self_occluded_thr;
-  h->max_iterations = p.max_iterations;
-  h->failure_after_max_iter = p.failure_after_max_iter;
-  h->min_correspondences = p.min_correspondences;
-  h->corr_mode = p.corr_mode;
-  h->k_normal_shooting = p.k_normal_shooting;
-  h->use_surface_normal_rej = p.use_surface_normal_rej;
-  h->use_self_occluded_rej = p.use_self_occluded_rej;
-  h->use_reciprocal = p.use_reciprocal;
-  h->estimator = p.estimator;
-  {
-    // Skip certificates (ope.h: skip_certificates): plain 1-NN runs.  Automatic: kept once an update moves no scene point by
-    // more than a quarter of the target's point spacing, estimated from the surface of its bounding box over its size (a
-    // closed surface sampled by n points inside that box: spacing ~ sqrt(area / n); the factor matters little — a run that starts keeping them
-    // early pays a few percent per launch for walks that report their bounds, one that starts late walks a little longer).
-    ctx->cert_run = p.corr_mode == OPE_CORR_NEAREST && !p.use_reciprocal && p.deterministic_sums == 0 && p.skip_certificates != OPE_CERT_OFF &&
-                    !dev_env("OPE_NO_CERT");
-    const double ex = (double)tgt->bb_hi[0] - tgt->bb_lo[0], ey = (double)tgt->bb_hi[1] - tgt->bb_lo[1], ez = (double)tgt->bb_hi[2] - tgt->bb_lo[2];
-    const double spacing = std::sqrt(2.0 * (ex * ey + ey * ez + ez * ex) / (double)std::max<size_t>(tgt->n, 1));
-    // When launches start keeping certificates (automatic mode).  A run on a clean source — every query near the surface: the
-    // grid kernel's case, or an index without a grid — profits as soon as surface points can hold one: the update that moves the
-    // scene by less than spacing / 24.  A run that starts on the tree kernel BECAUSE the device counted more than 3 % of its
-    // queries far outside the target (clutter) does not: its launches last as long as the walks of the far queries, whose
-    // neighbours lie within microns of each other in distance, whatever the surface points save (DESIGN 4.1d: C3's first
-    // hundred iterations got 6 % slower with the early threshold) — it waits until the scene moves by less than spacing / 512,
-    // shortly before those queries can hold certificates too.
-    const bool cluttered = ctx->grid_auto && !ctx->use_grid;
-    h->cert_thr = !ctx->cert_run ? -1.0f : p.skip_certificates == OPE_CERT_ALWAYS ? std::numeric_limits<float>::infinity()
-                                 : (float)(spacing / (cluttered ? 512.0 : (double)kCertWorth));
-    if (const char *e = dev_env("OPE_CERT_THR")) h->cert_thr = (float)atof(e);   // developer sweep (metres)
-    h->cert_mode = (ctx->cert_run && p.skip_certificates == OPE_CERT_ALWAYS) ? 1 : 0;
-    ctx->cert_seen = h->cert_mode != 0;
-    h->host_cert = (ctx->cert_run && !ctx->cert_seen) ? ctx->d_pace + 1 : nullptr;
-    // what a certificate is worth (icp_accumulate_kernel): the (kCertCand + 1)-th neighbour of a query D from a surface sampled at
-    // `spacing` lies ~ kCertCand spacing^2 / (2 pi D) further out than the nearest one, never more than about the spacing itself
-    h->cert_cap = (float)spacing;
-    h->cert_k = (float)((double)kCertCand * spacing * spacing / (2.0 * 3.14159265358979323846));
-    if (const char *e = dev_env("OPE_CERT_CAP")) h->cert_cap = (float)atof(e);   // developer sweep (metres)
-    double r2 = 0;
-    for (int d = 0; d < 3; ++d) {
-      h->src_c[d] = 0.5f * (src->bb_lo[d] + src->bb_hi[d]);
-      const double hd = 0.5 * ((double)src->bb_hi[d] - (double)src->bb_lo[d]);
-      r2 += hd * hd;
-    }
-    h->src_r = (float)std::sqrt(r2);
-    // positions index THIS target's point order: certificates never outlive the pairing ("no candidate 0" = no certificate);
-    // the per-query worth of a certificate is read off the previous launch's distance: none yet
-    if (ctx->cert_run) {
-      OPE_HIP(ctx, hipMemsetAsync(ctx->d_cert_pos, 0, sizeof(uint32_t) * std::max<size_t>(src->n, 1), ctx->stream));
-      OPE_HIP(ctx, hipMemsetAsync(ctx->d_corr_d2, 0x7f, sizeof(float) * std::max<size_t>(src->n, 1), ctx->stream));   // 0x7f7f7f7f = 3.4e38
-    }
-  }
-  {
-    // inverse of the guess (adjugate), rows layout
-    const double a = g[0], b = g[4], c = g[8], d = g[1], e = g[5], f = g[9], gg = g[2], hh = g[6], ii = g[10];
-    const double det = a * (e * ii - f * hh) - b * (d * ii - f * gg) + c * (d * hh - e * gg);
-    const double id = det != 0 ? 1.0 / det : 0.0;
-    const double M[9] = {(e * ii - f * hh) * id, (c * hh - b * ii) * id, (b * f - c * e) * id,
-                         (f * gg - d * ii) * id, (a * ii - c * gg) * id, (c * d - a * f) * id,
-                         (d * hh - e * gg) * id, (b * gg - a * hh) * id, (a * e - b * d) * id};
-    for (int r = 0; r < 3; ++r) {
-      h->Finv[4 * r + 0] = (float)M[3 * r]; h->Finv[4 * r + 1] = (float)M[3 * r + 1]; h->Finv[4 * r + 2] = (float)M[3 * r + 2];
-      h->Finv[4 * r + 3] = (float)(-(M[3 * r] * g[12] + M[3 * r + 1] * g[13] + M[3 * r + 2] * g[14]));
-    }
+  icp_state_init(h, src, tgt, guess, p, ctx->cert_run, ctx->grid_auto && !ctx->use_grid);
+  ctx->cert_seen = h->cert_mode != 0;
+  h->host_cert = (ctx->cert_run && !ctx->cert_seen) ? ctx->d_pace + 1 : nullptr;
+  // positions index THIS target's point order: certificates never outlive the pairing ("no candidate 0" = no certificate);
+  // the per-query worth of a certificate is read off the previous launch's distance: none yet
+  if (ctx->cert_run) {
+    OPE_HIP(ctx, hipMemsetAsync(ctx->d_cert_pos, 0, sizeof(uint32_t) * std::max<size_t>(src->n, 1), ctx->stream));
+    OPE_HIP(ctx, hipMemsetAsync(ctx->d_corr_d2, 0x7f, sizeof(float) * std::max<size_t>(src->n, 1), ctx->stream));   // 0x7f7f7f7f = 3.4e38
   }
   if (ctx->run_src_index) { ope_index_free(ctx->run_src_index); ctx->run_src_index = nullptr; }
   if (p.use_reciprocal) {

@@ -553,6 +553,12 @@ void build_bvh_host(const float *xyz, const int32_t *ids, const float *nrm, size
 // api.hip: ope_index_build's body; temporary = the index lives inside one entry point and its buffers come from (and go back to) the
 // stream's cache of temporaries instead of hipMalloc / hipFree
 int index_build_impl(ope_ctx *ctx, const ope_cloud *target, const ope_index_params *params, bool temporary, ope_index **out);
+// api.hip: the device state a run starts from, as ope_icp_begin fills it (thresholds per quirk Q1, the target index's pivot,
+// prev_mse, the inverse of the guess, the skip-certificate trigger) — one fill for ope_icp_begin and every problem of
+// ope_icp_run_batch.  guess: column-major, null = identity.  cert_run: the run may keep skip certificates; cluttered: it starts on
+// the tree kernel because of clutter (later certificates, see ope_icp_begin).  host_cert is left null.
+void icp_state_init(IcpState *h, const ope_cloud *src, const ope_index *tgt, const float *guess, const ope_icp_params &p, bool cert_run,
+                    bool cluttered);
 inline int index_build_tmp(ope_ctx *ctx, const ope_cloud *target, const ope_index_params *params, ope_index **out) {
   return index_build_impl(ctx, target, params, true, out);
 }

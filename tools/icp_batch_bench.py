@@ -1,0 +1,121 @@
+"""Batched ICP at the reference's fine-stage size (C1): one ope_icp_run_batch call against the same K problems as K
+ope_icp_run calls.
+
+Inputs as the fine stage makes them (tests/test_gpu_detect_and_localize.py, _fine_inputs_on_gpu): the decimated drill model's
+and the C1 scene's key points (device uniform_sampling(0.008)) with normals (device normals, k = 30).  The K candidate targets
+are the scene cluster plus seeded, rigidly moved copies of it and distractor clouds from synth; every problem starts from the
+fixture's guess with the fine stage's parameters (normal shooting k = 20, surface-normal rejector 0.7, 100 iterations).
+
+Host clock around each synchronous call, 5 warm-up and 20 timed repetitions, median and min-max.  Kernel times come from a
+separate run under rocprofv3 --kernel-trace --stats (--reps 3).  A/B builds of the library: PROBE_LIB=<name> loads
+libope_hip_<name>.so (make -C object-pose-estimation_amd VARIANT=<name> EXTRA=-DOPE_BATCH_BLOCK=256).
+
+    python tools/icp_batch_bench.py [--ks 1,8,32,128] [--warmup 5] [--reps 20] [--fitness] [--json out.json]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+ope = importlib.import_module("object-pose-estimation_amd")
+synth = importlib.import_module("object-pose-estimation_amd.synth")
+pcd = importlib.import_module("object-pose-estimation_amd.pcd")
+if os.environ.get("PROBE_LIB"):
+    ope.LIB_PATH = os.path.join(os.path.dirname(ope.LIB_PATH), f"libope_hip_{os.environ['PROBE_LIB']}.so")
+GOLD = os.path.join(ROOT, "tests", "golden")
+DBL_MAX = float(np.finfo(np.float64).max)
+FINE = dict(max_iterations=100, transformation_epsilon=1e-8, euclidean_fitness_epsilon=1e-8, corr_mode=1, k_normal_shooting=20,
+            use_surface_normal_rej=1, surface_normal_thr=0.7)
+
+
+def fine_inputs(ctx, cloud):
+    cloud = cloud[np.isfinite(cloud).all(1)]
+    keys = cloud[ctx.uniform_sampling(ctx.upload(cloud), 0.008)]
+    nrm, _ = ctx.normals(ctx.upload(keys), 30)
+    ok = np.isfinite(nrm).all(1)
+    return keys[ok], nrm[ok]
+
+
+def candidates(ctx, k, seed=0):
+    """The scene cluster first, then moved copies (odd positions) and synth distractors (even positions)."""
+    g = np.load(os.path.join(GOLD, "drill_scene_c1.npz"))
+    scene = g["scene"]
+    rng = np.random.default_rng(seed)
+    c = scene.mean(0)
+    out = []
+    for j in range(k):
+        if j == 0:
+            cloud = scene
+        elif j % 2:
+            R = synth.rot_xyz(*(rng.uniform(2, 20, 3) * rng.choice([-1, 1], 3))).astype(np.float32)
+            cloud = ((scene - c) @ R.T + c + rng.uniform(-0.02, 0.02, 3)).astype(np.float32)
+        else:
+            d = synth.model_surface(4000, seed=100 + j) * np.float32(rng.uniform(0.6, 1.2))
+            cloud = (d - d.mean(0) + c + rng.uniform(-0.01, 0.01, 3)).astype(np.float32)
+        out.append(fine_inputs(ctx, cloud))
+    return out, g["guess"]
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(t)), float(np.min(t)), float(np.max(t))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ks", default="1,8,32,128")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--fitness", action="store_true", help="also time getFitnessScore: in the batch launch / one ope_fitness per run")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    ctx = ope.Context(0)
+    model, _ = pcd.read_pcd(os.path.join(GOLD, "drill_model_decimated.pcd"))
+    sk, sn = fine_inputs(ctx, model)
+    ks = [int(k) for k in a.ks.split(",")]
+    cands, guess = candidates(ctx, max(ks))
+    cs = ctx.upload(sk, sn)
+    ix = [ctx.build_index(ctx.upload(tk, tn)) for tk, tn in cands]
+    p = ope.default_icp_params(**FINE)
+    fr = DBL_MAX if a.fitness else None
+    print(f"source {len(sk)} key points; targets {min(len(t) for t, _ in cands)}-{max(len(t) for t, _ in cands)} key points")
+    rows = []
+    for k in ks:
+        srcs, idx, gs = [cs] * k, ix[:k], [guess] * k
+        res = ctx.icp_batch(srcs, idx, p, gs, fr)
+        iters = sum(r.iterations for r in res)
+
+        def seq():
+            for x in idx:
+                out = ctx.icp(cs, x, p, guess)
+                if a.fitness:
+                    ctx.fitness(cs, x, out.T)
+
+        tb = timed(lambda: ctx.icp_batch(srcs, idx, p, gs, fr), a.warmup, a.reps)
+        ts = timed(seq, a.warmup, a.reps)
+        row = dict(K=k, iterations=iters, batch_ms=tb, sequential_ms=ts, speedup=ts[0] / tb[0],
+                   sequential_us_per_iteration=1e3 * ts[0] / iters, batch_us_per_problem_iteration=1e3 * tb[0] / iters)
+        rows.append(row)
+        print(f"K={k:4d} iterations {iters:6d} | batch {tb[0]:8.3f} ms [{tb[1]:.3f}-{tb[2]:.3f}] | {k} x ope_icp_run {ts[0]:8.3f} ms "
+              f"[{ts[1]:.3f}-{ts[2]:.3f}] | x{row['speedup']:.1f} | run {row['sequential_us_per_iteration']:.1f} us/iteration, "
+              f"batch {row['batch_us_per_problem_iteration']:.2f} us/problem-iteration", flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(block=os.environ.get("PROBE_LIB", "default"), fitness=a.fitness, rows=rows), f, indent=1)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
