@@ -490,6 +490,50 @@ int ope_sacia(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const
               const ope_index *tgt_index, const float *tgt_feat33, const ope_sacia_params *params,
               const int32_t *forced_samples, float out_T[16], double *best_error, int32_t *best_iteration);
 
+/* ---------------- batched coarse stage ---------------- */
+/* estimateCoarsePose (poseestimator.cpp:16-73) of one model against n candidate clusters in one call: the coarse half of the
+ * reference's candidate loop (rosinterface.cpp:243-262).  Each cloud is uniformly sampled at key_leaf, gets k-NN normals and
+ * FPFH on its key points, and SAC-IA aligns the model's key points (source) to each cluster's (target). */
+typedef struct {
+  float key_leaf;          /* UniformSampling radius, 0.01 (poseestimator.cpp:116) */
+  int normals_k;           /* 30 (:153) */
+  float viewpoint[3];      /* NormalEstimation's default, 0 0 0 */
+  float fpfh_radius;       /* 0.03 (:122) */
+  ope_sacia_params sacia;  /* 400 / 5 / 5 / 0.05 / 0.01, seed 1 */
+} ope_coarse_params;
+void ope_coarse_default_params(ope_coarse_params *p);
+
+/* Limits of one batch: points of one cloud (model or cluster), and key points of one cloud after sampling (each cloud's key
+ * points are staged in LDS).  Larger clouds go through the single-cloud calls. */
+#define OPE_COARSE_MAX_POINTS 65536
+#define OPE_COARSE_MAX_KEYS 4096
+
+enum { OPE_COARSE_OK = 0, OPE_COARSE_EMPTY_TARGET = 1, OPE_COARSE_FEW_TARGET_FEATURES = 2 };
+typedef struct {
+  float T[16];             /* coarse pose, column-major; identity unless status == OPE_COARSE_OK */
+  double best_error;       /* computeErrorMetric of the winning hypothesis */
+  int32_t best_iteration;  /* -1 unless OK */
+  int32_t n_src_keys;      /* model key points after UniformSampling */
+  int32_t n_tgt_keys;      /* this cluster's key points */
+  int32_t status;
+} ope_coarse_batch_result;
+
+/* Synchronous, on the context's stream; the single-run state of the context is untouched; n == 0 does nothing.
+ * Cluster i draws with seeds[i], or with params->sacia.seed + i when seeds is NULL (the i-th coarse call of an estimator).
+ * An empty cluster gives OPE_COARSE_EMPTY_TARGET, fewer than 10 cluster key points OPE_COARSE_FEW_TARGET_FEATURES (:40-45);
+ * both keep the identity.  The model's features are computed once per call.  Each cluster's result is byte-identical whatever
+ * else is in the batch and wherever it sits.  The number of kernel launches and host synchronisations does not depend on n.
+ * OPE_EINVAL, nothing launched: a model with fewer than sacia.nr_samples key points, normals_k outside 1..32,
+ * k_correspondences outside 1..8, key_leaf or fpfh_radius <= 0, a cloud of more than OPE_COARSE_MAX_POINTS points or more than
+ * OPE_COARSE_MAX_KEYS key points.  (Key points are counted on the host before anything is launched.) */
+int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                          const ope_coarse_params *params, const uint64_t *seeds, ope_coarse_batch_result *out);
+/* Key points (ORIGINAL indices into that cloud), normals (n*3) and FPFH rows (n*33) the last ope_coarse_pose_batch computed
+ * for `which` (-1 = the model, 0..n-1 = cluster), in key-point order; any output may be NULL.  *n_out = the key points; at
+ * most cap rows are written.  Like ope_icp_correspondences for the single run. */
+int ope_coarse_batch_features(ope_ctx *ctx, int which, int32_t *key_idx, float *normals, float *fpfh33, size_t cap,
+                              size_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

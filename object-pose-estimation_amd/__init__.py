@@ -25,6 +25,9 @@ CONV_NAMES = ["NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", 
 CORR_NEAREST, CORR_NORMAL_SHOOTING = 0, 1
 EST_SVD, EST_POINT_TO_PLANE_LLS, EST_POINT_TO_PLANE_LM = 0, 1, 2
 COMM_AUTO, COMM_RCCL, COMM_P2P = 0, 1, 2
+# ope_coarse_batch_result.status; per-cloud limits of ope_coarse_pose_batch
+COARSE_OK, COARSE_EMPTY_TARGET, COARSE_FEW_TARGET_FEATURES = 0, 1, 2
+COARSE_MAX_POINTS, COARSE_MAX_KEYS = 65536, 4096
 CERT_AUTO, CERT_OFF, CERT_ALWAYS = 0, 1, 2   # ope_icp_params.skip_certificates
 NUM_SUMS, NUM_SUMS_MAX = 17, 44
 COMM_ID_BYTES = 128
@@ -113,6 +116,27 @@ class SaciaParams(C.Structure):
     ]
 
 
+class CoarseParams(C.Structure):
+    _fields_ = [
+        ("key_leaf", C.c_float),
+        ("normals_k", C.c_int),
+        ("viewpoint", C.c_float * 3),
+        ("fpfh_radius", C.c_float),
+        ("sacia", SaciaParams),
+    ]
+
+
+class CoarseBatchResult(C.Structure):
+    _fields_ = [
+        ("T", C.c_float * 16),
+        ("best_error", C.c_double),
+        ("best_iteration", C.c_int32),
+        ("n_src_keys", C.c_int32),
+        ("n_tgt_keys", C.c_int32),
+        ("status", C.c_int32),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
 _dp = C.POINTER(C.c_double)
@@ -195,6 +219,10 @@ ABI = [
     ("ope_statistical_outlier_removal", C.c_int, [_vp, _vp, C.c_int, C.c_double, _ip, C.POINTER(C.c_size_t), _fp]),
     ("ope_sacia_default_params", None, [C.POINTER(SaciaParams)]),
     ("ope_sacia", C.c_int, [_vp, _vp, _fp, _vp, _vp, _fp, C.POINTER(SaciaParams), _ip, _fp, _dp, _ip]),
+    ("ope_coarse_default_params", None, [C.POINTER(CoarseParams)]),
+    ("ope_coarse_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(CoarseParams), C.POINTER(C.c_uint64),
+                                         C.POINTER(CoarseBatchResult)]),
+    ("ope_coarse_batch_features", C.c_int, [_vp, C.c_int, _ip, _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
 ]
 
 _lib = None
@@ -266,6 +294,16 @@ class IcpOut:
 class IcpBatchOut(IcpOut):
     fitness: float | None    # getFitnessScore(fitness_max_range) of T (DBL_MAX: no point in range)
     fitness_n: int | None    # points that entered it
+
+
+@dataclass
+class CoarseOut:
+    T: np.ndarray          # (4,4) math layout, float32 — the coarse pose (identity unless status == COARSE_OK)
+    best_error: float      # computeErrorMetric of the winning hypothesis
+    best_iteration: int    # -1 unless COARSE_OK
+    n_src_keys: int        # model key points
+    n_tgt_keys: int        # this cluster's key points
+    status: int            # COARSE_OK, COARSE_EMPTY_TARGET or COARSE_FEW_TARGET_FEATURES
 
 
 class Context:
@@ -454,6 +492,33 @@ class Context:
                                    r.n_corr, r.align_strength, o.fitness if fitness_max_range is not None else None,
                                    o.fitness_n if fitness_max_range is not None else None))
         return res
+
+    def coarse_pose_batch(self, model: "Cloud", clusters, params: CoarseParams | None = None, seeds=None) -> list:
+        """ope_coarse_pose_batch: estimateCoarsePose(model, clusters[i]) for every cluster in one call; one CoarseOut each.
+        seeds[i] (or params.sacia.seed + i without seeds) is cluster i's SAC-IA stream."""
+        n = len(clusters)
+        p = params or default_coarse_params()
+        hc = (_vp * max(n, 1))(*[c.h for c in clusters])
+        sd = None
+        if seeds is not None:
+            if len(seeds) != n:
+                raise ValueError("one seed per cluster")
+            sd = (C.c_uint64 * max(n, 1))(*[int(x) for x in seeds])
+        out = (CoarseBatchResult * max(n, 1))()
+        self._chk(lib().ope_coarse_pose_batch(self.h, model.h, n, hc, C.byref(p), sd, out))
+        return [CoarseOut(from_colmajor(np.frombuffer(o.T, np.float32)), o.best_error, o.best_iteration, o.n_src_keys, o.n_tgt_keys,
+                          o.status) for o in out[:n]]
+
+    def coarse_batch_features(self, which: int):
+        """What the last coarse_pose_batch computed for `which` (-1 = the model, i = cluster i): (key indices into that
+        cloud, normals (m,3), FPFH (m,33)), in key-point order."""
+        m = C.c_size_t(0)
+        self._chk(lib().ope_coarse_batch_features(self.h, which, None, None, None, 0, C.byref(m)))
+        idx = np.empty(max(m.value, 1), np.int32)
+        nrm = np.empty((max(m.value, 1), 3), np.float32)
+        f = np.empty((max(m.value, 1), 33), np.float32)
+        self._chk(lib().ope_coarse_batch_features(self.h, which, _p(idx, _ip), _p(nrm, _fp), _p(f, _fp), m.value, C.byref(m)))
+        return idx[: m.value].copy(), nrm[: m.value].copy(), f[: m.value].copy()
 
     def icp_begin(self, src: "Cloud", tgt: "Index", params: IcpParams | None = None, guess=None):
         p = params or default_icp_params()
@@ -711,6 +776,18 @@ def default_sacia_params(**kw) -> SaciaParams:
     lib().ope_sacia_default_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
+    return p
+
+
+def default_coarse_params(**kw) -> CoarseParams:
+    """ope_coarse_default_params (the reference's values); keyword arguments set fields, `sacia` takes a SaciaParams."""
+    p = CoarseParams()
+    lib().ope_coarse_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "viewpoint":
+            p.viewpoint[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
     return p
 
 

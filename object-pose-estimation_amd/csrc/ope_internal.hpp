@@ -265,6 +265,11 @@ struct ope_ctx {
 
   double last_fpfh_mean_neighbours = 0.0;
 
+  // what the last ope_coarse_pose_batch computed (ope_coarse_batch_features): segment 0 the model, 1..n the clusters;
+  // key points (original indices), normals (x y z) and FPFH rows, packed by segment from coarse_key_off
+  std::vector<int32_t> coarse_key_off, coarse_key_idx;
+  std::vector<float> coarse_nrm, coarse_fpfh;
+
   bool tracing = false;   // roctx ranges around the host side of the path (ope_ctx_set_tracing)
 
   // scratch
@@ -562,5 +567,9 @@ void icp_state_init(IcpState *h, const ope_cloud *src, const ope_index *tgt, con
 inline int index_build_tmp(ope_ctx *ctx, const ope_cloud *target, const ope_index_params *params, ope_index **out) {
   return index_build_impl(ctx, target, params, true, out);
 }
+// features.hip: the SAC-IA host side that ope_sacia and ope_coarse_pose_batch share (same draws, same fits)
+void sacia_draws(const float *xyz, int ns, int S, int K, int H, float min_sample_dist, uint64_t seed, int32_t *samp, int32_t *pick);
+void umeyama_host(const float *src, const float *dst, int n, float T[16]);
+void colmajor_to_rows12(const float *T, float rows[12]);
 
 }  // namespace ope
