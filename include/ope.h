@@ -534,6 +534,66 @@ int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const 
 int ope_coarse_batch_features(ope_ctx *ctx, int which, int32_t *key_idx, float *normals, float *fpfh33, size_t cap,
                               size_t *n_out);
 
+/* ---------------- batched final pose: the reference's first-frame candidate loop ---------------- */
+/* PoseEstimator::estimateFinalPose(model, cluster) (poseestimator.cpp:383-448) of one model against n candidate clusters in one
+ * call, as the reference's first frame runs it cluster by cluster (rosinterface.cpp:243-262): the coarse stage of
+ * ope_coarse_pose_batch, then the fine stage's preparation (:186-223) and its ICP (:229-363) with getFitnessScore, for every
+ * cluster at once.  The composite coarse * fine and the re-anchoring (rigidmodelPose) stay with the caller. */
+typedef struct {
+  ope_coarse_params coarse;  /* ope_coarse_default_params */
+  float fine_leaf;           /* UniformSampling radius of the fine clouds, 0.008 (poseestimator.cpp:196-216) */
+  int fine_normals_k;        /* 30 */
+  int min_fine_points;       /* 100 (:218-223): fewer fine target points and the fine pose is the identity */
+  ope_icp_params icp;        /* the fine stage: 100 iterations, 1e-8, 1e-8, normal shooting k = 20, surface-normal rejector 0.7 */
+  double fitness_max_range;  /* getFitnessScore's default: DBL_MAX */
+  double accept_fitness;     /* the loop stops at fitness < 1e-4 (rosinterface.cpp:256) */
+  double accept_strength;    /* ... or align strength > 0.4 */
+} ope_final_params;
+void ope_final_default_params(ope_final_params *p);
+
+/* ope_final_batch_result.status */
+enum {
+  OPE_FINAL_OK = 0,                  /* coarse pose found, fine ICP ran */
+  OPE_FINAL_EMPTY_TARGET = 1,        /* an empty cluster: the loop skips it (nothing ran) */
+  OPE_FINAL_FEW_TARGET_FEATURES = 2, /* fewer than 10 coarse key points: coarse pose = identity, fine ICP ran from the model
+                                        (only with min_fine_points lowered: < 10 cm-voxels hold < 100 fine points) */
+  OPE_FINAL_FEW_FINE_POINTS = 3      /* fewer than min_fine_points fine target points: fine pose = identity, no ICP */
+};
+typedef struct {
+  ope_coarse_batch_result coarse; /* as ope_coarse_pose_batch reports it */
+  uint64_t seed;                  /* the SAC-IA stream this cluster drew with; 0 if it did not reach SAC-IA */
+  ope_icp_batch_result fine;      /* the fine ICP from the identity (T, result, fitness, fitness_n); identity and zeros without ICP */
+  int32_t n_fine_src;             /* fine key points (after the NaN-normal drop) of the moved model */
+  int32_t n_fine_tgt;             /* ... and of the cluster */
+  int32_t status;                 /* OPE_FINAL_* */
+  int32_t accepted;               /* ICP ran and fitness < accept_fitness || align_strength > accept_strength */
+} ope_final_batch_result;
+
+/* Synchronous, on the context's stream; n == 0 does nothing.  Cluster i is what estimateFinalPose does on a fresh estimator:
+ *   coarse: ope_coarse_pose_batch's result, except that without seeds cluster i draws with coarse.sacia.seed + (the clusters
+ *           before it that reached SAC-IA): empty clusters and clusters with fewer than 10 key points use up no seed
+ *           (the estimator's coarse-call counter); seeds[i] if seeds is given;
+ *   fine source: the model moved by the coarse pose (pcl::transformPointCloud's float arithmetic, non-finite points left as they
+ *           are; identity unless the coarse status is OK), NaNs removed, UniformSampling(fine_leaf), k-NN normals
+ *           (fine_normals_k, coarse.viewpoint), rows with a non-finite normal dropped (withNormals);
+ *   fine target: the same preparation of the cluster;
+ *   fine ICP: ope_icp_run_batch of the two from the identity, the target indexed as ope_index_build indexes it (default leaf size),
+ *           with getFitnessScore(fitness_max_range).
+ * *selected = the first accepted cluster, or -1.  The launches and host synchronisations do not depend on n; each cluster's
+ * result is byte-identical whatever else is in the batch.  For ONE cluster the single-run calls are faster: one workgroup runs
+ * the whole fine ICP here (ope_icp_run_batch), so at C1 size one cluster takes ~1.3x one estimateFinalPose chain, while 8
+ * clusters take 3.4x less than 8 chains.
+ * OPE_EINVAL, nothing launched: what ope_coarse_pose_batch or ope_icp_run_batch refuses (LM, reciprocal correspondences, a context
+ * with a communicator, ...), fine_leaf <= 0, fine_normals_k outside 1..32, a cluster of more than OPE_COARSE_MAX_KEYS fine key
+ * points.  OPE_EINVAL after sampling (the moved model is only known there), nothing more launched and the context usable: a
+ * moved model with more than OPE_COARSE_MAX_KEYS fine key points, or a fine_leaf too small for it. */
+int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_final_params *params,
+                         const uint64_t *seeds, ope_final_batch_result *out, int32_t *selected);
+/* The fine inputs the last ope_final_pose_batch prepared: cluster `which`, side 0 = the moved model (source), 1 = the cluster
+ * (target); xyz (n*3) and normals (n*3) in key-point order, as they would be handed to ope_cloud_upload; either may be NULL.
+ * *n_out = the points; at most cap rows are written. */
+int ope_final_batch_inputs(ope_ctx *ctx, int which, int side, float *xyz, float *normals, size_t cap, size_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

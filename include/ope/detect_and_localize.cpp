@@ -2,11 +2,14 @@
 // been cut out (rosinterface.cpp:80 loads the model .pcd, :250 calls PoseEstimator::estimateFinalPose(model, cluster)),
 // with pcl:: replaced by the façade and the GPU library behind it.
 //
-//   detect_and_localize <model.pcd> <scene.pcd> [<scene2.pcd> ...] [--seed N] [--self-occluded]
+//   detect_and_localize <model.pcd> <scene.pcd> [<scene2.pcd> ...] [--seed N] [--self-occluded] [--candidates | --candidates-loop]
 //
 // One line per frame on stdout, parsed by tests/test_gpu_detect_and_localize.py:
 //   frame <k> fitness <f> strength <s> coarse_calls <n> icp_iterations <n> final <16 floats, column-major> coarse <16> fine <16> rigid <16>
 // and `aligned <path>` after saving the aligned model of the last frame next to the first scene file.
+// --candidates: the scene files are the clusters of ONE first frame (rosinterface.cpp:243-262), checked by
+// PoseEstimator::estimateFinalPoseCandidates in one call; --candidates-loop: the same frame by the reference's loop of
+// estimateFinalPose.  Either prints `candidates selected <i> clusters <n>`, then one `frame 1 ...` line.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,12 +30,15 @@ int main(int argc, char **argv) {
   std::vector<std::string> files;
   uint64_t seed = 1;
   bool self_occluded = false;
+  int candidates = 0;   // 1: estimateFinalPoseCandidates, 2: the reference's loop
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
+    else if (!std::strcmp(argv[i], "--candidates")) candidates = 1;
+    else if (!std::strcmp(argv[i], "--candidates-loop")) candidates = 2;
     else files.push_back(argv[i]);
   }
-  if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded]\n", argv[0]); return 2; }
+  if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded] [--candidates | --candidates-loop]\n", argv[0]); return 2; }
   typedef ope::PoseEstimator::PointT PointT;
   pcl::PointCloud<PointT>::Ptr cloudSourceOriginal(new pcl::PointCloud<PointT>), cloudSource(new pcl::PointCloud<PointT>);
   if (pcl::io::loadPCDFile(files[0], *cloudSourceOriginal) != 0) return 3;   // rosinterface.cpp:80
@@ -40,12 +46,7 @@ int main(int argc, char **argv) {
   ope::PoseEstimator poseEstimator;
   poseEstimator.setSacIaSeed(seed);
   poseEstimator.setUseSelfOccludedRejector(self_occluded);
-  for (size_t k = 1; k < files.size(); ++k) {
-    pcl::PointCloud<PointT>::Ptr cloudTargetSeg(new pcl::PointCloud<PointT>);
-    if (pcl::io::loadPCDFile(files[k], *cloudTargetSeg) != 0) return 3;
-    double fitnessScore = 10.0, alignedStrength = 0.0;
-    // later frames hand over the source as the previous call left it (rosinterface.cpp:285: cloudSource is not reset)
-    const pcl::Matrix4f pose = poseEstimator.estimateFinalPose(cloudSource, cloudTargetSeg, fitnessScore, alignedStrength);
+  auto print_frame = [&](size_t k, const pcl::Matrix4f &pose, double fitnessScore, double alignedStrength) {
     std::printf("frame %zu fitness %.12g strength %.12g coarse_calls %d icp_iterations %d", k, fitnessScore, alignedStrength,
                 poseEstimator.coarseCalls(), poseEstimator.lastIcpIterations());
     print16("final", pose);
@@ -53,6 +54,35 @@ int main(int argc, char **argv) {
     print16("fine", poseEstimator.lastFinePose());
     print16("rigid", poseEstimator.lastRigidModelPose());
     std::printf("\n");
+  };
+  if (candidates) {
+    std::vector<pcl::PointCloud<PointT>::Ptr> clusters;
+    for (size_t k = 1; k < files.size(); ++k) {
+      clusters.emplace_back(new pcl::PointCloud<PointT>);
+      if (pcl::io::loadPCDFile(files[k], *clusters.back()) != 0) return 3;
+    }
+    double fitnessScore = 10.0, alignedStrength = 0.0;
+    int selected = -1;
+    pcl::Matrix4f pose = pcl::Matrix4f::Identity();
+    if (candidates == 1) {
+      pose = poseEstimator.estimateFinalPoseCandidates(cloudSource, clusters, fitnessScore, alignedStrength, selected);
+    } else {
+      for (size_t i = 0; i < clusters.size(); ++i) {   // rosinterface.cpp:244-259
+        *cloudSource = *cloudSourceOriginal;
+        if (!clusters[i]->empty()) pose = poseEstimator.estimateFinalPose(cloudSource, clusters[i], fitnessScore, alignedStrength);
+        if (fitnessScore < 0.0001 || alignedStrength > 0.4) { selected = (int)i; break; }
+      }
+    }
+    std::printf("candidates selected %d clusters %zu\n", selected, clusters.size());
+    print_frame(1, pose, fitnessScore, alignedStrength);
+  }
+  for (size_t k = 1; !candidates && k < files.size(); ++k) {
+    pcl::PointCloud<PointT>::Ptr cloudTargetSeg(new pcl::PointCloud<PointT>);
+    if (pcl::io::loadPCDFile(files[k], *cloudTargetSeg) != 0) return 3;
+    double fitnessScore = 10.0, alignedStrength = 0.0;
+    // later frames hand over the source as the previous call left it (rosinterface.cpp:285: cloudSource is not reset)
+    const pcl::Matrix4f pose = poseEstimator.estimateFinalPose(cloudSource, cloudTargetSeg, fitnessScore, alignedStrength);
+    print_frame(k, pose, fitnessScore, alignedStrength);
   }
   const std::string out = files[1] + ".aligned.pcd";
   if (pcl::io::savePCDFile(out, *cloudSource, true) != 0) return 4;

@@ -17,6 +17,10 @@
 // the PCL version and on an ODR accident).
 #pragma once
 
+#include <cstring>
+#include <memory>
+#include <vector>
+
 #include "pcl_compat.hpp"
 
 namespace ope {
@@ -161,19 +165,89 @@ class PoseEstimator {
     Matrix4f coarsePose = Matrix4f::Identity(), finePose = Matrix4f::Identity();
     if (have_target && fitnessScoreFine > 0.0001) coarsePose = estimateCoarsePose(p_sourceCloud, p_targetCloud);
     if (have_target) finePose = estimateFinePose(alignedSource, p_targetCloud);
-    const Matrix4f pose = coarsePose * finePose;   // :421
-    // where the incoming source sits relative to the stored model: SVD fit over identity correspondences (:425-436)
-    Matrix4f rigidmodelPose = Matrix4f::Identity();
-    {
-      compat::Correspondences corres(cloudModel->points.size());
-      for (size_t i = 0; i < corres.size(); ++i) corres[i].index_query = corres[i].index_match = (int)i;
-      if (!corres.empty() && p_sourceCloud->size() >= corres.size()) svd.estimateRigidTransformation(*cloudModel, *p_sourceCloud, corres, rigidmodelPose);
-    }
-    finalPose = rigidmodelPose * pose;   // :439
-    *p_sourceCloud = *alignedSource;     // :441
+    finish(p_sourceCloud, coarsePose, finePose);
     fitnessScore = fitnessScoreFine;
     alignStrength = alignedStrength;
-    last_coarse_ = coarsePose; last_fine_ = finePose; last_rigid_ = rigidmodelPose;
+    return finalPose;
+  }
+
+  // The reference's first-frame candidate loop (rosinterface.cpp:243-262) in one call:
+  //     for each cluster: source = a copy of the original model; if the cluster is not empty, estimateFinalPose(source, cluster);
+  //                       stop once fitness < 1e-4 or strength > 0.4
+  // p_sourceCloud is the original model on entry.  Runs ope_final_pose_batch over all clusters, then leaves the estimator and
+  // p_sourceCloud exactly as that loop would: coarse calls counted only for clusters that reached SAC-IA, fitnessScoreFine /
+  // alignedStrength from the last cluster (up to the selected one) that ran a fine ICP, alignedSource / cloudModel / firstTimePose
+  // / the last* diagnostics as after the last non-empty cluster it processed; p_sourceCloud holds alignedSource, or the original
+  // model if the last cluster it visited was empty.  selected = the accepted cluster or -1; the pose is that of the last
+  // estimateFinalPose the loop made (finalPose unchanged if every cluster is empty).  When fitnessScoreFine <= 1e-4 on entry
+  // (the coarse stage would be skipped) or the batch refuses the clouds (ope.h: OPE_COARSE_MAX_POINTS / _MAX_KEYS), the loop runs
+  // as written above, one estimateFinalPose at a time.
+  Matrix4f estimateFinalPoseCandidates(Cloud::Ptr &p_sourceCloud, const std::vector<Cloud::Ptr> &clusters, double &fitnessScore,
+                                       double &alignStrength, int &selected) {
+    selected = -1;
+    const Cloud original(*p_sourceCloud);
+    std::vector<ope_final_batch_result> res(clusters.size());
+    int32_t sel = -1;
+    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty();
+    if (batched) {
+      ope_ctx *ctx = compat::default_context();
+      auto model = compat::upload(original, false);
+      std::vector<std::shared_ptr<compat::CloudHandle>> held;
+      std::vector<const ope_cloud *> hs;
+      for (const Cloud::Ptr &c : clusters) { held.push_back(compat::upload(*c, false)); hs.push_back(held.back()->h); }
+      ope_final_params p;
+      ope_final_default_params(&p);
+      p.coarse.sacia.seed = sacia_seed_ + (uint64_t)coarse_calls_;   // the k-th SAC-IA call draws with seed + k
+      if (use_self_occluded_) { p.icp.use_self_occluded_rej = 1; p.icp.self_occluded_thr = 0.6; }   // :291
+      batched = ctx && model->h && ope_final_pose_batch(ctx, model->h, hs.size(), hs.data(), &p, nullptr, res.data(), &sel) == OPE_OK;
+      if (!batched && ctx) compat::log_error("final_pose_batch (running the loop one cluster at a time)", ctx);
+    }
+    if (!batched) {
+      Matrix4f pose = finalPose;
+      for (size_t i = 0; i < clusters.size(); ++i) {
+        *p_sourceCloud = original;
+        if (clusters[i]->empty()) continue;
+        pose = estimateFinalPose(p_sourceCloud, clusters[i], fitnessScore, alignStrength);
+        if (fitnessScore < 0.0001 || alignStrength > 0.4) { selected = (int)i; break; }
+      }
+      fitnessScore = fitnessScoreFine;
+      alignStrength = alignedStrength;
+      return pose;
+    }
+    const size_t last = sel >= 0 ? (size_t)sel : clusters.size() - 1;   // the last cluster the loop visits
+    int applied = -1;
+    for (size_t i = 0; i <= last; ++i) {
+      const ope_final_batch_result &r = res[i];
+      if (r.status == OPE_FINAL_EMPTY_TARGET) continue;
+      if (firstTimePose == 0) *cloudModel = original;
+      ++firstTimePose;
+      if (r.coarse.status == OPE_COARSE_OK) ++coarse_calls_;
+      if (r.status == OPE_FINAL_OK || r.status == OPE_FINAL_FEW_TARGET_FEATURES) {
+        fitnessScoreFine = r.fine.fitness;
+        alignedStrength = r.fine.result.align_strength;
+        last_icp_iterations_ = r.fine.result.iterations;
+      }
+      applied = (int)i;
+    }
+    if (applied >= 0) {
+      const ope_final_batch_result &r = res[(size_t)applied];
+      Matrix4f coarsePose = Matrix4f::Identity(), finePose = Matrix4f::Identity();
+      std::memcpy(coarsePose.m, r.coarse.T, sizeof coarsePose.m);
+      if (r.coarse.status == OPE_COARSE_OK) compat::transformPointCloud(original, *alignedSource, coarsePose);   // :66-70
+      else *alignedSource = original;                                                                            // :40-45
+      if (r.status != OPE_FINAL_FEW_FINE_POINTS) {   // :358-360
+        std::memcpy(finePose.m, r.fine.T, sizeof finePose.m);
+        Cloud::Ptr moved(new Cloud);
+        compat::transformPointCloud(*alignedSource, *moved, finePose);
+        *alignedSource = *moved;
+      }
+      *p_sourceCloud = original;
+      finish(p_sourceCloud, coarsePose, finePose);
+    }
+    if (res[last].status == OPE_FINAL_EMPTY_TARGET) *p_sourceCloud = original;   // the loop's copy before an empty cluster
+    selected = sel;
+    fitnessScore = fitnessScoreFine;
+    alignStrength = alignedStrength;
     return finalPose;
   }
 
@@ -193,6 +267,21 @@ class PoseEstimator {
       out->push_back(q);
     }
     return out;
+  }
+
+  // the end of estimateFinalPose (:421-441): pose = coarse * fine, the re-anchoring fit of the incoming source against the stored
+  // model (SVD over identity correspondences, :425-436), finalPose = rigidmodelPose * pose, the source replaced by alignedSource
+  void finish(Cloud::Ptr &p_sourceCloud, const Matrix4f &coarsePose, const Matrix4f &finePose) {
+    const Matrix4f pose = coarsePose * finePose;   // :421
+    Matrix4f rigidmodelPose = Matrix4f::Identity();
+    {
+      compat::Correspondences corres(cloudModel->points.size());
+      for (size_t i = 0; i < corres.size(); ++i) corres[i].index_query = corres[i].index_match = (int)i;
+      if (!corres.empty() && p_sourceCloud->size() >= corres.size()) svd.estimateRigidTransformation(*cloudModel, *p_sourceCloud, corres, rigidmodelPose);
+    }
+    finalPose = rigidmodelPose * pose;   // :439
+    *p_sourceCloud = *alignedSource;     // :441
+    last_coarse_ = coarsePose; last_fine_ = finePose; last_rigid_ = rigidmodelPose;
   }
 
   // state that crosses frames (poseestimator.h:50-53)

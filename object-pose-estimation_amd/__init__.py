@@ -28,6 +28,8 @@ COMM_AUTO, COMM_RCCL, COMM_P2P = 0, 1, 2
 # ope_coarse_batch_result.status; per-cloud limits of ope_coarse_pose_batch
 COARSE_OK, COARSE_EMPTY_TARGET, COARSE_FEW_TARGET_FEATURES = 0, 1, 2
 COARSE_MAX_POINTS, COARSE_MAX_KEYS = 65536, 4096
+# ope_final_batch_result.status
+FINAL_OK, FINAL_EMPTY_TARGET, FINAL_FEW_TARGET_FEATURES, FINAL_FEW_FINE_POINTS = 0, 1, 2, 3
 CERT_AUTO, CERT_OFF, CERT_ALWAYS = 0, 1, 2   # ope_icp_params.skip_certificates
 NUM_SUMS, NUM_SUMS_MAX = 17, 44
 COMM_ID_BYTES = 128
@@ -137,6 +139,31 @@ class CoarseBatchResult(C.Structure):
     ]
 
 
+class FinalParams(C.Structure):
+    _fields_ = [
+        ("coarse", CoarseParams),
+        ("fine_leaf", C.c_float),
+        ("fine_normals_k", C.c_int),
+        ("min_fine_points", C.c_int),
+        ("icp", IcpParams),
+        ("fitness_max_range", C.c_double),
+        ("accept_fitness", C.c_double),
+        ("accept_strength", C.c_double),
+    ]
+
+
+class FinalBatchResult(C.Structure):
+    _fields_ = [
+        ("coarse", CoarseBatchResult),
+        ("seed", C.c_uint64),
+        ("fine", IcpBatchResult),
+        ("n_fine_src", C.c_int32),
+        ("n_fine_tgt", C.c_int32),
+        ("status", C.c_int32),
+        ("accepted", C.c_int32),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
 _dp = C.POINTER(C.c_double)
@@ -223,6 +250,10 @@ ABI = [
     ("ope_coarse_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(CoarseParams), C.POINTER(C.c_uint64),
                                          C.POINTER(CoarseBatchResult)]),
     ("ope_coarse_batch_features", C.c_int, [_vp, C.c_int, _ip, _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_final_default_params", None, [C.POINTER(FinalParams)]),
+    ("ope_final_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(FinalParams), C.POINTER(C.c_uint64),
+                                        C.POINTER(FinalBatchResult), _ip]),
+    ("ope_final_batch_inputs", C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
 ]
 
 _lib = None
@@ -304,6 +335,17 @@ class CoarseOut:
     n_src_keys: int        # model key points
     n_tgt_keys: int        # this cluster's key points
     status: int            # COARSE_OK, COARSE_EMPTY_TARGET or COARSE_FEW_TARGET_FEATURES
+
+
+@dataclass
+class FinalOut:
+    coarse: CoarseOut      # the coarse stage, as coarse_pose_batch reports it
+    seed: int              # the SAC-IA stream the cluster drew with (0: it did not reach SAC-IA)
+    fine: IcpBatchOut | None   # the fine ICP from the identity; None unless it ran (FINAL_OK, FINAL_FEW_TARGET_FEATURES)
+    n_fine_src: int        # fine key points of the moved model
+    n_fine_tgt: int        # ... and of the cluster
+    status: int            # FINAL_OK, FINAL_EMPTY_TARGET, FINAL_FEW_TARGET_FEATURES or FINAL_FEW_FINE_POINTS
+    accepted: bool         # fitness < accept_fitness or align strength > accept_strength
 
 
 class Context:
@@ -519,6 +561,42 @@ class Context:
         f = np.empty((max(m.value, 1), 33), np.float32)
         self._chk(lib().ope_coarse_batch_features(self.h, which, _p(idx, _ip), _p(nrm, _fp), _p(f, _fp), m.value, C.byref(m)))
         return idx[: m.value].copy(), nrm[: m.value].copy(), f[: m.value].copy()
+
+    def final_pose_batch(self, model: "Cloud", clusters, params: FinalParams | None = None, seeds=None):
+        """ope_final_pose_batch: estimateFinalPose(model, clusters[i]) of a fresh estimator for every cluster in one call.
+        Returns ([FinalOut per cluster], selected): selected = the first accepted cluster, or -1."""
+        n = len(clusters)
+        p = params or default_final_params()
+        hc = (_vp * max(n, 1))(*[c.h for c in clusters])
+        sd = None
+        if seeds is not None:
+            if len(seeds) != n:
+                raise ValueError("one seed per cluster")
+            sd = (C.c_uint64 * max(n, 1))(*[int(x) for x in seeds])
+        out = (FinalBatchResult * max(n, 1))()
+        sel = C.c_int32(-1)
+        self._chk(lib().ope_final_pose_batch(self.h, model.h, n, hc, C.byref(p), sd, out, C.byref(sel)))
+        res = []
+        for o in out[:n]:
+            c = o.coarse
+            co = CoarseOut(from_colmajor(np.frombuffer(c.T, np.float32)), c.best_error, c.best_iteration, c.n_src_keys, c.n_tgt_keys, c.status)
+            fine = None
+            if o.status in (FINAL_OK, FINAL_FEW_TARGET_FEATURES):
+                r = o.fine.result
+                fine = IcpBatchOut(from_colmajor(np.frombuffer(o.fine.T, np.float32)), r.iterations, bool(r.converged), r.state, r.last_mse,
+                                   r.n_corr, r.align_strength, o.fine.fitness, o.fine.fitness_n)
+            res.append(FinalOut(co, o.seed, fine, o.n_fine_src, o.n_fine_tgt, o.status, bool(o.accepted)))
+        return res, sel.value
+
+    def final_batch_inputs(self, which: int, side: int):
+        """The fine inputs the last final_pose_batch prepared for cluster `which`: side 0 the moved model, 1 the cluster.
+        (xyz (m,3), normals (m,3)) in key-point order, as they would be uploaded."""
+        m = C.c_size_t(0)
+        self._chk(lib().ope_final_batch_inputs(self.h, which, side, None, None, 0, C.byref(m)))
+        xyz = np.empty((max(m.value, 1), 3), np.float32)
+        nrm = np.empty((max(m.value, 1), 3), np.float32)
+        self._chk(lib().ope_final_batch_inputs(self.h, which, side, _p(xyz, _fp), _p(nrm, _fp), m.value, C.byref(m)))
+        return xyz[: m.value].copy(), nrm[: m.value].copy()
 
     def icp_begin(self, src: "Cloud", tgt: "Index", params: IcpParams | None = None, guess=None):
         p = params or default_icp_params()
@@ -788,6 +866,16 @@ def default_coarse_params(**kw) -> CoarseParams:
             p.viewpoint[:] = [float(x) for x in v]
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_final_params(**kw) -> FinalParams:
+    """ope_final_default_params (the reference's values); keyword arguments set fields (`coarse` a CoarseParams, `icp` an
+    IcpParams)."""
+    p = FinalParams()
+    lib().ope_final_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 

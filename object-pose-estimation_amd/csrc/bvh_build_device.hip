@@ -205,29 +205,23 @@ __device__ __noinline__ uint32_t split_key16(float x, float y, float z, float lx
 constexpr int kBotItems = 8;
 constexpr uint32_t kBotPoints = 256 * kBotItems;
 constexpr int kBotMaxLevels = 11;   // sub-nodes of a block's node: at most 2^10 (rows of the box table)
-__global__ __launch_bounds__(256) void bottom_levels_kernel(const float4 *__restrict__ pts, const uint32_t *__restrict__ order_in, uint32_t n, int D,
-                                                             int L0, uint32_t *__restrict__ order_out) {
-  using Sort = rocprim::block_radix_sort<uint32_t, 256, kBotItems, uint32_t>;
+// The levels L0..D-1 of node (L0, j0) inside one block: idx / leaf hold its range in blocked arrangement (item i of thread t is
+// position t * ITEMS + i; 0xffffffff past its end) and come back in the final order.  bottom_levels_kernel and the batched
+// build (bvh_batch_order_kernel) both run it.
+template <int ITEMS>
+__device__ __forceinline__ void bottom_levels_block(const float4 *__restrict__ pts, int D, int L0, uint32_t j0, uint32_t (&idx)[ITEMS],
+                                                    const uint32_t (&leaf)[ITEMS]) {
+  using Sort = rocprim::block_radix_sort<uint32_t, 256, ITEMS, uint32_t>;
   __shared__ typename Sort::storage_type s_sort;
   __shared__ uint32_t s_mn[3u << (kBotMaxLevels - 1)], s_mx[3u << (kBotMaxLevels - 1)];
-  const uint32_t j0 = blockIdx.x;   // node (L0, j0)
-  const uint32_t b = leaf_start((unsigned long long)j0 << (D - L0), n, D), e = leaf_start((unsigned long long)(j0 + 1) << (D - L0), n, D);
-  const uint32_t m = e - b;
-  uint32_t idx[kBotItems], leaf[kBotItems];
-#pragma unroll
-  for (int i = 0; i < kBotItems; ++i) {   // blocked arrangement: item i of thread t is position t * kBotItems + i of the range
-    const uint32_t p = threadIdx.x * kBotItems + i;
-    idx[i] = p < m ? order_in[b + p] : 0xffffffffu;
-    leaf[i] = p < m ? leaf_of(b + p, n, D) : 0u;
-  }
   for (int level = L0; level < D; ++level) {
     const uint32_t nsub = 1u << (level - L0), sub0 = j0 << (level - L0);
     for (uint32_t k = threadIdx.x; k < nsub * 3u; k += 256u) { s_mn[k] = 0xffffffffu; s_mx[k] = 0u; }
     __syncthreads();
-    float c[kBotItems][3];
-    uint32_t sub[kBotItems];
+    float c[ITEMS][3];
+    uint32_t sub[ITEMS];
 #pragma unroll
-    for (int i = 0; i < kBotItems; ++i) {
+    for (int i = 0; i < ITEMS; ++i) {
       const bool live = idx[i] != 0xffffffffu;
       sub[i] = live ? (leaf[i] >> (D - level)) - sub0 : 0u;
       const float4 q = pts[live ? idx[i] : 0u];
@@ -238,9 +232,9 @@ __global__ __launch_bounds__(256) void bottom_levels_kernel(const float4 *__rest
       }
     }
     __syncthreads();
-    uint32_t keys[kBotItems];
+    uint32_t keys[ITEMS];
 #pragma unroll
-    for (int i = 0; i < kBotItems; ++i) {
+    for (int i = 0; i < ITEMS; ++i) {
       const bool live = idx[i] != 0xffffffffu;
       const uint32_t sn = sub[i];
       const uint32_t q16 = split_key16(c[i][0], c[i][1], c[i][2], dec_f32(s_mn[3u * sn]), dec_f32(s_mn[3u * sn + 1u]), dec_f32(s_mn[3u * sn + 2u]),
@@ -251,6 +245,20 @@ __global__ __launch_bounds__(256) void bottom_levels_kernel(const float4 *__rest
     Sort().sort(keys, idx, s_sort, 0, 32);
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(256) void bottom_levels_kernel(const float4 *__restrict__ pts, const uint32_t *__restrict__ order_in, uint32_t n, int D,
+                                                             int L0, uint32_t *__restrict__ order_out) {
+  const uint32_t j0 = blockIdx.x;   // node (L0, j0)
+  const uint32_t b = leaf_start((unsigned long long)j0 << (D - L0), n, D), e = leaf_start((unsigned long long)(j0 + 1) << (D - L0), n, D);
+  const uint32_t m = e - b;
+  uint32_t idx[kBotItems], leaf[kBotItems];
+#pragma unroll
+  for (int i = 0; i < kBotItems; ++i) {   // blocked arrangement: item i of thread t is position t * kBotItems + i of the range
+    const uint32_t p = threadIdx.x * kBotItems + i;
+    idx[i] = p < m ? order_in[b + p] : 0xffffffffu;
+    leaf[i] = p < m ? leaf_of(b + p, n, D) : 0u;
+  }
+  bottom_levels_block<kBotItems>(pts, D, L0, j0, idx, leaf);
 #pragma unroll
   for (int i = 0; i < kBotItems; ++i) {
     const uint32_t p = threadIdx.x * kBotItems + i;
@@ -332,13 +340,13 @@ __device__ void jacobi_eig3_dev(double S[9], double V[9]) {
 
 // One block per node of `level`: oriented box of the node's points (final order), written in the 48-byte layout.
 // BLOCK = 256 for the populous levels, 64 (one wave, no barriers in the reductions) where a node holds few points.
+// (the body is fit_obb_node, which the batched build runs too)
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void fit_obb_kernel(const float4 *__restrict__ pts, uint32_t n, int D, int level, double scale,
-                                                            float *__restrict__ nodes, float4 *__restrict__ axis2) {
+__device__ __forceinline__ void fit_obb_node(const float4 *__restrict__ pts, uint32_t n, int D, int level, uint32_t j, double scale,
+                                             float *__restrict__ nodes, float4 *__restrict__ axis2) {
   __shared__ double s_tmp[BLOCK / 64];
   __shared__ double s_A[9];
   __shared__ float s_cf[3];
-  const uint32_t j = blockIdx.x;
   const uint32_t node = (1u << level) + j;
   const uint32_t b = leaf_start((unsigned long long)j << (D - level), n, D), e = leaf_start((unsigned long long)(j + 1) << (D - level), n, D);
   float *o = nodes + (size_t)kNodeFloats * node;
@@ -417,6 +425,11 @@ __global__ __launch_bounds__(BLOCK) void fit_obb_kernel(const float4 *__restrict
     o[0] = cf0; o[1] = cf1; o[2] = cf2;
     for (int k = 0; k < 3; ++k) o[4 * k + 3] = nextafterf((float)(h[k] + margin), FLT_MAX);
   }
+}
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void fit_obb_kernel(const float4 *__restrict__ pts, uint32_t n, int D, int level, double scale,
+                                                            float *__restrict__ nodes, float4 *__restrict__ axis2) {
+  fit_obb_node<BLOCK>(pts, n, D, level, blockIdx.x, scale, nodes, axis2);
 }
 
 
@@ -661,6 +674,47 @@ __global__ __launch_bounds__(kFitBlock) void top_write_kernel(const TopWork *__r
   for (int k = 0; k < 3; ++k) o[4 * k + 3] = nextafterf((float)(__longlong_as_double((long long)w->ext[node][k]) + margin), FLT_MAX);
 }
 
+// ---- many small trees at once (build_bvh_batch_device): one block per tree carries the whole point order, one launch per level
+// and block size fits the nodes of every tree.  Same device code as build_bvh_device's bottom_levels_kernel and fit_obb_kernel.
+constexpr int kBatchItems = 16;   // 256 threads x 16 items: a tree of up to 4096 points in one block
+static_assert(256 * kBatchItems >= OPE_COARSE_MAX_KEYS, "a batched tree must fit one block");
+
+// the order of every tree (the one bottom_levels_kernel gives a cloud that fits one block: L0 = 0 from the identity order), then
+// the gather of points and normals into it
+__global__ __launch_bounds__(256) void bvh_batch_order_kernel(const BvhBatchTree *__restrict__ trees) {
+  const BvhBatchTree t = trees[blockIdx.x];
+  uint32_t idx[kBatchItems], leaf[kBatchItems];
+#pragma unroll
+  for (int i = 0; i < kBatchItems; ++i) {
+    const uint32_t p = threadIdx.x * kBatchItems + i;
+    idx[i] = p < t.n ? p : 0xffffffffu;
+    leaf[i] = p < t.n ? leaf_of(p, t.n, t.D) : 0u;
+  }
+  bottom_levels_block<kBatchItems>(t.src, t.D, 0, 0u, idx, leaf);
+#pragma unroll
+  for (int i = 0; i < kBatchItems; ++i) {
+    const uint32_t p = threadIdx.x * kBatchItems + i;
+    if (p >= t.n) continue;
+    t.pts[p] = t.src[idx[i]];
+    if (t.nrm) { float4 m = t.src_nrm[idx[i]]; m.w = 0.f; t.nrm[p] = m; }
+  }
+}
+
+// node (level, blockIdx.x) of tree blockIdx.y, for the trees whose nodes at this level take this block size in build_bvh_device
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void bvh_batch_fit_kernel(const BvhBatchTree *__restrict__ trees, int level) {
+  const BvhBatchTree &t = trees[blockIdx.y];
+  if (level > t.D || blockIdx.x >= (1u << level) || ((t.n >> level) > 512) != (BLOCK == kFitBlock)) return;
+  fit_obb_node<BLOCK>(t.pts, t.n, t.D, level, blockIdx.x, t.scale, reinterpret_cast<float *>(t.nodes), t.axis2);
+}
+
+// node 0 is unused: the root box, so stray reads are harmless (build_bvh_device's two copies)
+__global__ __launch_bounds__(64) void bvh_batch_root_kernel(const BvhBatchTree *__restrict__ trees) {
+  const BvhBatchTree &t = trees[blockIdx.x];
+  if (threadIdx.x < 3) t.nodes[threadIdx.x] = t.nodes[3 + threadIdx.x];
+  if (threadIdx.x == 3) t.axis2[0] = t.axis2[1];
+}
+
 }  // namespace
 
 // The level sorts: rocPRIM's default takes its merge sort up to 2^20 items — two dozen launches of 5-8 us for a 17..25-bit key over
@@ -672,6 +726,19 @@ __global__ __launch_bounds__(kFitBlock) void top_write_kernel(const TopWork *__r
 #endif
 using LevelSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, OPE_LEVEL_MERGE_SORT_LIMIT>;
 
+int bvh_depth(size_t n, int leaf_size) {
+  if (leaf_size < 1) leaf_size = 16;
+  int D = 0;
+  while (((n + ((size_t)1 << D) - 1) >> D) > (size_t)leaf_size) ++D;
+  return D > kMaxDepth ? kMaxDepth : D;
+}
+
+double bvh_scale(const float bb_lo[3], const float bb_hi[3]) {
+  return std::max({(double)bb_hi[0] - bb_lo[0], (double)bb_hi[1] - bb_lo[1], (double)bb_hi[2] - bb_lo[2], 1e-3}) +
+         std::max({std::fabs((double)bb_lo[0]), std::fabs((double)bb_hi[0]), std::fabs((double)bb_lo[1]), std::fabs((double)bb_hi[1]),
+                   std::fabs((double)bb_lo[2]), std::fabs((double)bb_hi[2])});
+}
+
 // d_src: n finite points (float4, w = original index bits) in any order, d_src_nrm optional (same order).
 // Allocates *d_nodes ((2 << D) * 48 B), *d_pts and (if normals) *d_nrm.
 // tmp_alloc: the index is a temporary of one entry point (the outlier filter's, a feature stage's): its buffers come from the
@@ -681,15 +748,10 @@ hipError_t build_bvh_device(hipStream_t stream, const float4 *d_src, const float
                             const float bb_lo[3], const float bb_hi[3], int *out_depth, float4 **d_nodes, float4 **d_pts,
                             float4 **d_nrm, float4 **d_axis2, bool tmp_alloc) {
   auto alloc = [&](void **p, size_t bytes) { return tmp_alloc ? tmp_malloc(stream, p, bytes) : hipMalloc(p, bytes); };
-  if (leaf_size < 1) leaf_size = 16;
-  int D = 0;
-  while (((n + ((size_t)1 << D) - 1) >> D) > (size_t)leaf_size) ++D;
-  if (D > kMaxDepth) D = kMaxDepth;
+  const int D = bvh_depth(n, leaf_size);
   *out_depth = D;
   const size_t n_nodes = (size_t)2 << D;
-  const double scale = std::max({(double)bb_hi[0] - bb_lo[0], (double)bb_hi[1] - bb_lo[1], (double)bb_hi[2] - bb_lo[2], 1e-3}) +
-                       std::max({std::fabs((double)bb_lo[0]), std::fabs((double)bb_hi[0]), std::fabs((double)bb_lo[1]),
-                                 std::fabs((double)bb_hi[1]), std::fabs((double)bb_lo[2]), std::fabs((double)bb_hi[2])});
+  const double scale = bvh_scale(bb_lo, bb_hi);
   unsigned long long *d_keys = nullptr, *d_keys2 = nullptr;
   uint32_t *d_order = nullptr, *d_order2 = nullptr, *d_mn = nullptr, *d_mx = nullptr;
   void *d_tmp = nullptr;
@@ -783,6 +845,26 @@ hipError_t build_bvh_device(hipStream_t stream, const float4 *d_src, const float
   for (void *p : {(void *)d_keys, (void *)d_keys2, (void *)d_order, (void *)d_order2, (void *)d_mn, (void *)d_mx, d_tmp, (void *)d_top})
     tmp_free(stream, p);
   return e;
+}
+
+hipError_t build_bvh_batch_device(ope_ctx *ctx, const BvhBatchTree *d_trees, size_t n_trees, int max_depth) {
+  if (n_trees == 0) return hipSuccess;
+  hipStream_t stream = ctx->stream;
+  {
+    KernelTimer kt(ctx, "bvh_batch_order_kernel", 0.0);
+    hipLaunchKernelGGL(bvh_batch_order_kernel, dim3((unsigned)n_trees), dim3(256), 0, stream, d_trees);
+  }
+  for (int level = 0; level <= max_depth; ++level) {
+    const dim3 grid(1u << level, (unsigned)n_trees);
+    KernelTimer kt(ctx, "bvh_batch_fit_kernel", 0.0);
+    hipLaunchKernelGGL(bvh_batch_fit_kernel<kFitBlock>, grid, dim3(kFitBlock), 0, stream, d_trees, level);
+    hipLaunchKernelGGL(bvh_batch_fit_kernel<64>, grid, dim3(64), 0, stream, d_trees, level);
+  }
+  {
+    KernelTimer kt(ctx, "bvh_batch_root_kernel", 0.0);
+    hipLaunchKernelGGL(bvh_batch_root_kernel, dim3((unsigned)n_trees), dim3(64), 0, stream, d_trees);
+  }
+  return hipGetLastError();
 }
 
 }  // namespace ope

@@ -24,31 +24,15 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "coarse_stages.hpp"
 #include "feature_math.hpp"
 
 namespace ope {
 
-constexpr int kCoarseBlock = 256;
 constexpr int kIdxBits = 17;        // original index < 65536 in 17 bits: no valid key has all its low bits set
 constexpr int kKeyBits = kIdxBits + 31;   // voxel < 2^31 (PCL's int leaf index): every valid key fits 48 bits
 constexpr int kListK = kKnnMaxK;    // register k-list length (k <= 32 is used)
 constexpr int kSpfhRow = 36;        // 33 bins padded, as in features.hip
-
-struct CoarseSeg {
-  CloudView c;
-  int min_b[3];
-  uint32_t div_x, div_xy;
-  float inv_leaf;
-};
-
-__device__ __forceinline__ uint32_t seg_of(const uint32_t *__restrict__ off, uint32_t nseg, uint32_t p) {
-  uint32_t lo = 0, hi = nseg;   // last segment whose start is <= p
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) / 2;
-    if (off[mid] <= p) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // 1a. key = voxel << 17 | original index (voxel_key_kernel per segment); non-finite points ~0, last in their segment
 __global__ __launch_bounds__(kCoarseBlock) void coarse_voxel_key_kernel(const CoarseSeg *__restrict__ segs, const uint32_t *__restrict__ off,
@@ -296,9 +280,7 @@ static int32_t orig_index(const float4 &q) {
   return i;
 }
 
-// distinct voxels of a cloud's finite points at `leaf` (= its uniform-sampling key points), counted on the host with the
-// device's arithmetic; -1 if PCL would refuse the leaf (the voxel index overflows an int)
-static long long host_key_count(const ope_cloud *c, float inv) {
+long long host_key_count(const ope_cloud *c, float inv) {
   if (c->n_valid == 0) return 0;
   long long min_b[3], div_b[3];
   for (int d = 0; d < 3; ++d) {
@@ -320,6 +302,77 @@ static long long host_key_count(const ope_cloud *c, float inv) {
   return (long long)(std::unique(v.begin(), v.end()) - v.begin());
 }
 
+hipError_t coarse_sample_segments(ope_ctx *ctx, CallTmp &tmp, const CoarseSeg *d_segs, const uint32_t *d_off, size_t nseg, uint32_t total,
+                                  float4 **d_kp_out, uint32_t **d_key_off_out, std::vector<uint32_t> &key_off, const char *&what,
+                                  const void *d_extra, void *h_extra, size_t extra_bytes) {
+  hipError_t e = hipSuccess;
+  what = "buffers";
+  const uint32_t nt1 = total + 1;
+  auto *d_keys = (unsigned long long *)tmp.get(8 * (size_t)nt1, e);
+  auto *d_keys2 = (unsigned long long *)tmp.get(8 * (size_t)nt1, e);
+  auto *d_vals = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
+  auto *d_vals2 = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
+  auto *d_win = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
+  auto *d_flags = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
+  auto *d_slot = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
+  auto *d_kp = (float4 *)tmp.get(16 * (size_t)nt1, e);
+  auto *d_key_off = (uint32_t *)tmp.get(4 * (nseg + 1), e);
+  if (e != hipSuccess) return e;
+  *d_kp_out = d_kp;
+  *d_key_off_out = d_key_off;
+  key_off.assign(nseg + 1, 0);
+  TraceRange r(ctx, "coarse_uniform_sampling");
+  what = "uniform sampling";
+  const unsigned nb = (unsigned)((std::max(total, (uint32_t)nseg) + kCoarseBlock) / kCoarseBlock);
+  size_t tb_sort = 0, tb_scan = 0;
+  e = rocprim::segmented_radix_sort_pairs(nullptr, tb_sort, d_keys, d_keys2, d_vals, d_vals2, total, (unsigned)nseg, d_off, d_off + 1, 0,
+                                          kKeyBits, ctx->stream);
+  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tb_scan, d_flags, d_slot, 0u, (size_t)nt1, rocprim::plus<uint32_t>(), ctx->stream);
+  size_t tb = std::max(tb_sort, tb_scan);
+  void *d_tmp = tmp.get(tb, e);
+  if (e != hipSuccess) return e;
+  {
+    KernelTimer kt(ctx, "coarse_voxel_key_kernel", 28.0 * total);
+    if (total) hipLaunchKernelGGL(coarse_voxel_key_kernel, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off, (uint32_t)nseg, total,
+                                  d_keys, d_vals);
+  }
+  what = "segmented sort";
+  if (total) e = rocprim::segmented_radix_sort_pairs(d_tmp, tb, d_keys, d_keys2, d_vals, d_vals2, total, (unsigned)nseg, d_off, d_off + 1, 0,
+                                                     kKeyBits, ctx->stream);
+  if (e != hipSuccess) return e;
+  {
+    KernelTimer kt(ctx, "coarse_voxel_pick_kernel", 40.0 * total);
+    hipLaunchKernelGGL(coarse_voxel_pick_kernel, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off, (uint32_t)nseg, total, d_keys2,
+                       d_vals2, d_win, d_flags);
+  }
+  what = "scan";
+  tb = std::max(tb_sort, tb_scan);
+  e = rocprim::exclusive_scan(d_tmp, tb, d_flags, d_slot, 0u, (size_t)nt1, rocprim::plus<uint32_t>(), ctx->stream);
+  if (e != hipSuccess) return e;
+  {
+    KernelTimer kt(ctx, "coarse_key_pack_kernel", 28.0 * total);
+    hipLaunchKernelGGL(coarse_key_pack_kernel, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off, (uint32_t)nseg, total, d_win,
+                       d_flags, d_slot, d_kp, d_key_off);
+  }
+  what = "uniform sampling";
+  e = hipMemcpyAsync(key_off.data(), d_key_off, 4 * (nseg + 1), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && extra_bytes) e = hipMemcpyAsync(h_extra, d_extra, extra_bytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  return e;
+}
+
+hipError_t coarse_normals_launch(ope_ctx *ctx, const float4 *d_kp, const uint32_t *d_key_off, const int2 *d_tiles, size_t n_tiles,
+                                 uint32_t nkeys, uint32_t max_keys, int k, const float vp[3], float4 *d_nrm) {
+  if (n_tiles == 0) return hipSuccess;
+  const size_t lds = 16 * (size_t)max_keys;
+  const hipError_t e = hipFuncSetAttribute((const void *)coarse_normals_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  KernelTimer kt(ctx, "coarse_normals_kernel", (double)nkeys * (12.0 + 12.0 * k + 16.0));
+  hipLaunchKernelGGL(coarse_normals_kernel, dim3((unsigned)n_tiles), dim3(kCoarseBlock), lds, ctx->stream, d_kp, d_key_off, d_tiles, k, vp[0],
+                     vp[1], vp[2], d_nrm);
+  return hipGetLastError();
+}
+
 }  // namespace ope
 
 using namespace ope;
@@ -337,6 +390,13 @@ void ope_coarse_default_params(ope_coarse_params *p) {
 
 int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                           const ope_coarse_params *params, const uint64_t *seeds, ope_coarse_batch_result *out) {
+  return coarse_pose_batch_impl(ctx, model, n, clusters, params, seeds, false, out, nullptr);
+}
+
+}  // extern "C"
+
+int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params *params,
+                                const uint64_t *seeds, bool seed_by_rank, ope_coarse_batch_result *out, uint64_t *seeds_used) {
   static const char *who = "ope_coarse_pose_batch: ";
   if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_coarse_pose_batch: bad argument");
   if (n == 0) return OPE_OK;
@@ -397,72 +457,23 @@ int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const 
   }
   const uint32_t total = off[nseg];
 
-  // every device buffer of the call; freed on every way out
-  struct Tmp {
-    hipStream_t st;
-    std::vector<void *> ps;
-    void *get(size_t bytes, hipError_t &e) {
-      void *q = nullptr;
-      if (e == hipSuccess) e = tmp_malloc(st, &q, bytes);
-      if (q) ps.push_back(q);
-      return q;
-    }
-    ~Tmp() { for (void *q : ps) tmp_free(st, q); }
-  } tmp{ctx->stream, {}};
+  CallTmp tmp{ctx->stream, {}};
   hipError_t e = hipSuccess;
   auto fail = [&](const char *what) { return set_err(ctx, OPE_EHIP, std::string(who) + what + ": " + hipGetErrorString(e)); };
-  const uint32_t nt1 = total + 1;
   auto *d_segs = (CoarseSeg *)tmp.get(sizeof(CoarseSeg) * nseg, e);
   auto *d_off = (uint32_t *)tmp.get(4 * (nseg + 1), e);
-  auto *d_keys = (unsigned long long *)tmp.get(8 * (size_t)nt1, e);
-  auto *d_keys2 = (unsigned long long *)tmp.get(8 * (size_t)nt1, e);
-  auto *d_vals = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
-  auto *d_vals2 = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
-  auto *d_win = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
-  auto *d_flags = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
-  auto *d_slot = (uint32_t *)tmp.get(4 * (size_t)nt1, e);
-  auto *d_kp = (float4 *)tmp.get(16 * (size_t)nt1, e);
-  auto *d_key_off = (uint32_t *)tmp.get(4 * (nseg + 1), e);
   if (e == hipSuccess) e = h2d_copy(ctx->stream, d_segs, segs.data(), sizeof(CoarseSeg) * nseg);
   if (e == hipSuccess) e = h2d_copy(ctx->stream, d_off, off.data(), 4 * (nseg + 1));
   if (e != hipSuccess) return fail("buffers");
 
   // ---- 1. uniform sampling of all segments
-  std::vector<uint32_t> key_off(nseg + 1, 0);
+  std::vector<uint32_t> key_off;
+  float4 *d_kp = nullptr;
+  uint32_t *d_key_off = nullptr;
   {
-    TraceRange r(ctx, "coarse_uniform_sampling");
-    const unsigned nb = (unsigned)((std::max(total, (uint32_t)nseg) + kCoarseBlock) / kCoarseBlock);
-    size_t tb_sort = 0, tb_scan = 0;
-    e = rocprim::segmented_radix_sort_pairs(nullptr, tb_sort, d_keys, d_keys2, d_vals, d_vals2, total, (unsigned)nseg, d_off, d_off + 1, 0,
-                                            kKeyBits, ctx->stream);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tb_scan, d_flags, d_slot, 0u, (size_t)nt1, rocprim::plus<uint32_t>(), ctx->stream);
-    size_t tb = std::max(tb_sort, tb_scan);
-    void *d_tmp = tmp.get(tb, e);
-    if (e != hipSuccess) return fail("uniform sampling");
-    {
-      KernelTimer kt(ctx, "coarse_voxel_key_kernel", 28.0 * total);
-      if (total) hipLaunchKernelGGL(coarse_voxel_key_kernel, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off, (uint32_t)nseg, total,
-                                    d_keys, d_vals);
-    }
-    if (total) e = rocprim::segmented_radix_sort_pairs(d_tmp, tb, d_keys, d_keys2, d_vals, d_vals2, total, (unsigned)nseg, d_off, d_off + 1, 0,
-                                                       kKeyBits, ctx->stream);
-    if (e != hipSuccess) return fail("segmented sort");
-    {
-      KernelTimer kt(ctx, "coarse_voxel_pick_kernel", 40.0 * total);
-      hipLaunchKernelGGL(coarse_voxel_pick_kernel, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off, (uint32_t)nseg, total, d_keys2,
-                         d_vals2, d_win, d_flags);
-    }
-    tb = std::max(tb_sort, tb_scan);
-    e = rocprim::exclusive_scan(d_tmp, tb, d_flags, d_slot, 0u, (size_t)nt1, rocprim::plus<uint32_t>(), ctx->stream);
-    if (e != hipSuccess) return fail("scan");
-    {
-      KernelTimer kt(ctx, "coarse_key_pack_kernel", 28.0 * total);
-      hipLaunchKernelGGL(coarse_key_pack_kernel, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off, (uint32_t)nseg, total, d_win,
-                         d_flags, d_slot, d_kp, d_key_off);
-    }
-    e = hipMemcpyAsync(key_off.data(), d_key_off, 4 * (nseg + 1), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail("uniform sampling");
+    const char *what = "";
+    e = coarse_sample_segments(ctx, tmp, d_segs, d_off, nseg, total, &d_kp, &d_key_off, key_off, what);
+    if (e != hipSuccess) return fail(what);
   }
   const uint32_t nkeys = key_off[nseg];
   uint32_t max_keys = 0;
@@ -485,16 +496,14 @@ int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const 
   const float r2 = p.fpfh_radius * p.fpfh_radius;
   if (!tiles.empty()) {
     const size_t lds1 = 16 * (size_t)max_keys, lds2 = 32 * (size_t)max_keys;
-    e = hipFuncSetAttribute((const void *)coarse_normals_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)coarse_spfh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+    e = hipFuncSetAttribute((const void *)coarse_spfh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)coarse_fpfh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
     if (e != hipSuccess) return fail("LDS size");
     const dim3 grid((unsigned)tiles.size());
     {
       TraceRange r(ctx, "coarse_normals");
-      KernelTimer kt(ctx, "coarse_normals_kernel", (double)nkeys * (12.0 + 12.0 * p.normals_k + 16.0));
-      hipLaunchKernelGGL(coarse_normals_kernel, grid, dim3(kCoarseBlock), lds1, ctx->stream, d_kp, d_key_off, d_tiles, p.normals_k,
-                         p.viewpoint[0], p.viewpoint[1], p.viewpoint[2], d_nrm);
+      e = coarse_normals_launch(ctx, d_kp, d_key_off, d_tiles, tiles.size(), nkeys, max_keys, p.normals_k, p.viewpoint, d_nrm);
+      if (e != hipSuccess) return fail("LDS size");
     }
     {
       TraceRange r(ctx, "coarse_fpfh");
@@ -527,6 +536,7 @@ int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const 
     o.n_src_keys = (int32_t)nsk;
     o.n_tgt_keys = (int32_t)(key_off[i + 2] - key_off[i + 1]);
     o.status = clusters[i]->n == 0 ? OPE_COARSE_EMPTY_TARGET : o.n_tgt_keys < 10 ? OPE_COARSE_FEW_TARGET_FEATURES : OPE_COARSE_OK;
+    if (seeds_used) seeds_used[i] = 0;
     if (o.status == OPE_COARSE_OK) { active.push_back(make_int2((int)(i + 1), 0)); active_cluster.push_back(i); }
   }
   const size_t na = active.size();
@@ -558,7 +568,8 @@ int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const 
   int max_uniq = 0;
   for (size_t a = 0; a < na; ++a) {
     const size_t i = active_cluster[a];
-    const uint64_t seed = seeds ? seeds[i] : p.sacia.seed + (uint64_t)i;
+    const uint64_t seed = seeds ? seeds[i] : p.sacia.seed + (uint64_t)(seed_by_rank ? a : i);
+    if (seeds_used) seeds_used[i] = seed;
     sacia_draws(model_xyz.data(), (int)nsk, S, K, H, p.sacia.min_sample_dist, seed, samp[a].data(), pick[a].data());
     for (int32_t s : samp[a]) slot[a].emplace(s, (int)slot[a].size());
     active[a].y = (int)slot[a].size();
@@ -630,6 +641,8 @@ int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const 
   }
   return OPE_OK;
 }
+
+extern "C" {
 
 int ope_coarse_batch_features(ope_ctx *ctx, int which, int32_t *key_idx, float *normals, float *fpfh33, size_t cap, size_t *n_out) {
   if (!ctx || !n_out) return set_err(ctx, OPE_EINVAL, "ope_coarse_batch_features: bad argument");

@@ -1,0 +1,68 @@
+// coarse_stages.hpp — the segmented stages of ope_coarse_pose_batch (coarse_batch.hip) that the batched final pose
+// (final_batch.hip) runs again on its fine clouds: uniform sampling of many clouds ("segments") in one pass and k-NN normals of
+// every segment's key points.  The kernels live in coarse_batch.hip; these are their host-side launchers.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "ope_internal.hpp"
+
+namespace ope {
+
+constexpr int kCoarseBlock = 256;
+
+// one segment of a segmented stage: its points (finite ones first, w = original index) and its voxel geometry at inv_leaf
+// (min_b / div as UniformSampling derives them from the cloud's bounding box)
+struct CoarseSeg {
+  CloudView c;
+  int min_b[3];
+  uint32_t div_x, div_xy;
+  float inv_leaf;
+};
+
+// the segment that holds point p of the packed points (off: nseg + 1 starts)
+__device__ __forceinline__ uint32_t seg_of(const uint32_t *__restrict__ off, uint32_t nseg, uint32_t p) {
+  uint32_t lo = 0, hi = nseg;   // last segment whose start is <= p
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) / 2;
+    if (off[mid] <= p) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// every device buffer of one call; freed on every way out
+struct CallTmp {
+  hipStream_t st;
+  std::vector<void *> ps;
+  void *get(size_t bytes, hipError_t &e) {
+    void *q = nullptr;
+    if (e == hipSuccess) e = tmp_malloc(st, &q, bytes);
+    if (q) ps.push_back(q);
+    return q;
+  }
+  ~CallTmp() { for (void *q : ps) tmp_free(st, q); }
+};
+
+// Uniform sampling of nseg segments (d_segs, d_off: nseg + 1 point offsets, total points): one segmented radix sort, PCL's
+// survivor rule per voxel run, one scan.  *d_kp (total + 1 float4): the key points packed by segment (w = original index);
+// *d_key_off (nseg + 1): first slot of every segment.  key_off receives *d_key_off on the host: the call's one
+// synchronisation (work enqueued before it on the stream is complete too); extra_bytes from d_extra (the caller's) come back to
+// h_extra in the same synchronisation.  On failure, `what` names the step.
+hipError_t coarse_sample_segments(ope_ctx *ctx, CallTmp &tmp, const CoarseSeg *d_segs, const uint32_t *d_off, size_t nseg, uint32_t total,
+                                  float4 **d_kp, uint32_t **d_key_off, std::vector<uint32_t> &key_off, const char *&what,
+                                  const void *d_extra = nullptr, void *h_extra = nullptr, size_t extra_bytes = 0);
+// NormalEstimation (k-NN, self included, viewpoint vp) of every key point against its own segment: one workgroup per tile
+// (segment, first query) of d_tiles; nkeys = all key points, max_keys = the most of one segment (the LDS it stages).
+hipError_t coarse_normals_launch(ope_ctx *ctx, const float4 *d_kp, const uint32_t *d_key_off, const int2 *d_tiles, size_t n_tiles,
+                                 uint32_t nkeys, uint32_t max_keys, int k, const float vp[3], float4 *d_nrm);
+// distinct voxels of a cloud's finite points at 1 / inv (= its uniform-sampling key points), counted on the host with the
+// device's arithmetic; -1 if PCL would refuse the leaf (the voxel index overflows an int)
+long long host_key_count(const ope_cloud *c, float inv);
+// ope_coarse_pose_batch.  seed_by_rank: without seeds, cluster i draws with sacia.seed + (clusters before i that reached SAC-IA)
+// instead of sacia.seed + i.  seeds_used (optional, n): the seed each cluster drew with, 0 for those that did not.
+int coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params *params,
+                           const uint64_t *seeds, bool seed_by_rank, ope_coarse_batch_result *out, uint64_t *seeds_used);
+
+}  // namespace ope

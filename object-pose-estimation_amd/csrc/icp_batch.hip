@@ -297,17 +297,9 @@ extern "C" int ope_icp_run_batch(ope_ctx *ctx, size_t n, const ope_cloud *const 
   ope_icp_params p;
   ope_icp_default_params(&p);
   if (params) p = *params;
-  if (ctx->nccl_comm != nullptr || ctx->p2p_ok || ctx->p2p_broken)
-    return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: not on a context with a communicator (batched problems are not sharded)");
-  if (p.use_reciprocal) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: reciprocal correspondences are not supported");
-  if (p.estimator == OPE_EST_POINT_TO_PLANE_LM) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: the LM estimator is not supported");
-  if (p.estimator != OPE_EST_SVD && p.estimator != OPE_EST_POINT_TO_PLANE_LLS) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: unknown estimator");
-  if (p.corr_mode != OPE_CORR_NEAREST && p.corr_mode != OPE_CORR_NORMAL_SHOOTING) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: unknown corr_mode");
-  if (p.corr_mode == OPE_CORR_NORMAL_SHOOTING && (p.k_normal_shooting < 1 || p.k_normal_shooting > 32))
-    return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: 1 <= k_normal_shooting <= 32");
+  { const int rc = icp_batch_check_params(ctx, p); if (rc != OPE_OK) return rc; }
   const bool need_src_nrm = p.corr_mode == OPE_CORR_NORMAL_SHOOTING || p.use_surface_normal_rej || p.use_self_occluded_rej;
   const bool p2p = p.estimator == OPE_EST_POINT_TO_PLANE_LLS;
-  size_t n_hints = 0;
   for (size_t i = 0; i < n; ++i) {
     const std::string at = " (problem " + std::to_string(i) + ")";
     if (!src[i]) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: no source cloud" + at);
@@ -319,8 +311,31 @@ extern "C" int ope_icp_run_batch(ope_ctx *ctx, size_t n, const ope_cloud *const 
       return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: more than 65536 valid source points (use ope_icp_run)" + at);
     if (ctx->n_fixed > 0 && ctx->fixed_src == src[i])
       return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: fixed correspondences are set for this source cloud" + at);
-    n_hints += src[i]->n_valid;
   }
+  return icp_batch_core(ctx, n, src, tgt, guesses, p, fitness_max_range, out);
+}
+
+int ope::icp_batch_check_params(ope_ctx *ctx, const ope_icp_params &p) {
+  if (ctx->nccl_comm != nullptr || ctx->p2p_ok || ctx->p2p_broken)
+    return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: not on a context with a communicator (batched problems are not sharded)");
+  if (p.use_reciprocal) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: reciprocal correspondences are not supported");
+  if (p.estimator == OPE_EST_POINT_TO_PLANE_LM) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: the LM estimator is not supported");
+  if (p.estimator != OPE_EST_SVD && p.estimator != OPE_EST_POINT_TO_PLANE_LLS) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: unknown estimator");
+  if (p.corr_mode != OPE_CORR_NEAREST && p.corr_mode != OPE_CORR_NORMAL_SHOOTING) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: unknown corr_mode");
+  if (p.corr_mode == OPE_CORR_NORMAL_SHOOTING && (p.k_normal_shooting < 1 || p.k_normal_shooting > 32))
+    return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: 1 <= k_normal_shooting <= 32");
+  return OPE_OK;
+}
+
+// problems that passed ope_icp_run_batch's checks: ope_icp_run_batch and ope_final_pose_batch (its fine stage, on clouds and trees
+// that live in that call's buffers)
+int ope::icp_batch_core(ope_ctx *ctx, size_t n, const ope_cloud *const *src, const ope_index *const *tgt, const float *guesses,
+                        const ope_icp_params &p, double fitness_max_range, ope_icp_batch_result *out) {
+  if (n == 0) return OPE_OK;
+  const bool need_src_nrm = p.corr_mode == OPE_CORR_NORMAL_SHOOTING || p.use_surface_normal_rej || p.use_self_occluded_rej;
+  const bool p2p = p.estimator == OPE_EST_POINT_TO_PLANE_LLS;
+  size_t n_hints = 0;
+  for (size_t i = 0; i < n; ++i) n_hints += src[i]->n_valid;
   OPE_HIP(ctx, hipSetDevice(ctx->device));
 
   // one temporary block: [problems | states | results | start leaves]; the first two go up in one copy

@@ -269,6 +269,10 @@ struct ope_ctx {
   // key points (original indices), normals (x y z) and FPFH rows, packed by segment from coarse_key_off
   std::vector<int32_t> coarse_key_off, coarse_key_idx;
   std::vector<float> coarse_nrm, coarse_fpfh;
+  // the fine inputs of the last ope_final_pose_batch (ope_final_batch_inputs): cloud 2i the source of cluster i, 2i + 1 its
+  // target; xyz and normals (x y z), packed by cloud from final_off
+  std::vector<uint32_t> final_off;
+  std::vector<float> final_xyz, final_nrm;
 
   bool tracing = false;   // roctx ranges around the host side of the path (ope_ctx_set_tracing)
 
@@ -558,6 +562,22 @@ void build_bvh_host(const float *xyz, const int32_t *ids, const float *nrm, size
 // api.hip: ope_index_build's body; temporary = the index lives inside one entry point and its buffers come from (and go back to) the
 // stream's cache of temporaries instead of hipMalloc / hipFree
 int index_build_impl(ope_ctx *ctx, const ope_cloud *target, const ope_index_params *params, bool temporary, ope_index **out);
+// bvh_build_device.hip: the depth and the margin scale build_bvh_device gives a cloud of n points with this bounding box; the
+// trees of many small clouds (at most OPE_COARSE_MAX_KEYS points each) built at once, each exactly as build_bvh_device builds it
+int bvh_depth(size_t n, int leaf_size);
+double bvh_scale(const float bb_lo[3], const float bb_hi[3]);
+struct BvhBatchTree {
+  const float4 *src, *src_nrm;   // n finite points (w = original index) and their normals (or NULL)
+  uint32_t n;
+  int D;                         // bvh_depth(n, leaf size)
+  double scale;                  // bvh_scale of the cloud's bounding box
+  float4 *nodes, *pts, *nrm, *axis2;   // (2 << D) * 3, n (+ kPtsPad, zeroed by the caller), n, 2 << D
+};
+hipError_t build_bvh_batch_device(ope_ctx *ctx, const BvhBatchTree *d_trees, size_t n_trees, int max_depth);
+// icp_batch.hip: the parameter checks of ope_icp_run_batch, and its run once every problem has been checked
+int icp_batch_check_params(ope_ctx *ctx, const ope_icp_params &p);
+int icp_batch_core(ope_ctx *ctx, size_t n, const ope_cloud *const *src, const ope_index *const *tgt, const float *guesses,
+                   const ope_icp_params &p, double fitness_max_range, ope_icp_batch_result *out);
 // api.hip: the device state a run starts from, as ope_icp_begin fills it (thresholds per quirk Q1, the target index's pivot,
 // prev_mse, the inverse of the guess, the skip-certificate trigger) — one fill for ope_icp_begin and every problem of
 // ope_icp_run_batch.  guess: column-major, null = identity.  cert_run: the run may keep skip certificates; cluttered: it starts on

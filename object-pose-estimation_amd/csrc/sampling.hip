@@ -18,6 +18,7 @@
 #include <cmath>
 #include <vector>
 
+#include "morton.hpp"
 #include "ope_internal.hpp"
 
 namespace ope {
@@ -359,28 +360,11 @@ void fill_iota(hipStream_t stream, uint32_t *v, uint32_t n) {
 // float4 {x, y, z, input index}.  Keys are unique, so the order equals a host std::sort of the same keys.
 namespace ope {
 
-__device__ __forceinline__ uint32_t expand_bits10_dev(uint32_t v) {
-  v = (v * 0x00010001u) & 0xFF0000FFu;
-  v = (v * 0x00000101u) & 0x0F00F00Fu;
-  v = (v * 0x00000011u) & 0xC30C30C3u;
-  v = (v * 0x00000005u) & 0x49249249u;
-  return v;
-}
-
 __global__ __launch_bounds__(256) void morton_key_kernel(const float *__restrict__ raw, uint32_t n, float lox, float loy, float loz,
                                                           float ivx, float ivy, float ivz, uint32_t *__restrict__ keys, uint32_t *__restrict__ vals) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float x = raw[3 * (size_t)i], y = raw[3 * (size_t)i + 1], z = raw[3 * (size_t)i + 2];
-  uint32_t code;
-  if (!(isfinite(x) && isfinite(y) && isfinite(z))) code = 1u << 30;
-  else {
-    const uint32_t qx = min(1023u, (uint32_t)fmaxf(0.f, __fmul_rn(__fsub_rn(x, lox), ivx)));
-    const uint32_t qy = min(1023u, (uint32_t)fmaxf(0.f, __fmul_rn(__fsub_rn(y, loy), ivy)));
-    const uint32_t qz = min(1023u, (uint32_t)fmaxf(0.f, __fmul_rn(__fsub_rn(z, loz), ivz)));
-    code = expand_bits10_dev(qx) | (expand_bits10_dev(qy) << 1) | (expand_bits10_dev(qz) << 2);
-  }
-  keys[i] = code;
+  keys[i] = morton_code_dev(raw[3 * (size_t)i], raw[3 * (size_t)i + 1], raw[3 * (size_t)i + 2], lox, loy, loz, ivx, ivy, ivz);
   vals[i] = i;
 }
 
