@@ -22,7 +22,6 @@ void plan_heavy(hipStream_t, const uint32_t *, uint32_t, float, float, uint32_t,
 void plan_slots(hipStream_t, const uint32_t *, uint32_t, const uint32_t *, uint32_t *);
 int icp_accumulate_blocks_per_cu(bool, bool, bool);
 int icp_accumulate_cert_blocks_per_cu(bool, bool, bool);
-extern bool g_plan_no_alone;
 int chunk_plan(hipStream_t, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *, uint32_t, void *, size_t &);
 void fill_iota(hipStream_t, uint32_t *, uint32_t);
 hipError_t morton_order_device(hipStream_t, const float *, size_t, const float[3], const float[3], float4 *, int32_t *);
@@ -65,15 +64,6 @@ constexpr double kGridMaxTreeShare = 0.03, kGridMinTreeShare = 0.015;
 constexpr size_t kGridMinQueries = 0;
 constexpr float kHeavyLoadFactor = 1.5f;   // launches that fill the GPU: group walks for chunks beyond this multiple of a wave's fair share (C3, slots listed by duration: 1.0 183 us, 1.2 166, 1.45 153, 1.7 157; without the list 1.45 was 174)
 constexpr float kHeavyMaxChunksPerWave = 1.8f;   // beyond this the launch is throughput-bound: no 8-lane group walks
-
-// Developer A/B switches and sweeps (tools/*.py) read the environment only in builds made with -DOPE_DEVELOPER
-// (`make DEVELOPER=1`); the product library's launch path depends on one environment variable only (ROCPROF_COUNTER_COLLECTION,
-// ope_ctx_create: a counter-collecting profiler serialises dispatches, so updates are launched in line).
-#ifdef OPE_DEVELOPER
-static const char *dev_env(const char *name) { return getenv(name); }
-#else
-static const char *dev_env(const char *) { return nullptr; }
-#endif
 
 int set_err(ope_ctx *ctx, int code, const std::string &msg) {
   if (ctx) ctx->err = msg;
@@ -154,12 +144,6 @@ static int grid_probe_issue(ope_ctx *ctx, hipStream_t stream = nullptr) {
   ctx->grid_probe_pending = true;
   return OPE_OK;
 }
-static float heavy_load_factor() {
-  static const bool once = [] { g_plan_no_alone = dev_env("OPE_NO_ALONE") != nullptr; return true; }();  // developer A/B switch
-  (void)once;
-  static const float f = [] { const char *e = dev_env("OPE_HEAVY_LOAD"); return e ? (float)atof(e) : kHeavyLoadFactor; }();  // developer sweep
-  return f;
-}
 // returns +1: switch to the grid kernel, -1: switch to the tree kernel, 0: stay
 static int grid_probe_poll(ope_ctx *ctx, int it_done) {
   if (!ctx->grid_probe_pending) return 0;
@@ -171,9 +155,6 @@ static int grid_probe_poll(ope_ctx *ctx, int it_done) {
   ctx->grid_probe_pending = false;
   const uint32_t n_far = *ctx->h_grid_probe;
   const double share = (double)n_far / (double)std::max<size_t>(ctx->run_src->n_valid, 1);
-  if (dev_env("OPE_TRACE_GRID"))
-    fprintf(stderr, "[ope] launch %d (%s kernel): %u of %zu queries beyond one cell of the target (share %.4f)\n", it_done,
-            ctx->use_grid ? "grid" : "tree", n_far, ctx->run_src->n_valid, share);
   if (ctx->use_grid && share > kGridMaxTreeShare) return -1;
   if (!ctx->use_grid && share < kGridMinTreeShare) return +1;
   return 0;
@@ -221,29 +202,33 @@ static void pace_wait(ope_ctx *ctx) {
   }
 }
 
+// Plan steps re-sort the chunks by the cost they measured: after launches 1, 2, 4, ..., 32, then every 32, and after the launch
+// a kernel switch names (force_plan_at).  Each follows a measuring launch, which runs without group walks and is ~40 us slower:
+// more frequent plans cost more than they gain.
+constexpr int kPlanPeriod = 32;
+static bool plan_step_after(const ope_ctx *ctx, int launch) {
+  return ((launch & (launch - 1)) == 0 && launch <= kPlanPeriod) || launch % kPlanPeriod == 0 || launch == ctx->force_plan_at;
+}
+
 static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
   pace_wait(ctx);
   if (ctx->cert_run && !ctx->cert_seen && ctx->h_pace != nullptr && *(volatile uint32_t *)(ctx->h_pace + 1) != 0u) ctx->cert_seen = true;
-  // re-sort the chunks by the cost they measured: after launches 1, 2, 4, ..., 32 and then every 32
-  static const bool no_plan_env = dev_env("OPE_NO_PLAN") != nullptr;  // developer A/B switch
   const int it_done = ctx->acc_launches++;
   const uint32_t nch = (uint32_t)((ctx->run_src->n_valid + 63) / 64);
   // (a k-NN launch with dozens of chunks per resident wave is bound by throughput, its tail is one chunk of forty: the cost-sorted
   // order buys nothing there and its sorts queue up behind the launch — BuildModel's loop, 20 views of 500 k points: 1.50 s with plans,
   // 1.46-1.47 s without)
-  const bool no_plan = no_plan_env || ctx->run_params.deterministic_sums != 0 ||
-                       (ctx->run_params.corr_mode == OPE_CORR_NORMAL_SHOOTING && nch > 8u * (uint32_t)ctx->n_cu * 4u * 4u && !dev_env("OPE_NS_PLAN_ALWAYS"));
+  const bool no_plan = ctx->run_params.deterministic_sums != 0 ||
+                       (ctx->run_params.corr_mode == OPE_CORR_NORMAL_SHOOTING && nch > 8u * (uint32_t)ctx->n_cu * 4u * 4u);
   // Chunk costs are double-buffered by launch parity: launch L writes half L & 1, and a plan made beside launch L (on the side
   // stream) reads the half launch L - 1 wrote — the measuring launch in front of every plan, in which every chunk reports.
   // Launch L + 1, which writes that half again, waits for the plan first (ev_plan_done).  (Round 3 copied the one buffer on the
   // side stream while launch L was rewriting it: the snapshot mixed two launches' costs.)
   uint32_t *const cost_w = ctx->d_chunk_cost + (size_t)(it_done & 1) * ctx->chunk_cap;
   const uint32_t *const cost_r = ctx->d_chunk_cost + (size_t)((it_done + 1) & 1) * ctx->chunk_cap;
-  static const int plan_every = [] { const char *e = dev_env("OPE_PLAN_EVERY"); return e ? std::max(1, atoi(e)) : 32; }();  // developer sweep
   {
     // the launch before a plan step measures: no 8-lane group walks (their chunks would keep the cost of the last
     // per-lane walk they had, however old), flagged to the kernels through plan_info[4]
-    const int nx = it_done + 1;
     // (round 3: letting a group-walked chunk report an estimate of its per-lane cost instead — the duration of one of its
     // slots over kOctSlotShare — did away with these launches and with a good schedule: steady state 172-186 us against
     // 152-157; a slot lasts 51-60 us whatever its chunk costs per lane.  Measured, not kept.)
@@ -252,16 +237,15 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
     // (round 4, with the costs double-buffered: a plan after EVERY launch of 5..16, 8..16 or 8..32 — the launches that creep from
     // 150 to 175 us behind a plan then stay at 160-168: kernel 163-167 us against 161-165, value 5 250-5 590 against 5 700-5 810.  The
     // plan is at its best right behind a measuring launch, whose costs are the only complete ones; plan period 6/8/12/16/24: 32 stays best)
-    const bool measuring = !no_plan && nch > 1 && ((((nx & (nx - 1)) == 0 && nx <= plan_every) || nx % plan_every == 0 || nx == ctx->force_plan_at));
+    const bool measuring = !no_plan && nch > 1 && plan_step_after(ctx, it_done + 1);
     ctx->measuring_flag = measuring;   // handed to the launch as a kernel argument (round 2 kept it in device memory: two memset dispatches per plan step on the critical path)
   }
   if (ctx->use_grid) {
-    // GRID instantiation (1-NN, no reciprocal check, device-built index).  Plan steps at the same launches as below;
+    // GRID instantiation (1-NN, no reciprocal check, device-built index).  Plan steps at the tree kernel's (plan_step_after);
     // the query order is re-partitioned by class at launches 1, 2, 4 and then with every plan step.
     const ope_icp_params &p = ctx->run_params;
     const bool nrm = p.use_surface_normal_rej || p.use_self_occluded_rej || p.estimator == OPE_EST_POINT_TO_PLANE_LLS;
-    const bool plan_step = !no_plan && nch > 1 && it_done >= 1 &&
-                           (((it_done & (it_done - 1)) == 0 && it_done <= plan_every) || it_done % plan_every == 0 || it_done == ctx->force_plan_at);
+    const bool plan_step = !no_plan && nch > 1 && it_done >= 1 && plan_step_after(ctx, it_done);
     if (grid_probe_poll(ctx, it_done) < 0) {
       const int rcs = switch_kernel(ctx, false, it_done, nch);
       if (rcs != OPE_OK) return rcs;
@@ -269,11 +253,10 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
       return enqueue_accumulate(ctx, atomic_sums);
     }
     if (plan_step) {
-      static const float heavy_env = [] { const char *e = dev_env("OPE_HEAVY_FACTOR"); return e ? (float)atof(e) : -1.0f; }();
-      const bool repart = it_done <= 4 || it_done % plan_every == 0 || it_done == ctx->force_plan_at;
+      const bool repart = it_done <= 4 || it_done % kPlanPeriod == 0 || it_done == ctx->force_plan_at;
       if (grid_plan(ctx->stream, repart, ctx->d_qclass, (uint32_t)ctx->run_src->n_valid, ctx->d_qorder, ctx->d_work_counter + 8, cost_r,
                     ctx->d_chunk_keys, ctx->d_chunk_cost_sorted, ctx->d_chunk_ids, ctx->d_chunk_order, nch,
-                    (uint32_t)ctx->acc_blocks * (kAccBlock / 64), heavy_env, heavy_load_factor(), ctx->d_part_tmp, ctx->part_tmp_bytes) != 0)
+                    (uint32_t)ctx->acc_blocks * (kAccBlock / 64), -1.0f /* no factor override */, kHeavyLoadFactor, ctx->d_part_tmp, ctx->part_tmp_bytes) != 0)
         return set_err(ctx, OPE_EHIP, "grid plan step failed");
       ctx->plan_valid = true;
       if (it_done == 1 || it_done >= 8) {   // after launch 0 (decided before launch 2, see grid_probe_poll), then with the later plans
@@ -312,35 +295,25 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
     ctx->plan_valid = true;
     ctx->plan_pending = false;
   }
-  static const bool plan_sync_env = dev_env("OPE_PLAN_SYNC") != nullptr;     // developer A/B: the plan between two launches, as in round 2
-  // plan steps: after launches 1, 2, 4, ..., 32 and then every 32 (each follows a measuring launch, which runs without group
-  // walks and is ~40 us slower: more frequent plans cost more than they gain)
-  const bool plan_step = !no_plan && nch > 1 && it_done >= 1 &&
-                         (((it_done & (it_done - 1)) == 0 && it_done <= plan_every) || it_done % plan_every == 0 || it_done == ctx->force_plan_at);
+  const bool plan_step = !no_plan && nch > 1 && it_done >= 1 && plan_step_after(ctx, it_done);
   if (plan_step) {
     // Chunks costlier than `factor` x the median chunk are walked by 8-lane groups: a third of the dependent trips for
     // ~2.7x the lane-cycles.  That trade pays while the launch is bound by its slowest wave, i.e. while there are few
     // chunks per resident wave; once the waves are busy for several rounds the extra lane-cycles only lengthen the launch.
-    // Measured (tools/heavy_sweep4.py, model 100 k, steady state, kernel us at factor none / 2 / 3 / 5):
+    // Measured (model 100 k, steady state, kernel us at factor none / 2 / 3 / 5):
     //   0.25 chunks per wave (C2)  98 / 62 / 62 / 80      0.3 (a 1/8 shard) 130 / 70 / 69 / 100      0.6  154 / 79 / 99 / 139
     //   1.3 (500 k queries)       168 / 138 / 132 / 156   2.5 (C3)          177 / 261 / 232 / 254  <- none is best
-    static const float heavy_env = [] { const char *e = dev_env("OPE_HEAVY_FACTOR"); return e ? (float)atof(e) : -1.0f; }();
     const float chunks_per_wave = (float)nch / (float)(ctx->n_cu * 4 * kAccWavesPerSimd);
-    const float heavy_factor = heavy_env >= 0.f ? heavy_env
-                               : (chunks_per_wave > kHeavyMaxChunksPerWave ? 0.0f : std::min(7.0f, std::max(2.0f, 1.2f + 1.5f * chunks_per_wave)));
-    const float load_factor = (heavy_env < 0.f && chunks_per_wave > kHeavyMaxChunksPerWave) ? heavy_load_factor() : 0.0f;
+    const float heavy_factor = chunks_per_wave > kHeavyMaxChunksPerWave ? 0.0f : std::min(7.0f, std::max(2.0f, 1.2f + 1.5f * chunks_per_wave));
+    const float load_factor = chunks_per_wave > kHeavyMaxChunksPerWave ? kHeavyLoadFactor : 0.0f;
     // (a one-launch plan — costs bucketed at 16 per octave, counting sort, same rules on the buckets — took 2.5 us per
     // iteration off the driver's twenty-step window and put 5-9 us on its search kernel: the coarser order is the worse
     // schedule while the costs still move; a one-block rocprim::block_radix_sort of the 15 625 keys took 63 us on its single
     // CU: both measured in round 2, not kept)
-    const bool async = !plan_sync_env;
-    hipStream_t ps = async ? ctx->plan_stream : ctx->stream;
+    hipStream_t ps = ctx->plan_stream;
     const int nxt = ctx->plan_cur ^ 1;
-    const uint32_t *costs = cost_r;
-    if (async) {
-      OPE_HIP(ctx, hipEventRecord(ctx->ev_acc_done, ctx->stream));       // every launch before this one has finished ...
-      OPE_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_acc_done, 0));         // ... before their costs are read (this launch writes the other half)
-    }
+    OPE_HIP(ctx, hipEventRecord(ctx->ev_acc_done, ctx->stream));       // every launch before this one has finished ...
+    OPE_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_acc_done, 0));         // ... before their costs are read (this launch writes the other half)
     // the count of far queries that may move the run back to the grid kernel rides on the same side stream (three dispatches
     // off the launch stream; it reads the distances while this launch rewrites them: a count of two consecutive launches'
     // values, for a decision that is polled without waiting anyway)
@@ -349,22 +322,15 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
       if (rcp != OPE_OK) return rcp;
     }
     size_t tb = ctx->plan_tmp_bytes;
-    if (chunk_plan(ps, costs, ctx->d_plan_sorted[nxt], ctx->d_chunk_ids, ctx->d_plan_order[nxt], nch, ctx->d_plan_tmp, tb) != 0)
+    if (chunk_plan(ps, cost_r, ctx->d_plan_sorted[nxt], ctx->d_chunk_ids, ctx->d_plan_order[nxt], nch, ctx->d_plan_tmp, tb) != 0)
       return set_err(ctx, OPE_EHIP, "chunk plan sort failed");
     uint32_t *out = ctx->d_plan_out + 8 * nxt;
     plan_heavy(ps, ctx->d_plan_sorted[nxt], nch, heavy_factor, load_factor, (uint32_t)ctx->acc_blocks * (kAccBlock / 64), out);
-    static const bool no_slot_list = dev_env("OPE_NO_SLOT_LIST") != nullptr;  // developer A/B switch
-    const bool slots = !no_slot_list && ctx->run_params.corr_mode == OPE_CORR_NEAREST && !ctx->run_params.use_reciprocal;
+    const bool slots = ctx->run_params.corr_mode == OPE_CORR_NEAREST && !ctx->run_params.use_reciprocal;
     if (slots) plan_slots(ps, ctx->d_plan_sorted[nxt], nch, out, ctx->d_plan_slots[nxt]);
-    if (async) {
-      OPE_HIP(ctx, hipEventRecord(ctx->ev_plan_done, ps));
-      ctx->plan_pending = true;
-      ctx->plan_pending_slots = slots;
-    } else {
-      ctx->plan_cur = nxt;
-      ctx->plan_cur_slots = slots;
-      ctx->plan_valid = true;
-    }
+    OPE_HIP(ctx, hipEventRecord(ctx->ev_plan_done, ps));
+    ctx->plan_pending = true;
+    ctx->plan_pending_slots = slots;
   }
   const ope_icp_params &p = ctx->run_params;
   const bool nrm = p.corr_mode == OPE_CORR_NORMAL_SHOOTING || p.use_surface_normal_rej || p.use_self_occluded_rej ||
@@ -373,11 +339,9 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
   const bool recip = p.use_reciprocal != 0;
   // packet walks for coherent chunks pay off when the launch fills the GPU (C3: 195 -> 184 us); on an underfilled
   // one (a 1/8 shard, C2) the longer dependent chain of a packet costs more than its gathers save (77 -> 88 us)
-  static const bool no_packet = dev_env("OPE_NO_PACKET") != nullptr;  // developer A/B switch
-  static const int packet_min_env = [] { const char *e = dev_env("OPE_PACKET_MIN_CHUNKS"); return e ? atoi(e) : -1; }();  // developer sweep
-  const uint32_t packet_min = packet_min_env >= 0 ? (uint32_t)packet_min_env : (uint32_t)ctx->n_cu * 4u * (uint32_t)kAccWavesPerSimd;
+  const uint32_t packet_min = (uint32_t)ctx->n_cu * 4u * (uint32_t)kAccWavesPerSimd;   // one chunk per resident wave
   const bool packet = p.tree_walk == OPE_WALK_PACKET ? (ctx->run_tgt->d_axis2 != nullptr && p.corr_mode == OPE_CORR_NEAREST && !recip)
-                      : p.tree_walk == OPE_WALK_LANE ? false : (!no_packet && nch > packet_min);
+                      : p.tree_walk == OPE_WALK_LANE ? false : nch > packet_min;
   ++ctx->kernel_launches[p.corr_mode != OPE_CORR_NEAREST ? OPE_KERNEL_KNN : (packet && !recip) ? OPE_KERNEL_TREE_PACKET : OPE_KERNEL_TREE_LANE];
   const bool certify = ctx->cert_run && ctx->cert_seen && p.corr_mode == OPE_CORR_NEAREST && !recip;
   const int blocks = certify ? std::min(ctx->acc_blocks, ctx->acc_blocks_cert) : ctx->acc_blocks;   // (the certifying instantiation holds fewer blocks per CU)
@@ -386,7 +350,7 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
                         recip ? ctx->run_src_index->view() : ctx->run_tgt->view(), ctx->d_state, ctx->d_partials, ctx->d_corr_match, ctx->d_corr_d2, ctx->d_work_counter, ctx->d_hint,
                         ctx->plan_valid ? ctx->d_plan_order[ctx->plan_cur] : nullptr, cost_w, ctx->d_work_counter + 8, packet, p.k_normal_shooting, atomic_sums ? sums_ptr(ctx) : nullptr,
                         (ctx->plan_valid && ctx->plan_cur_slots) ? ctx->d_plan_slots[ctx->plan_cur] : nullptr,
-                        (p.corr_mode == OPE_CORR_NORMAL_SHOOTING && !dev_env("OPE_NO_KNN_BOUND")) ? ctx->d_knn_rk : nullptr, ctx->d_plan_out + 8 * ctx->plan_cur,
+                        p.corr_mode == OPE_CORR_NORMAL_SHOOTING ? ctx->d_knn_rk : nullptr, ctx->d_plan_out + 8 * ctx->plan_cur,
                         timed ? ctx->prof_events[2 * ctx->prof_used] : nullptr, timed ? ctx->prof_events[2 * ctx->prof_used + 1] : nullptr,
                         ctx->measuring_flag, ctx->chain_on ? chain_ptr(ctx) : nullptr, ctx->chain_seq, certify ? ctx->d_cert_q : nullptr, ctx->d_cert_pos, ctx->d_pace, ++ctx->launch_no, ctx->wait_ticks, ctx->d_cert_l);
   if (timed) ++ctx->prof_used;
@@ -442,7 +406,7 @@ int ope_ctx_create(ope_ctx **out, int device_ordinal) {
   // A profiler that collects hardware counters serialises dispatches (rocprofv3 --pmc sets ROCPROF_COUNTER_COLLECTION), and a
   // serialised update launch would wait its 2 s for an accumulate launch that cannot start beside it: such processes launch their
   // updates in line from the start.  The one environment variable the product library looks at.
-  if (const char *e = getenv("ROCPROF_COUNTER_COLLECTION"); e != nullptr && *e != 0 && *e != '0' && !dev_env("OPE_CHAIN_UNDER_COUNTERS")) ctx->chain_broken = true;
+  if (const char *e = getenv("ROCPROF_COUNTER_COLLECTION"); e != nullptr && *e != 0 && *e != '0') ctx->chain_broken = true;
   if (hipMalloc(&ctx->d_state, sizeof(IcpState)) != hipSuccess ||
       hipMalloc(&ctx->d_partials, sizeof(double) * kNumSumsMax * kAccMaxBlocks) != hipSuccess ||
       hipMalloc((void **)&ctx->d_work_counter, 256) != hipSuccess ||
@@ -636,7 +600,6 @@ int ope_cloud_upload(ope_ctx *ctx, const void *base, size_t n, size_t stride_byt
     return set_err(ctx, OPE_EHIP, std::string("ope_cloud_upload: ") + hipGetErrorString(e));
   }
   *out = c;
-  OPE_DUMP_HASH("cloud_upload xyzw", c->d_xyzw, 16 * n, true);
   if (normal_off >= 0) {
     std::vector<float> nrm(n * 3);
     for (size_t i = 0; i < n; ++i) std::memcpy(&nrm[3 * i], b + i * stride_bytes + (size_t)normal_off, 12);
@@ -770,80 +733,28 @@ int ope::index_build_impl(ope_ctx *ctx, const ope_cloud *target, const ope_index
   ope_index_default_params(&dp);
   if (params) dp = *params;
   const size_t n = target->n_valid;
-  static const bool host_build = dev_env("OPE_HOST_BUILD") != nullptr;  // developer A/B switch: the host reference builder
-  if (host_build) { const int rch = target->ensure_host(); if (rch != OPE_OK) return rch; }
-  if (!host_build) {
-    // the finite points are the first n_valid records of the Morton-sorted device copy (w = original index)
-    ope_index *ix = new ope_index();
-    ix->ctx = ctx;
-    ix->n = n;
-    ix->n_total = target->n;
-    std::memcpy(ix->bb_lo, target->bb_lo, sizeof ix->bb_lo);
-    std::memcpy(ix->bb_hi, target->bb_hi, sizeof ix->bb_hi);
-    for (int d = 0; d < 3; ++d) ix->pivot[d] = 0.5 * ((double)target->bb_lo[d] + (double)target->bb_hi[d]);
-    if (dev_env("OPE_NO_TMP_INDEX")) temporary = false;   // developer A/B switch
-    ix->tmp_alloc = temporary;
-    ix->alloc_stream = ctx->stream;
-    const hipError_t e = build_bvh_device(ctx->stream, target->d_xyzw, target->d_nrm, n, dp.leaf_size, target->bb_lo, target->bb_hi,
-                                          &ix->depth, &ix->d_nodes, &ix->d_pts, &ix->d_nrm, &ix->d_axis2, temporary);
-    if (e != hipSuccess) {
-      ope_index_free(ix);
-      return set_err(ctx, OPE_EHIP, std::string("ope_index_build: ") + hipGetErrorString(e));
-    }
-    // the bucketed side of the index (grid_build.hip) is built by the first 1-NN ICP run that uses this index: the
-    // indexes behind normals, FPFH and the filters never need it
-    ix->want_grid = dp.grid != 0;
-    ix->grid_mode = dp.grid;
-    ix->grid_fill = dp.grid_fill;
-    ix->grid_max_cells = dp.grid_max_cells;
-    OPE_DUMP_HASH("index_build nodes", ix->d_nodes, 48 * ((size_t)2 << ix->depth), true);
-    OPE_DUMP_HASH("index_build pts", ix->d_pts, 16 * ix->n, true);
-    *out = ix;
-    return OPE_OK;
-  }
-  std::vector<float> xyz(n * 3), nrm;
-  std::vector<int32_t> ids(n);
-  size_t m = 0;
-  for (size_t i = 0; i < target->n; ++i) {
-    const float *p = &target->h_xyz[3 * i];
-    if (!finite3(p)) continue;
-    xyz[3 * m] = p[0]; xyz[3 * m + 1] = p[1]; xyz[3 * m + 2] = p[2];
-    ids[m++] = (int32_t)i;
-  }
-  if (target->d_nrm) {
-    // fetch normals back in original order
-    std::vector<float> packed(target->n * 4);
-    OPE_HIP(ctx, hipMemcpy(packed.data(), target->d_nrm, sizeof(float4) * target->n, hipMemcpyDeviceToHost));
-    std::vector<float> orig(target->n * 3);
-    for (size_t i = 0; i < target->n; ++i)
-      for (int d = 0; d < 3; ++d) orig[3 * (size_t)target->perm[i] + d] = packed[4 * i + d];
-    nrm.resize(n * 3);
-    for (size_t k = 0; k < n; ++k)
-      for (int d = 0; d < 3; ++d) nrm[3 * k + d] = orig[3 * (size_t)ids[k] + d];
-  }
-  HostBvh hb;
-  build_bvh_host(xyz.data(), ids.data(), nrm.empty() ? nullptr : nrm.data(), n, dp.leaf_size, hb);
+  // the finite points are the first n_valid records of the Morton-sorted device copy (w = original index)
   ope_index *ix = new ope_index();
   ix->ctx = ctx;
   ix->n = n;
   ix->n_total = target->n;
-  ix->depth = hb.depth;
   std::memcpy(ix->bb_lo, target->bb_lo, sizeof ix->bb_lo);
   std::memcpy(ix->bb_hi, target->bb_hi, sizeof ix->bb_hi);
   for (int d = 0; d < 3; ++d) ix->pivot[d] = 0.5 * ((double)target->bb_lo[d] + (double)target->bb_hi[d]);
-  hipError_t e = hipMalloc((void **)&ix->d_nodes, sizeof(float) * hb.nodes.size());
-  if (e == hipSuccess) e = h2d_copy(ctx->stream, ix->d_nodes, hb.nodes.data(), sizeof(float) * hb.nodes.size());
-  if (e == hipSuccess) e = hipMalloc((void **)&ix->d_pts, sizeof(float4) * (n + kPtsPad));
-  if (e == hipSuccess) e = hipMemset(ix->d_pts + n, 0, sizeof(float4) * kPtsPad);
-  if (e == hipSuccess) e = h2d_copy(ctx->stream, ix->d_pts, hb.pts4.data(), sizeof(float4) * n);
-  if (e == hipSuccess && !hb.nrm4.empty()) {
-    e = hipMalloc((void **)&ix->d_nrm, sizeof(float4) * n);
-    if (e == hipSuccess) e = h2d_copy(ctx->stream, ix->d_nrm, hb.nrm4.data(), sizeof(float4) * n);
-  }
+  ix->tmp_alloc = temporary;
+  ix->alloc_stream = ctx->stream;
+  const hipError_t e = build_bvh_device(ctx->stream, target->d_xyzw, target->d_nrm, n, dp.leaf_size, target->bb_lo, target->bb_hi,
+                                        &ix->depth, &ix->d_nodes, &ix->d_pts, &ix->d_nrm, &ix->d_axis2, temporary);
   if (e != hipSuccess) {
     ope_index_free(ix);
     return set_err(ctx, OPE_EHIP, std::string("ope_index_build: ") + hipGetErrorString(e));
   }
+  // the bucketed side of the index (grid_build.hip) is built by the first 1-NN ICP run that uses this index: the
+  // indexes behind normals, FPFH and the filters never need it
+  ix->want_grid = dp.grid != 0;
+  ix->grid_mode = dp.grid;
+  ix->grid_fill = dp.grid_fill;
+  ix->grid_max_cells = dp.grid_max_cells;
   *out = ix;
   return OPE_OK;
 }
@@ -1084,13 +995,11 @@ void ope::icp_state_init(IcpState *h, const ope_cloud *src, const ope_index *tgt
     // shortly before those queries can hold certificates too.
     h->cert_thr = !cert_run ? -1.0f : p.skip_certificates == OPE_CERT_ALWAYS ? std::numeric_limits<float>::infinity()
                                  : (float)(spacing / (cluttered ? 512.0 : (double)kCertWorth));
-    if (const char *e = dev_env("OPE_CERT_THR")) h->cert_thr = (float)atof(e);   // developer sweep (metres)
     h->cert_mode = (cert_run && p.skip_certificates == OPE_CERT_ALWAYS) ? 1 : 0;
     // what a certificate is worth (icp_accumulate_kernel): the (kCertCand + 1)-th neighbour of a query D from a surface sampled at
     // `spacing` lies ~ kCertCand spacing^2 / (2 pi D) further out than the nearest one, never more than about the spacing itself
     h->cert_cap = (float)spacing;
     h->cert_k = (float)((double)kCertCand * spacing * spacing / (2.0 * 3.14159265358979323846));
-    if (const char *e = dev_env("OPE_CERT_CAP")) h->cert_cap = (float)atof(e);   // developer sweep (metres)
     double r2 = 0;
     for (int d = 0; d < 3; ++d) {
       h->src_c[d] = 0.5f * (src->bb_lo[d] + src->bb_hi[d]);
@@ -1287,8 +1196,7 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
   OPE_HIP(ctx, hipMemsetAsync(ctx->d_hint, 0, sizeof(uint32_t) * std::max<size_t>(src->n, 1), ctx->stream));
 
   // Skip certificates (ope.h: skip_certificates): plain 1-NN runs.
-  ctx->cert_run = p.corr_mode == OPE_CORR_NEAREST && !p.use_reciprocal && p.deterministic_sums == 0 && p.skip_certificates != OPE_CERT_OFF &&
-                  !dev_env("OPE_NO_CERT");
+  ctx->cert_run = p.corr_mode == OPE_CORR_NEAREST && !p.use_reciprocal && p.deterministic_sums == 0 && p.skip_certificates != OPE_CERT_OFF;
   IcpState *h = ctx->h_state;
   icp_state_init(h, src, tgt, guess, p, ctx->cert_run, ctx->grid_auto && !ctx->use_grid);
   ctx->cert_seen = h->cert_mode != 0;
@@ -1306,7 +1214,7 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
   }
   OPE_HIP(ctx, hipMemcpyAsync(ctx->d_state, h, sizeof *h, hipMemcpyHostToDevice, ctx->stream));
   // k-NN runs of more than one pass: start leaves for the first launch (icp_kernels.hip: seed_hints_kernel)
-  if (p.corr_mode == OPE_CORR_NORMAL_SHOOTING && p.max_iterations > 1 && src->n_valid > 0 && !dev_env("OPE_NO_SEED"))
+  if (p.corr_mode == OPE_CORR_NORMAL_SHOOTING && p.max_iterations > 1 && src->n_valid > 0)
     launch_seed_hints(ctx->stream, src->view(), tgt->view(), ctx->d_state, ctx->d_hint);
   if (ctx->d_sums_ext)
     OPE_HIP(ctx, hipMemsetAsync(ctx->d_sums_ext, 0, sizeof(double) * (p.estimator == OPE_EST_POINT_TO_PLANE_LLS ? kNumSumsMax : kNumSums), ctx->stream));
@@ -1320,22 +1228,7 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
   // (every launch of the previous run is over: nothing writes the pace words any more)
   ctx->h_pace[0] = 0u; ctx->h_pace[1] = 0u;
   ctx->launch_no = 0;
-  ctx->pace_off = dev_env("OPE_NO_PACE") != nullptr;
-
-#ifdef OPE_DEVELOPER
-  if (dev_env("OPE_DUMP_HASH")) {   // developer probe: checksums of everything the run reads, to stderr
-    auto fnv = [&](const void *d, size_t bytes) -> unsigned long long {
-      std::vector<unsigned char> h(bytes);
-      if (bytes && d) (void)hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost);
-      unsigned long long x = 1469598103934665603ull;
-      if (d) for (unsigned char c : h) { x ^= c; x *= 1099511628211ull; }
-      return x;
-    };
-    std::fprintf(stderr, "[hash] begin src n %zu valid %zu xyzw %016llx nrm %016llx | tgt n %zu depth %d nodes %016llx pts %016llx nrm %016llx\n", src->n,
-                 src->n_valid, fnv(src->d_xyzw, 16 * src->n), fnv(src->d_nrm, 16 * src->n), tgt->n, tgt->depth,
-                 fnv(tgt->d_nodes, 48 * ((size_t)2 << tgt->depth)), fnv(tgt->d_pts, 16 * tgt->n), fnv(tgt->d_nrm, 16 * tgt->n));
-  }
-#endif
+  ctx->pace_off = false;
   ctx->run_src = src;
   ctx->run_tgt = tgt;
   ctx->corr_run_n = src->n;
@@ -1359,7 +1252,7 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
   // update's wave finds room beside it whenever it arrives.
   ctx->chained = p.update_launch == OPE_UPDATE_OVERLAPPED && !ctx->chain_broken && p.corr_mode == OPE_CORR_NEAREST && !p.use_reciprocal &&
                  p.deterministic_sums == 0 && p.estimator != OPE_EST_POINT_TO_PLANE_LM && ctx->nccl_comm == nullptr && !ctx->p2p_ok &&
-                 ctx->n_fixed == 0 && !dev_env("OPE_NO_CHAIN");
+                 ctx->n_fixed == 0;
   ctx->n_fixed_run = ctx->n_fixed;
   ctx->chain_on = false;
   ctx->chain_seq = 0;
@@ -1382,7 +1275,6 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
     if (per_cu > 0) ctx->acc_blocks = std::max(1, std::min(ctx->acc_blocks, per_cu * ctx->n_cu - ctx->n_xcd));
     else ctx->chained = false;
   }
-  if (const char *e = dev_env("OPE_ACC_BLOCKS")) ctx->acc_blocks = std::max(1, std::min(atoi(e), (int)kAccMaxBlocks));
   if (ctx->n_src_total <= 0) ctx->n_src_total = (int64_t)src->n;
   if (ctx->n_tgt_total <= 0) ctx->n_tgt_total = (int64_t)tgt->n_total;
   guard.ok = true;
@@ -1515,7 +1407,6 @@ int ope_icp_iterate(ope_ctx *ctx, int n_iterations) {
   // a context with a communicator takes the accumulate -> all-reduce -> update sequence, also with one rank
   // (that is how a one-GPU box exercises the path the multi-GPU runs take)
   const bool sharded = ctx->nccl_comm != nullptr || ctx->p2p_ok;
-  static const bool split_update = dev_env("OPE_SPLIT_UPDATE") != nullptr;  // developer A/B switch
   const bool atomic = atomic_sums(ctx);
   // Overlapped update launches (icp_kernels.hip, acc_launch_begin): the updates go to their own stream, which waits for the
   // launch stream once per run; the launch stream waits for it only when something is about to read or rewrite the state
@@ -1591,7 +1482,7 @@ int ope_icp_iterate(ope_ctx *ctx, int n_iterations) {
     } else if (atomic) {
       enqueue_fixed_pairs(ctx);
       launch_icp_update(ctx->stream, ctx->d_state, sums_ptr(ctx), run_nsums(ctx), nullptr);
-    } else if (split_update || ctx->n_fixed_run > 0) {
+    } else if (ctx->n_fixed_run > 0) {
       launch_icp_reduce_update(ctx->stream, ctx->d_state, ctx->d_partials, sums_ptr(ctx), ctx->acc_blocks, false, ctx->d_work_counter);
       enqueue_fixed_pairs(ctx);
       launch_icp_update(ctx->stream, ctx->d_state, sums_ptr(ctx), run_nsums(ctx), nullptr);
@@ -1639,18 +1530,6 @@ int ope_icp_profile_launches(ope_ctx *ctx, float *ms, size_t cap, size_t *n_out)
   *n_out = n;
   return OPE_OK;
 }
-
-#ifdef OPE_DEVELOPER
-// tools/cost_probe.py: the per-chunk costs the last launches measured (s_memtime ticks >> 4), the plan's order and plan_info
-int ope_debug_chunk_costs(ope_ctx *ctx, uint32_t *cost, uint32_t *order, uint32_t *plan_info4, int n) {
-  if (!ctx || !ctx->run_active) return OPE_ESTATE;
-  OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  OPE_HIP(ctx, hipMemcpy(cost, ctx->d_chunk_cost + (size_t)((ctx->acc_launches + 1) & 1) * ctx->chunk_cap, 4 * (size_t)n, hipMemcpyDeviceToHost));   // the half the last launch wrote
-  OPE_HIP(ctx, hipMemcpy(order, ctx->use_grid ? ctx->d_chunk_order : ctx->d_plan_order[ctx->plan_cur], 4 * (size_t)n, hipMemcpyDeviceToHost));
-  OPE_HIP(ctx, hipMemcpy(plan_info4, ctx->use_grid ? ctx->d_work_counter + 8 : ctx->d_plan_out + 8 * ctx->plan_cur, 16, hipMemcpyDeviceToHost));
-  return OPE_OK;
-}
-#endif
 
 int ope_icp_update(ope_ctx *ctx) {
   if (!ctx || !ctx->run_active) return set_err(ctx, OPE_ESTATE, "ope_icp_update: no run in progress");

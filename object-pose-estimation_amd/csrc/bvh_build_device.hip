@@ -1,8 +1,7 @@
 // bvh_build_device.hip — construction of the implicit balanced OBB tree on the device.
 //
 // Replaces the kd-tree build inside Registration::initCompute (vPCL impl/registration_mod.hpp:80-84:
-// tree_->setInputCloud(target_)).  Same structure and the same conservative box margins as the host builder
-// (bvh_build.cpp, kept as the A/B reference behind OPE_HOST_BUILD): a perfect binary tree whose node (l, j)
+// tree_->setInputCloud(target_)).  A perfect binary tree whose node (l, j)
 // owns the contiguous point range [start(j << (D-l)), start((j+1) << (D-l))), start(k) = k*n >> D.
 //
 //   for every level l < D:   per-node bounding box (wave-reduced atomics on order-preserving integer images of
@@ -13,8 +12,8 @@
 //                            Jacobi, mid-range centre along the rounded axes, half extents about the ROUNDED
 //                            centre plus the margin that covers the traversal's fp32 evaluation.
 //
-// The tree differs from the host builder's only where equal coordinates straddle a median; the search is exact
-// for any tree whose boxes contain their points.
+// Where equal coordinates straddle a median either child may hold them; the search is exact for any tree whose
+// boxes contain their points.
 #include <cstring>
 #include <string>
 
@@ -420,7 +419,7 @@ __device__ __forceinline__ void fit_obb_node(const float4 *__restrict__ pts, uin
   for (int k = 0; k < 3; ++k) h[k] = block_reduce<OpMax, BLOCK>(h[k], s_tmp, OpMax());
   if (threadIdx.x == 0) {
     // margin covering the traversal's fp32 evaluation of the projections (relative 4e-6 of the offset, i.e.
-    // > 10 fp32 ulps, and an absolute floor), exactly as bvh_build.cpp
+    // > 10 fp32 ulps, and an absolute floor)
     const double margin = 4e-6 * far + 1e-7 * scale;
     o[0] = cf0; o[1] = cf1; o[2] = cf2;
     for (int k = 0; k < 3; ++k) o[4 * k + 3] = nextafterf((float)(h[k] + margin), FLT_MAX);
@@ -669,7 +668,7 @@ __global__ __launch_bounds__(kFitBlock) void top_write_kernel(const TopWork *__r
   if (node == 0 || node >= kTopSlices) return;
   float *o = nodes + (size_t)kNodeFloats * node;
   const double far = __longlong_as_double((long long)w->ext[node][3]);
-  const double margin = 4e-6 * far + 1e-7 * scale;   // as fit_obb_kernel / bvh_build.cpp
+  const double margin = 4e-6 * far + 1e-7 * scale;   // as fit_obb_kernel
   o[0] = w->cf[node][0]; o[1] = w->cf[node][1]; o[2] = w->cf[node][2];
   for (int k = 0; k < 3; ++k) o[4 * k + 3] = nextafterf((float)(__longlong_as_double((long long)w->ext[node][k]) + margin), FLT_MAX);
 }
@@ -721,10 +720,8 @@ __global__ __launch_bounds__(64) void bvh_batch_root_kernel(const BvhBatchTree *
 // 913 k points (165 us per level, nine levels: half of that index's build) — where three or four Onesweep passes do.
 // Measured (ope_index_build, ms, default / Onesweep above 64 k items): 100 k points 0.92 / 1.15, 500 k 2.1 / 1.98, 1 M 2.75 / 2.5,
 // the outlier filter of the C3 frame (914 k points) 5.45 / 4.85: Onesweep from 256 k items on.
-#ifndef OPE_LEVEL_MERGE_SORT_LIMIT
-#define OPE_LEVEL_MERGE_SORT_LIMIT 262144
-#endif
-using LevelSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, OPE_LEVEL_MERGE_SORT_LIMIT>;
+constexpr size_t kLevelMergeSortLimit = 262144;
+using LevelSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, kLevelMergeSortLimit>;
 
 int bvh_depth(size_t n, int leaf_size) {
   if (leaf_size < 1) leaf_size = 16;

@@ -245,9 +245,7 @@ template <> struct leaf_rescan_is_harmless<NearestVisitor> { static constexpr bo
 // Exact: a deferred leaf is scanned before the walk returns, and a bound that is tested against an older `best` only
 // lets more through.  The leaf of the start hint is scanned up front (it gives the bound everything else is pruned with)
 // and so is the first leaf of a walk that has no candidate yet.
-#ifndef OPE_SCAN_BATCH
-#define OPE_SCAN_BATCH 8u
-#endif
+constexpr uint32_t kScanBatch = 8u;   // leaf points fetched per batch
 __device__ __forceinline__ void scan_leaf_nearest(const BvhView &t, uint32_t node, float qx, float qy, float qz, NearestVisitor &v) {
   const uint32_t j = node - (1u << t.depth);
   const uint32_t s = (uint32_t)(((unsigned long long)j * t.n) >> t.depth);
@@ -260,27 +258,21 @@ __device__ __forceinline__ void scan_leaf_nearest(const BvhView &t, uint32_t nod
     v.best = c_ ? d_ : v.best;                                                                           \
     v.pos = c_ ? (IDX) : v.pos;                                                                          \
   }
-  if (e - s >= OPE_SCAN_BATCH) {
-    for (uint32_t i = s;; i += OPE_SCAN_BATCH) {
-      const bool last = i + OPE_SCAN_BATCH >= e;
-      const uint32_t b = last ? e - OPE_SCAN_BATCH : i;
+  if (e - s >= kScanBatch) {
+    for (uint32_t i = s;; i += kScanBatch) {
+      const bool last = i + kScanBatch >= e;
+      const uint32_t b = last ? e - kScanBatch : i;
       const float4 *p = t.pts + b;
-#if OPE_SCAN_BATCH == 8
       const v4f p0 = ld16(p), p1 = ld16(p + 1), p2 = ld16(p + 2), p3 = ld16(p + 3), p4 = ld16(p + 4), p5 = ld16(p + 5),
                 p6 = ld16(p + 6), p7 = ld16(p + 7);
-#else
-      const v4f p0 = ld16(p), p1 = ld16(p + 1), p2 = ld16(p + 2), p3 = ld16(p + 3);
-#endif
       OPE_LEAF_POINT_SEL(p0, b);
       OPE_LEAF_POINT_SEL(p1, b + 1u);
       OPE_LEAF_POINT_SEL(p2, b + 2u);
       OPE_LEAF_POINT_SEL(p3, b + 3u);
-#if OPE_SCAN_BATCH == 8
       OPE_LEAF_POINT_SEL(p4, b + 4u);
       OPE_LEAF_POINT_SEL(p5, b + 5u);
       OPE_LEAF_POINT_SEL(p6, b + 6u);
       OPE_LEAF_POINT_SEL(p7, b + 7u);
-#endif
       if (last) break;
     }
   } else {
@@ -401,14 +393,6 @@ __device__ __forceinline__ void bvh_traverse_deferred(const BvhView &t, float qx
 // ahead of the back-up that reaches it keeps 32 more SGPRs alive, which the 80-VGPR build pays with 83 spilled VGPRs.
 constexpr int kPacketMaxLeaves = 6;
 
-// Developer builds count what a packet walk did (tools/chain_probe.py); the product build compiles the counters away.
-struct PacketStats { uint32_t steps, leaves, backups; };
-#ifdef OPE_DEVELOPER
-#define OPE_PKT_COUNT(ps, field) do { if (ps) ++(ps)->field; } while (0)
-#else
-#define OPE_PKT_COUNT(ps, field) do { } while (0)
-#endif
-
 // A 16-byte load through the CONSTANT address space: with a wave-uniform address the compiler selects s_load_dwordx4
 // (scalar cache, result in SGPRs).  Legal because the index is never written while a search kernel runs.
 typedef const __attribute__((address_space(4))) v4f *scalar_ptr_v4f;
@@ -513,7 +497,7 @@ __device__ __forceinline__ void packet_scan_leaf(const BvhView &t, uint32_t node
 
 template <class Visitor>
 __device__ __forceinline__ bool bvh_traverse_packet(const BvhView &t, float qx, float qy, float qz, bool active, Visitor &v,
-                                                    uint32_t hint, float *stk, int stk_stride, PacketStats *ps = nullptr) {
+                                                    uint32_t hint, float *stk, int stk_stride) {
   const uint32_t leaf0 = 1u << t.depth;
   const int D = t.depth;
   const unsigned long long act = __ballot(active);
@@ -556,18 +540,16 @@ __device__ __forceinline__ bool bvh_traverse_packet(const BvhView &t, float qx, 
       if (__ballot(stk[(31 - __clz(node)) * stk_stride] < v.bound()) != 0ull) { more = true; break; }
     }
     if (!more) return true;
-    OPE_PKT_COUNT(ps, backups);
     // walk down from there
     for (;;) {
       if (node >= leaf0) {
         bool dup = false;
         for (int q = 0; q < nd; ++q) dup = dup || (seen[q] == node);
-        if (!dup) { packet_scan_leaf(t, node, qx, qy, qz, v); OPE_PKT_COUNT(ps, leaves); }
+        if (!dup) packet_scan_leaf(t, node, qx, qy, qz, v);
         break;
       }
       PacketNode cl, cr;
       load_packet_children(t, node, cl, cr);
-      OPE_PKT_COUNT(ps, steps);
       const float d0 = packet_node_bound(cl, qx, qy, qz), d1 = packet_node_bound(cr, qx, qy, qz);
       const unsigned long long n0 = __ballot(d0 < v.bound()), n1 = __ballot(d1 < v.bound());
       if ((n0 | n1) == 0ull) break;
@@ -721,19 +703,11 @@ struct KnnVisitor {
 // it with the queue drained only when a lane's is full and at the walk's end, exact to the last correspondence: 8 entries
 // at four waves per SIMD 0.574 ms against 0.537, 14 entries at three waves 0.711; and with a 32-entry buffer selected from
 // at the end, under the previous launch's bound: 2.05 ms.  Same conclusion.)
-#ifdef OPE_KNN_STATS   // (developer counters: executions at wave level are counted by the first active lane)
-#define OPE_KNN_STAT(J) do { if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__ballot(true))) ++stat[J]; } while (0)
-#else
-#define OPE_KNN_STAT(J) do { } while (0)
-#endif
 template <int K>
 struct KnnRegVisitor {
   float d[K];
   uint32_t p[K];
   int count;
-#ifdef OPE_KNN_STATS
-  uint32_t stat[5] = {0, 0, 0, 0, 0};   // presentations, insertion sequences, node steps, - (wave level); passing candidates (per lane)
-#endif
   uint32_t leaf;   // leaf of the current nearest entry (next iteration's start hint)
   // bound: only points strictly closer than this can enter the list (+inf: plain k-NN; a finite value that is known to
   // lie above the K-th neighbour's distance gives the same list and prunes from the first box on)
@@ -747,12 +721,7 @@ struct KnnRegVisitor {
   __device__ __forceinline__ float bound() const { return d[K - 1]; }
   __device__ __forceinline__ void point(float dist, const v4f &, uint32_t i, uint32_t lf) {
     const bool ins = dist < d[K - 1];
-#ifdef OPE_KNN_STATS
-    OPE_KNN_STAT(0);             // point presentations (wave level)
-    if (ins) ++stat[4];          // candidates that pass (per lane)
-#endif
     if (__ballot(ins) == 0ull) return;
-    OPE_KNN_STAT(1);             // insertion sequences executed (wave level)
     if (ins && dist < d[0]) leaf = lf;
     count += (ins && count < K) ? 1 : 0;
     // Sorted insert of `dist` into ascending d[]: new d[j] = median(d[j-1], d[j], dist) — one v_med3_f32 per slot —
@@ -770,7 +739,7 @@ struct KnnRegVisitor {
     p[0] = lt_hi ? i : p[0];
     d[0] = fminf(d[0], dist);
   }
-  __device__ __forceinline__ void on_node() { OPE_KNN_STAT(2); }
+  __device__ __forceinline__ void on_node() {}
 };
 
 constexpr int kKnnBlock = 256;

@@ -518,7 +518,6 @@ static int normals_impl(ope_ctx *ctx, ope_cloud *cloud, const ope_index *index, 
     OPE_HIP(ctx, h2d_copy(ctx->stream, cloud->d_nrm, nan4.data(), sizeof(float4) * n));
     if (want_host) packed = nan4;
   }
-  OPE_DUMP_HASH("normals d_nrm", cloud->d_nrm, 16 * n, true);
   if (!want_host) return OPE_OK;
   { const int rch = cloud->ensure_host(); if (rch != OPE_OK) return rch; }
   for (size_t i = 0; i < n; ++i) {

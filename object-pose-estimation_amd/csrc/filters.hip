@@ -207,7 +207,6 @@ static int box_filter(ope_ctx *ctx, const ope_cloud *cloud, const float lo[3], c
   if (count) e = hipMemcpy(out_idx, d_out, 4 * (size_t)count, hipMemcpyDeviceToHost);
   tmp_free(ctx->stream, d_out);
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + ": " + hipGetErrorString(e));
-  OPE_DUMP_HASH(who, out_idx, 4 * (size_t)count, false);
   *n_out = count;
   return OPE_OK;
 }

@@ -19,10 +19,7 @@
 namespace ope {
 
 // Threads per workgroup: 512 (eight waves, two per SIMD) was faster than 256 at C1 size, DESIGN.md 4.6.
-#ifndef OPE_BATCH_BLOCK
-#define OPE_BATCH_BLOCK 512
-#endif
-constexpr int kBatchBlock = OPE_BATCH_BLOCK;
+constexpr int kBatchBlock = 512;
 constexpr int kBatchRows = kBatchBlock / 16;   // 16-lane rows: one LDS row of partial sums each
 constexpr size_t kBatchMaxSrc = 65536;        // valid source points of one problem at most (larger runs belong to ope_icp_run)
 

@@ -24,17 +24,12 @@
 
 namespace ope {
 
-#ifdef OPE_DEVELOPER
-// tools/chain_probe.py: per chunk {path: 0 per-lane / 1 packet / 2 groups, packet steps, packet leaf scans, packet back-ups}
-__device__ uint32_t *g_chunk_stats = nullptr;
-#endif
-
 typedef const __attribute__((address_space(3))) float *lds_cfloat_ptr;   // a pointer that stays an LDS pointer
 static_assert(kCertCand >= 1 && kCertCand <= 8, "skip certificates: candidates per query");
 
 // ---- update launches overlapped with the accumulate launches (round 3; host side: api.hip, ope_icp_iterate) -------------
 // In line, an iteration is accumulate -> update -> accumulate on one stream, and the two kernel boundaries around the
-// 64-thread update launch cost the iteration 13-17 us (tools/gap_probe.sh).  Overlapped, update j is launched on a stream of
+// 64-thread update launch cost the iteration 13-17 us (measured in round 3).  Overlapped, update j is launched on a stream of
 // its own next to accumulate launch j, is resident long before that launch ends and waits ON THE DEVICE for its blocks
 // (chain[0], one ticket per block, taken after the block's sums are in); accumulate launch j + 1 follows launch j on the
 // launch stream — the one boundary left runs while the update lane computes — and its blocks wait for update j's word
@@ -229,16 +224,11 @@ __device__ __forceinline__ bool cert_worth_building(float d2_prev, float cert_k,
 // if the nearest SOURCE point of target point j is i again.  The reference searches a kd-tree rebuilt
 // over the transformed source every iteration; here the source index is built once in the source's own
 // frame and queried with F^-1 * t_j (a rigid map preserves the ranking up to fp32 rounding).
-#ifdef OPE_KNN_STATS
-__device__ unsigned long long g_knn_stats[8];
-#endif
+// Waves per SIMD of the k-NN instantiations.  k = 20 on C3: 4 waves (128 VGPRs, 9 spilled) 0.545-0.554 ms per iteration; 3 waves
+// (139 VGPRs, none spilled) 0.68; 5 waves (96 VGPRs, 53 spilled) 0.90: the walks need the fourth wave more than their nine registers
+constexpr int kKnnWavesPerSimd = 4;
 template <int MODE, bool NRM, bool RECIP = false, bool PACKET = false, int KREG = 20, bool CERT = false>
-#ifndef OPE_KNN_WAVES
-#define OPE_KNN_WAVES 4   // waves per SIMD of the k-NN instantiations (developer A/B: make VARIANT=... EXTRA=-DOPE_KNN_WAVES=3).
-// k = 20 on C3, tools/ns_bench.py: 4 waves (128 VGPRs, 9 spilled) 0.545-0.554 ms per iteration; 3 waves (139 VGPRs, none spilled) 0.68;
-// 5 waves (96 VGPRs, 53 spilled) 0.90: the walks need the fourth wave more than their nine registers
-#endif
-__global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !RECIP && !CERT) ? kAccWavesPerSimd : (MODE == 2 ? OPE_KNN_WAVES : 4)) void icp_accumulate_kernel(
+__global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !RECIP && !CERT) ? kAccWavesPerSimd : (MODE == 2 ? kKnnWavesPerSimd : 4)) void icp_accumulate_kernel(
     CloudView src, BvhView tgt, BvhView srcix, const IcpState *__restrict__ st, double *__restrict__ partials,
     int32_t *__restrict__ corr_match, float *__restrict__ corr_d2, uint32_t *__restrict__ work_counter,
     uint32_t *__restrict__ hint, const uint32_t *__restrict__ chunk_order, uint32_t *__restrict__ chunk_cost,
@@ -401,15 +391,9 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
       float c_best = INFINITY;
       uint32_t c_pos = 0u;
       if (active) need = !cert_check(tgt, cert_q, cert_l, cert_pos, cstride, i, x, y, z, best_init, cst[17], c_best, c_pos, stuck, has_cert);
-#ifdef OPE_DEVELOPER   // tools/cert_probe.py: why certificates fail {expired, stuck where it was built, none yet}
-      if (need && owner) atomicAdd(work_counter + (!has_cert ? 46 : stuck ? 45 : 44), 1u);
-#endif
       // (in a slot walked by 8-lane groups the eight lanes of a group carry the same query: one of them builds)
       const bool build = need && !stuck && owner && cert_worth_building(corr_d2[i], cst[18], cst[19], cst[17]);
       const uint32_t h = need ? hint[i] : 0u;   // start leaf of the walks (queries answered from their certificate need none)
-#ifdef OPE_DEVELOPER
-      if (owner && build) atomicAdd(work_counter + 47, 1u);   // walks that build a certificate
-#endif
       const bool fast = need && !build && !(oct && __shfl((int)build, (int)(lane_id & ~7u), 64) != 0);   // (a group whose query builds does not walk as well)
       NearestVisitor v{fast ? best_init : -INFINITY, kNoPos, 0};
       const unsigned long long fmask = __ballot(fast);
@@ -458,25 +442,10 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
       const uint32_t h = active ? hint[i] : 0u;
       if (OCT_OK && oct) {
         if (active) bvh_traverse_oct(tgt, x, y, z, v, &s_stk[0][threadIdx.x & ~7u], BLOCK, h);
-#ifdef OPE_DEVELOPER
-        if (g_chunk_stats && lane_id == 0) {   // path, and the longest of the eight slots' walks (same units as chunk_cost)
-          g_chunk_stats[4 * (size_t)chunk] = 2u;
-          atomicMax(g_chunk_stats + 4 * (size_t)chunk + 1, (uint32_t)((__builtin_amdgcn_s_memtime() - t_begin) >> 4));
-        }
-#endif
       } else {
         // coherent chunks (a handful of start leaves for 64 queries) take one packet walk through the scalar cache
         // (PACKET instantiation: launches that fill the GPU); everything else the per-lane walk from its own leaf
-#ifdef OPE_DEVELOPER
-        PacketStats pst{0, 0, 0};
-        const bool done = PACKET && bvh_traverse_packet(tgt, x, y, z, active, v, h, stk, BLOCK, &pst);
-        if (g_chunk_stats && lane_id == 0) {
-          uint32_t *o = g_chunk_stats + 4 * (size_t)chunk;
-          o[0] = done ? 1u : 0u; o[1] = pst.steps; o[2] = pst.leaves; o[3] = pst.backups;
-        }
-#else
         const bool done = PACKET && bvh_traverse_packet(tgt, x, y, z, active, v, h, stk, BLOCK);
-#endif
         // (the queue of deferred leaves lives in the rows of the parked-bound column above the tree's depth: 8 entries up to
         // 2^13 leaves, at least one always)
         if (!done && active) bvh_traverse_deferred(tgt, x, y, z, v, stk, BLOCK, h, min(8, kMaxDepth + 1 - tgt.depth));
@@ -530,13 +499,6 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
         todo = retry;
         bound0 = INFINITY;
       }
-#ifdef OPE_KNN_STATS
-      {
-        unsigned long long t[5];
-        for (int j = 0; j < 5; ++j) { t[j] = v.stat[j]; for (int off = 32; off >= 1; off >>= 1) t[j] += __shfl_xor(t[j], off, 64); }
-        if (lane_id == 0) { for (int j = 0; j < 5; ++j) atomicAdd(&g_knn_stats[j], t[j]); atomicAdd(&g_knn_stats[5], 1ull); }
-      }
-#endif
       if (!active) v.init(false);
       if (active) {
         hint[i] = v.leaf;
@@ -1547,253 +1509,3 @@ void launch_fitness(hipStream_t stream, int nblocks, const CloudView &q, const B
 }
 
 }  // namespace ope
-
-#ifdef OPE_DEVELOPER   // `make DEVELOPER=1`: instrumentation kernels are not part of the product library
-extern "C" int ope_debug_cert_reasons(ope_ctx *ctx, uint32_t out[4], int reset) {
-  OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  OPE_HIP(ctx, hipMemcpy(out, ctx->d_work_counter + 44, 16, hipMemcpyDeviceToHost));
-  if (reset) OPE_HIP(ctx, hipMemset(ctx->d_work_counter + 44, 0, 16));
-  return OPE_OK;
-}
-// tools/chain_probe.py: switch the per-chunk path/packet counters of the tree kernel on (device buffer of 4 words per
-// chunk, handed back by ope_debug_chunk_stats_read) or off (nullptr)
-extern "C" int ope_debug_chunk_stats(ope_ctx *ctx, uint32_t n_chunks, uint32_t *read_into) {
-  static uint32_t *d_buf = nullptr;
-  static uint32_t cap = 0;
-  if (read_into) {
-    if (!d_buf || n_chunks > cap) return OPE_ESTATE;
-    OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    OPE_HIP(ctx, hipMemcpy(read_into, d_buf, 16 * (size_t)n_chunks, hipMemcpyDeviceToHost));
-    return OPE_OK;
-  }
-  if (d_buf) { (void)hipFree(d_buf); d_buf = nullptr; cap = 0; }
-  if (n_chunks) {
-    OPE_HIP(ctx, hipMalloc((void **)&d_buf, 16 * (size_t)n_chunks));
-    OPE_HIP(ctx, hipMemset(d_buf, 0, 16 * (size_t)n_chunks));
-    cap = n_chunks;
-  }
-  OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  OPE_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(ope::g_chunk_stats), &d_buf, sizeof d_buf));
-  return OPE_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Developer instrumentation (tools/visit_stats.py): per-query node / leaf-point visit counts of the
-// private per-lane traversal.  Not part of include/ope.h.
-namespace ope {
-struct CountingVisitor {
-  float best;
-  int points, nodes;
-  __device__ __forceinline__ bool prune(float bound) const { return !(bound < best); }
-  __device__ __forceinline__ void point(float d, const v4f &, uint32_t, uint32_t) {
-    ++points;
-    if (d < best) best = d;
-  }
-  __device__ __forceinline__ void on_node() { ++nodes; }
-};
-
-__global__ __launch_bounds__(256) void debug_visit_kernel(CloudView q, BvhView t, const float *__restrict__ T,
-                                                           int32_t *nodes_out, int32_t *points_out) {
-  __shared__ float s_stk[kMaxDepth + 1][256];
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= q.n_valid) return;
-  const float4 s = q.xyzw[i];
-  const float qx = xform_row(T + 0, s.x, s.y, s.z), qy = xform_row(T + 4, s.x, s.y, s.z), qz = xform_row(T + 8, s.x, s.y, s.z);
-  CountingVisitor v{INFINITY, 0, 0};
-  bvh_traverse(t, qx, qy, qz, v, &s_stk[0][threadIdx.x], 256);
-  nodes_out[i] = v.nodes;
-  points_out[i] = v.points;
-}
-}  // namespace ope
-
-extern "C" int ope_debug_visit_counts(ope_ctx *ctx, const ope_cloud *q, const ope_index *ix, const float *T_colmajor,
-                                      int32_t *nodes, int32_t *points) {
-  using namespace ope;
-  const size_t n = q->n_valid;
-  int32_t *d_n, *d_p;
-  float *d_T;
-  float rows[12];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 4; ++c) rows[4 * r + c] = T_colmajor[4 * c + r];
-  OPE_HIP(ctx, hipMalloc((void **)&d_n, 4 * n));
-  OPE_HIP(ctx, hipMalloc((void **)&d_p, 4 * n));
-  OPE_HIP(ctx, hipMalloc((void **)&d_T, sizeof rows));
-  OPE_HIP(ctx, h2d_copy(ctx->stream, d_T, rows, sizeof rows));
-  hipLaunchKernelGGL(debug_visit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, q->view(), ix->view(),
-                     d_T, d_n, d_p);
-  OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<int32_t> hn(n), hp(n);
-  OPE_HIP(ctx, hipMemcpy(hn.data(), d_n, 4 * n, hipMemcpyDeviceToHost));
-  OPE_HIP(ctx, hipMemcpy(hp.data(), d_p, 4 * n, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < n; ++i) { nodes[q->perm[i]] = hn[i]; points[q->perm[i]] = hp[i]; }
-  (void)hipFree(d_n); (void)hipFree(d_p); (void)hipFree(d_T);
-  return OPE_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// Developer instrumentation (tools/chunk_profile.py): one wave per 64-query chunk, start hints taken
-// from the last ICP run; per chunk the elapsed shader cycles and the lane-maximum step counts.
-namespace ope {
-struct StepVisitor {
-  float best;
-  uint32_t pos, leaf;
-  int nodes, points;
-  __device__ __forceinline__ bool prune(float bound) const { return !(bound < best); }
-  __device__ __forceinline__ void point(float d, const v4f &, uint32_t i, uint32_t lf) {
-    ++points;
-    if (d < best) { best = d; pos = i; leaf = lf; }
-  }
-  __device__ __forceinline__ void on_node() { ++nodes; }
-};
-
-#define OPE_STAMP(var)                                                                    \
-  do {                                                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                     \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");            \
-    __builtin_amdgcn_sched_barrier(0);                                                     \
-  } while (0)
-
-__global__ __launch_bounds__(kAccBlock, kAccWavesPerSimd) void debug_chunk_kernel(CloudView src, BvhView tgt, const float *__restrict__ T,
-                                                                     const uint32_t *__restrict__ hint, int use_hint,
-                                                                     long long *__restrict__ out) {
-  __shared__ float s_stk[kMaxDepth + 1][kAccBlock];
-  const uint32_t lane_id = threadIdx.x & 63u;
-  const uint32_t chunk = blockIdx.x * (kAccBlock / 64) + (threadIdx.x >> 6);
-  const uint32_t base = chunk * 64u;
-  if (base >= src.n_valid) return;
-  const uint32_t i = base + lane_id;
-  const bool active = i < src.n_valid;
-  unsigned long long t0, t1, ta, tb;
-  unsigned long long c_node = 0, c_leaf = 0, c_pop = 0, c_eager = 0, n_node = 0;
-  int my_trips = 0;  // trips in which THIS lane still had work: sum over lanes / (64 * trips) = lane utilisation of the walk
-  OPE_STAMP(t0);
-  const float4 s4 = src.xyzw[active ? i : base];
-  const float qx = xform_row(T + 0, s4.x, s4.y, s4.z), qy = xform_row(T + 4, s4.x, s4.y, s4.z), qz = xform_row(T + 8, s4.x, s4.y, s4.z);
-  StepVisitor v{active ? INFINITY : -INFINITY, kNoPos, 0, 0, 0};
-  // ---- instrumented copy of bvh_traverse's flat loop (no LDS top copy) ----
-  const BvhView &t = tgt;
-  float *stk = &s_stk[0][threadIdx.x];
-  const int stk_stride = kAccBlock;
-  const uint32_t leaf0 = 1u << t.depth;
-  uint32_t node = 1, trail = 0;
-  const uint32_t start_leaf = (active && use_hint) ? hint[i] : 0u;
-  bool alive = active;
-  OPE_STAMP(ta);
-  if (alive && start_leaf != 0) {
-    node = start_leaf;
-    trail = leaf0 - 1u;
-    const int D = t.depth;
-    for (int k = 0; k < D; k += 4) {
-      v4f a0, b0, c0, a1, b1, c1, a2, b2, c2, a3, b3, c3;
-      const uint32_t s0 = (start_leaf >> k) ^ 1u;
-      const uint32_t s1 = (k + 1 < D) ? ((start_leaf >> (k + 1)) ^ 1u) : s0;
-      const uint32_t s2 = (k + 2 < D) ? ((start_leaf >> (k + 2)) ^ 1u) : s0;
-      const uint32_t s3 = (k + 3 < D) ? ((start_leaf >> (k + 3)) ^ 1u) : s0;
-      load_node(t, s0, a0, b0, c0); load_node(t, s1, a1, b1, c1);
-      load_node(t, s2, a2, b2, c2); load_node(t, s3, a3, b3, c3);
-      stk[(D - k) * stk_stride] = obb_dist2(a0, b0, c0, qx, qy, qz);
-      if (k + 1 < D) stk[(D - k - 1) * stk_stride] = obb_dist2(a1, b1, c1, qx, qy, qz);
-      if (k + 2 < D) stk[(D - k - 2) * stk_stride] = obb_dist2(a2, b2, c2, qx, qy, qz);
-      if (k + 3 < D) stk[(D - k - 3) * stk_stride] = obb_dist2(a3, b3, c3, qx, qy, qz);
-    }
-  }
-  OPE_STAMP(tb);
-  c_eager += tb - ta;
-  while (__ballot(alive) != 0ull) {
-    bool do_pop = false;
-    my_trips += alive ? 1 : 0;
-    OPE_STAMP(ta);
-    if (alive && node < leaf0) {
-      v.on_node();
-      v4f c0, c1, c2, c3, c4, c5;
-      load_node(t, 2 * node, c0, c1, c2);
-      load_node(t, 2 * node + 1, c3, c4, c5);
-      const float d0 = obb_dist2(c0, c1, c2, qx, qy, qz);
-      const float d1 = obb_dist2(c3, c4, c5, qx, qy, qz);
-      const bool right = d1 < d0;
-      const float dn = right ? d1 : d0, df = right ? d0 : d1;
-      if (!v.prune(dn)) {
-        node = 2 * node + (right ? 1u : 0u);
-        const bool pend = !v.prune(df);
-        trail = (trail << 1) | (pend ? 1u : 0u);
-        if (pend) stk[(31 - __clz(node)) * stk_stride] = df;
-      } else {
-        do_pop = true;
-      }
-    }
-    OPE_STAMP(tb);
-    c_node += tb - ta; n_node += 1;
-    const bool leaf_now = alive && !do_pop && node >= leaf0 && false;
-    (void)leaf_now;
-    OPE_STAMP(ta);
-    if (alive && !do_pop && node >= leaf0) {
-      const uint32_t j = node - leaf0;
-      const uint32_t sb = (uint32_t)(((unsigned long long)j * t.n) >> t.depth);
-      const uint32_t e = (uint32_t)(((unsigned long long)(j + 1) * t.n) >> t.depth);
-      for (uint32_t q = sb; q < e; q += 4) {
-        const uint32_t i1 = min(q + 1, e - 1), i2 = min(q + 2, e - 1), i3 = min(q + 3, e - 1);
-        const v4f p0 = ld16(t.pts + q), p1 = ld16(t.pts + i1), p2 = ld16(t.pts + i2), p3 = ld16(t.pts + i3);
-        v.point(sq_dist3(__fsub_rn(qx, p0.x), __fsub_rn(qy, p0.y), __fsub_rn(qz, p0.z)), p0, q, node);
-        if (q + 1 < e) v.point(sq_dist3(__fsub_rn(qx, p1.x), __fsub_rn(qy, p1.y), __fsub_rn(qz, p1.z)), p1, i1, node);
-        if (q + 2 < e) v.point(sq_dist3(__fsub_rn(qx, p2.x), __fsub_rn(qy, p2.y), __fsub_rn(qz, p2.z)), p2, i2, node);
-        if (q + 3 < e) v.point(sq_dist3(__fsub_rn(qx, p3.x), __fsub_rn(qy, p3.y), __fsub_rn(qz, p3.z)), p3, i3, node);
-      }
-      do_pop = true;
-    }
-    OPE_STAMP(tb);
-    c_leaf += tb - ta;
-    OPE_STAMP(ta);
-    if (alive && do_pop) {
-      for (;;) {
-        if (trail == 0) { alive = false; break; }
-        const int k = __builtin_ctz(trail);
-        node = (node >> k) ^ 1u;
-        trail = (trail >> k) & ~1u;
-        if (!v.prune(stk[(31 - __clz(node)) * stk_stride])) break;
-      }
-    }
-    OPE_STAMP(tb);
-    c_pop += tb - ta;
-  }
-  OPE_STAMP(t1);
-  int mn = v.nodes, mp = v.points;
-  int st = my_trips;
-  for (int off = 32; off >= 1; off >>= 1) { mn = max(mn, __shfl_xor(mn, off, 64)); mp = max(mp, __shfl_xor(mp, off, 64)); st += __shfl_xor(st, off, 64); }
-  if (lane_id == 0) {
-    long long *o = out + 10 * (size_t)chunk;
-    o[0] = (long long)(t1 - t0); o[1] = mn; o[2] = mp; o[3] = (long long)c_eager; o[4] = (long long)c_node;
-    o[5] = (long long)c_leaf; o[6] = (long long)c_pop; o[7] = (long long)n_node; o[8] = st; o[9] = 0;
-  }
-}
-}  // namespace ope
-
-extern "C" int ope_debug_chunk_profile(ope_ctx *ctx, const ope_cloud *q, const ope_index *ix, const float *T_colmajor,
-                                       int use_hint, long long *out /* n_chunks * 6 */) {
-  using namespace ope;
-  const size_t nch = (q->n_valid + 63) / 64;
-  float rows[12];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 4; ++c) rows[4 * r + c] = T_colmajor[4 * c + r];
-  float *d_T;
-  long long *d_out;
-  OPE_HIP(ctx, hipMalloc((void **)&d_T, sizeof rows));
-  OPE_HIP(ctx, hipMalloc((void **)&d_out, sizeof(long long) * 10 * nch));
-  OPE_HIP(ctx, hipMemset(d_out, 0, sizeof(long long) * 10 * nch));
-  OPE_HIP(ctx, h2d_copy(ctx->stream, d_T, rows, sizeof rows));
-  const unsigned nb = (unsigned)((nch + kAccBlock / 64 - 1) / (kAccBlock / 64));
-  hipLaunchKernelGGL(debug_chunk_kernel, dim3(nb), dim3(kAccBlock), 0, ctx->stream, q->view(), ix->view(), d_T, ctx->d_hint,
-                     (use_hint && ctx->d_hint) ? 1 : 0, d_out);
-  OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  OPE_HIP(ctx, hipMemcpy(out, d_out, sizeof(long long) * 10 * nch, hipMemcpyDeviceToHost));
-  (void)hipFree(d_T); (void)hipFree(d_out);
-  return OPE_OK;
-}
-#endif  // OPE_DEVELOPER
-
-#ifdef OPE_KNN_STATS
-extern "C" int ope_dev_knn_stats(unsigned long long out[8], int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ope::g_knn_stats), 64) != hipSuccess) return -1;
-  if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(ope::g_knn_stats), z, 64) != hipSuccess) return -1; }
-  return 0;
-}
-#endif

@@ -114,7 +114,7 @@ struct P2pView {
   int nranks, rank;
 };
 
-constexpr float kOctSlotShare = 0.42f;   // one of a group-walked chunk's eight slots lasts about this share of the chunk's per-lane duration (tools/chain_probe.py: 0.39-0.53)
+constexpr float kOctSlotShare = 0.42f;   // one of a group-walked chunk's eight slots lasts about this share of the chunk's per-lane duration (measured: 0.39-0.53)
 constexpr float kCertWorth = 24.0f;     // a query builds a certificate when the slack it can expect is worth this many launches of the scene's current displacement
 constexpr int kCertCand = 5;            // skip certificates: candidates kept per query (built by a (kCertCand + 1)-nearest walk)
 constexpr int kNumSums = 17;
@@ -332,7 +332,7 @@ namespace ope {
 // plain hipMalloc.
 // (Round 3 first took these from the device's memory pool, hipMallocAsync / hipFreeAsync.  In a fresh process the first
 // use of a newly grown pool block came back ZERO, or partly written, to the kernels behind a completed, synchronised copy into
-// it: 4-15 of 16 runs of the C++ facade uploaded a 749-point cloud as zeros, tools/flake_hash.sh.  Memory from hipMalloc
+// it: 4-15 of 16 runs of the C++ facade uploaded a 749-point cloud as zeros.  Memory from hipMalloc
 // never did.)
 struct TmpCache {
   struct Block { void *p; size_t cap; hipStream_t stream; int device; };
@@ -386,11 +386,7 @@ inline hipError_t tmp_malloc(hipStream_t s, void **p, size_t bytes) {
   }
   c.live.push_back(b);
   *p = b.p;
-#ifdef OPE_POISON_TMP   // (A/B build: every temporary starts out as 0xA5 bytes — a read of memory nobody wrote changes results)
-  return hipMemsetAsync(b.p, 0xA5, bytes, s);
-#else
   return hipSuccess;
-#endif
 }
 
 inline void tmp_free(hipStream_t, void *p) {
@@ -485,29 +481,6 @@ inline hipError_t h2d_copy(hipStream_t stream, void *dst, const void *src, size_
   return hipSuccess;
 }
 
-#ifdef OPE_DEVELOPER
-// developer probe (OPE_DUMP_HASH=1): FNV-1a checksum of a host or device buffer to stderr
-inline void dev_dump_hash(const char *what, const void *p, size_t bytes, bool device) {
-  static const bool on = std::getenv("OPE_DUMP_HASH") != nullptr;
-  if (!on) return;
-  std::vector<unsigned char> h(bytes);
-  if (bytes && p) { if (device) (void)hipMemcpy(h.data(), p, bytes, hipMemcpyDeviceToHost); else std::memcpy(h.data(), p, bytes); }
-  unsigned long long x = 1469598103934665603ull;
-  if (p) for (unsigned char c : h) { x ^= c; x *= 1099511628211ull; }
-  std::fprintf(stderr, "[hash] %s bytes %zu %016llx\n", what, bytes, x);
-  if (const char *dir = std::getenv("OPE_DUMP_DIR")) {   // and the buffer itself, numbered in call order
-    static int seq = 0;
-    char path[512];
-    std::snprintf(path, sizeof path, "%s/%03d_%zu.bin", dir, seq++, bytes);
-    if (bytes <= 65536) if (FILE *f = std::fopen(path, "wb")) { std::fwrite(h.data(), 1, bytes, f); std::fclose(f); }
-  }
-}
-#define OPE_DUMP_HASH(WHAT, P, BYTES, DEVICE) ope_dump_hash_fn(WHAT, P, BYTES, DEVICE)
-inline void ope_dump_hash_fn(const char *w, const void *p, size_t b, bool d) { dev_dump_hash(w, p, b, d); }
-#else
-#define OPE_DUMP_HASH(WHAT, P, BYTES, DEVICE) ((void)0)
-#endif
-
 // RAII HIP-event bracket around ONE kernel launch on the context stream, recorded under `name` together with the
 // launch's algorithmic bytes (SURVEY.md §8d formulas) when ope_profile_kernels(ctx, 1) is on; otherwise a no-op.
 class KernelTimer {
@@ -545,20 +518,11 @@ class TraceRange {
       return ::ope::set_err((ctx), OPE_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
   } while (0)
 
-// Host-side index build (bvh_build.cpp).  pts: n*3 floats (finite only), ids: their ORIGINAL
-// indices, nrm optional n*3.  Outputs host arrays ready for upload.
-struct HostBvh {
-  int depth = 0;
-  std::vector<float> nodes;   // (2^(D+1))*kNodeFloats
-  std::vector<float> pts4;    // n*4 (x,y,z, original index bits)
-  std::vector<float> nrm4;    // n*4 or empty
-};
 // sampling.hip: a new cloud from n_sel ORIGINAL indices (device array) of a device-resident cloud
 int select_cloud_device(ope_ctx *ctx, const ope_cloud *cloud, const int32_t *d_idx, size_t n_sel, ope_cloud **out);
 // the same for order-preserving filters: keep = one byte per ORIGINAL index (device); no re-sort (sampling.hip)
 int compact_cloud_device(ope_ctx *ctx, const ope_cloud *cloud, const unsigned char *d_keep, ope_cloud **out, int32_t *d_idx_out, size_t *n_out);
 
-void build_bvh_host(const float *xyz, const int32_t *ids, const float *nrm, size_t n, int leaf_size, HostBvh &out);
 // api.hip: ope_index_build's body; temporary = the index lives inside one entry point and its buffers come from (and go back to) the
 // stream's cache of temporaries instead of hipMalloc / hipFree
 int index_build_impl(ope_ctx *ctx, const ope_cloud *target, const ope_index_params *params, bool temporary, ope_index **out);

@@ -123,7 +123,6 @@ __device__ __forceinline__ uint32_t count_costlier(const uint32_t *cost_sorted_d
 //   the waves that are left, L = (work not yet given away) / (waves not yet given away), iterated to its fixed point.  A
 //   group-walked chunk counts as kOctWork x its per-lane cost (eight slots of about a third of the duration each).
 constexpr double kOctWork = 8.0 * kOctSlotShare;  // wave-time of a group-walked chunk relative to its per-lane walk
-bool g_plan_no_alone = false;   // developer A/B switch (OPE_NO_ALONE, set by api.hip in DEVELOPER builds)
 __device__ __forceinline__ double block_sum_range(const uint32_t *v, uint32_t a, uint32_t b, double *s_sum) {
   double acc = 0.0;
   for (uint32_t i = a + threadIdx.x; i < b; i += 256) acc += (double)v[i];
@@ -233,7 +232,6 @@ void plan_slots(hipStream_t stream, const uint32_t *cost_sorted_desc, uint32_t n
 void plan_heavy(hipStream_t stream, const uint32_t *cost_sorted_desc, uint32_t n, float factor, float load_factor, uint32_t n_waves,
                 uint32_t *plan_info) {
   hipLaunchKernelGGL(plan_heavy_kernel, dim3(1), dim3(1024), 0, stream, cost_sorted_desc, n, factor, load_factor, n_waves, plan_info);
-  if (g_plan_no_alone) (void)hipMemsetAsync(plan_info + 5, 0, 4, stream);
 }
 
 // ---- plan step of the GRID accumulate kernel (icp_accumulate_grid_kernel): everything stays on the device
@@ -335,7 +333,6 @@ int grid_plan(hipStream_t stream, bool repartition, const unsigned char *qclass,
   e = rocprim::radix_sort_pairs_desc(tmp, tb, keys, cost_sorted, ids, order, nch, 0, 32, stream);
   if (e != hipSuccess) return -1;
   hipLaunchKernelGGL(grid_plan_heavy_kernel, dim3(1), dim3(256), 0, stream, cost_sorted, cost, n_valid, n_waves, factor_override, load_factor, plan_info);
-  if (g_plan_no_alone) (void)hipMemsetAsync(plan_info + 5, 0, 4, stream);
   return 0;
 }
 
@@ -755,7 +752,6 @@ extern "C" int ope_uniform_sampling(ope_ctx *ctx, const ope_cloud *cloud, float 
   if (count) e = hipMemcpy(out_idx, d_out, 4 * (size_t)count, hipMemcpyDeviceToHost);
   tmp_free(ctx->stream, d_out);
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string("ope_uniform_sampling: ") + hipGetErrorString(e));
-  OPE_DUMP_HASH("uniform_sampling idx", out_idx, 4 * (size_t)count, false);
   *n_out = count;
   return OPE_OK;
 }

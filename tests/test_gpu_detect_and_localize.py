@@ -189,7 +189,7 @@ def test_facade_runs_are_reproducible_across_processes(tmp_path):
     """Three fresh processes on the same files print the same frames, digit for digit.  (Round 3: the first use of a newly
     grown block of the device memory pool could reach the kernels as zeros, so 4-15 of 16 facade processes uploaded one of
     their small clouds wrongly and the fine poses differed from run to run in the fourth digit; temporaries now come from a
-    cache over hipMalloc, tools/flake_hash.sh is the probe that found it.)"""
+    cache over hipMalloc.  The probe that found it, tools/flake_hash.sh, is in the git history: git show 6d3613c:tools/flake_hash.sh.)"""
     model = synth.model_surface(30_000, 1)
     gt = np.eye(4); gt[:3, :3] = synth.rot_xyz(20.0, -15.0, 40.0); gt[:3, 3] = [0.03, -0.02, 0.7]
     scene = (synth.model_surface(30_000, 2).astype(np.float64) @ gt[:3, :3].T + gt[:3, 3]).astype(np.float32)

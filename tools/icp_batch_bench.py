@@ -7,8 +7,7 @@ are the scene cluster plus seeded, rigidly moved copies of it and distractor clo
 fixture's guess with the fine stage's parameters (normal shooting k = 20, surface-normal rejector 0.7, 100 iterations).
 
 Host clock around each synchronous call, 5 warm-up and 20 timed repetitions, median and min-max.  Kernel times come from a
-separate run under rocprofv3 --kernel-trace --stats (--reps 3).  A/B builds of the library: PROBE_LIB=<name> loads
-libope_hip_<name>.so (make -C object-pose-estimation_amd VARIANT=<name> EXTRA=-DOPE_BATCH_BLOCK=256).
+separate run under rocprofv3 --kernel-trace --stats (--reps 3).
 
     python tools/icp_batch_bench.py [--ks 1,8,32,128] [--warmup 5] [--reps 20] [--fitness] [--json out.json]
 """
@@ -26,8 +25,6 @@ sys.path.insert(0, ROOT)
 ope = importlib.import_module("object-pose-estimation_amd")
 synth = importlib.import_module("object-pose-estimation_amd.synth")
 pcd = importlib.import_module("object-pose-estimation_amd.pcd")
-if os.environ.get("PROBE_LIB"):
-    ope.LIB_PATH = os.path.join(os.path.dirname(ope.LIB_PATH), f"libope_hip_{os.environ['PROBE_LIB']}.so")
 GOLD = os.path.join(ROOT, "tests", "golden")
 DBL_MAX = float(np.finfo(np.float64).max)
 FINE = dict(max_iterations=100, transformation_epsilon=1e-8, euclidean_fitness_epsilon=1e-8, corr_mode=1, k_normal_shooting=20,
@@ -113,7 +110,7 @@ def main():
               f"batch {row['batch_us_per_problem_iteration']:.2f} us/problem-iteration", flush=True)
     if a.json:
         with open(a.json, "w") as f:
-            json.dump(dict(block=os.environ.get("PROBE_LIB", "default"), fitness=a.fitness, rows=rows), f, indent=1)
+            json.dump(dict(fitness=a.fitness, rows=rows), f, indent=1)
     ctx.close()
 
 

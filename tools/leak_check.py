@@ -1,4 +1,4 @@
-"""Developer probe: device memory before / after many upload + index + ICP + feature cycles (leak check)."""
+"""Device memory before / after many upload + index + ICP + feature cycles (leak check)."""
 import importlib, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
