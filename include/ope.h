@@ -594,6 +594,75 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
  * *n_out = the points; at most cap rows are written. */
 int ope_final_batch_inputs(ope_ctx *ctx, int which, int side, float *xyz, float *normals, size_t cap, size_t *n_out);
 
+/* ---------------- tracking: the reference's later frames ---------------- */
+/* Every frame after the first (rosinterface.cpp:264-313): the centroid of each cluster and of the source (the model as the
+ * previous frame aligned it) by pcl::compute3DCentroid, the first non-empty cluster within gate_distance gets
+ * estimateFinalPose(source, cluster); when none did and the LAST distance computed exceeds gate_distance, the candidate loop
+ * runs again from the original model. */
+enum {
+  OPE_TRACK_NO_CLUSTERS = 0,  /* no clusters: nothing runs */
+  OPE_TRACK_GATED = 1,        /* gate.selected is the first non-empty cluster with distance < gate_distance */
+  OPE_TRACK_REALIGN_ALL = 2,  /* no cluster gated and the last distance > gate_distance: the candidate loop from the model */
+  OPE_TRACK_NOTHING = 3,      /* no cluster gated and the last distance <= gate_distance (an empty last cluster, say): nothing */
+  OPE_TRACK_REALIGN_LOOP = 4  /* ope_track_pose only: REALIGN_ALL with fitness_fine <= coarse_fitness on entry, so the loop's
+                                 coarse stages would be skipped; nothing ran and the caller runs the loop one call at a time */
+};
+#define OPE_TRACK_COARSE_SKIPPED (-1) /* ope_track_result.coarse_status: fitness_fine <= coarse_fitness on entry */
+typedef struct {
+  double gate_distance;   /* 0.05: "distance < 0.05" (rosinterface.cpp:279), "distance > 0.05" (:304), float against double */
+  double coarse_fitness;  /* 1e-4: the coarse stage runs while fitnessScoreFine > 1e-4 (poseestimator.cpp:399) */
+  ope_final_params final; /* ope_final_default_params: the stages; accept_fitness 1e-4 / accept_strength 0.4 for the re-align */
+} ope_track_params;
+void ope_track_default_params(ope_track_params *p);
+typedef struct {
+  float centroid[3]; /* pcl::compute3DCentroid: the sequential float sum in the cloud's own order / count; 0 0 0 if count == 0 */
+  int32_t count;     /* points summed: all of a cluster's (is_dense), the source's finite ones (!is_dense) */
+  float distance;    /* (centroid - source centroid).lpNorm<2>() in float; 0 for the source itself */
+} ope_track_centroid;
+typedef struct {
+  int32_t branch;     /* OPE_TRACK_* */
+  int32_t selected;   /* the gated cluster, -1 unless GATED */
+  ope_track_centroid source;
+} ope_track_gate_result;
+/* The gate alone, synchronous on the context's stream.  Three launches and one synchronisation whatever n is (none for n == 0:
+ * NO_CLUSTERS).  centroids (n, may be NULL): each cluster's centroid, count and distance.  Clouds of any size. */
+int ope_track_gate(ope_ctx *ctx, const ope_cloud *source, size_t n, const ope_cloud *const *clusters, const ope_track_params *params,
+                   ope_track_gate_result *out, ope_track_centroid *centroids);
+
+typedef struct {
+  ope_track_gate_result gate; /* the branch taken (REALIGN_LOOP included) */
+  int32_t selected;           /* GATED: the gated cluster; REALIGN_ALL: ope_final_pose_batch's selected; -1 otherwise */
+  int32_t coarse_status;      /* GATED: OPE_COARSE_* of the coarse stage, or OPE_TRACK_COARSE_SKIPPED */
+  uint64_t seed;              /* GATED: the SAC-IA stream it drew with (0: SAC-IA did not run) */
+  float coarse[16];           /* GATED, column-major: coarsePose, finePose, rigidmodelPose and finalPose = rigid * (coarse * fine) */
+  float fine[16];
+  float rigid[16];
+  float final_pose[16];
+  ope_icp_result icp;         /* GATED: the fine ICP (iterations, align_strength, ...); zeros without ICP */
+  double fitness;             /* GATED: getFitnessScore(final.fitness_max_range) of the fine pose; DBL_MAX without ICP */
+  int64_t fitness_n;
+  int32_t n_fine_src;         /* GATED: fine key points of the (moved) source and of the cluster */
+  int32_t n_fine_tgt;
+  int32_t status;             /* GATED: OPE_FINAL_* (OPE_FINAL_OK when the coarse stage was skipped and ICP ran) */
+  int32_t reserved;
+} ope_track_result;
+/* One later frame of the reference, synchronous on the context's stream.  model = the original model (the estimator's cloudModel),
+ * source = cloudSource (the model as the previous frame aligned it), fitness_fine / coarse_calls = the estimator's
+ * fitnessScoreFine and SAC-IA calls so far (the k-th call draws with final.coarse.sacia.seed + k).
+ *   GATED: estimateFinalPose(source, cluster): the coarse stage of ope_coarse_pose_batch when fitness_fine > coarse_fitness, the
+ *          fine preparation of ope_final_pose_batch (the source as it is when the coarse stage is skipped), the single-problem ICP
+ *          of ope_icp_run with getFitnessScore, the re-anchoring SVD fit of model to source over identity pairs; *aligned = a new
+ *          cloud (free it with ope_cloud_free): the source moved by the coarse, then the fine pose (pcl::transformPointCloud's
+ *          float arithmetic), the next frame's source.
+ *   REALIGN_ALL: ope_final_pose_batch(model, clusters) with the estimator's seeds; realign (n) receives its results.
+ *   REALIGN_LOOP, NOTHING, NO_CLUSTERS: nothing beyond the gate runs.
+ * centroids (n) may be NULL; realign is required for n > 0.  OPE_EINVAL, nothing launched: what ope_final_pose_batch refuses for
+ * (model, clusters) and, with fitness_fine > coarse_fitness, what the coarse stage refuses for (source, clusters); a model or
+ * source of more than OPE_COARSE_MAX_POINTS points. */
+int ope_track_pose(ope_ctx *ctx, const ope_cloud *model, const ope_cloud *source, double fitness_fine, int64_t coarse_calls, size_t n,
+                   const ope_cloud *const *clusters, const ope_track_params *params, ope_track_result *out, ope_track_centroid *centroids,
+                   ope_final_batch_result *realign, ope_cloud **aligned);
+
 #ifdef __cplusplus
 }
 #endif

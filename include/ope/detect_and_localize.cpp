@@ -10,12 +10,23 @@
 // --candidates: the scene files are the clusters of ONE first frame (rosinterface.cpp:243-262), checked by
 // PoseEstimator::estimateFinalPoseCandidates in one call; --candidates-loop: the same frame by the reference's loop of
 // estimateFinalPose.  Either prints `candidates selected <i> clusters <n>`, then one `frame 1 ...` line.
+//
+//   detect_and_localize --track <model.pcd> --frame <a.pcd> [<b.pcd> ...] [--frame ...] [--seed N] [--self-occluded] [--time]
+//   detect_and_localize --track-loop <model.pcd> --frame ... (same)
+// DetectAndLocalize's per-frame policy (rosinterface.cpp:226-313) over a sequence of camera frames, one --frame per frame with
+// that frame's clusters (none: an empty frame).  --track: ope::ObjectTracker::localize (the gate and the gated pose on the
+// device); --track-loop: ObjectTracker::localizeLoop (host compute3DCentroid and estimateFinalPose, as the reference writes it).
+// Per frame: `track frame <k> branch <b> selected <i> clusters <n>`, then the `frame ...` line; --time adds `time frame <k> ms <t>`
+// (host clock around the synchronised call).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include <chrono>
+
+#include "object_tracker.hpp"
 #include "pcd_io.hpp"
 #include "pose_estimator.hpp"
 
@@ -26,7 +37,76 @@ static void print16(const char *tag, const pcl::Matrix4f &m) {
   for (int i = 0; i < 16; ++i) std::printf(" %.9g", (double)m.m[i]);
 }
 
+static const char *branch_name(int b) {
+  switch (b) {
+    case ope::ObjectTracker::FIRST: return "FIRST";
+    case ope::ObjectTracker::GATED: return "GATED";
+    case ope::ObjectTracker::REALIGN: return "REALIGN";
+    case ope::ObjectTracker::NOTHING: return "NOTHING";
+    default: return "NO_CLUSTERS";
+  }
+}
+
+// --track / --track-loop
+static int track_main(int argc, char **argv) {
+  int mode = 0;   // 1: --track, 2: --track-loop
+  std::string model_path;
+  std::vector<std::vector<std::string>> frames;
+  uint64_t seed = 1;
+  bool self_occluded = false, timed = false;
+  for (int i = 1; i < argc; ++i) {
+    if ((!std::strcmp(argv[i], "--track") || !std::strcmp(argv[i], "--track-loop")) && i + 1 < argc) {
+      mode = !std::strcmp(argv[i], "--track") ? 1 : 2;
+      model_path = argv[++i];
+    } else if (!std::strcmp(argv[i], "--frame")) frames.emplace_back();
+    else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
+    else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
+    else if (!std::strcmp(argv[i], "--time")) timed = true;
+    else if (!frames.empty()) frames.back().push_back(argv[i]);
+    else { std::fprintf(stderr, "unexpected argument %s\n", argv[i]); return 2; }
+  }
+  if (!mode || frames.empty()) { std::fprintf(stderr, "usage: %s --track|--track-loop <model.pcd> --frame <cluster.pcd> ... [--frame ...]\n", argv[0]); return 2; }
+  typedef ope::PoseEstimator::PointT PointT;
+  pcl::PointCloud<PointT> model;
+  if (pcl::io::loadPCDFile(model_path, model) != 0) return 3;
+  ope::ObjectTracker tracker(model);
+  tracker.estimator().setSacIaSeed(seed);
+  tracker.estimator().setUseSelfOccludedRejector(self_occluded);
+  double fitnessScore = 10.0, alignedStrength = 0.0;   // rosinterface.h: kept across frames
+  for (size_t k = 0; k < frames.size(); ++k) {
+    std::vector<pcl::PointCloud<PointT>::Ptr> clusters;
+    for (const std::string &f : frames[k]) {
+      clusters.emplace_back(new pcl::PointCloud<PointT>);
+      if (pcl::io::loadPCDFile(f, *clusters.back()) != 0) return 3;
+    }
+    ope_ctx *ctx = pcl::default_context();
+    if (ctx) ope_ctx_sync(ctx);
+    const auto t0 = std::chrono::steady_clock::now();
+    const pcl::Matrix4f pose = mode == 1 ? tracker.localize(clusters, fitnessScore, alignedStrength)
+                                         : tracker.localizeLoop(clusters, fitnessScore, alignedStrength);
+    if (ctx) ope_ctx_sync(ctx);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const ope::PoseEstimator &e = tracker.estimator();
+    std::printf("track frame %zu branch %s selected %d clusters %zu\n", k + 1, branch_name(tracker.lastBranch()), tracker.lastSelected(),
+                clusters.size());
+    if (timed) std::printf("time frame %zu ms %.4f\n", k + 1, ms);
+    std::printf("frame %zu fitness %.12g strength %.12g coarse_calls %d icp_iterations %d", k + 1, fitnessScore, alignedStrength,
+                e.coarseCalls(), e.lastIcpIterations());
+    print16("final", pose);
+    print16("coarse", e.lastCoarsePose());
+    print16("fine", e.lastFinePose());
+    print16("rigid", e.lastRigidModelPose());
+    std::printf("\n");
+  }
+  const std::string out = model_path + ".tracked.pcd";
+  if (pcl::io::savePCDFile(out, tracker.source(), true) != 0) return 4;
+  std::printf("aligned %s\n", out.c_str());
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  for (int i = 1; i < argc; ++i)
+    if (!std::strcmp(argv[i], "--track") || !std::strcmp(argv[i], "--track-loop")) return track_main(argc, argv);
   std::vector<std::string> files;
   uint64_t seed = 1;
   bool self_occluded = false;

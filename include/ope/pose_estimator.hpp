@@ -214,7 +214,23 @@ class PoseEstimator {
       alignStrength = alignedStrength;
       return pose;
     }
-    const size_t last = sel >= 0 ? (size_t)sel : clusters.size() - 1;   // the last cluster the loop visits
+    return replayCandidates(p_sourceCloud, res, sel, fitnessScore, alignStrength, selected);
+  }
+
+  // ---- the narrow state hand-over of ope::ObjectTracker (object_tracker.hpp): what ope_track_pose needs on entry, and the
+  // replay of its results into this estimator exactly as the calls it stands for would have left it
+  double fineFitness() const { return fitnessScoreFine; }
+  uint64_t sacIaSeed() const { return sacia_seed_; }
+  bool useSelfOccludedRejector() const { return use_self_occluded_; }
+  // the coarse-skipped fine stage starts from alignedSource (:404): the tracker's device source must be that cloud
+  bool alignedSourceIs(const Cloud &c) const {
+    return c.size() == alignedSource->size() && (c.empty() || !std::memcmp(c.points.data(), alignedSource->points.data(), sizeof(PointT) * c.size()));
+  }
+  // estimateFinalPoseCandidates' batch, from its results: p_sourceCloud = the original model on entry
+  Matrix4f replayCandidates(Cloud::Ptr &p_sourceCloud, const std::vector<ope_final_batch_result> &res, int32_t sel, double &fitnessScore,
+                            double &alignStrength, int &selected) {
+    const Cloud original(*p_sourceCloud);
+    const size_t last = sel >= 0 ? (size_t)sel : res.size() - 1;   // the last cluster the loop visits
     int applied = -1;
     for (size_t i = 0; i <= last; ++i) {
       const ope_final_batch_result &r = res[i];
@@ -246,6 +262,37 @@ class PoseEstimator {
     }
     if (res[last].status == OPE_FINAL_EMPTY_TARGET) *p_sourceCloud = original;   // the loop's copy before an empty cluster
     selected = sel;
+    fitnessScore = fitnessScoreFine;
+    alignStrength = alignedStrength;
+    return finalPose;
+  }
+  // estimateFinalPose(p_sourceCloud, cluster) from ope_track_pose's GATED result (the rigid fit came from the device)
+  Matrix4f replayTrackedFrame(Cloud::Ptr &p_sourceCloud, const ope_track_result &r, double &fitnessScore, double &alignStrength) {
+    if (firstTimePose == 0) *cloudModel = *p_sourceCloud;
+    ++firstTimePose;
+    Matrix4f coarsePose = Matrix4f::Identity(), finePose = Matrix4f::Identity(), rigid = Matrix4f::Identity();
+    if (r.coarse_status != OPE_TRACK_COARSE_SKIPPED) {
+      std::memcpy(coarsePose.m, r.coarse, sizeof coarsePose.m);
+      if (r.coarse_status == OPE_COARSE_OK) {
+        ++coarse_calls_;
+        compat::transformPointCloud(*p_sourceCloud, *alignedSource, coarsePose);   // :66-70
+      } else {
+        *alignedSource = *p_sourceCloud;                                           // :40-45
+      }
+    }
+    if (r.status != OPE_FINAL_FEW_FINE_POINTS) {   // :354-363
+      std::memcpy(finePose.m, r.fine, sizeof finePose.m);
+      Cloud::Ptr moved(new Cloud);
+      compat::transformPointCloud(*alignedSource, *moved, finePose);
+      *alignedSource = *moved;
+      fitnessScoreFine = r.fitness;
+      alignedStrength = r.icp.align_strength;
+      last_icp_iterations_ = r.icp.iterations;
+    }
+    std::memcpy(rigid.m, r.rigid, sizeof rigid.m);
+    finalPose = rigid * (coarsePose * finePose);   // :421, :439
+    *p_sourceCloud = *alignedSource;               // :441
+    last_coarse_ = coarsePose; last_fine_ = finePose; last_rigid_ = rigid;
     fitnessScore = fitnessScoreFine;
     alignStrength = alignedStrength;
     return finalPose;

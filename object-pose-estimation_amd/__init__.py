@@ -30,6 +30,10 @@ COARSE_OK, COARSE_EMPTY_TARGET, COARSE_FEW_TARGET_FEATURES = 0, 1, 2
 COARSE_MAX_POINTS, COARSE_MAX_KEYS = 65536, 4096
 # ope_final_batch_result.status
 FINAL_OK, FINAL_EMPTY_TARGET, FINAL_FEW_TARGET_FEATURES, FINAL_FEW_FINE_POINTS = 0, 1, 2, 3
+# ope_track_gate_result.branch; ope_track_result.coarse_status when the coarse stage was skipped
+TRACK_NO_CLUSTERS, TRACK_GATED, TRACK_REALIGN_ALL, TRACK_NOTHING, TRACK_REALIGN_LOOP = 0, 1, 2, 3, 4
+TRACK_BRANCH_NAMES = ["NO_CLUSTERS", "GATED", "REALIGN_ALL", "NOTHING", "REALIGN_LOOP"]
+TRACK_COARSE_SKIPPED = -1
 CERT_AUTO, CERT_OFF, CERT_ALWAYS = 0, 1, 2   # ope_icp_params.skip_certificates
 NUM_SUMS, NUM_SUMS_MAX = 17, 44
 COMM_ID_BYTES = 128
@@ -164,6 +168,50 @@ class FinalBatchResult(C.Structure):
     ]
 
 
+class TrackParams(C.Structure):
+    _fields_ = [
+        ("gate_distance", C.c_double),
+        ("coarse_fitness", C.c_double),
+        ("final", FinalParams),
+    ]
+
+
+class TrackCentroid(C.Structure):
+    _fields_ = [
+        ("centroid", C.c_float * 3),
+        ("count", C.c_int32),
+        ("distance", C.c_float),
+    ]
+
+
+class TrackGateResult(C.Structure):
+    _fields_ = [
+        ("branch", C.c_int32),
+        ("selected", C.c_int32),
+        ("source", TrackCentroid),
+    ]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [
+        ("gate", TrackGateResult),
+        ("selected", C.c_int32),
+        ("coarse_status", C.c_int32),
+        ("seed", C.c_uint64),
+        ("coarse", C.c_float * 16),
+        ("fine", C.c_float * 16),
+        ("rigid", C.c_float * 16),
+        ("final_pose", C.c_float * 16),
+        ("icp", IcpResult),
+        ("fitness", C.c_double),
+        ("fitness_n", C.c_int64),
+        ("n_fine_src", C.c_int32),
+        ("n_fine_tgt", C.c_int32),
+        ("status", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
 _dp = C.POINTER(C.c_double)
@@ -254,6 +302,11 @@ ABI = [
     ("ope_final_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(FinalParams), C.POINTER(C.c_uint64),
                                         C.POINTER(FinalBatchResult), _ip]),
     ("ope_final_batch_inputs", C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_track_default_params", None, [C.POINTER(TrackParams)]),
+    ("ope_track_gate", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(TrackParams), C.POINTER(TrackGateResult),
+                                  C.POINTER(TrackCentroid)]),
+    ("ope_track_pose", C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int64, C.c_size_t, C.POINTER(_vp), C.POINTER(TrackParams),
+                                  C.POINTER(TrackResult), C.POINTER(TrackCentroid), C.POINTER(FinalBatchResult), C.POINTER(_vp)]),
 ]
 
 _lib = None
@@ -346,6 +399,52 @@ class FinalOut:
     n_fine_tgt: int        # ... and of the cluster
     status: int            # FINAL_OK, FINAL_EMPTY_TARGET, FINAL_FEW_TARGET_FEATURES or FINAL_FEW_FINE_POINTS
     accepted: bool         # fitness < accept_fitness or align strength > accept_strength
+
+
+@dataclass
+class GateOut:
+    branch: int                # TRACK_NO_CLUSTERS, TRACK_GATED, TRACK_REALIGN_ALL, TRACK_NOTHING (track_pose: TRACK_REALIGN_LOOP)
+    selected: int              # the gated cluster, -1 unless TRACK_GATED
+    source_centroid: np.ndarray   # (3,) float32, pcl::compute3DCentroid of the source (finite points)
+    source_count: int
+    centroids: np.ndarray      # (n, 3) float32, each cluster's centroid (all its points)
+    counts: np.ndarray         # (n,) int32
+    distances: np.ndarray      # (n,) float32, to the source centroid
+
+
+@dataclass
+class TrackOut:
+    gate: GateOut
+    selected: int              # GATED: the gated cluster; REALIGN_ALL: final_pose_batch's selected; -1 otherwise
+    coarse: np.ndarray | None  # GATED: (4,4) float32 coarsePose, finePose, rigidmodelPose, finalPose = rigid * (coarse * fine)
+    fine: np.ndarray | None
+    rigid: np.ndarray | None
+    final: np.ndarray | None
+    coarse_status: int         # GATED: COARSE_* or TRACK_COARSE_SKIPPED
+    seed: int                  # GATED: the SAC-IA stream (0: SAC-IA did not run)
+    icp: IcpBatchOut | None    # GATED: the fine ICP with its fitness; None unless it ran
+    n_fine_src: int
+    n_fine_tgt: int
+    status: int                # GATED: FINAL_*
+    realign: list | None       # REALIGN_ALL: [FinalOut per cluster], as final_pose_batch returns them
+    aligned: "Cloud | None"    # GATED: the source moved by the coarse, then the fine pose, on the device (the next source)
+
+
+def _gate_out(g: "TrackGateResult", cent, n: int) -> GateOut:
+    return GateOut(g.branch, g.selected, np.array(g.source.centroid, np.float32), g.source.count,
+                   np.array([list(c.centroid) for c in cent[:n]], np.float32).reshape(n, 3),
+                   np.array([c.count for c in cent[:n]], np.int32), np.array([c.distance for c in cent[:n]], np.float32))
+
+
+def _final_out(o) -> FinalOut:
+    c = o.coarse
+    co = CoarseOut(from_colmajor(np.frombuffer(c.T, np.float32)), c.best_error, c.best_iteration, c.n_src_keys, c.n_tgt_keys, c.status)
+    fine = None
+    if o.status in (FINAL_OK, FINAL_FEW_TARGET_FEATURES):
+        r = o.fine.result
+        fine = IcpBatchOut(from_colmajor(np.frombuffer(o.fine.T, np.float32)), r.iterations, bool(r.converged), r.state, r.last_mse,
+                           r.n_corr, r.align_strength, o.fine.fitness, o.fine.fitness_n)
+    return FinalOut(co, o.seed, fine, o.n_fine_src, o.n_fine_tgt, o.status, bool(o.accepted))
 
 
 class Context:
@@ -576,17 +675,42 @@ class Context:
         out = (FinalBatchResult * max(n, 1))()
         sel = C.c_int32(-1)
         self._chk(lib().ope_final_pose_batch(self.h, model.h, n, hc, C.byref(p), sd, out, C.byref(sel)))
-        res = []
-        for o in out[:n]:
-            c = o.coarse
-            co = CoarseOut(from_colmajor(np.frombuffer(c.T, np.float32)), c.best_error, c.best_iteration, c.n_src_keys, c.n_tgt_keys, c.status)
-            fine = None
-            if o.status in (FINAL_OK, FINAL_FEW_TARGET_FEATURES):
-                r = o.fine.result
-                fine = IcpBatchOut(from_colmajor(np.frombuffer(o.fine.T, np.float32)), r.iterations, bool(r.converged), r.state, r.last_mse,
-                                   r.n_corr, r.align_strength, o.fine.fitness, o.fine.fitness_n)
-            res.append(FinalOut(co, o.seed, fine, o.n_fine_src, o.n_fine_tgt, o.status, bool(o.accepted)))
+        res = [_final_out(o) for o in out[:n]]
         return res, sel.value
+
+    def track_gate(self, source: "Cloud", clusters, params: TrackParams | None = None) -> GateOut:
+        """ope_track_gate: the centroid gate of the reference's later frames (rosinterface.cpp:264-304)."""
+        n = len(clusters)
+        hc = (_vp * max(n, 1))(*[c.h for c in clusters])
+        out = TrackGateResult()
+        cent = (TrackCentroid * max(n, 1))()
+        self._chk(lib().ope_track_gate(self.h, source.h, n, hc, C.byref(params) if params else None, C.byref(out), cent))
+        return _gate_out(out, cent, n)
+
+    def track_pose(self, model: "Cloud", source: "Cloud", clusters, fitness_fine: float = 10.0, coarse_calls: int = 0,
+                   params: TrackParams | None = None) -> TrackOut:
+        """ope_track_pose: one later frame of the reference (the gate, then the gated estimateFinalPose or the re-align).
+        fitness_fine / coarse_calls: the estimator's state on entry (a fresh one: 10.0 and 0)."""
+        n = len(clusters)
+        hc = (_vp * max(n, 1))(*[c.h for c in clusters])
+        out = TrackResult()
+        cent = (TrackCentroid * max(n, 1))()
+        re = (FinalBatchResult * max(n, 1))()
+        h = _vp()
+        self._chk(lib().ope_track_pose(self.h, model.h, source.h, float(fitness_fine), int(coarse_calls), n, hc,
+                                       C.byref(params) if params else None, C.byref(out), cent, re, C.byref(h)))
+        gate = _gate_out(out.gate, cent, n)
+        gated = out.gate.branch == TRACK_GATED
+        mat = (lambda t: from_colmajor(np.frombuffer(t, np.float32))) if gated else (lambda t: None)
+        icp = None
+        if gated and out.status in (FINAL_OK, FINAL_FEW_TARGET_FEATURES):
+            r = out.icp
+            icp = IcpBatchOut(mat(out.fine), r.iterations, bool(r.converged), r.state, r.last_mse, r.n_corr, r.align_strength,
+                              out.fitness, out.fitness_n)
+        realign = [_final_out(o) for o in re[:n]] if out.gate.branch == TRACK_REALIGN_ALL else None
+        aligned = Cloud(self, h, source.n) if h.value else None
+        return TrackOut(gate, out.selected, mat(out.coarse), mat(out.fine), mat(out.rigid), mat(out.final_pose), out.coarse_status,
+                        out.seed, icp, out.n_fine_src, out.n_fine_tgt, out.status, realign, aligned)
 
     def final_batch_inputs(self, which: int, side: int):
         """The fine inputs the last final_pose_batch prepared for cluster `which`: side 0 the moved model, 1 the cluster.
@@ -866,6 +990,15 @@ def default_coarse_params(**kw) -> CoarseParams:
             p.viewpoint[:] = [float(x) for x in v]
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_track_params(**kw) -> TrackParams:
+    """ope_track_default_params (gate 0.05, coarse stage above 1e-4, the final stages' defaults); keyword arguments set fields."""
+    p = TrackParams()
+    lib().ope_track_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 

@@ -395,16 +395,11 @@ int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const 
 
 }  // extern "C"
 
-int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params *params,
-                                const uint64_t *seeds, bool seed_by_rank, ope_coarse_batch_result *out, uint64_t *seeds_used) {
+// ope_coarse_pose_batch's refusals (n >= 1, clusters not NULL checked by the caller), before anything is launched: parameters,
+// sizes, and the key points of every cloud that could exceed the cap.  *model_keys = the model's key points.
+int ope::coarse_batch_check(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params &p,
+                            long long *model_keys) {
   static const char *who = "ope_coarse_pose_batch: ";
-  if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_coarse_pose_batch: bad argument");
-  if (n == 0) return OPE_OK;
-  if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
-  if (n > 65535) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 65535 clusters (one grid row each)");
-  ope_coarse_params p;
-  ope_coarse_default_params(&p);
-  if (params) p = *params;
   const int S = p.sacia.nr_samples, K = p.sacia.k_correspondences, H = p.sacia.max_iterations;
   if (!(p.key_leaf > 0) || !(p.fpfh_radius > 0)) return set_err(ctx, OPE_EINVAL, std::string(who) + "key_leaf and fpfh_radius must be > 0");
   if (p.normals_k < 1 || p.normals_k > kKnnMaxK) return set_err(ctx, OPE_EINVAL, std::string(who) + "1 <= normals_k <= 32");
@@ -417,7 +412,7 @@ int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, 
   const size_t nseg = n + 1;
   const float inv = 1.0f / p.key_leaf;
   auto cloud_of = [&](size_t s) { return s == 0 ? model : clusters[s - 1]; };
-  long long model_keys = -2;
+  long long mk = -2;
   for (size_t s = 0; s < nseg; ++s) {
     const ope_cloud *c = cloud_of(s);
     const std::string at = s == 0 ? std::string(" (model)") : " (cluster " + std::to_string(s - 1) + ")";
@@ -428,12 +423,32 @@ int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, 
       const long long kc = host_key_count(c, inv);
       if (kc < 0) return set_err(ctx, OPE_EINVAL, std::string(who) + "leaf size too small for the input dataset" + at);
       if (kc > OPE_COARSE_MAX_KEYS) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than OPE_COARSE_MAX_KEYS key points" + at);
-      if (s == 0) model_keys = kc;
+      if (s == 0) mk = kc;
     } else if (c->n_valid > 0 && host_key_count(c, inv) < 0) {
       return set_err(ctx, OPE_EINVAL, std::string(who) + "leaf size too small for the input dataset" + at);
     }
   }
-  if (model_keys < S) return set_err(ctx, OPE_EINVAL, std::string(who) + "the model has fewer key points than nr_samples");
+  if (mk < S) return set_err(ctx, OPE_EINVAL, std::string(who) + "the model has fewer key points than nr_samples");
+  if (model_keys) *model_keys = mk;
+  return OPE_OK;
+}
+
+int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params *params,
+                                const uint64_t *seeds, bool seed_by_rank, ope_coarse_batch_result *out, uint64_t *seeds_used) {
+  static const char *who = "ope_coarse_pose_batch: ";
+  if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_coarse_pose_batch: bad argument");
+  if (n == 0) return OPE_OK;
+  if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
+  if (n > 65535) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 65535 clusters (one grid row each)");
+  ope_coarse_params p;
+  ope_coarse_default_params(&p);
+  if (params) p = *params;
+  const int S = p.sacia.nr_samples, K = p.sacia.k_correspondences, H = p.sacia.max_iterations;
+  long long model_keys = -2;
+  { const int rc = coarse_batch_check(ctx, model, n, clusters, p, &model_keys); if (rc != OPE_OK) return rc; }
+  const size_t nseg = n + 1;
+  const float inv = 1.0f / p.key_leaf;
+  auto cloud_of = [&](size_t s) { return s == 0 ? model : clusters[s - 1]; };
 
   OPE_HIP(ctx, hipSetDevice(ctx->device));
   TraceRange r_all(ctx, "coarse_batch");

@@ -65,4 +65,26 @@ long long host_key_count(const ope_cloud *c, float inv);
 int coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params *params,
                            const uint64_t *seeds, bool seed_by_rank, ope_coarse_batch_result *out, uint64_t *seeds_used);
 
+// coarse_pose_batch_impl's refusals, before anything is launched (n >= 1); *model_keys = the model's key points (optional)
+int coarse_batch_check(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params &p,
+                       long long *model_keys);
+
+// final_batch.hip: ope_final_pose_batch's refusals before anything is launched, and its fine preparation (steps 1-4: move,
+// sample, normals, NaN-normal drop and upload order, target trees) of n (model, cluster) pairs.  Segment s < n is the model moved
+// by coarse[s].T when coarse[s].status == OPE_COARSE_OK (as it is otherwise), segment n + i cluster i; per segment its fine
+// points at d_fxyz / d_fnrm + key_off[s] (cnt[s] of them, box fbox[6s..6s+5]); status[i] = OPE_FINAL_*, icp_of = the clusters
+// that run a fine ICP, trees[a] the target tree of icp_of[a].  who: the entry point its errors name.
+struct FinePrep {
+  std::vector<uint32_t> key_off, cnt;
+  std::vector<float> fbox;
+  std::vector<int32_t> status;
+  std::vector<size_t> icp_of;
+  std::vector<BvhBatchTree> trees;
+  uint32_t nkeys = 0;
+  float4 *d_fxyz = nullptr, *d_fnrm = nullptr;
+};
+int final_batch_check(ope_ctx *ctx, size_t n, const ope_cloud *const *clusters, const ope_final_params &p);
+int final_fine_prepare(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                       const ope_final_params &p, const ope_coarse_batch_result *coarse, FinePrep &out);
+
 }  // namespace ope

@@ -190,44 +190,10 @@ __global__ __launch_bounds__(kCoarseBlock) void fine_order_kernel(const float4 *
 
 }  // namespace
 
-}  // namespace ope
-
-using namespace ope;
-
-extern "C" {
-
-void ope_final_default_params(ope_final_params *p) {
-  if (!p) return;
-  std::memset(p, 0, sizeof *p);
-  ope_coarse_default_params(&p->coarse);
-  p->fine_leaf = 0.008f;
-  p->fine_normals_k = 30;
-  p->min_fine_points = 100;
-  ope_icp_default_params(&p->icp);
-  p->icp.max_iterations = 100;
-  p->icp.transformation_epsilon = 1e-8;
-  p->icp.euclidean_fitness_epsilon = 1e-8;
-  p->icp.corr_mode = OPE_CORR_NORMAL_SHOOTING;
-  p->icp.k_normal_shooting = 20;
-  p->icp.use_surface_normal_rej = 1;
-  p->icp.surface_normal_thr = 0.7;
-  p->fitness_max_range = DBL_MAX;
-  p->accept_fitness = 1e-4;
-  p->accept_strength = 0.4;
-}
-
-int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_final_params *params,
-                         const uint64_t *seeds, ope_final_batch_result *out, int32_t *selected) {
+// ope_final_pose_batch's refusals before anything is launched (n >= 1): parameters, and the clusters' sizes and fine key points
+// (the moved models' can only be counted after sampling)
+int final_batch_check(ope_ctx *ctx, size_t n, const ope_cloud *const *clusters, const ope_final_params &p) {
   static const char *who = "ope_final_pose_batch: ";
-  if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_final_pose_batch: bad argument");
-  if (selected) *selected = -1;
-  ctx->final_off.clear();   // (ope_final_batch_inputs reports "no call yet" unless this call succeeds)
-  if (n == 0) return OPE_OK;
-  if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
-  if (n > 65535) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 65535 clusters (one grid row each)");
-  ope_final_params p;
-  ope_final_default_params(&p);
-  if (params) p = *params;
   if (!(p.fine_leaf > 0)) return set_err(ctx, OPE_EINVAL, std::string(who) + "fine_leaf must be > 0");
   if (p.fine_normals_k < 1 || p.fine_normals_k > kKnnMaxK) return set_err(ctx, OPE_EINVAL, std::string(who) + "1 <= fine_normals_k <= 32");
   { const int rc = icp_batch_check_params(ctx, p.icp); if (rc != OPE_OK) return rc; }
@@ -245,15 +211,21 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
     if (kc > OPE_COARSE_MAX_KEYS) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than OPE_COARSE_MAX_KEYS fine key points" + at);
   }
 
-  // ---- 0. the coarse stage (its own refusals come before it launches anything)
-  std::vector<ope_coarse_batch_result> coarse(n);
-  std::vector<uint64_t> seed_used(n, 0);
-  {
-    const int rc = coarse_pose_batch_impl(ctx, model, n, clusters, &p.coarse, seeds, seeds == nullptr, coarse.data(), seed_used.data());
-    if (rc != OPE_OK) return rc;
-  }
-  OPE_HIP(ctx, hipSetDevice(ctx->device));
-  TraceRange r_all(ctx, "final_batch");
+  return OPE_OK;
+}
+
+// Steps 1-4 of ope_final_pose_batch for n (model, cluster) pairs: segment i < n is the model moved by coarse[i].T when
+// coarse[i].status == OPE_COARSE_OK (as it is otherwise), segment n + i cluster i.  Buffers come from tmp.
+int final_fine_prepare(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                       const ope_final_params &p, const ope_coarse_batch_result *coarse, FinePrep &out) {
+  const float inv = 1.0f / p.fine_leaf;
+  std::vector<uint32_t> &key_off = out.key_off, &cnt = out.cnt;
+  std::vector<float> &fbox = out.fbox;
+  std::vector<int32_t> &status = out.status;
+  std::vector<size_t> &icp_of = out.icp_of;
+  std::vector<BvhBatchTree> &trees = out.trees;
+  uint32_t &nkeys = out.nkeys;
+  float4 *&d_fxyz = out.d_fxyz, *&d_fnrm = out.d_fnrm;
   const size_t nseg = 2 * n;
   std::vector<FineIn> fin(nseg);
   std::vector<CoarseSeg> segs(nseg);
@@ -269,7 +241,6 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
   }
   const uint32_t total = off[nseg];
 
-  CallTmp tmp{ctx->stream, {}};
   hipError_t e = hipSuccess;
   auto fail = [&](const char *what) { return set_err(ctx, OPE_EHIP, std::string(who) + what + ": " + hipGetErrorString(e)); };
   auto *d_fin = (FineIn *)tmp.get(sizeof(FineIn) * nseg, e);
@@ -315,7 +286,6 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
   }
 
   // ---- 2. uniform sampling (one synchronisation: the key counts), refusals, normals
-  std::vector<uint32_t> key_off;
   float4 *d_kp = nullptr;
   uint32_t *d_key_off = nullptr;
   uint32_t bad = 0;   // (comes back with the key offsets)
@@ -326,7 +296,7 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
   }
   if (bad & 2u) return set_err(ctx, OPE_EINVAL, std::string(who) + "a coarse pose moves a finite model point out of float range");
   if (bad & 1u) return set_err(ctx, OPE_EINVAL, std::string(who) + "fine_leaf too small for a moved model");
-  const uint32_t nkeys = key_off[nseg];
+  nkeys = key_off[nseg];
   uint32_t max_keys = 0;
   for (size_t s = 0; s < nseg; ++s) {
     const uint32_t m = key_off[s + 1] - key_off[s];
@@ -341,8 +311,8 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
   const size_t nk1 = std::max<size_t>(nkeys, 1);
   auto *d_tiles = (int2 *)tmp.get(sizeof(int2) * std::max<size_t>(tiles.size(), 1), e);
   auto *d_nrm = (float4 *)tmp.get(16 * nk1, e);
-  auto *d_fxyz = (float4 *)tmp.get(16 * nk1, e);
-  auto *d_fnrm = (float4 *)tmp.get(16 * nk1, e);
+  d_fxyz = (float4 *)tmp.get(16 * nk1, e);
+  d_fnrm = (float4 *)tmp.get(16 * nk1, e);
   auto *d_cnt = (uint32_t *)tmp.get(4 * nseg + 4 * 6 * nseg, e);
   if (e == hipSuccess && !tiles.empty()) e = h2d_copy(ctx->stream, d_tiles, tiles.data(), sizeof(int2) * tiles.size());
   if (e != hipSuccess) return fail("buffers");
@@ -359,8 +329,8 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
     hipLaunchKernelGGL(fine_order_kernel, dim3((unsigned)nseg), dim3(kCoarseBlock), 0, ctx->stream, d_kp, d_nrm, d_key_off, d_fxyz, d_fnrm, d_cnt,
                        d_fbox);
   }
-  std::vector<uint32_t> cnt(nseg);
-  std::vector<float> fbox(6 * nseg);
+  cnt.assign(nseg, 0u);
+  fbox.assign(6 * nseg, 0.f);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, 4 * nseg, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(fbox.data(), d_fbox, 4 * 6 * nseg, hipMemcpyDeviceToHost, ctx->stream);
@@ -368,8 +338,8 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
   if (e != hipSuccess) return fail("fine clouds");
 
   // ---- 4. the target trees of every cluster that runs ICP
-  std::vector<int32_t> status(n);
-  std::vector<size_t> icp_of;   // problem -> cluster
+  status.assign(n, 0);
+  icp_of.clear();
   for (size_t i = 0; i < n; ++i) {
     const uint32_t nt = cnt[n + i];
     if (clusters[i]->n == 0) status[i] = OPE_FINAL_EMPTY_TARGET;
@@ -378,11 +348,10 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
     if (status[i] == OPE_FINAL_OK || status[i] == OPE_FINAL_FEW_TARGET_FEATURES) icp_of.push_back(i);
   }
   const size_t np = icp_of.size();
-  std::vector<ope_icp_batch_result> icp_out(std::max<size_t>(np, 1));
   if (np) {
     ope_index_params ip;
     ope_index_default_params(&ip);
-    std::vector<BvhBatchTree> trees(np);
+    trees.assign(np, BvhBatchTree{});
     std::vector<size_t> node_off(np), pts_off(np);
     size_t nodes_total = 0, pts_total = 0;
     int max_depth = bvh_depth(OPE_COARSE_MAX_KEYS, ip.leaf_size);   // the fit launches of any batch: those of the deepest tree allowed
@@ -422,6 +391,76 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
     }
     if (e != hipSuccess) return fail("index build");
 
+  }
+  return OPE_OK;
+}
+
+}  // namespace ope
+
+using namespace ope;
+
+extern "C" {
+
+void ope_final_default_params(ope_final_params *p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  ope_coarse_default_params(&p->coarse);
+  p->fine_leaf = 0.008f;
+  p->fine_normals_k = 30;
+  p->min_fine_points = 100;
+  ope_icp_default_params(&p->icp);
+  p->icp.max_iterations = 100;
+  p->icp.transformation_epsilon = 1e-8;
+  p->icp.euclidean_fitness_epsilon = 1e-8;
+  p->icp.corr_mode = OPE_CORR_NORMAL_SHOOTING;
+  p->icp.k_normal_shooting = 20;
+  p->icp.use_surface_normal_rej = 1;
+  p->icp.surface_normal_thr = 0.7;
+  p->fitness_max_range = DBL_MAX;
+  p->accept_fitness = 1e-4;
+  p->accept_strength = 0.4;
+}
+
+int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_final_params *params,
+                         const uint64_t *seeds, ope_final_batch_result *out, int32_t *selected) {
+  static const char *who = "ope_final_pose_batch: ";
+  if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_final_pose_batch: bad argument");
+  if (selected) *selected = -1;
+  ctx->final_off.clear();   // (ope_final_batch_inputs reports "no call yet" unless this call succeeds)
+  if (n == 0) return OPE_OK;
+  if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
+  if (n > 65535) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 65535 clusters (one grid row each)");
+  ope_final_params p;
+  ope_final_default_params(&p);
+  if (params) p = *params;
+  { const int rc = final_batch_check(ctx, n, clusters, p); if (rc != OPE_OK) return rc; }
+
+  // ---- 0. the coarse stage (its own refusals come before it launches anything)
+  std::vector<ope_coarse_batch_result> coarse(n);
+  std::vector<uint64_t> seed_used(n, 0);
+  {
+    const int rc = coarse_pose_batch_impl(ctx, model, n, clusters, &p.coarse, seeds, seeds == nullptr, coarse.data(), seed_used.data());
+    if (rc != OPE_OK) return rc;
+  }
+  OPE_HIP(ctx, hipSetDevice(ctx->device));
+  TraceRange r_all(ctx, "final_batch");
+  const size_t nseg = 2 * n;
+  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  CallTmp tmp{ctx->stream, {}};
+  FinePrep fp;
+  { const int rc = final_fine_prepare(ctx, tmp, who, model, n, clusters, p, coarse.data(), fp); if (rc != OPE_OK) return rc; }
+  const std::vector<uint32_t> &key_off = fp.key_off, &cnt = fp.cnt;
+  const std::vector<float> &fbox = fp.fbox;
+  const std::vector<int32_t> &status = fp.status;
+  const std::vector<size_t> &icp_of = fp.icp_of;
+  const std::vector<BvhBatchTree> &trees = fp.trees;
+  const uint32_t nkeys = fp.nkeys;
+  float4 *const d_fxyz = fp.d_fxyz, *const d_fnrm = fp.d_fnrm;
+  hipError_t e = hipSuccess;
+  auto fail = [&](const char *what) { return set_err(ctx, OPE_EHIP, std::string(who) + what + ": " + hipGetErrorString(e)); };
+  const size_t np = icp_of.size();
+  std::vector<ope_icp_batch_result> icp_out(std::max<size_t>(np, 1));
+  if (np) {
     // ---- 5. the fine ICP: ope_icp_run_batch on clouds and indexes that view these buffers
     std::vector<ope_cloud> src_v(np);
     std::vector<ope_index> tgt_v(np);
