@@ -663,6 +663,53 @@ int ope_track_pose(ope_ctx *ctx, const ope_cloud *model, const ope_cloud *source
                    const ope_cloud *const *clusters, const ope_track_params *params, ope_track_result *out, ope_track_centroid *centroids,
                    ope_final_batch_result *realign, ope_cloud **aligned);
 
+/* ---------------- segmentation: Euclidean cluster extraction ---------------- */
+/* ObjectSegmentationPlane::getClusters (DetectAndLocalize/src/objectsegmentationplane.cpp:79-93): pcl::EuclideanClusterExtraction
+ * of the non-plane cloud, the cloudClusterVector rosinterface.cpp:243-320 loops over. */
+typedef struct {
+  double tolerance; /* setClusterTolerance: 0.05 (objectsegmentationplane.cpp:85) */
+  int32_t min_size; /* setMinClusterSize: 300 (:86) */
+  int32_t max_size; /* setMaxClusterSize(1e5): 100000 (:87) */
+} ope_cluster_params;
+void ope_cluster_default_params(ope_cluster_params *p);
+/* What EuclideanClusterExtraction::extract returns (PCL 1.7/1.8 extract_clusters.hpp): the connected components of the graph
+ * that joins two finite points iff d2 <= r2, with d2 = (dx*dx + dy*dy) + dz*dz in float (FLANN's order, no contraction) and
+ * r2 = (float)((double)(float)tolerance * (double)(float)tolerance) (PCL casts the tolerance to float, KdTreeFLANN squares it
+ * in double).
+ *  - a non-finite point is a component of its own (PCL's tree does not hold it): kept only when min_size <= 1;
+ *  - a component with fewer than min_size or more than max_size points is dropped whole;
+ *  - the points of a cluster are ORIGINAL indices, ascending;
+ *  - clusters come by size, descending, then by their smallest index, ascending.  This is PCL's order (std::sort of
+ *    comparePointClusters over reverse iterators) for up to 16 clusters, where libstdc++'s insertion sort is stable; beyond 16,
+ *    PCL's order among equal sizes is implementation-defined and this rule is kept;
+ *  - unlike PCL, two exact duplicates with no other neighbour are one cluster (PCL's search skips the first sorted radius
+ *    result as if it were the query, so such a pair can come out as two singletons).
+ * *n_clusters = the full count; the first min(count, max_clusters) clusters are written: cluster k is
+ * out_idx[out_offsets[k] .. out_offsets[k + 1]) (out_idx: room for every point; out_offsets: max_clusters + 1).  out_label
+ * (optional, n, ORIGINAL order): the rank of the written cluster holding the point, -1 for every other point.
+ * Synchronous; kernel launches and host synchronisations do not depend on the number of clusters (one synchronisation).
+ * An empty cloud gives 0 clusters.  OPE_EINVAL, nothing launched: tolerance <= 0 (or not finite), min_size < 1,
+ * max_size < min_size, more than 2^31 - 1 points.  OPE_ERANGE, nothing launched: a cloud whose grid of cells of edge
+ * 0.999 x tolerance / sqrt(3) over its finite points would have 2^36 cells or more along one axis (40 000 km at a 1 mm
+ * tolerance) or 2^62 or more in all (a cube of 960 m at 1 mm); grids of more than 2^32 cells are fine. */
+int ope_euclidean_clusters(ope_ctx *ctx, const ope_cloud *cloud, const ope_cluster_params *params, size_t max_clusters, size_t *n_clusters,
+                           int32_t *out_idx, int32_t *out_offsets, int32_t *out_label);
+/* The same, with each written cluster also as a new device cloud: out_clouds[k] is exactly what ope_cloud_select(cloud,
+ * indices of cluster k) builds (its original order the cluster's ascending indices, normals carried, the Morton order of
+ * ope_cloud_upload over its own box), made for all clusters at once in batched launches; free each with ope_cloud_free.
+ * out_clouds: max_clusters entries; out_idx / out_offsets optional (as above).  Two synchronisations. */
+int ope_euclidean_clusters_cloud(ope_ctx *ctx, const ope_cloud *cloud, const ope_cluster_params *params, size_t max_clusters, size_t *n_clusters,
+                                 ope_cloud **out_clouds, int32_t *out_idx, int32_t *out_offsets);
+/* What the last ope_euclidean_clusters* call of this context did: kernel launches enqueued (a rocPRIM sort or scan counts as
+ * one), host synchronisations, occupied grid cells, and cell pairs whose points were compared. */
+typedef struct {
+  int64_t launches;
+  int64_t host_syncs;
+  int64_t cells;
+  int64_t pairs_tested;
+} ope_cluster_stats;
+int ope_cluster_last_stats(const ope_ctx *ctx, ope_cluster_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,11 @@
 // PoseEstimator::estimateFinalPoseCandidates in one call; --candidates-loop: the same frame by the reference's loop of
 // estimateFinalPose.  Either prints `candidates selected <i> clusters <n>`, then one `frame 1 ...` line.
 //
+//   detect_and_localize --segment <model.pcd> <not_plane.pcd> [--seed N] [--self-occluded]
+// The first frame from the non-plane cloud: ObjectSegmentationPlane::getClusters as the reference writes it
+// (pcl::EuclideanClusterExtraction, tolerance 0.05, 300 .. 1e5 points), each cluster copied by index (rosinterface.cpp:246-255),
+// then the clusters as --candidates takes them.  Prints `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
+//
 //   detect_and_localize --track <model.pcd> --frame <a.pcd> [<b.pcd> ...] [--frame ...] [--seed N] [--self-occluded] [--time]
 //   detect_and_localize --track-loop <model.pcd> --frame ... (same)
 // DetectAndLocalize's per-frame policy (rosinterface.cpp:226-313) over a sequence of camera frames, one --frame per frame with
@@ -111,14 +116,16 @@ int main(int argc, char **argv) {
   uint64_t seed = 1;
   bool self_occluded = false;
   int candidates = 0;   // 1: estimateFinalPoseCandidates, 2: the reference's loop
+  bool segment = false; // --segment: the clusters come from getClusters over the one scene file (the non-plane cloud)
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--candidates")) candidates = 1;
     else if (!std::strcmp(argv[i], "--candidates-loop")) candidates = 2;
+    else if (!std::strcmp(argv[i], "--segment")) { segment = true; candidates = 1; }
     else files.push_back(argv[i]);
   }
-  if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded] [--candidates | --candidates-loop]\n", argv[0]); return 2; }
+  if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded] [--candidates | --candidates-loop | --segment]\n", argv[0]); return 2; }
   typedef ope::PoseEstimator::PointT PointT;
   pcl::PointCloud<PointT>::Ptr cloudSourceOriginal(new pcl::PointCloud<PointT>), cloudSource(new pcl::PointCloud<PointT>);
   if (pcl::io::loadPCDFile(files[0], *cloudSourceOriginal) != 0) return 3;   // rosinterface.cpp:80
@@ -137,7 +144,33 @@ int main(int argc, char **argv) {
   };
   if (candidates) {
     std::vector<pcl::PointCloud<PointT>::Ptr> clusters;
-    for (size_t k = 1; k < files.size(); ++k) {
+    if (segment) {
+      // ObjectSegmentationPlane::getClusters as the reference writes it (objectsegmentationplane.cpp:79-93), then each cluster's
+      // points copied by index (rosinterface.cpp:246-255)
+      pcl::PointCloud<PointT>::Ptr notPlane(new pcl::PointCloud<PointT>);
+      if (files.size() != 2 || pcl::io::loadPCDFile(files[1], *notPlane) != 0) return 3;
+      pcl::search::KdTree<PointT>::Ptr tree(new pcl::search::KdTree<PointT>);
+      std::vector<pcl::PointIndices> cluster_indices;
+      pcl::EuclideanClusterExtraction<PointT> ec;
+      ec.setClusterTolerance(0.05);
+      ec.setMinClusterSize(300);
+      ec.setMaxClusterSize(1e5);
+      ec.setSearchMethod(tree);
+      ec.setInputCloud(notPlane);
+      ec.extract(cluster_indices);
+      std::printf("segment clusters %zu sizes", cluster_indices.size());
+      for (const pcl::PointIndices &it : cluster_indices) {
+        pcl::PointCloud<PointT>::Ptr cloudCluster(new pcl::PointCloud<PointT>);
+        for (int pit : it.indices) cloudCluster->points.push_back(notPlane->points[pit]);
+        cloudCluster->width = (uint32_t)cloudCluster->points.size();
+        cloudCluster->height = 1;
+        cloudCluster->is_dense = true;
+        clusters.push_back(cloudCluster);
+        std::printf(" %zu", it.indices.size());
+      }
+      std::printf("\n");
+    }
+    for (size_t k = 1; !segment && k < files.size(); ++k) {
       clusters.emplace_back(new pcl::PointCloud<PointT>);
       if (pcl::io::loadPCDFile(files[k], *clusters.back()) != 0) return 3;
     }

@@ -766,6 +766,35 @@ template <class PointT> class StatisticalOutlierRemoval {
   double mul_ = 0.0;
 };
 
+struct PointIndices { std::vector<int> indices; };
+
+// ObjectSegmentationPlane::getClusters (objectsegmentationplane.cpp:79-93): the clusters of ope_euclidean_clusters, each as
+// ORIGINAL indices ascending, by size descending then smallest index (PCL's order; see ope.h for the one documented difference)
+template <class PointT> class EuclideanClusterExtraction {
+ public:
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &c) { input_ = c; }
+  template <class Tree> void setSearchMethod(const Tree &) {}   // accepted, unused: the device builds its own grid
+  void setClusterTolerance(double t) { p_.tolerance = t; }
+  void setMinClusterSize(int n) { p_.min_size = n; }
+  void setMaxClusterSize(int n) { p_.max_size = n; }
+  void extract(std::vector<PointIndices> &clusters) {
+    clusters.clear();
+    ope_ctx *ctx = default_context();
+    if (!ctx || !input_ || input_->empty()) return;
+    auto dev = upload(*input_, false);
+    if (!dev->h) return;
+    const size_t n = input_->size();
+    std::vector<int32_t> idx(n), off(n + 1);
+    size_t k = 0;
+    if (ope_euclidean_clusters(ctx, dev->h, &p_, n, &k, idx.data(), off.data(), nullptr) != OPE_OK) { log_error("EuclideanClusterExtraction", ctx); return; }
+    clusters.resize(k);
+    for (size_t c = 0; c < k; ++c) clusters[c].indices.assign(idx.begin() + off[c], idx.begin() + off[c + 1]);
+  }
+ private:
+  typename PointCloud<PointT>::ConstPtr input_;
+  ope_cluster_params p_{0.0, 1, 0x7fffffff};   // PCL's defaults: no tolerance set (extract refuses), min 1, max INT_MAX
+};
+
 template <class PointSource, class PointTarget, class FeatureT> class SampleConsensusInitialAlignment {
  public:
   SampleConsensusInitialAlignment() { ope_sacia_default_params(&p_); p_.max_iterations = 10; p_.nr_samples = 3; p_.k_correspondences = 10; p_.min_sample_dist = 0.f; p_.max_corr_dist = std::sqrt(DBL_MAX); }

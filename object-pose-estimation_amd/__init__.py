@@ -212,6 +212,23 @@ class TrackResult(C.Structure):
     ]
 
 
+class ClusterParams(C.Structure):
+    _fields_ = [
+        ("tolerance", C.c_double),
+        ("min_size", C.c_int32),
+        ("max_size", C.c_int32),
+    ]
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+        ("cells", C.c_int64),
+        ("pairs_tested", C.c_int64),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
 _dp = C.POINTER(C.c_double)
@@ -307,6 +324,11 @@ ABI = [
                                   C.POINTER(TrackCentroid)]),
     ("ope_track_pose", C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int64, C.c_size_t, C.POINTER(_vp), C.POINTER(TrackParams),
                                   C.POINTER(TrackResult), C.POINTER(TrackCentroid), C.POINTER(FinalBatchResult), C.POINTER(_vp)]),
+    ("ope_cluster_default_params", None, [C.POINTER(ClusterParams)]),
+    ("ope_euclidean_clusters", C.c_int, [_vp, _vp, C.POINTER(ClusterParams), C.c_size_t, C.POINTER(C.c_size_t), _ip, _ip, _ip]),
+    ("ope_euclidean_clusters_cloud", C.c_int, [_vp, _vp, C.POINTER(ClusterParams), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_vp),
+                                                _ip, _ip]),
+    ("ope_cluster_last_stats", C.c_int, [_vp, C.POINTER(ClusterStats)]),
 ]
 
 _lib = None
@@ -678,6 +700,55 @@ class Context:
         res = [_final_out(o) for o in out[:n]]
         return res, sel.value
 
+    def _cluster_args(self, cloud, tolerance, min_size, max_size):
+        if not isinstance(cloud, Cloud):
+            cloud = self.upload(cloud)
+        p = ClusterParams(float(tolerance), int(min_size), int(max_size))
+        return cloud, p
+
+    def euclidean_clusters(self, cloud, tolerance: float = 0.05, min_size: int = 300, max_size: int = 100000, want_labels: bool = False,
+                           max_clusters: int | None = None):
+        """ope_euclidean_clusters: pcl::EuclideanClusterExtraction (objectsegmentationplane.cpp:79-93) of a Cloud (or an (n, 3)
+        array, uploaded first).  Returns the clusters as int32 arrays of ORIGINAL indices, ascending, by size descending then
+        smallest index; with want_labels, (clusters, labels): labels (n,) the rank of each point's cluster or -1."""
+        cloud, p = self._cluster_args(cloud, tolerance, min_size, max_size)
+        n = cloud.n
+        cap = n if max_clusters is None else int(max_clusters)
+        idx = np.empty(max(n, 1), np.int32)
+        off = np.zeros(cap + 1, np.int32)
+        lab = np.empty(max(n, 1), np.int32) if want_labels else None
+        k = C.c_size_t(0)
+        self._chk(lib().ope_euclidean_clusters(self.h, cloud.h, C.byref(p), cap, C.byref(k), _p(idx, _ip), _p(off, _ip),
+                                               _p(lab, _ip) if lab is not None else None))
+        kw = min(k.value, cap)
+        out = [idx[off[i]:off[i + 1]].copy() for i in range(kw)]
+        self.last_cluster_count = k.value
+        return (out, lab[:n].copy()) if want_labels else out
+
+    def euclidean_clusters_cloud(self, cloud, tolerance: float = 0.05, min_size: int = 300, max_size: int = 100000,
+                                 max_clusters: int | None = None):
+        """ope_euclidean_clusters_cloud: the clusters as new device clouds (each what select(cloud, indices) builds) and their
+        indices.  Returns (clouds, indices)."""
+        cloud, p = self._cluster_args(cloud, tolerance, min_size, max_size)
+        n = cloud.n
+        cap = n if max_clusters is None else int(max_clusters)
+        idx = np.empty(max(n, 1), np.int32)
+        off = np.zeros(cap + 1, np.int32)
+        hs = (_vp * max(cap, 1))()
+        k = C.c_size_t(0)
+        self._chk(lib().ope_euclidean_clusters_cloud(self.h, cloud.h, C.byref(p), cap, C.byref(k), hs, _p(idx, _ip), _p(off, _ip)))
+        kw = min(k.value, cap)
+        self.last_cluster_count = k.value
+        indices = [idx[off[i]:off[i + 1]].copy() for i in range(kw)]
+        clouds = [Cloud(self, _vp(hs[i]), len(indices[i])) for i in range(kw)]
+        return clouds, indices
+
+    def cluster_stats(self) -> dict:
+        """ope_cluster_last_stats: launches, host synchronisations, occupied cells and compared cell pairs of the last call."""
+        s = ClusterStats()
+        self._chk(lib().ope_cluster_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in ClusterStats._fields_}
+
     def track_gate(self, source: "Cloud", clusters, params: TrackParams | None = None) -> GateOut:
         """ope_track_gate: the centroid gate of the reference's later frames (rosinterface.cpp:264-304)."""
         n = len(clusters)
@@ -990,6 +1061,15 @@ def default_coarse_params(**kw) -> CoarseParams:
             p.viewpoint[:] = [float(x) for x in v]
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_cluster_params(**kw) -> ClusterParams:
+    """ope_cluster_default_params (tolerance 0.05, min 300, max 100000: objectsegmentationplane.cpp:85-87)."""
+    p = ClusterParams()
+    lib().ope_cluster_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 

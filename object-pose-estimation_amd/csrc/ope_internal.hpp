@@ -265,6 +265,8 @@ struct ope_ctx {
 
   double last_fpfh_mean_neighbours = 0.0;
 
+  ope_cluster_stats cluster_stats{};   // what the last ope_euclidean_clusters* call did (clusters.hip)
+
   // what the last ope_coarse_pose_batch computed (ope_coarse_batch_features): segment 0 the model, 1..n the clusters;
   // key points (original indices), normals (x y z) and FPFH rows, packed by segment from coarse_key_off
   std::vector<int32_t> coarse_key_off, coarse_key_idx;

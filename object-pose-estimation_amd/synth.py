@@ -217,3 +217,71 @@ def frame_views(n_frames: int, n_per_frame: int, noise_sigma: float = 0.0002, re
         out = [_frame_view(*a) for a in args]
     frames, poses = [f for f, _ in out], [T for _, T in out]
     return (frames, poses) if return_poses else frames
+
+
+def _box_surface(rng: np.random.Generator, size, n: int) -> np.ndarray:
+    """n points on the surface of an axis-aligned box of edge lengths `size`, centred at 0, area-uniform."""
+    sx, sy, sz = size
+    faces = np.array([sy * sz, sy * sz, sx * sz, sx * sz, sx * sy, sx * sy])
+    f = rng.choice(6, n, p=faces / faces.sum())
+    u = rng.uniform(-0.5, 0.5, (n, 3)) * np.array(size)
+    ax, sign = f // 2, np.where(f % 2 == 0, -0.5, 0.5)
+    u[np.arange(n), ax] = sign * np.array(size)[ax]
+    return u
+
+
+def _cylinder_surface(rng: np.random.Generator, r: float, h: float, n: int) -> np.ndarray:
+    """n points on the mantle and the top disc of an upright cylinder (axis z, base at z = -h/2)."""
+    a_side, a_top = 2 * np.pi * r * h, np.pi * r * r
+    top = rng.random(n) < a_top / (a_side + a_top)
+    phi = rng.uniform(0, 2 * np.pi, n)
+    rad = np.where(top, r * np.sqrt(rng.random(n)), r)
+    z = np.where(top, h / 2, rng.uniform(-h / 2, h / 2, n))
+    return np.stack([rad * np.cos(phi), rad * np.sin(phi), z], axis=1)
+
+
+def _sphere_cap(rng: np.random.Generator, r: float, n: int) -> np.ndarray:
+    """n points on the upper half of a sphere of radius r (the half a camera above the table sees)."""
+    v = rng.standard_normal((n, 3))
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    v[:, 2] = np.abs(v[:, 2])
+    return r * v
+
+
+def tabletop_objects(n_drill: int = 8000, density: float = 62500.0, seed: int = 21):
+    """The non-plane cloud of one table-top frame (what ObjectSegmentationPlane hands to getClusters): the model ("drill")
+    surface at the ground-truth pose, four distractors at camera-like density (`density` points per m^2: 4 mm spacing by
+    default) standing on a table 0.12 m below the model's centre (two boxes, a cylinder, a sphere cap), five stray blobs of
+    40-250 points and a thin strip of table edge, shuffled.  The cylinder stands 3 cm from the first box, under the reference's
+    5 cm tolerance, so the two are one cluster; every other gap is at least 10 cm.
+    Returns (points float32 (n, 3), object id int32 (n,)): 0 the model, 1 box, 2 cylinder (merges with 1), 3 sphere cap,
+    4 second box, 5 table-edge strip, 6-10 the blobs."""
+    rng = np.random.default_rng(seed)
+    parts, ids = [], []
+
+    def add(p, i):
+        parts.append(np.asarray(p, np.float64))
+        ids.append(np.full(len(p), i, np.int32))
+
+    add(model_surface(n_drill, seed + 1).astype(np.float64) @ GT_R.T + GT_T, 0)
+    table_z = GT_T[2] - 0.12
+    box = (0.08, 0.06, 0.10)
+    box_c = np.array([0.40, 0.0, table_z + box[2] / 2])
+    add(_box_surface(rng, box, int(density * 2 * (box[0] * box[1] + box[0] * box[2] + box[1] * box[2]))) + box_c, 1)
+    r_cyl, h_cyl = 0.04, 0.12
+    cyl_c = np.array([box_c[0] + box[0] / 2 + 0.03 + r_cyl, 0.0, table_z + h_cyl / 2])
+    add(_cylinder_surface(rng, r_cyl, h_cyl, int(density * (2 * np.pi * r_cyl * h_cyl + np.pi * r_cyl ** 2))) + cyl_c, 2)
+    r_cap = 0.05
+    add(_sphere_cap(rng, r_cap, int(density * 2 * np.pi * r_cap ** 2)) + np.array([-0.40, 0.05, table_z]), 3)
+    box2 = (0.05, 0.12, 0.07)
+    add(_box_surface(rng, box2, int(density * 2 * (box2[0] * box2[1] + box2[0] * box2[2] + box2[1] * box2[2])))
+        + np.array([0.0, 0.42, table_z + box2[2] / 2]), 4)
+    strip = np.stack([rng.uniform(-0.45, 0.45, 1200), rng.uniform(-0.003, 0.003, 1200), np.full(1200, table_z)], axis=1)
+    add(strip + np.array([0.0, -0.40, 0.0]), 5)
+    for k, (c, m) in enumerate([((-0.30, -0.22), 40), ((0.30, -0.25), 120), ((-0.25, 0.35), 250), ((0.35, 0.35), 90),
+                                ((-0.55, -0.10), 180)]):
+        add(rng.normal(0.0, 0.006, (m, 3)) + np.array([c[0], c[1], table_z + 0.01]), 6 + k)
+    pts = np.concatenate(parts).astype(np.float32)
+    oid = np.concatenate(ids)
+    order = rng.permutation(len(pts))
+    return pts[order], oid[order]
