@@ -710,6 +710,85 @@ typedef struct {
 } ope_cluster_stats;
 int ope_cluster_last_stats(const ope_ctx *ctx, ope_cluster_stats *out);
 
+/* ---------------- segmentation: RANSAC plane fit, polygonal prism, table-top ---------------- */
+/* pcl::SACSegmentation with SACMODEL_PLANE, SAC_RANSAC (getPlaneIndicesAndCoeffSAC, objectsegmentationplane.cpp:36-55).
+ * The reference also calls setAxis / setEpsAngle (:44-45); they have no effect on SACMODEL_PLANE in PCL (only the
+ * PERPENDICULAR / PARALLEL plane models read them) and have no parameter here. */
+typedef struct {
+  double distance_threshold;      /* 0.01 (objectsegmentationplane.cpp:43) */
+  double probability;             /* 0.99 (SACSegmentation's default) */
+  int32_t max_iterations;         /* 50 (SACSegmentation's default); at most OPE_PLANE_MAX_ITERATIONS */
+  int32_t optimize_coefficients;  /* 1 (:39) */
+  uint64_t seed;                  /* 12345: std::mt19937's seed in PCL when `random` is false */
+} ope_plane_params;
+#define OPE_PLANE_MAX_ITERATIONS 1023
+void ope_plane_default_params(ope_plane_params *p);
+/* What the last ope_plane_segment of this context did (for ope_tabletop_segment: its SECOND fit, with the launches and
+ * synchronisations of the whole call). */
+typedef struct {
+  int64_t iterations;   /* iterations RandomSampleConsensus::computeModel would have run */
+  int64_t hypotheses;   /* hypotheses drawn and scored (max_iterations + 1 unless the draws ran dry) */
+  int64_t launches;     /* kernel launches enqueued (a rocPRIM scan counts as one) */
+  int64_t host_syncs;
+  int32_t best;         /* the winning hypothesis, -1 without a model */
+  int32_t found;        /* 1: a model was found; 0: none (the façade leaves ModelCoefficients::values empty) */
+} ope_plane_stats;
+/* The plane of a cloud: every one of the max_iterations + 1 samples RANSAC can reach is drawn on the device
+ * (SampleConsensusModel::drawIndexSample over ALL points in ORIGINAL order, isSampleGood, computeModelCoefficients), all
+ * are scored in ONE pass over the cloud (countWithinDistance), the counts come back and the loop of
+ * RandomSampleConsensus::computeModel is replayed on the host; then selectWithinDistance, optimizeModelCoefficients
+ * (optimize_coefficients) and selectWithinDistance again.  DESIGN 4.11 has the float order of every step.
+ *   samples (optional, n_samples triples of ORIGINAL indices): taken instead of the draws, unchecked, n_samples <= max_iterations + 1;
+ *   coeff: a b c d;  out_idx (room for every point) / *n_inliers: the inliers, ORIGINAL indices ascending;
+ *   plane / not_plane (optional): new device clouds, exactly ope_cloud_select(cloud, inliers) and ope_cloud_select(cloud, the
+ *   other indices, ascending) (ExtractIndices, negative false / true).
+ * No model (fewer than 3 points, or no good sample): OPE_OK, *n_inliers = 0, coeff untouched, stats.found = 0, the clouds as
+ * for an empty inlier list.  Launches and synchronisations do not depend on the number of points or of iterations.
+ * out_idx is written as one copy of the whole index buffer, before the host knows the count: its entries from *n_inliers on
+ * are unspecified (the same holds for every index output of ope_prism_extract and ope_tabletop_segment past its count).
+ * In the stats a cloud selection (each output cloud, and the prism's cloud inside ope_tabletop_segment) is BOOKED as 4 launches
+ * and 1 synchronisation (2 when the cloud carries normals), not counted: it is ope_cloud_select's device path, whose launches
+ * depend on neither the points nor the iterations either (an empty selection launches nothing and is booked all the same). */
+int ope_plane_segment(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_params *params, const int32_t *samples, size_t n_samples,
+                      float coeff[4], int32_t *out_idx, size_t *n_inliers, ope_cloud **plane, ope_cloud **not_plane);
+int ope_plane_last_stats(const ope_ctx *ctx, ope_plane_stats *out);
+/* The hypotheses of the last ope_plane_segment: samples (3 ORIGINAL indices each), coefficients (4 floats each) and inlier
+ * counts, in drawing order; any output may be NULL; at most cap are written, *n_out = how many there were. */
+int ope_plane_last_hypotheses(const ope_ctx *ctx, int32_t *samples, float *coeffs, int32_t *counts, size_t cap, size_t *n_out);
+
+/* pcl::ExtractPolygonalPrismData::segment with PCL's defaults (height limits 0 .. FLT_MAX unless given, viewpoint 0 0 0): the
+ * plane of the hull's m >= 3 vertices (computeMeanAndCovarianceMatrix, eigen33, flipped towards the viewpoint and then
+ * re-anchored on vertex 0), and per point the signed distance against the limits, the projection into that plane and the
+ * crossing test against the hull with the normal's dominant axis dropped.  hull: m x 3 floats (host).
+ * out_idx (optional, room for every point) / *n_out: the survivors, ORIGINAL indices ascending; out (optional): the survivors
+ * as ope_cloud_select builds them.  hull_coeff (optional): the hull's plane. */
+int ope_prism_extract(ope_ctx *ctx, const ope_cloud *cloud, const float *hull, size_t m, double height_min, double height_max,
+                      int32_t *out_idx, size_t *n_out, ope_cloud **out, float hull_coeff[4]);
+
+enum {
+  OPE_TABLETOP_OK = 0,
+  OPE_TABLETOP_NO_PLANE_FIRST = 1,    /* the first fit found no model (objectsegmentationplane.cpp:156-159: false, the input back) */
+  OPE_TABLETOP_NO_PLANE_SECOND = 2    /* the fit on the prism's points found none (:229-232) */
+};
+typedef struct {
+  int32_t status;
+  int32_t n_prism;            /* points inside the prism (cloudObjWithPlane) */
+  int32_t n_plane, n_not_plane;
+  float coeff_first[4];       /* the first fit */
+  float coeff_second[4];      /* the fit on the prism's points */
+  float corners[12];          /* the four hull corners, x y z each (:174-188) */
+  int64_t iterations_first, iterations_second;
+  int64_t launches, host_syncs;
+} ope_tabletop_result;
+/* getSegmentedObjectsOnPlane up to getClusters (objectsegmentationplane.cpp:124-235): plane fit, the inliers projected
+ * into it and their extreme x and y (what getMinMax3D of their convex hull returns), the four corners, the prism, the plane fit
+ * of the prism's points (re-indexed in ascending order, the same seed), plane and non-plane cloud.
+ * plane / not_plane (required): new device clouds (NULL unless the status is OK);  prism_idx (optional, room for every point):
+ * the prism's points as indices into `cloud`;  plane_idx / not_plane_idx (optional, room for every point): both clouds' points
+ * as indices into `cloud`.  Launches and synchronisations do not depend on the number of points or of iterations. */
+int ope_tabletop_segment(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_params *params, ope_tabletop_result *out,
+                         ope_cloud **plane, ope_cloud **not_plane, int32_t *prism_idx, int32_t *plane_idx, int32_t *not_plane_idx);
+
 #ifdef __cplusplus
 }
 #endif

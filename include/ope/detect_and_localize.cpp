@@ -16,6 +16,12 @@
 // (pcl::EuclideanClusterExtraction, tolerance 0.05, 300 .. 1e5 points), each cluster copied by index (rosinterface.cpp:246-255),
 // then the clusters as --candidates takes them.  Prints `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
 //
+//   detect_and_localize --frame <model.pcd> <frame.pcd> [--limits x0 x1 y0 y1 z0 z1] [--seed N] [--self-occluded]
+// The first frame from the camera frame itself (rosinterface.cpp:212-262): ProcessingPcd::getPassThrough (three pcl::PassThrough,
+// the -l limits; without --limits only non-finite points go), ope::ObjectSegmentationPlane::getSegmentedObjectsOnPlane (plane
+// fit, prism, second fit and clusters on the device), then the clusters as --candidates takes them.  Prints
+// `segment plane <n>`, `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
+//
 //   detect_and_localize --track <model.pcd> --frame <a.pcd> [<b.pcd> ...] [--frame ...] [--seed N] [--self-occluded] [--time]
 //   detect_and_localize --track-loop <model.pcd> --frame ... (same)
 // DetectAndLocalize's per-frame policy (rosinterface.cpp:226-313) over a sequence of camera frames, one --frame per frame with
@@ -23,6 +29,7 @@
 // device); --track-loop: ObjectTracker::localizeLoop (host compute3DCentroid and estimateFinalPose, as the reference writes it).
 // Per frame: `track frame <k> branch <b> selected <i> clusters <n>`, then the `frame ...` line; --time adds `time frame <k> ms <t>`
 // (host clock around the synchronised call).
+#include <cfloat>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +38,7 @@
 
 #include <chrono>
 
+#include "object_segmentation_plane.hpp"
 #include "object_tracker.hpp"
 #include "pcd_io.hpp"
 #include "pose_estimator.hpp"
@@ -117,15 +125,19 @@ int main(int argc, char **argv) {
   bool self_occluded = false;
   int candidates = 0;   // 1: estimateFinalPoseCandidates, 2: the reference's loop
   bool segment = false; // --segment: the clusters come from getClusters over the one scene file (the non-plane cloud)
+  bool frame = false;   // --frame: the clusters come from getSegmentedObjectsOnPlane over the one scene file (a camera frame)
+  float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--candidates")) candidates = 1;
     else if (!std::strcmp(argv[i], "--candidates-loop")) candidates = 2;
     else if (!std::strcmp(argv[i], "--segment")) { segment = true; candidates = 1; }
+    else if (!std::strcmp(argv[i], "--frame")) { frame = true; candidates = 1; }
+    else if (!std::strcmp(argv[i], "--limits") && i + 6 < argc) { for (int d = 0; d < 6; ++d) limits[d] = std::strtof(argv[++i], nullptr); }
     else files.push_back(argv[i]);
   }
-  if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded] [--candidates | --candidates-loop | --segment]\n", argv[0]); return 2; }
+  if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded] [--candidates | --candidates-loop | --segment | --frame]\n", argv[0]); return 2; }
   typedef ope::PoseEstimator::PointT PointT;
   pcl::PointCloud<PointT>::Ptr cloudSourceOriginal(new pcl::PointCloud<PointT>), cloudSource(new pcl::PointCloud<PointT>);
   if (pcl::io::loadPCDFile(files[0], *cloudSourceOriginal) != 0) return 3;   // rosinterface.cpp:80
@@ -170,7 +182,29 @@ int main(int argc, char **argv) {
       }
       std::printf("\n");
     }
-    for (size_t k = 1; !segment && k < files.size(); ++k) {
+    if (frame) {
+      // rosinterface.cpp:212-213: the pass-through crop, then the table-top segmentation
+      pcl::PointCloud<PointT>::Ptr cloudTarget(new pcl::PointCloud<PointT>), cloudPlane;
+      if (segment || files.size() != 2 || pcl::io::loadPCDFile(files[1], *cloudTarget) != 0) return 3;
+      const char *fields[3] = {"x", "y", "z"};
+      for (int d = 0; d < 3; ++d) {   // ProcessingPcd::getPassThrough (processingpcd.cpp:13-33)
+        pcl::PointCloud<PointT>::Ptr cloudFiltered(new pcl::PointCloud<PointT>);
+        pcl::PassThrough<PointT> pass;
+        pass.setInputCloud(cloudTarget);
+        pass.setFilterFieldName(fields[d]);
+        pass.setFilterLimits(limits[2 * d], limits[2 * d + 1]);
+        pass.filter(*cloudFiltered);
+        cloudTarget = cloudFiltered;
+      }
+      ope::ObjectSegmentationPlane objSegPlane;
+      const bool isPlane = objSegPlane.getSegmentedObjectsOnPlane(cloudTarget, clusters, cloudPlane);
+      if (!isPlane) { std::printf("segment no plane (status %d)\n", objSegPlane.lastResult().status); return 5; }
+      std::printf("segment plane %zu\n", cloudPlane->size());
+      std::printf("segment clusters %zu sizes", clusters.size());
+      for (const auto &c : clusters) std::printf(" %zu", c->size());
+      std::printf("\n");
+    }
+    for (size_t k = 1; !segment && !frame && k < files.size(); ++k) {
       clusters.emplace_back(new pcl::PointCloud<PointT>);
       if (pcl::io::loadPCDFile(files[k], *clusters.back()) != 0) return 3;
     }

@@ -1,0 +1,147 @@
+// object_segmentation_plane.hpp — DetectAndLocalize's ObjectSegmentationPlane (objectsegmentationplane.cpp) on the device:
+//
+//     ope::ObjectSegmentationPlane objSegPlane;
+//     bool isPlane = objSegPlane.getSegmentedObjectsOnPlane(cloudTargetFiltered, cloudClusterVector, cloudPlane);   // rosinterface.cpp:213
+//
+// getSegmentedObjectsOnPlane keeps the reference's signature and return values.  Steps 2-7 (:124-235) are one ope_tabletop_segment
+// call on the uploaded frame, step 8 (getClusters, :239) is ope_euclidean_clusters_cloud on the non-plane cloud it left on the
+// device; only index lists come back, and the output clouds are gathered on the host from the input through them, so every
+// field of the point type (the colour) is carried although device clouds hold xyz only.  The members the reference exposes
+// one by one (getPlaneIndicesAndCoeffSAC, getPlaneAndNonPlaneCloud, getClusters, getProjectedCloud) are here too, written
+// with the façade's classes as the reference writes them with PCL's.  No ConvexHull: the reference uses the hull only through
+// getMinMax3D, and the extremes of a planar set are attained at its hull's vertices.
+#pragma once
+
+#include <memory>
+#include <vector>
+
+#include "pcl_compat.hpp"
+
+namespace ope {
+
+class ObjectSegmentationPlane {
+ public:
+  typedef compat::PointXYZRGB PointTObj;
+  typedef compat::PointCloud<PointTObj> Cloud;
+
+  void setSeed(uint64_t s) { seed_ = s; }
+  const ope_tabletop_result &lastResult() const { return last_; }
+
+  // objectsegmentationplane.cpp:36-55
+  bool getPlaneIndicesAndCoeffSAC(Cloud::Ptr p_cloudInput, compat::PointIndices::Ptr p_indices, compat::ModelCoefficients::Ptr p_modelCoeff) {
+    sacSeg.setOptimizeCoefficients(true);
+    sacSeg.setInputCloud(p_cloudInput);
+    sacSeg.setModelType(compat::SACMODEL_PLANE);
+    sacSeg.setMethodType(compat::SAC_RANSAC);
+    sacSeg.setDistanceThreshold(0.01);
+    sacSeg.setAxis(compat::Vector3f(0.0, 0.0, 1.0));
+    sacSeg.setEpsAngle(10.0f * (3.14 / 180.0f));
+    sacSeg.setSeed(seed_);
+    sacSeg.segment(*p_indices, *p_modelCoeff);
+    return p_modelCoeff->values.size() != 0;
+  }
+
+  // :58-71
+  void getPlaneAndNonPlaneCloud(Cloud::Ptr p_cloudInput, compat::PointIndices::Ptr p_indices, Cloud::Ptr p_cloudPlane, Cloud::Ptr p_cloudNotPlane) {
+    extractIndices.setInputCloud(p_cloudInput);
+    extractIndices.setIndices(p_indices);
+    extractIndices.setNegative(false);
+    extractIndices.filter(*p_cloudPlane);
+    extractIndices.setNegative(true);
+    extractIndices.filter(*p_cloudNotPlane);
+  }
+
+  // :74-90
+  std::vector<compat::PointIndices> getClusters(Cloud::Ptr p_cloudInput) {
+    compat::search::KdTree<PointTObj>::Ptr kdTree(new compat::search::KdTree<PointTObj>);
+    std::vector<compat::PointIndices> clusterIndices;
+    euclideanClustExtraction.setInputCloud(p_cloudInput);
+    euclideanClustExtraction.setSearchMethod(kdTree);
+    euclideanClustExtraction.setClusterTolerance(0.05);
+    euclideanClustExtraction.setMinClusterSize(300);
+    euclideanClustExtraction.setMaxClusterSize(1e5);
+    euclideanClustExtraction.extract(clusterIndices);
+    return clusterIndices;
+  }
+
+  // :95-107
+  Cloud::Ptr getProjectedCloud(Cloud::Ptr p_cloudInput, compat::PointIndices::Ptr p_indices, compat::ModelCoefficients::Ptr p_modelCoeff) {
+    Cloud::Ptr cloudOutput(new Cloud);
+    compat::ProjectInliers<PointTObj> projectInliers;
+    projectInliers.setInputCloud(p_cloudInput);
+    projectInliers.setModelType(compat::SACMODEL_PLANE);
+    projectInliers.setIndices(p_indices);
+    projectInliers.setModelCoefficients(p_modelCoeff);
+    projectInliers.filter(*cloudOutput);
+    return cloudOutput;
+  }
+
+  // :122-282.  false: no plane (first or second fit); the input is handed back as cluster 0, as the reference does.
+  bool getSegmentedObjectsOnPlane(Cloud::Ptr p_cloudInput, std::vector<Cloud::Ptr> &cloudClusterVector, Cloud::Ptr &p_cloudPlane) {
+    p_cloudPlane = Cloud::Ptr(new Cloud);
+    last_ = ope_tabletop_result{};
+    last_.status = OPE_TABLETOP_NO_PLANE_FIRST;
+    auto hand_back = [&]() {   // copyPointCloud(*cloudFiltered, *cloudClusterVector.at(0)) (:157, :230)
+      if (cloudClusterVector.empty()) cloudClusterVector.push_back(Cloud::Ptr(new Cloud));
+      *cloudClusterVector[0] = *p_cloudInput;
+      return false;
+    };
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || !p_cloudInput) return p_cloudInput ? hand_back() : false;
+    auto frame = compat::upload(*p_cloudInput, false);
+    if (!frame->h) return hand_back();
+    const size_t n = p_cloudInput->size();
+    ope_plane_params p;
+    ope_plane_default_params(&p);
+    p.seed = seed_;
+    compat::CloudHandle plane, notPlane;
+    std::vector<int32_t> planeIdx(n + 1), notPlaneIdx(n + 1);
+    if (ope_tabletop_segment(ctx, frame->h, &p, &last_, &plane.h, &notPlane.h, nullptr, planeIdx.data(), notPlaneIdx.data()) != OPE_OK) {
+      compat::log_error("getSegmentedObjectsOnPlane", ctx);
+      return hand_back();
+    }
+    if (last_.status != OPE_TABLETOP_OK) return hand_back();
+    auto gather = [&](Cloud &out, const int32_t *map, const int32_t *idx, size_t m) {
+      out.points.resize(m);
+      for (size_t j = 0; j < m; ++j) out.points[j] = p_cloudInput->points[map[idx ? idx[j] : (int32_t)j]];
+      out.width = (uint32_t)m;
+      out.height = 1;
+      out.is_dense = true;
+    };
+    gather(*p_cloudPlane, planeIdx.data(), nullptr, (size_t)last_.n_plane);   // copyPointCloud(*cloudplane, *p_cloudPlane) (:235)
+    // getClusters on the device cloud (:239), each cluster's points by index (:247-277)
+    const size_t m = (size_t)last_.n_not_plane;
+    ope_cluster_params cp;
+    ope_cluster_default_params(&cp);
+    std::vector<ope_cloud *> clouds(m + 1, nullptr);
+    std::vector<int32_t> idx(m + 1), off(m + 2);
+    size_t k = 0;
+    if (ope_euclidean_clusters_cloud(ctx, notPlane.h, &cp, m, &k, clouds.data(), idx.data(), off.data()) != OPE_OK) {
+      compat::log_error("getSegmentedObjectsOnPlane", ctx);
+      return true;
+    }
+    deviceClusters_.clear();
+    for (size_t c = 0; c < k && c < m; ++c) {
+      auto h = std::make_shared<compat::CloudHandle>();
+      h->h = clouds[c];
+      deviceClusters_.push_back(h);
+      Cloud::Ptr cloudCluster(new Cloud);
+      gather(*cloudCluster, notPlaneIdx.data(), idx.data() + off[c], (size_t)(off[c + 1] - off[c]));
+      cloudClusterVector.push_back(cloudCluster);
+    }
+    return true;
+  }
+
+  // the clusters of the last successful call as they were left on the device (for ope_final_pose_batch / ope_track_pose without an upload)
+  const std::vector<std::shared_ptr<compat::CloudHandle>> &deviceClusters() const { return deviceClusters_; }
+
+ private:
+  compat::SACSegmentation<PointTObj> sacSeg;
+  compat::ExtractIndices<PointTObj> extractIndices;
+  compat::EuclideanClusterExtraction<PointTObj> euclideanClustExtraction;
+  uint64_t seed_ = 12345;
+  ope_tabletop_result last_{};
+  std::vector<std::shared_ptr<compat::CloudHandle>> deviceClusters_;
+};
+
+}  // namespace ope

@@ -766,7 +766,11 @@ template <class PointT> class StatisticalOutlierRemoval {
   double mul_ = 0.0;
 };
 
-struct PointIndices { std::vector<int> indices; };
+struct PointIndices {
+  typedef std::shared_ptr<PointIndices> Ptr;
+  typedef std::shared_ptr<const PointIndices> ConstPtr;
+  std::vector<int> indices;
+};
 
 // ObjectSegmentationPlane::getClusters (objectsegmentationplane.cpp:79-93): the clusters of ope_euclidean_clusters, each as
 // ORIGINAL indices ascending, by size descending then smallest index (PCL's order; see ope.h for the one documented difference)
@@ -793,6 +797,158 @@ template <class PointT> class EuclideanClusterExtraction {
  private:
   typename PointCloud<PointT>::ConstPtr input_;
   ope_cluster_params p_{0.0, 1, 0x7fffffff};   // PCL's defaults: no tolerance set (extract refuses), min 1, max INT_MAX
+};
+
+// ------------------------------------------------------------------------------------------ table-top segmentation
+// The classes ObjectSegmentationPlane uses (objectsegmentationplane.cpp:36-71, 95-107, 169-214), with its call shapes.
+struct ModelCoefficients {
+  typedef std::shared_ptr<ModelCoefficients> Ptr;
+  typedef std::shared_ptr<const ModelCoefficients> ConstPtr;
+  std::vector<float> values;
+};
+enum SacModel { SACMODEL_PLANE = 0 };
+enum SacMethod { SAC_RANSAC = 0 };
+struct Vector3f {   // what setAxis takes; SACMODEL_PLANE never reads it
+  float v[3];
+  Vector3f(float x = 0.f, float y = 0.f, float z = 0.f) : v{x, y, z} {}
+};
+
+// pcl::SACSegmentation, SACMODEL_PLANE + SAC_RANSAC only (ope_plane_segment).  An empty `values` means no model, as in PCL.
+template <class PointT> class SACSegmentation {
+ public:
+  SACSegmentation() { ope_plane_default_params(&p_); p_.optimize_coefficients = 0; }   // PCL's default: optimize_coefficients_ (true) is set by the caller at :39
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &c) { input_ = c; }
+  void setModelType(int m) { model_ = m; }
+  void setMethodType(int m) { method_ = m; }
+  void setOptimizeCoefficients(bool on) { p_.optimize_coefficients = on ? 1 : 0; }
+  void setDistanceThreshold(double t) { p_.distance_threshold = t; }
+  void setMaxIterations(int n) { p_.max_iterations = n; }
+  void setProbability(double pr) { p_.probability = pr; }
+  void setAxis(const Vector3f &) {}      // no effect on SACMODEL_PLANE
+  void setEpsAngle(double) {}            // no effect on SACMODEL_PLANE
+  void setSeed(uint64_t s) { p_.seed = s; }
+  void segment(PointIndices &inliers, ModelCoefficients &coefficients) {
+    inliers.indices.clear();
+    coefficients.values.clear();
+    ope_ctx *ctx = default_context();
+    if (!ctx || !input_ || model_ != SACMODEL_PLANE || method_ != SAC_RANSAC) return;
+    auto dev = upload(*input_, false);
+    if (!dev->h) return;
+    std::vector<int32_t> idx(input_->size() + 1);
+    float c[4];
+    size_t n = 0;
+    if (ope_plane_segment(ctx, dev->h, &p_, nullptr, 0, c, idx.data(), &n, nullptr, nullptr) != OPE_OK) { log_error("SACSegmentation", ctx); return; }
+    ope_plane_stats st;
+    if (ope_plane_last_stats(ctx, &st) != OPE_OK || !st.found) return;
+    coefficients.values.assign(c, c + 4);
+    inliers.indices.assign(idx.begin(), idx.begin() + n);
+  }
+ private:
+  typename PointCloud<PointT>::ConstPtr input_;
+  ope_plane_params p_;
+  int model_ = -1, method_ = SAC_RANSAC;
+};
+
+// pcl::ExtractIndices: the listed points in list order, or (negative) the others in input order.  Host-side: nothing is computed.
+template <class PointT> class ExtractIndices {
+ public:
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &c) { input_ = c; }
+  void setIndices(const PointIndices::ConstPtr &i) { indices_ = i; }
+  void setNegative(bool n) { negative_ = n; }
+  void filter(PointCloud<PointT> &out) {
+    PointCloud<PointT> tmp;
+    if (input_ && indices_) {
+      if (!negative_) {
+        for (int i : indices_->indices) tmp.points.push_back(input_->points[i]);
+      } else {
+        std::vector<char> listed(input_->size(), 0);
+        for (int i : indices_->indices) listed[i] = 1;
+        for (size_t i = 0; i < input_->size(); ++i)
+          if (!listed[i]) tmp.points.push_back(input_->points[i]);
+      }
+    }
+    tmp.width = (uint32_t)tmp.points.size();
+    tmp.is_dense = input_ ? input_->is_dense : true;
+    out = std::move(tmp);
+  }
+ private:
+  typename PointCloud<PointT>::ConstPtr input_;
+  PointIndices::ConstPtr indices_;
+  bool negative_ = false;
+};
+
+// pcl::ProjectInliers with SACMODEL_PLANE (SampleConsensusModelPlane::projectPoints, copy_all_data false): the listed points
+// projected, in list order, other fields copied.  Float arithmetic in the order DESIGN 4.11 fixes: n' = n / sqrt((a a + b b) + c c),
+// dist = ((a' x + b' y) + c' z) + d, p - n' dist.  A handful of float operations per point: on the host.
+template <class PointT> class ProjectInliers {
+ public:
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &c) { input_ = c; }
+  void setModelType(int m) { model_ = m; }
+  void setIndices(const PointIndices::ConstPtr &i) { indices_ = i; }
+  void setModelCoefficients(const ModelCoefficients::ConstPtr &m) { coeff_ = m; }
+  void filter(PointCloud<PointT> &out) {
+    PointCloud<PointT> tmp;
+    if (input_ && coeff_ && coeff_->values.size() == 4 && model_ == SACMODEL_PLANE) {
+      const float a = coeff_->values[0], b = coeff_->values[1], c = coeff_->values[2], d = coeff_->values[3];
+      volatile float aa = a * a, bb = b * b, cc = c * c;   // (volatile: every product rounded on its own, no contraction into the sums)
+      volatile float s1 = aa + bb;
+      const float len = std::sqrt(s1 + cc);
+      const float ua = a / len, ub = b / len, uc = c / len;
+      const size_t m = indices_ ? indices_->indices.size() : input_->size();
+      tmp.points.reserve(m);
+      for (size_t j = 0; j < m; ++j) {
+        PointT p = input_->points[indices_ ? (size_t)indices_->indices[j] : j];
+        volatile float t0 = ua * p.x, t1 = ub * p.y, t2 = uc * p.z;
+        volatile float dist = t0 + t1; dist = dist + t2; dist = dist + d;
+        volatile float mx = ua * dist, my = ub * dist, mz = uc * dist;
+        p.x = p.x - mx; p.y = p.y - my; p.z = p.z - mz;
+        tmp.points.push_back(p);
+      }
+    }
+    tmp.width = (uint32_t)tmp.points.size();
+    out = std::move(tmp);
+  }
+ private:
+  typename PointCloud<PointT>::ConstPtr input_;
+  PointIndices::ConstPtr indices_;
+  ModelCoefficients::ConstPtr coeff_;
+  int model_ = -1;
+};
+
+// pcl::getMinMax3D: componentwise extremes; points with a non-finite coordinate are skipped unless the cloud is dense
+template <class PointT> inline void getMinMax3D(const PointCloud<PointT> &cloud, PointT &min_pt, PointT &max_pt) {
+  float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  for (const PointT &p : cloud.points) {
+    if (!cloud.is_dense && !(std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z))) continue;
+    const float v[3] = {p.x, p.y, p.z};
+    for (int d = 0; d < 3; ++d) { if (v[d] < lo[d]) lo[d] = v[d]; if (v[d] > hi[d]) hi[d] = v[d]; }
+  }
+  min_pt.x = lo[0]; min_pt.y = lo[1]; min_pt.z = lo[2];
+  max_pt.x = hi[0]; max_pt.y = hi[1]; max_pt.z = hi[2];
+}
+
+// pcl::ExtractPolygonalPrismData (ope_prism_extract): height limits 0 .. FLT_MAX and the viewpoint at the origin by default
+template <class PointT> class ExtractPolygonalPrismData {
+ public:
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &c) { input_ = c; }
+  void setInputPlanarHull(const typename PointCloud<PointT>::ConstPtr &h) { hull_ = h; }
+  void setHeightLimits(double lo, double hi) { lo_ = lo; hi_ = hi; }
+  void segment(PointIndices &output) {
+    output.indices.clear();
+    ope_ctx *ctx = default_context();
+    if (!ctx || !input_ || !hull_ || hull_->size() < 3) return;
+    auto dev = upload(*input_, false);
+    if (!dev->h) return;
+    std::vector<float> hull(3 * hull_->size());
+    for (size_t v = 0; v < hull_->size(); ++v) { hull[3 * v] = hull_->points[v].x; hull[3 * v + 1] = hull_->points[v].y; hull[3 * v + 2] = hull_->points[v].z; }
+    std::vector<int32_t> idx(input_->size() + 1);
+    size_t n = 0;
+    if (ope_prism_extract(ctx, dev->h, hull.data(), hull_->size(), lo_, hi_, idx.data(), &n, nullptr, nullptr) != OPE_OK) { log_error("ExtractPolygonalPrismData", ctx); return; }
+    output.indices.assign(idx.begin(), idx.begin() + n);
+  }
+ private:
+  typename PointCloud<PointT>::ConstPtr input_, hull_;
+  double lo_ = 0.0, hi_ = FLT_MAX;
 };
 
 template <class PointSource, class PointTarget, class FeatureT> class SampleConsensusInitialAlignment {

@@ -229,6 +229,45 @@ class ClusterStats(C.Structure):
     ]
 
 
+class PlaneParams(C.Structure):
+    _fields_ = [
+        ("distance_threshold", C.c_double),
+        ("probability", C.c_double),
+        ("max_iterations", C.c_int32),
+        ("optimize_coefficients", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+class PlaneStats(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int64),
+        ("hypotheses", C.c_int64),
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+        ("best", C.c_int32),
+        ("found", C.c_int32),
+    ]
+
+
+class TabletopResult(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("n_prism", C.c_int32),
+        ("n_plane", C.c_int32),
+        ("n_not_plane", C.c_int32),
+        ("coeff_first", C.c_float * 4),
+        ("coeff_second", C.c_float * 4),
+        ("corners", C.c_float * 12),
+        ("iterations_first", C.c_int64),
+        ("iterations_second", C.c_int64),
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+    ]
+
+
+TABLETOP_OK, TABLETOP_NO_PLANE_FIRST, TABLETOP_NO_PLANE_SECOND = 0, 1, 2
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
 _dp = C.POINTER(C.c_double)
@@ -329,6 +368,14 @@ ABI = [
     ("ope_euclidean_clusters_cloud", C.c_int, [_vp, _vp, C.POINTER(ClusterParams), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_vp),
                                                 _ip, _ip]),
     ("ope_cluster_last_stats", C.c_int, [_vp, C.POINTER(ClusterStats)]),
+    ("ope_plane_default_params", None, [C.POINTER(PlaneParams)]),
+    ("ope_plane_segment", C.c_int, [_vp, _vp, C.POINTER(PlaneParams), _ip, C.c_size_t, _fp, _ip, C.POINTER(C.c_size_t), C.POINTER(_vp),
+                                     C.POINTER(_vp)]),
+    ("ope_plane_last_stats", C.c_int, [_vp, C.POINTER(PlaneStats)]),
+    ("ope_plane_last_hypotheses", C.c_int, [_vp, _ip, _fp, _ip, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_prism_extract", C.c_int, [_vp, _vp, _fp, C.c_size_t, C.c_double, C.c_double, _ip, C.POINTER(C.c_size_t), C.POINTER(_vp), _fp]),
+    ("ope_tabletop_segment", C.c_int, [_vp, _vp, C.POINTER(PlaneParams), C.POINTER(TabletopResult), C.POINTER(_vp), C.POINTER(_vp), _ip, _ip,
+                                        _ip]),
 ]
 
 _lib = None
@@ -450,6 +497,38 @@ class TrackOut:
     status: int                # GATED: FINAL_*
     realign: list | None       # REALIGN_ALL: [FinalOut per cluster], as final_pose_batch returns them
     aligned: "Cloud | None"    # GATED: the source moved by the coarse, then the fine pose, on the device (the next source)
+
+
+@dataclass
+class PlaneOut:
+    found: bool                # a model was found (PCL: ModelCoefficients::values not empty)
+    coeff: "np.ndarray | None"  # a b c d, float32
+    inliers: np.ndarray        # ORIGINAL indices, ascending
+    iterations: int            # iterations RANSAC would have run
+    best: int                  # the winning hypothesis
+    samples: np.ndarray        # (h, 3) the drawn triples
+    hyp_coeffs: np.ndarray     # (h, 4) their planes
+    counts: np.ndarray         # (h,) their inlier counts
+    plane: "Cloud | None"
+    not_plane: "Cloud | None"
+    stats: dict
+
+
+@dataclass
+class TabletopOut:
+    status: int                # TABLETOP_OK / NO_PLANE_FIRST / NO_PLANE_SECOND
+    coeff_first: np.ndarray
+    coeff_second: np.ndarray
+    corners: np.ndarray        # (4, 3)
+    prism_idx: np.ndarray      # the prism's points, indices into the input
+    plane_idx: "np.ndarray | None"
+    not_plane_idx: "np.ndarray | None"
+    plane: "Cloud | None"
+    not_plane: "Cloud | None"
+    iterations_first: int
+    iterations_second: int
+    launches: int
+    host_syncs: int
 
 
 def _gate_out(g: "TrackGateResult", cent, n: int) -> GateOut:
@@ -748,6 +827,74 @@ class Context:
         s = ClusterStats()
         self._chk(lib().ope_cluster_last_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in ClusterStats._fields_}
+
+    def plane_segment(self, cloud, params: "PlaneParams | None" = None, samples=None, want_clouds: bool = False) -> "PlaneOut":
+        """ope_plane_segment: pcl::SACSegmentation (SACMODEL_PLANE, SAC_RANSAC; objectsegmentationplane.cpp:36-55) of a Cloud (or
+        an (n, 3) array, uploaded first).  samples: (k, 3) ORIGINAL indices taken instead of the draws."""
+        if not isinstance(cloud, Cloud):
+            cloud = self.upload(cloud)
+        p = params if params is not None else default_plane_params()
+        smp = np.ascontiguousarray(samples, np.int32).reshape(-1, 3) if samples is not None else None
+        coeff = np.zeros(4, np.float32)
+        idx = np.empty(max(cloud.n, 1), np.int32)
+        k = C.c_size_t(0)
+        hp, hn = _vp(), _vp()
+        self._chk(lib().ope_plane_segment(self.h, cloud.h, C.byref(p), _p(smp, _ip) if smp is not None and len(smp) else None,
+                                          len(smp) if smp is not None else 0, _p(coeff, _fp), _p(idx, _ip), C.byref(k),
+                                          C.byref(hp) if want_clouds else None, C.byref(hn) if want_clouds else None))
+        st = self.plane_stats()
+        hs, hc, hk = self.plane_hypotheses()
+        plane = Cloud(self, hp, k.value) if want_clouds else None
+        rest = Cloud(self, hn, cloud.n - k.value) if want_clouds else None
+        return PlaneOut(bool(st["found"]), coeff if st["found"] else None, idx[: k.value].copy(), st["iterations"], st["best"], hs, hc, hk,
+                        plane, rest, st)
+
+    def plane_stats(self) -> dict:
+        """ope_plane_last_stats: iterations, hypotheses scored, launches, host synchronisations, winner, found."""
+        s = PlaneStats()
+        self._chk(lib().ope_plane_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in PlaneStats._fields_}
+
+    def plane_hypotheses(self):
+        """ope_plane_last_hypotheses: (samples (h, 3) int32, coefficients (h, 4) float32, counts (h,) int32) in drawing order."""
+        n = C.c_size_t(0)
+        self._chk(lib().ope_plane_last_hypotheses(self.h, None, None, None, 0, C.byref(n)))
+        h = n.value
+        s, c, k = np.empty((max(h, 1), 3), np.int32), np.empty((max(h, 1), 4), np.float32), np.empty(max(h, 1), np.int32)
+        self._chk(lib().ope_plane_last_hypotheses(self.h, _p(s, _ip), _p(c, _fp), _p(k, _ip), h, C.byref(n)))
+        return s[:h].copy(), c[:h].copy(), k[:h].copy()
+
+    def prism_extract(self, cloud, hull, height_min: float = 0.0, height_max: float = float(np.finfo(np.float32).max),
+                      want_cloud: bool = False):
+        """ope_prism_extract: pcl::ExtractPolygonalPrismData (viewpoint 0 0 0).  Returns (indices, hull plane (4,), Cloud or None)."""
+        if not isinstance(cloud, Cloud):
+            cloud = self.upload(cloud)
+        hull = _f32(hull, 3)
+        idx = np.empty(max(cloud.n, 1), np.int32)
+        k = C.c_size_t(0)
+        h = _vp()
+        hc = np.zeros(4, np.float32)
+        self._chk(lib().ope_prism_extract(self.h, cloud.h, _p(hull, _fp), len(hull), float(height_min), float(height_max), _p(idx, _ip),
+                                          C.byref(k), C.byref(h) if want_cloud else None, _p(hc, _fp)))
+        return idx[: k.value].copy(), hc, (Cloud(self, h, k.value) if want_cloud else None)
+
+    def tabletop_segment(self, cloud, params: "PlaneParams | None" = None) -> "TabletopOut":
+        """ope_tabletop_segment: getSegmentedObjectsOnPlane up to getClusters (objectsegmentationplane.cpp:124-235)."""
+        if not isinstance(cloud, Cloud):
+            cloud = self.upload(cloud)
+        p = params if params is not None else default_plane_params()
+        r = TabletopResult()
+        hp, hn = _vp(), _vp()
+        n1 = max(cloud.n, 1)
+        pi, li, ni = np.empty(n1, np.int32), np.empty(n1, np.int32), np.empty(n1, np.int32)
+        self._chk(lib().ope_tabletop_segment(self.h, cloud.h, C.byref(p), C.byref(r), C.byref(hp), C.byref(hn), _p(pi, _ip), _p(li, _ip),
+                                             _p(ni, _ip)))
+        ok = r.status == TABLETOP_OK
+        return TabletopOut(r.status, np.array(r.coeff_first, np.float32), np.array(r.coeff_second, np.float32),
+                           np.array(r.corners, np.float32).reshape(4, 3), pi[: r.n_prism].copy(),
+                           li[: r.n_plane].copy() if ok else None, ni[: r.n_not_plane].copy() if ok else None,
+                           Cloud(self, hp, r.n_plane) if ok else None, Cloud(self, hn, r.n_not_plane) if ok else None,
+                           r.iterations_first, r.iterations_second, r.launches, r.host_syncs)
 
     def track_gate(self, source: "Cloud", clusters, params: TrackParams | None = None) -> GateOut:
         """ope_track_gate: the centroid gate of the reference's later frames (rosinterface.cpp:264-304)."""
@@ -1068,6 +1215,15 @@ def default_cluster_params(**kw) -> ClusterParams:
     """ope_cluster_default_params (tolerance 0.05, min 300, max 100000: objectsegmentationplane.cpp:85-87)."""
     p = ClusterParams()
     lib().ope_cluster_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_plane_params(**kw) -> PlaneParams:
+    """ope_plane_default_params (threshold 0.01, 50 iterations, probability 0.99, optimised coefficients, seed 12345)."""
+    p = PlaneParams()
+    lib().ope_plane_default_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -267,6 +267,11 @@ struct ope_ctx {
 
   ope_cluster_stats cluster_stats{};   // what the last ope_euclidean_clusters* call did (clusters.hip)
 
+  // the last ope_plane_segment (plane.hip): what it did, and its hypotheses in drawing order (ope_plane_last_hypotheses)
+  ope_plane_stats plane_stats{};
+  std::vector<int32_t> plane_samples, plane_counts;
+  std::vector<float> plane_coeffs;
+
   // what the last ope_coarse_pose_batch computed (ope_coarse_batch_features): segment 0 the model, 1..n the clusters;
   // key points (original indices), normals (x y z) and FPFH rows, packed by segment from coarse_key_off
   std::vector<int32_t> coarse_key_off, coarse_key_idx;

@@ -285,3 +285,50 @@ def tabletop_objects(n_drill: int = 8000, density: float = 62500.0, seed: int = 
     oid = np.concatenate(ids)
     order = rng.permutation(len(pts))
     return pts[order], oid[order]
+
+
+def tabletop_camera_pose():
+    """(R, t): scene coordinates of tabletop_objects() -> the camera frame of tabletop_frame() (camera at the origin looking
+    along +z, the table tilted 35 degrees against the optical axis and rolled 7 degrees: its normal has no zero component)."""
+    th = np.deg2rad(35.0)
+    tilt = np.array([[1.0, 0.0, 0.0], [0.0, -np.sin(th), -np.cos(th)], [0.0, np.cos(th), -np.sin(th)]])
+    return rot_xyz(0.0, 0.0, 7.0) @ tilt, np.array([0.05, 0.30, 1.60])
+
+
+def tabletop_frame(n: int = 307200, seed: int = 31):
+    """A whole cropped camera frame of n points, as a sensor in front of a table would see it: the table top (a 1.5 m x 1.2 m
+    rectangle, the largest plane by far), the objects of tabletop_objects() standing on it (thinned for small n), floor 0.7 m
+    below and a low wall behind, both only OUTSIDE the table's rectangle, range noise of 1 mm along the viewing ray, 2 % NaN points;
+    shuffled.  Two sizes are used: n = 20000 for host-side reference runs, n = 307200 (640 x 480) for the device.
+    Returns (points float32 (n, 3), label int32 (n,)): 0-10 the object ids of tabletop_objects(), 100 table, 101 floor, 102 wall,
+    -1 a NaN point."""
+    rng = np.random.default_rng(seed)
+    small = n < 100000
+    obj, oid = tabletop_objects(n_drill=1500, density=8000.0, seed=seed + 1) if small else tabletop_objects(seed=seed + 1)
+    if len(obj) > n // 3:
+        raise ValueError("tabletop_frame: n is too small for the objects")
+    n_nan = n // 50
+    n_rest = n - len(obj) - n_nan
+    n_table, n_floor = int(n_rest * 0.62), int(n_rest * 0.22)
+    n_wall = n_rest - n_table - n_floor
+    table_z = GT_T[2] - 0.12
+    half = np.array([0.75, 0.60])
+    table = np.concatenate([rng.uniform(-half, half, (n_table, 2)), np.full((n_table, 1), table_z)], axis=1)
+    # floor: a 3.2 m x 2.8 m sheet 0.7 m below the table, minus the table's rectangle (with 5 cm to spare)
+    floor = np.zeros((0, 2))
+    while len(floor) < n_floor:
+        c = rng.uniform([-1.6, -1.4], [1.6, 1.4], (2 * n_floor, 2))
+        floor = np.concatenate([floor, c[(np.abs(c) > half + 0.05).any(axis=1)]])
+    floor = np.concatenate([floor[:n_floor], np.full((n_floor, 1), table_z - 0.7)], axis=1)
+    # wall: upright, 0.8 m behind the table's far edge, ending 5 cm below the table top (nothing but the table lies in its plane)
+    wall = np.stack([rng.uniform(-1.6, 1.6, n_wall), np.full(n_wall, half[1] + 0.8), rng.uniform(table_z - 0.7, table_z - 0.05, n_wall)], axis=1)
+    pts = np.concatenate([obj.astype(np.float64), table, floor, wall])
+    lab = np.concatenate([oid, np.full(n_table, 100, np.int32), np.full(n_floor, 101, np.int32), np.full(n_wall, 102, np.int32)])
+    R, t = tabletop_camera_pose()
+    cam = pts @ R.T + t
+    rng_len = np.linalg.norm(cam, axis=1, keepdims=True)
+    cam = cam * (1.0 + rng.normal(0.0, 0.001, (len(cam), 1)) / rng_len)
+    cam = np.concatenate([cam, np.full((n_nan, 3), np.nan)])
+    lab = np.concatenate([lab, np.full(n_nan, -1, np.int32)])
+    order = rng.permutation(n)
+    return cam[order].astype(np.float32), lab[order].astype(np.int32)
