@@ -789,6 +789,67 @@ typedef struct {
 int ope_tabletop_segment(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_params *params, ope_tabletop_result *out,
                          ope_cloud **plane, ope_cloud **not_plane, int32_t *prism_idx, int32_t *plane_idx, int32_t *not_plane_idx);
 
+/* ---------------- ingest: the sensor's depth image -> the frame's cloud ---------------- */
+/* DataGrabber::rgbd2Pcl (DetectAndLocalize/src/datagrabber.cpp:65-118, called once per frame at rosinterface.cpp:422) with
+ * depthToMeter (:121-174), optionally followed by getPassThrough (rosinterface.cpp:212), on the device: the caller hands over
+ * the 16-bit depth image and receives the cloud the later stages consume; no host cloud of the frame is built or uploaded.
+ *
+ * Arithmetic (all float, each operation rounded once, no contraction; division correctly rounded), datagrabber.cpp:169-171:
+ *     Z = (float)depth / scale
+ *     y = ((row - c_row) * Z) / f_row
+ *     x = ((col - c_col) * Z) / f_col
+ * A pixel is dropped iff depth == 0 (:127,142,155 with :90) or (double)Z > z_max (:90, "Z > 2.0": float against double).
+ *
+ * THE REFERENCE'S QUIRK.  rgbd2Pcl passes the ROW as p_FeatX and the COLUMN as p_FeatY (:86), depthToMeter applies cx / fx to
+ * p_FeatX and cy / fy to p_FeatY (:170-171), and rgbd2Pcl stores X into .y and Y into .x (:98-99).  So the reference's cx / fx
+ * act on the row and its cy / fy on the column: for the Kinect preset c_row = 319.5, f_row = 525, c_col = 239.5, f_col = 525 —
+ * the principal point is swapped against the image's axes.  ope_depth_sensor_params reproduces this, because the rest of the
+ * reference (the workspace limits, the model) was tuned on clouds made this way.  A caller with a correctly calibrated sensor
+ * fills the struct itself: the names below say what each value multiplies. */
+typedef struct {
+  float f_row, c_row;   /* y = (row - c_row) * Z / f_row */
+  float f_col, c_col;   /* x = (col - c_col) * Z / f_col */
+  float scale;          /* Z = (float)depth / scale; 1000 (:137,150,163) */
+  double z_max;         /* a pixel is dropped iff depth == 0 or (double)Z > z_max; 2.0 (:90) */
+} ope_depth_params;
+enum { OPE_SENSOR_KINECT = 0, OPE_SENSOR_ASTRA = 1, OPE_SENSOR_EUCLID = 2 };
+/* The reference's three intrinsics sets (fx fy cx cy as float, scale 1000, z_max 2.0):
+ *   Euclid 306.178 306.929 158.523 122.747 (:133-137), Kinect 525 525 319.5 239.5 (:146-150), Astra 570.342 570.342 314.5 235.5
+ *   (:159-163), with f_row = fx, c_row = cx, f_col = fy, c_col = cy (the quirk above).  OPE_EINVAL for another sensor. */
+int ope_depth_sensor_params(int sensor, ope_depth_params *p);
+/* depth: rows x cols samples, row r at (const char *)depth + r * row_stride_bytes (cv::Mat::step).
+ * lo / hi: both NULL for no crop; otherwise a point also has to satisfy lo[d] <= p[d] <= hi[d] for d = x, y, z
+ * (ope_pass_through's rule), and *out is exactly the cloud ope_pass_through_cloud(uncropped cloud, lo, hi) builds.
+ * *out (free it with ope_cloud_free): the surviving pixels in the reference's loop order, COLUMNS OUTER, ROWS INNER (:77-79) — the
+ * ORIGINAL order of the cloud — and otherwise what ope_cloud_upload of the reference's host cloud would build: same points,
+ * same bounding box, same Morton order.  out_pixel (optional, room for rows * cols): out_pixel[k] = row * cols + col of
+ * point k, for a caller that gathers colours (the overload of :9-62); *n_out (optional) the number of points.  An image with
+ * no surviving pixel gives an empty cloud and OPE_OK.
+ * Synchronous on the context's stream.  The image travels as 2 bytes per pixel; a workgroup transposes a 64 x 64 tile
+ * through LDS, a count pass and one scan place every (column, 64-row) segment, a second pass writes the points, their pixel
+ * indices and the bounding box.  The sequence of launches and host synchronisations is fixed for an image of up to 32 MB (the
+ * pinned staging block): it depends on neither the content nor the size.  A larger image travels in blocks, one more copy and
+ * one more synchronisation per block.
+ * OPE_EINVAL, nothing launched: a NULL ctx, depth, params or out; rows * cols == 0 or > 2^31 - 1; row_stride_bytes < 2 * cols
+ * or odd; scale, f_row or f_col not positive and finite; c_row or c_col not finite (no point would be finite, where the
+ * cloud of an upload has n_valid == n); one image row, padded to a multiple of 64 samples, above 32 MB; exactly one of lo / hi. */
+int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t rows, size_t cols, size_t row_stride_bytes,
+                       const ope_depth_params *params, const float lo[3], const float hi[3], ope_cloud **out, int32_t *out_pixel,
+                       size_t *n_out);
+/* What the last ope_depth_to_cloud of this context did.  launches and host_syncs are BOOKED along the call's fixed path, not
+ * observed from the runtime: one per kernel, copy or rocPRIM call this function enqueues (a rocPRIM call counts as one, however
+ * many kernels it issues inside) and one per stream synchronisation.  The Morton ordering of the new cloud is booked as 3
+ * launches and 1 synchronisation, for an empty cloud too, which orders nothing; the copy of out_pixel as 1 when asked for.
+ * They say that the call has no loop over the content; for what really ran, take a kernel trace. */
+typedef struct {
+  int64_t launches;
+  int64_t host_syncs;
+  int64_t pixels;   /* rows * cols */
+  int64_t valid;    /* pixels with depth != 0 and Z <= z_max */
+  int64_t kept;     /* points of the cloud (valid and inside the crop) */
+} ope_depth_stats;
+int ope_depth_last_stats(const ope_ctx *ctx, ope_depth_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

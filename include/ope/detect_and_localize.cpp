@@ -29,6 +29,16 @@
 // device); --track-loop: ObjectTracker::localizeLoop (host compute3DCentroid and estimateFinalPose, as the reference writes it).
 // Per frame: `track frame <k> branch <b> selected <i> clusters <n>`, then the `frame ...` line; --time adds `time frame <k> ms <t>`
 // (host clock around the synchronised call).
+//
+//   detect_and_localize --depth <model.pcd> <d0.pgm> [<d1.pgm> ...] [--sensor kinect|astra|euclid] [--limits x0 x1 y0 y1 z0 z1] [--seed N] [--time]
+//   detect_and_localize --depth-host <model.pcd> <d0.pgm> ... (same)
+// The body of the reference's per-frame loop from the sensor's depth image on (rosinterface.cpp:422, 212-313), one 16-bit PGM per
+// frame.  --depth: ope::DataGrabber::rgbd2PclDevice (conversion and the -l crop on the device), getSegmentedObjectsOnPlane on
+// that device frame, ObjectTracker::localize.  --depth-host: DataGrabber::rgbd2Pcl (the reference's loop on the host, no device
+// code), the three pcl::PassThrough, the upload inside getSegmentedObjectsOnPlane — the same frames the way they arrived before
+// the device ingest.  Per frame: `depth frame <k> points <n> plane <n> clusters <n> sizes ...`, then the --track lines; --time adds
+// `time frame <k> ms <t>` over the whole frame and `time ingest frame <k> ms <t> segment <t>`: until the cropped frame is ready
+// (--depth: on the device, synchronised; --depth-host: on the host), and getSegmentedObjectsOnPlane (--depth-host: with its upload).
 #include <cfloat>
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +48,7 @@
 
 #include <chrono>
 
+#include "data_grabber.hpp"
 #include "object_segmentation_plane.hpp"
 #include "object_tracker.hpp"
 #include "pcd_io.hpp"
@@ -117,7 +128,99 @@ static int track_main(int argc, char **argv) {
   return 0;
 }
 
+// --depth / --depth-host
+static int depth_main(int argc, char **argv) {
+  int mode = 0;   // 1: --depth, 2: --depth-host
+  std::vector<std::string> files;
+  std::string sensor = "kinect";
+  uint64_t seed = 1;
+  bool timed = false, limited = false;
+  float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
+  for (int i = 1; i < argc; ++i) {
+    if (!std::strcmp(argv[i], "--depth")) mode = 1;
+    else if (!std::strcmp(argv[i], "--depth-host")) mode = 2;
+    else if (!std::strcmp(argv[i], "--sensor") && i + 1 < argc) sensor = argv[++i];
+    else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
+    else if (!std::strcmp(argv[i], "--time")) timed = true;
+    else if (!std::strcmp(argv[i], "--limits") && i + 6 < argc) { limited = true; for (int d = 0; d < 6; ++d) limits[d] = std::strtof(argv[++i], nullptr); }
+    else files.push_back(argv[i]);
+  }
+  const bool euclid = sensor == "euclid", kinect = sensor == "kinect", astra = sensor == "astra";
+  if (!mode || files.size() < 2 || !(euclid || kinect || astra)) {
+    std::fprintf(stderr, "usage: %s --depth|--depth-host <model.pcd> <d0.pgm> [<d1.pgm> ...] [--sensor kinect|astra|euclid] [--limits ...] [--seed N] [--time]\n", argv[0]);
+    return 2;
+  }
+  typedef ope::PoseEstimator::PointT PointT;
+  pcl::PointCloud<PointT> model;
+  if (pcl::io::loadPCDFile(files[0], model) != 0) return 3;
+  ope::DataGrabber dataGrabber(euclid, kinect, astra);   // rosinterface.cpp:70
+  ope::ObjectTracker tracker(model);
+  tracker.estimator().setSacIaSeed(seed);
+  const float lo[3] = {limits[0], limits[2], limits[4]}, hi[3] = {limits[1], limits[3], limits[5]};
+  double fitnessScore = 10.0, alignedStrength = 0.0;
+  for (size_t k = 1; k < files.size(); ++k) {
+    ope::DepthImage imageDepth;
+    if (ope::io::loadPGM(files[k], imageDepth) != 0) return 3;
+    ope_ctx *ctx = pcl::default_context();
+    if (ctx) ope_ctx_sync(ctx);
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<pcl::PointCloud<PointT>::Ptr> clusters;
+    pcl::PointCloud<PointT>::Ptr cloudPlane;
+    ope::ObjectSegmentationPlane objSegPlane;
+    size_t points = 0;
+    bool isPlane = false;
+    auto t1 = t0;
+    if (mode == 1) {
+      auto frame = dataGrabber.rgbd2PclDevice(imageDepth, limited ? lo : nullptr, limited ? hi : nullptr);
+      if (!frame->h) return 4;
+      points = ope_cloud_size(frame->h);
+      t1 = std::chrono::steady_clock::now();   // (ope_depth_to_cloud returns synchronised)
+      isPlane = objSegPlane.getSegmentedObjectsOnPlane(*frame, clusters, cloudPlane);
+    } else {
+      pcl::PointCloud<PointT>::Ptr cloudTarget = dataGrabber.rgbd2Pcl(imageDepth);   // rosinterface.cpp:422
+      const char *fields[3] = {"x", "y", "z"};
+      for (int d = 0; limited && d < 3; ++d) {   // ProcessingPcd::getPassThrough (processingpcd.cpp:13-33)
+        pcl::PointCloud<PointT>::Ptr cloudFiltered(new pcl::PointCloud<PointT>);
+        pcl::PassThrough<PointT> pass;
+        pass.setInputCloud(cloudTarget);
+        pass.setFilterFieldName(fields[d]);
+        pass.setFilterLimits(limits[2 * d], limits[2 * d + 1]);
+        pass.filter(*cloudFiltered);
+        cloudTarget = cloudFiltered;
+      }
+      points = cloudTarget->size();
+      t1 = std::chrono::steady_clock::now();
+      isPlane = objSegPlane.getSegmentedObjectsOnPlane(cloudTarget, clusters, cloudPlane);
+    }
+    const auto t2 = std::chrono::steady_clock::now();
+    if (!isPlane) clusters.clear();   // (no table in this frame: nothing to localize against)
+    const pcl::Matrix4f pose = tracker.localize(clusters, fitnessScore, alignedStrength);
+    if (ctx) ope_ctx_sync(ctx);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const ope::PoseEstimator &e = tracker.estimator();
+    std::printf("depth frame %zu points %zu plane %zu clusters %zu sizes", k, points, isPlane ? cloudPlane->size() : (size_t)0, clusters.size());
+    for (const auto &c : clusters) std::printf(" %zu", c->size());
+    std::printf("\n");
+    std::printf("track frame %zu branch %s selected %d clusters %zu\n", k, branch_name(tracker.lastBranch()), tracker.lastSelected(), clusters.size());
+    if (timed) {
+      std::printf("time frame %zu ms %.4f\n", k, ms);
+      std::printf("time ingest frame %zu ms %.4f segment %.4f\n", k, std::chrono::duration<double, std::milli>(t1 - t0).count(),
+                  std::chrono::duration<double, std::milli>(t2 - t1).count());
+    }
+    std::printf("frame %zu fitness %.12g strength %.12g coarse_calls %d icp_iterations %d", k, fitnessScore, alignedStrength, e.coarseCalls(),
+                e.lastIcpIterations());
+    print16("final", pose);
+    print16("coarse", e.lastCoarsePose());
+    print16("fine", e.lastFinePose());
+    print16("rigid", e.lastRigidModelPose());
+    std::printf("\n");
+  }
+  return 0;
+}
+
 int main(int argc, char **argv) {
+  for (int i = 1; i < argc; ++i)
+    if (!std::strcmp(argv[i], "--depth") || !std::strcmp(argv[i], "--depth-host")) return depth_main(argc, argv);
   for (int i = 1; i < argc; ++i)
     if (!std::strcmp(argv[i], "--track") || !std::strcmp(argv[i], "--track-loop")) return track_main(argc, argv);
   std::vector<std::string> files;

@@ -12,6 +12,7 @@
 // getMinMax3D, and the extremes of a planar set are attained at its hull's vertices.
 #pragma once
 
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -90,20 +91,66 @@ class ObjectSegmentationPlane {
     if (!ctx || !p_cloudInput) return p_cloudInput ? hand_back() : false;
     auto frame = compat::upload(*p_cloudInput, false);
     if (!frame->h) return hand_back();
-    const size_t n = p_cloudInput->size();
+    // the output clouds are gathered from the input, so every field of the point type (the colour) is carried
+    return segmentDeviceFrame(ctx, frame->h, p_cloudInput->size(), [&](size_t i) { return p_cloudInput->points[i]; }, hand_back,
+                              cloudClusterVector, p_cloudPlane);
+  }
+
+  // The same for a frame that is already on the device (DataGrabber::rgbd2PclDevice: converted from the depth image and cropped
+  // there): the frame is not uploaded.  The host clouds the reference's signature asks for are built from ONE download of the
+  // frame's xyz (12 B per point; the device clusters are in deviceClusters() for a caller that needs no host clouds), white like
+  // DataGrabber::rgbd2Pcl's points (datagrabber.cpp:102-106).  false without a plane: cluster 0 is the frame.
+  bool getSegmentedObjectsOnPlane(const compat::CloudHandle &p_frame, std::vector<Cloud::Ptr> &cloudClusterVector, Cloud::Ptr &p_cloudPlane) {
+    p_cloudPlane = Cloud::Ptr(new Cloud);
+    last_ = ope_tabletop_result{};
+    last_.status = OPE_TABLETOP_NO_PLANE_FIRST;
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || !p_frame.h) return false;
+    const size_t n = ope_cloud_size(p_frame.h);
+    std::vector<float> xyz(3 * n + 3);
+    if (ope_cloud_download(ctx, p_frame.h, xyz.data()) != OPE_OK) { compat::log_error("getSegmentedObjectsOnPlane", ctx); return false; }
+    auto point = [&](size_t i) {
+      const uint32_t white = 0x00ffffffu;
+      PointTObj q;
+      q.x = xyz[3 * i]; q.y = xyz[3 * i + 1]; q.z = xyz[3 * i + 2];
+      std::memcpy(&q.rgb, &white, 4);
+      return q;
+    };
+    auto hand_back = [&]() {
+      if (cloudClusterVector.empty()) cloudClusterVector.push_back(Cloud::Ptr(new Cloud));
+      Cloud &out = *cloudClusterVector[0];
+      out.points.resize(n);
+      for (size_t i = 0; i < n; ++i) out.points[i] = point(i);
+      out.width = (uint32_t)n;
+      out.height = 1;
+      out.is_dense = true;
+      return false;
+    };
+    return segmentDeviceFrame(ctx, p_frame.h, n, point, hand_back, cloudClusterVector, p_cloudPlane);
+  }
+
+  // the clusters of the last successful call as they were left on the device (for ope_final_pose_batch / ope_track_pose without an upload)
+  const std::vector<std::shared_ptr<compat::CloudHandle>> &deviceClusters() const { return deviceClusters_; }
+
+ private:
+  // Steps 2-8 on a frame of n points that is on the device.  point(i): the host point of frame index i, from which the output
+  // clouds are gathered; hand_back(): what is returned when there is no plane.
+  template <class PointAt, class HandBack>
+  bool segmentDeviceFrame(ope_ctx *ctx, const ope_cloud *frame, size_t n, PointAt point, HandBack hand_back,
+                          std::vector<Cloud::Ptr> &cloudClusterVector, Cloud::Ptr &p_cloudPlane) {
     ope_plane_params p;
     ope_plane_default_params(&p);
     p.seed = seed_;
     compat::CloudHandle plane, notPlane;
     std::vector<int32_t> planeIdx(n + 1), notPlaneIdx(n + 1);
-    if (ope_tabletop_segment(ctx, frame->h, &p, &last_, &plane.h, &notPlane.h, nullptr, planeIdx.data(), notPlaneIdx.data()) != OPE_OK) {
+    if (ope_tabletop_segment(ctx, frame, &p, &last_, &plane.h, &notPlane.h, nullptr, planeIdx.data(), notPlaneIdx.data()) != OPE_OK) {
       compat::log_error("getSegmentedObjectsOnPlane", ctx);
       return hand_back();
     }
     if (last_.status != OPE_TABLETOP_OK) return hand_back();
     auto gather = [&](Cloud &out, const int32_t *map, const int32_t *idx, size_t m) {
       out.points.resize(m);
-      for (size_t j = 0; j < m; ++j) out.points[j] = p_cloudInput->points[map[idx ? idx[j] : (int32_t)j]];
+      for (size_t j = 0; j < m; ++j) out.points[j] = point((size_t)map[idx ? idx[j] : (int32_t)j]);
       out.width = (uint32_t)m;
       out.height = 1;
       out.is_dense = true;
@@ -132,10 +179,6 @@ class ObjectSegmentationPlane {
     return true;
   }
 
-  // the clusters of the last successful call as they were left on the device (for ope_final_pose_batch / ope_track_pose without an upload)
-  const std::vector<std::shared_ptr<compat::CloudHandle>> &deviceClusters() const { return deviceClusters_; }
-
- private:
   compat::SACSegmentation<PointTObj> sacSeg;
   compat::ExtractIndices<PointTObj> extractIndices;
   compat::EuclideanClusterExtraction<PointTObj> euclideanClustExtraction;

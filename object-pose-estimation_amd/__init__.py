@@ -268,6 +268,32 @@ class TabletopResult(C.Structure):
 
 TABLETOP_OK, TABLETOP_NO_PLANE_FIRST, TABLETOP_NO_PLANE_SECOND = 0, 1, 2
 
+
+class DepthParams(C.Structure):
+    """ope_depth_params: the reference applies its cx / fx to the ROW and its cy / fy to the COLUMN (datagrabber.cpp:86,170-171)."""
+    _fields_ = [
+        ("f_row", C.c_float),
+        ("c_row", C.c_float),
+        ("f_col", C.c_float),
+        ("c_col", C.c_float),
+        ("scale", C.c_float),
+        ("z_max", C.c_double),
+    ]
+
+
+class DepthStats(C.Structure):
+    _fields_ = [
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+        ("pixels", C.c_int64),
+        ("valid", C.c_int64),
+        ("kept", C.c_int64),
+    ]
+
+
+SENSOR_KINECT, SENSOR_ASTRA, SENSOR_EUCLID = 0, 1, 2
+SENSORS = {"kinect": SENSOR_KINECT, "astra": SENSOR_ASTRA, "euclid": SENSOR_EUCLID}
+
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
 _dp = C.POINTER(C.c_double)
@@ -376,6 +402,10 @@ ABI = [
     ("ope_prism_extract", C.c_int, [_vp, _vp, _fp, C.c_size_t, C.c_double, C.c_double, _ip, C.POINTER(C.c_size_t), C.POINTER(_vp), _fp]),
     ("ope_tabletop_segment", C.c_int, [_vp, _vp, C.POINTER(PlaneParams), C.POINTER(TabletopResult), C.POINTER(_vp), C.POINTER(_vp), _ip, _ip,
                                         _ip]),
+    ("ope_depth_sensor_params", C.c_int, [C.c_int, C.POINTER(DepthParams)]),
+    ("ope_depth_to_cloud", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(DepthParams), _fp, _fp, C.POINTER(_vp), _ip,
+                                      C.POINTER(C.c_size_t)]),
+    ("ope_depth_last_stats", C.c_int, [_vp, C.POINTER(DepthStats)]),
 ]
 
 _lib = None
@@ -420,6 +450,19 @@ def colmajor(T) -> np.ndarray:
 
 def from_colmajor(t16) -> np.ndarray:
     return np.asarray(t16, np.float32).reshape(4, 4).T.copy()
+
+
+def default_depth_params(sensor="kinect", **kw) -> DepthParams:
+    """ope_depth_sensor_params: one of the reference's three presets ("kinect", "astra", "euclid" or an OPE_SENSOR_* value)."""
+    p = DepthParams()
+    code = SENSORS[sensor] if isinstance(sensor, str) else int(sensor)
+    if lib().ope_depth_sensor_params(code, C.byref(p)) != OPE_OK:
+        raise ValueError(f"unknown sensor {sensor!r}")
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
 
 
 def default_icp_params(**kw) -> IcpParams:
@@ -895,6 +938,38 @@ class Context:
                            li[: r.n_plane].copy() if ok else None, ni[: r.n_not_plane].copy() if ok else None,
                            Cloud(self, hp, r.n_plane) if ok else None, Cloud(self, hn, r.n_not_plane) if ok else None,
                            r.iterations_first, r.iterations_second, r.launches, r.host_syncs)
+
+    def depth_to_cloud(self, depth, params: "DepthParams | None" = None, lo=None, hi=None, want_pixels: bool = False):
+        """ope_depth_to_cloud: a (rows, cols) uint16 depth image -> the frame's Cloud (rgbd2Pcl, optionally cropped to lo .. hi).
+        Rows may be strided (a view with a row pitch); samples within a row must be contiguous.  Returns the Cloud, or
+        (Cloud, pixel indices row * cols + col) with want_pixels."""
+        depth = np.asarray(depth)
+        if depth.dtype != np.uint16 or depth.ndim != 2:
+            raise ValueError("depth_to_cloud: expected a 2-D uint16 image")
+        rows, cols = depth.shape
+        if rows * cols and (depth.strides[1] != 2 or (rows > 1 and depth.strides[0] < 2 * cols)):
+            depth = np.ascontiguousarray(depth)
+        stride = depth.strides[0] if rows > 1 and rows * cols else 2 * cols
+        if (lo is None) != (hi is None):
+            raise ValueError("depth_to_cloud: give both lo and hi, or neither")
+        if lo is not None:
+            lo = np.ascontiguousarray(lo, np.float32); hi = np.ascontiguousarray(hi, np.float32)
+            if lo.shape != (3,) or hi.shape != (3,):
+                raise ValueError("depth_to_cloud: lo and hi are 3-vectors")
+        p = params if params is not None else default_depth_params()
+        pix = np.empty(max(rows * cols, 1), np.int32) if want_pixels else None
+        n = C.c_size_t(0)
+        h = _vp()
+        self._chk(lib().ope_depth_to_cloud(self.h, _vp(depth.ctypes.data), rows, cols, stride, C.byref(p), _p(lo, _fp), _p(hi, _fp),
+                                           C.byref(h), _p(pix, _ip), C.byref(n)))
+        c = Cloud(self, h, n.value)
+        return (c, pix[: n.value].copy()) if want_pixels else c
+
+    def depth_stats(self) -> dict:
+        """ope_depth_last_stats: launches, host synchronisations, pixels, valid pixels, points kept."""
+        s = DepthStats()
+        self._chk(lib().ope_depth_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in DepthStats._fields_}
 
     def track_gate(self, source: "Cloud", clusters, params: TrackParams | None = None) -> GateOut:
         """ope_track_gate: the centroid gate of the reference's later frames (rosinterface.cpp:264-304)."""

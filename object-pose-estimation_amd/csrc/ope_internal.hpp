@@ -272,6 +272,8 @@ struct ope_ctx {
   std::vector<int32_t> plane_samples, plane_counts;
   std::vector<float> plane_coeffs;
 
+  ope_depth_stats depth_stats{};   // what the last ope_depth_to_cloud did (depth.hip)
+
   // what the last ope_coarse_pose_batch computed (ope_coarse_batch_features): segment 0 the model, 1..n the clusters;
   // key points (original indices), normals (x y z) and FPFH rows, packed by segment from coarse_key_off
   std::vector<int32_t> coarse_key_off, coarse_key_idx;

@@ -332,3 +332,19 @@ def tabletop_frame(n: int = 307200, seed: int = 31):
     lab = np.concatenate([lab, np.full(n_nan, -1, np.int32)])
     order = rng.permutation(n)
     return cam[order].astype(np.float32), lab[order].astype(np.int32)
+
+
+TABLETOP_DEPTH_CAMERA_SHIFT = np.array([0.0, 0.22, 0.40])
+
+
+def tabletop_depth_image(rows: int = 480, cols: int = 640, seed: int = 31, drill_shift=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """The scene of tabletop_frame() as the sensor's 16-bit depth image (millimetres, holes 0): its rows * cols points seen
+    from TABLETOP_DEPTH_CAMERA_SHIFT (0.40 m closer, 0.22 m lower) off tabletop_camera_pose() (the table then lies inside the Kinect preset's 2 m and
+    around its swapped principal point), rendered through that preset by depth.render_depth.  The floor lies beyond 2 m and
+    drops out in the conversion.  drill_shift moves the model ("drill") by that much in the scene's coordinates (along the table:
+    x, y), for the later frames of a sequence."""
+    from .depth import preset_params, render_depth
+    pts, lab = tabletop_frame(rows * cols, seed)
+    pts = pts.astype(np.float64)
+    pts[lab == 0] += tabletop_camera_pose()[0] @ np.asarray(drill_shift, np.float64)
+    return render_depth(pts - TABLETOP_DEPTH_CAMERA_SHIFT, preset_params("kinect"), rows, cols)
