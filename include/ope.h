@@ -98,14 +98,29 @@ int ope_cloud_upload(ope_ctx *ctx, const void *base, size_t n, size_t stride_byt
                      ptrdiff_t normal_off, ope_cloud **out);
 /* Attach / replace normals (n*3 packed floats, original order). */
 int ope_cloud_set_normals(ope_ctx *ctx, ope_cloud *cloud, const float *normals_xyz);
+/* The colour payload of a cloud: one word per point, the 32 bits of pcl::PointXYZRGB::rgb (r << 16 | g << 8 | b, top byte as
+ * given), kept on the device beside the points.  ope_cloud_set_rgb attaches / replaces it from n words in ORIGINAL order; NULL
+ * detaches it (the cloud is then what it was before: nothing else about a cloud depends on its colours).  ope_cloud_has_rgb: 1 or
+ * 0 (0 for NULL).  ope_cloud_download_rgb: the n words in ORIGINAL order; OPE_EINVAL when the cloud has no colours.
+ * CARRIED: every entry point that makes a cloud from clouds hands the payload on with the points, in the launches that move the
+ * points (no further launch or synchronisation): ope_cloud_select (repeats and any order), ope_cloud_concat (below), the _cloud
+ * forms of the filters (ope_remove_nan_cloud, ope_pass_through_cloud, ope_statistical_outlier_removal_cloud,
+ * ope_uniform_sampling_cloud: the chosen point's colour), plane / not_plane of ope_plane_segment and ope_tabletop_segment, out of
+ * ope_prism_extract, the clusters of ope_euclidean_clusters_cloud, and ope_depth_to_cloud_rgb makes it.  An empty cloud made from a
+ * coloured one has colours.  NOT carried: *aligned of ope_track_pose (the moved model; the tracker reads no colours). */
+int ope_cloud_set_rgb(ope_ctx *ctx, ope_cloud *cloud, const uint32_t *rgb);
+int ope_cloud_has_rgb(const ope_cloud *cloud);
+int ope_cloud_download_rgb(ope_ctx *ctx, const ope_cloud *cloud, uint32_t *out);
 /* pcl::transformPointCloud(a, ., T_a) followed by operator+= (BuildModel regmeshpcd.cpp:203,254: cloudTemp = aligned + target),
  * built on the device: out holds T_a * a (T_a may be NULL: identity) followed by b, ORIGINAL indices a's then b's.  Neither
- * input travels through the host; normals are not carried (re-estimated per pair in the reference, :72-90). */
+ * input travels through the host; normals are not carried (re-estimated per pair in the reference, :72-90).  Colours are
+ * carried when BOTH a and b have them (operator+= keeps rgb; T_a does not touch them): a's words, then b's.  With colours on
+ * one side only the result has none. */
 int ope_cloud_concat(ope_ctx *ctx, const ope_cloud *a, const float T_a[16], const ope_cloud *b, ope_cloud **out);
 /* xyz of a cloud in ORIGINAL order (n*3 floats): the way out for clouds made by ope_cloud_concat. */
 int ope_cloud_download(ope_ctx *ctx, const ope_cloud *cloud, float *out_xyz);
 /* A new cloud from n ORIGINAL indices of `cloud` (host array, any order, repeats allowed), gathered on the device: the new
- * cloud's original order is the order of idx; normals attached to `cloud` are carried.  What `cloud[idx]` would be after an
+ * cloud's original order is the order of idx; normals and colours attached to `cloud` are carried.  What `cloud[idx]` would be after an
  * upload, without the trip through the host (the hand-over between the stages in front of the path:
  * rosinterface.cpp:212-213 -> poseestimator.cpp:141-156). */
 int ope_cloud_select(ope_ctx *ctx, const ope_cloud *cloud, const int32_t *idx, size_t n, ope_cloud **out);
@@ -836,7 +851,23 @@ int ope_depth_sensor_params(int sensor, ope_depth_params *p);
 int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t rows, size_t cols, size_t row_stride_bytes,
                        const ope_depth_params *params, const float lo[3], const float hi[3], ope_cloud **out, int32_t *out_pixel,
                        size_t *n_out);
-/* What the last ope_depth_to_cloud of this context did.  launches and host_syncs are BOOKED along the call's fixed path, not
+/* rgbd2Pcl(p_imageRgb, p_imageDepth), the two-image overload (BuildModel/src/datagrabber.cpp:9-64): ope_depth_to_cloud of `depth`
+ * — geometry, drop rule, order, crop, bounding box and Morton order bit for bit — whose point k also carries
+ * r << 16 | g << 8 | b of its pixel as the cloud's colour payload (ope_cloud_download_rgb), where b, g, r are bytes 0, 1, 2 of
+ * pixel (row, col) of a CV_8UC3 image (:48-51): pixel (r, c) at bgr + r * bgr_stride_bytes + 3 * c.  The top byte is 0.  The
+ * cloud has colours also when it is empty.
+ * The colour image travels as 3 bytes per pixel in the same pinned block and the same copy as the depth image (a staged row is
+ * the depth row followed by its colour row, 5 bytes per padded pixel); the second pass reads a tile's 64 x 64 pixels as 16-byte
+ * loads, transposes them through LDS beside the depth tile (12 KB) and writes the colour word with the point; the Morton
+ * ordering's gather moves it with the point.  Launches and synchronisations are those of ope_depth_to_cloud, one for one,
+ * whatever the images hold and, up to 32 MB of staged rows (6.7 M pixels), whatever their size; above, depth and colour travel
+ * together in blocks of whole rows, one more copy and one more synchronisation per block.  ope_depth_last_stats reports the call.
+ * OPE_EINVAL, nothing launched: the cases of ope_depth_to_cloud (one padded row here at 5 bytes per pixel); bgr NULL;
+ * bgr_stride_bytes < 3 * cols. */
+int ope_depth_to_cloud_rgb(ope_ctx *ctx, const uint16_t *depth, size_t rows, size_t cols, size_t depth_stride_bytes,
+                           const unsigned char *bgr, size_t bgr_stride_bytes, const ope_depth_params *params, const float lo[3],
+                           const float hi[3], ope_cloud **out, int32_t *out_pixel, size_t *n_out);
+/* What the last ope_depth_to_cloud or ope_depth_to_cloud_rgb of this context did.  launches and host_syncs are BOOKED along the call's fixed path, not
  * observed from the runtime: one per kernel, copy or rocPRIM call this function enqueues (a rocPRIM call counts as one, however
  * many kernels it issues inside) and one per stream synchronisation.  The Morton ordering of the new cloud is booked as 3
  * launches and 1 synchronisation, for an empty cloud too, which orders nothing; the copy of out_pixel as 1 when asked for.

@@ -3,19 +3,92 @@
 //
 //   build_model <out.pcd> <corrRejThresh> <maxIter> <frame0.pcd> <frame1.pcd> [...]
 //
+// and from the sensor's images, BuildModel's whole sequence (rgbd2Pcl(rgb, depth) of datagrabber.cpp:9-64 in front of
+// main.cpp:171-198: getPassThrough, getSegmentedObjectsOnPlane, cluster 0), every step on the device:
+//
+//   build_model --scan <kinect|astra|euclid> --limits x0 x1 y0 y1 z0 z1 <out.pcd> <corrRejThresh> <maxIter> <depth0.pgm> <rgb0.ppm> [...]
+//
+// Depth images are 16-bit binary PGM, colour images 8-bit binary PPM (depth_io.hpp).  A frame without a supporting plane or
+// without a cluster ends the program with a message and status 5 (the reference's cloudClusterVector.at(0) throws).
 // Prints one `pair <k> iterations <n> converged <0|1> fitness <f> T <16 floats, column-major>` line per registration.
+// Status: 2 usage, 3 a file that does not load, 4 the model could not be written, 5 a frame without plane or cluster, 6 a
+// device failure.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
+#include "data_grabber.hpp"
+#include "object_segmentation_plane.hpp"
 #include "pcd_io.hpp"
 #include "reg_mesh_pcd.hpp"
 
 namespace pcl = ope::compat;
 
+static int usage(const char *prog) {
+  std::fprintf(stderr,
+               "usage: %s <out.pcd> <corrRejThresh> <maxIter> <frame0.pcd> <frame1.pcd> [...]\n"
+               "       %s --scan <kinect|astra|euclid> --limits x0 x1 y0 y1 z0 z1 <out.pcd> <corrRejThresh> <maxIter> <depth0.pgm> <rgb0.ppm> "
+               "[<depth1.pgm> <rgb1.ppm> ...]\n",
+               prog, prog);
+  return 2;
+}
+
+static void print_pairs(const ope::RegMeshPcd &reg) {
+  for (size_t k = 0; k < reg.pairs().size(); ++k) {
+    const auto &p = reg.pairs()[k];
+    std::printf("pair %zu iterations %d converged %d fitness %.12g T", k, p.iterations, (int)p.converged, p.fitness);
+    for (int i = 0; i < 16; ++i) std::printf(" %.9g", (double)p.T.m[i]);
+    std::printf("\n");
+  }
+}
+
+// build_model --scan: argv[2] the sensor, argv[3] "--limits", argv[4..9] the box, argv[10..12] out / thresh / iterations, then the pairs
+static int scan_main(int argc, char **argv) {
+  if (argc < 15 || (argc - 13) % 2 != 0 || std::strcmp(argv[3], "--limits") != 0) return usage(argv[0]);
+  const std::string sensor = argv[2];
+  if (sensor != "kinect" && sensor != "astra" && sensor != "euclid") return usage(argv[0]);
+  float lo[3], hi[3];
+  for (int d = 0; d < 3; ++d) {
+    char *end = nullptr;
+    lo[d] = std::strtof(argv[4 + 2 * d], &end);
+    if (end == argv[4 + 2 * d] || *end) return usage(argv[0]);
+    hi[d] = std::strtof(argv[5 + 2 * d], &end);
+    if (end == argv[5 + 2 * d] || *end) return usage(argv[0]);
+  }
+  const std::string out_path = argv[10];
+  const float corrRejThresh = (float)std::atof(argv[11]);
+  const int maxIter = std::atoi(argv[12]);
+  ope::DataGrabber dataGrabber(sensor == "euclid", sensor == "kinect", sensor == "astra");
+  ope::ObjectSegmentationPlane objSegPlane;
+  std::vector<std::shared_ptr<pcl::CloudHandle>> cloudVectorSeg;
+  for (int i = 13; i + 1 < argc; i += 2) {
+    ope::DepthImage imageDepth;
+    ope::ColorImage imageRgb;
+    if (ope::io::loadPGM(argv[i], imageDepth) != 0 || ope::io::loadPPM(argv[i + 1], imageRgb) != 0) return 3;
+    auto frame = dataGrabber.rgbd2PclDevice(imageRgb, imageDepth, lo, hi);   // rgbd2Pcl + getPassThrough (main.cpp:180)
+    if (!frame->h) return 6;
+    std::printf("%zu\n", ope_cloud_size(frame->h));                          // :177
+    const bool isPlane = objSegPlane.segmentOnDevice(*frame);               // :181, no host clouds
+    if (objSegPlane.deviceFailed()) return 6;
+    if (!isPlane) { std::fprintf(stderr, "build_model: no supporting plane in %s\n", argv[i]); return 5; }
+    if (objSegPlane.deviceClusters().empty()) { std::fprintf(stderr, "build_model: no cluster on the plane in %s\n", argv[i]); return 5; }
+    cloudVectorSeg.push_back(objSegPlane.deviceClusters()[0]);              // :182
+  }
+  std::printf("Finished segmentation of %zu point clouds!\n", cloudVectorSeg.size());
+  ope::RegMeshPcd regMeshPcd;
+  auto cloudAligned = regMeshPcd.registerPointClouds(cloudVectorSeg, 0.005f, corrRejThresh, maxIter);   // :207
+  if (cloudAligned->empty()) return 6;
+  print_pairs(regMeshPcd);
+  if (pcl::io::savePCDFile(out_path, *cloudAligned, true) != 0) return 4;   // :221
+  std::printf("Saved %zu data points to %s.\n", cloudAligned->size(), out_path.c_str());
+  return 0;
+}
+
 int main(int argc, char **argv) {
-  if (argc < 6) { std::fprintf(stderr, "usage: %s <out.pcd> <corrRejThresh> <maxIter> <frame0.pcd> <frame1.pcd> [...]\n", argv[0]); return 2; }
+  if (argc > 1 && std::strcmp(argv[1], "--scan") == 0) return scan_main(argc, argv);
+  if (argc < 6) return usage(argv[0]);
   const std::string out_path = argv[1];
   const float corrRejThresh = (float)std::atof(argv[2]);
   const int maxIter = std::atoi(argv[3]);
@@ -28,12 +101,7 @@ int main(int argc, char **argv) {
   }
   ope::RegMeshPcd regMeshPcd;
   pcl::PointCloud<PointTReg>::Ptr cloudAligned = regMeshPcd.registerPointClouds(cloudVector, 0.005f, corrRejThresh, maxIter);   // main.cpp:207
-  for (size_t k = 0; k < regMeshPcd.pairs().size(); ++k) {
-    const auto &p = regMeshPcd.pairs()[k];
-    std::printf("pair %zu iterations %d converged %d fitness %.12g T", k, p.iterations, (int)p.converged, p.fitness);
-    for (int i = 0; i < 16; ++i) std::printf(" %.9g", (double)p.T.m[i]);
-    std::printf("\n");
-  }
+  print_pairs(regMeshPcd);
   if (pcl::io::savePCDFile(out_path, *cloudAligned, true) != 0) return 4;   // main.cpp:221
   std::printf("Saved %zu data points to %s.\n", cloudAligned->size(), out_path.c_str());
   return 0;

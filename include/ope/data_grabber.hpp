@@ -59,6 +59,32 @@ class DataGrabber {
     return cloud;
   }
 
+  // BuildModel datagrabber.cpp:9-64, the reference's own signature with the images in place of its cv::Mat: the loop on the host
+  Cloud::Ptr rgbd2Pcl(const ColorImage &p_imageRgb, const DepthImage &p_imageDepth) {
+    if (p_imageRgb.rows != p_imageDepth.rows || p_imageRgb.cols != p_imageDepth.cols) {
+      std::fprintf(stderr, "[ope::DataGrabber] the colour image is not of the depth image's size\n");
+      return Cloud::Ptr(new Cloud);
+    }
+    return rgbd2Pcl(p_imageRgb.data.data(), p_imageRgb.step, p_imageDepth);
+  }
+
+  // The coloured frame as a device cloud (ope_depth_to_cloud_rgb), cropped to lo .. hi (both null: no crop): the points carry
+  // their colours on the device, through the segmentation and the registration behind it.  An empty handle on failure.
+  std::shared_ptr<compat::CloudHandle> rgbd2PclDevice(const ColorImage &p_imageRgb, const DepthImage &p_imageDepth, const float *lo = nullptr,
+                                                      const float *hi = nullptr) {
+    auto r = std::make_shared<compat::CloudHandle>();
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || !valid_ || p_imageDepth.empty() || p_imageRgb.rows != p_imageDepth.rows || p_imageRgb.cols != p_imageDepth.cols) {
+      if (ctx && !valid_) std::fprintf(stderr, "[ope::DataGrabber] no sensor was selected\n");
+      else if (ctx && !p_imageDepth.empty()) std::fprintf(stderr, "[ope::DataGrabber] the colour image is not of the depth image's size\n");
+      return r;
+    }
+    if (ope_depth_to_cloud_rgb(ctx, p_imageDepth.data.data(), p_imageDepth.rows, p_imageDepth.cols, p_imageDepth.step, p_imageRgb.data.data(),
+                               p_imageRgb.step, &params_, lo, hi, &r->h, nullptr, nullptr) != OPE_OK)
+      compat::log_error("DataGrabber::rgbd2Pcl", ctx);
+    return r;
+  }
+
   // The frame as a device cloud, cropped to lo .. hi (both null: no crop); an empty handle on failure.  pixel (optional): the
   // pixel index row * cols + col of every point.
   std::shared_ptr<compat::CloudHandle> rgbd2PclDevice(const DepthImage &p_imageDepth, const float *lo = nullptr, const float *hi = nullptr,

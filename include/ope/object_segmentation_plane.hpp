@@ -5,8 +5,8 @@
 //
 // getSegmentedObjectsOnPlane keeps the reference's signature and return values.  Steps 2-7 (:124-235) are one ope_tabletop_segment
 // call on the uploaded frame, step 8 (getClusters, :239) is ope_euclidean_clusters_cloud on the non-plane cloud it left on the
-// device; only index lists come back, and the output clouds are gathered on the host from the input through them, so every
-// field of the point type (the colour) is carried although device clouds hold xyz only.  The members the reference exposes
+// device; only index lists come back, and the output clouds of a HOST frame are gathered on the host from the input through
+// them, so every field of the point type is carried.  A DEVICE frame with a colour payload hands it on to the clusters.  The members the reference exposes
 // one by one (getPlaneIndicesAndCoeffSAC, getPlaneAndNonPlaneCloud, getClusters, getProjectedCloud) are here too, written
 // with the façade's classes as the reference writes them with PCL's.  No ConvexHull: the reference uses the hull only through
 // getMinMax3D, and the extremes of a planar set are attained at its hull's vertices.
@@ -100,6 +100,8 @@ class ObjectSegmentationPlane {
   // there): the frame is not uploaded.  The host clouds the reference's signature asks for are built from ONE download of the
   // frame's xyz (12 B per point; the device clusters are in deviceClusters() for a caller that needs no host clouds), white like
   // DataGrabber::rgbd2Pcl's points (datagrabber.cpp:102-106).  false without a plane: cluster 0 is the frame.
+  // A frame that carries colours (the coloured rgbd2PclDevice): the device clusters carry them too, and every host cloud takes
+  // its colours from one ope_cloud_download_rgb of the device cloud it mirrors (the frame's own when it is handed back).
   bool getSegmentedObjectsOnPlane(const compat::CloudHandle &p_frame, std::vector<Cloud::Ptr> &cloudClusterVector, Cloud::Ptr &p_cloudPlane) {
     p_cloudPlane = Cloud::Ptr(new Cloud);
     last_ = ope_tabletop_result{};
@@ -109,16 +111,22 @@ class ObjectSegmentationPlane {
     const size_t n = ope_cloud_size(p_frame.h);
     std::vector<float> xyz(3 * n + 3);
     if (ope_cloud_download(ctx, p_frame.h, xyz.data()) != OPE_OK) { compat::log_error("getSegmentedObjectsOnPlane", ctx); return false; }
+    const bool coloured = ope_cloud_has_rgb(p_frame.h) != 0;
+    std::vector<uint32_t> frameRgb;   // fetched only when the frame itself is handed back
     auto point = [&](size_t i) {
       const uint32_t white = 0x00ffffffu;
       PointTObj q;
       q.x = xyz[3 * i]; q.y = xyz[3 * i + 1]; q.z = xyz[3 * i + 2];
-      std::memcpy(&q.rgb, &white, 4);
+      std::memcpy(&q.rgb, frameRgb.empty() ? &white : &frameRgb[i], 4);
       return q;
     };
     auto hand_back = [&]() {
       if (cloudClusterVector.empty()) cloudClusterVector.push_back(Cloud::Ptr(new Cloud));
       Cloud &out = *cloudClusterVector[0];
+      if (coloured && n) {
+        frameRgb.resize(n);
+        if (ope_cloud_download_rgb(ctx, p_frame.h, frameRgb.data()) != OPE_OK) { compat::log_error("getSegmentedObjectsOnPlane", ctx); frameRgb.clear(); }
+      }
       out.points.resize(n);
       for (size_t i = 0; i < n; ++i) out.points[i] = point(i);
       out.width = (uint32_t)n;
@@ -129,6 +137,22 @@ class ObjectSegmentationPlane {
     return segmentDeviceFrame(ctx, p_frame.h, n, point, hand_back, cloudClusterVector, p_cloudPlane);
   }
 
+  // The same without any host cloud: only deviceClusters() is filled (BuildModel's scan loop hands cluster 0 straight to the
+  // registration).  false without a plane, or when a device call failed (deviceFailed() tells the two apart); true with
+  // deviceClusters() empty when nothing on the plane is a cluster.
+  bool segmentOnDevice(const compat::CloudHandle &p_frame) {
+    last_ = ope_tabletop_result{};
+    last_.status = OPE_TABLETOP_NO_PLANE_FIRST;
+    deviceClusters_.clear();
+    deviceFailed_ = false;
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || !p_frame.h) { deviceFailed_ = true; return false; }
+    compat::CloudHandle plane;
+    return runOnDevice(ctx, p_frame.h, plane, nullptr, nullptr, nullptr, nullptr) == 0 && !deviceFailed_;
+  }
+  // the last call ended because a device call failed (its message is on stderr), not because the frame has no plane
+  bool deviceFailed() const { return deviceFailed_; }
+
   // the clusters of the last successful call as they were left on the device (for ope_final_pose_batch / ope_track_pose without an upload)
   const std::vector<std::shared_ptr<compat::CloudHandle>> &deviceClusters() const { return deviceClusters_; }
 
@@ -138,45 +162,71 @@ class ObjectSegmentationPlane {
   template <class PointAt, class HandBack>
   bool segmentDeviceFrame(ope_ctx *ctx, const ope_cloud *frame, size_t n, PointAt point, HandBack hand_back,
                           std::vector<Cloud::Ptr> &cloudClusterVector, Cloud::Ptr &p_cloudPlane) {
-    ope_plane_params p;
-    ope_plane_default_params(&p);
-    p.seed = seed_;
-    compat::CloudHandle plane, notPlane;
-    std::vector<int32_t> planeIdx(n + 1), notPlaneIdx(n + 1);
-    if (ope_tabletop_segment(ctx, frame, &p, &last_, &plane.h, &notPlane.h, nullptr, planeIdx.data(), notPlaneIdx.data()) != OPE_OK) {
-      compat::log_error("getSegmentedObjectsOnPlane", ctx);
-      return hand_back();
-    }
-    if (last_.status != OPE_TABLETOP_OK) return hand_back();
-    auto gather = [&](Cloud &out, const int32_t *map, const int32_t *idx, size_t m) {
+    compat::CloudHandle plane;
+    std::vector<int32_t> planeIdx(n + 1), notPlaneIdx(n + 1), idx, off;
+    deviceFailed_ = false;
+    const int rc = runOnDevice(ctx, frame, plane, planeIdx.data(), notPlaneIdx.data(), &idx, &off);
+    if (rc != 0) return hand_back();
+    // dev: the device cloud `out` mirrors; when it carries colours they overwrite the gathered ones (one download per cloud)
+    std::vector<uint32_t> rgb;
+    auto gather = [&](Cloud &out, const int32_t *map, const int32_t *idx, size_t m, const ope_cloud *dev) {
       out.points.resize(m);
       for (size_t j = 0; j < m; ++j) out.points[j] = point((size_t)map[idx ? idx[j] : (int32_t)j]);
+      if (dev && m && ope_cloud_has_rgb(dev)) {
+        rgb.resize(m);
+        if (ope_cloud_download_rgb(ctx, dev, rgb.data()) == OPE_OK)
+          for (size_t j = 0; j < m; ++j) std::memcpy(&out.points[j].rgb, &rgb[j], 4);
+        else compat::log_error("getSegmentedObjectsOnPlane", ctx);
+      }
       out.width = (uint32_t)m;
       out.height = 1;
       out.is_dense = true;
     };
-    gather(*p_cloudPlane, planeIdx.data(), nullptr, (size_t)last_.n_plane);   // copyPointCloud(*cloudplane, *p_cloudPlane) (:235)
-    // getClusters on the device cloud (:239), each cluster's points by index (:247-277)
+    gather(*p_cloudPlane, planeIdx.data(), nullptr, (size_t)last_.n_plane, plane.h);   // copyPointCloud(*cloudplane, *p_cloudPlane) (:235)
+    // each cluster's points by index (:247-277)
+    for (size_t c = 0; !deviceFailed_ && c < deviceClusters_.size(); ++c) {
+      Cloud::Ptr cloudCluster(new Cloud);
+      gather(*cloudCluster, notPlaneIdx.data(), idx.data() + off[c], (size_t)(off[c + 1] - off[c]), deviceClusters_[c]->h);
+      cloudClusterVector.push_back(cloudCluster);
+    }
+    return true;
+  }
+
+  // Steps 2-7 (ope_tabletop_segment, the estimator's seed) and step 8 (getClusters, :239: ope_euclidean_clusters_cloud on the
+  // non-plane cloud) on a device frame: deviceClusters_ is filled, `plane` receives the plane cloud.  planeIdx / notPlaneIdx (room
+  // for every point of the frame) and idx / off (the clusters' points as indices into the non-plane cloud) are optional.
+  // 0: a plane (a failed clustering call leaves no clusters and sets deviceFailed_); 1: no plane; -1: the segmentation call failed.
+  int runOnDevice(ope_ctx *ctx, const ope_cloud *frame, compat::CloudHandle &plane, int32_t *planeIdx, int32_t *notPlaneIdx,
+                  std::vector<int32_t> *idx, std::vector<int32_t> *off) {
+    ope_plane_params p;
+    ope_plane_default_params(&p);
+    p.seed = seed_;
+    compat::CloudHandle notPlane;
+    if (ope_tabletop_segment(ctx, frame, &p, &last_, &plane.h, &notPlane.h, nullptr, planeIdx, notPlaneIdx) != OPE_OK) {
+      compat::log_error("getSegmentedObjectsOnPlane", ctx);
+      deviceFailed_ = true;
+      return -1;
+    }
+    if (last_.status != OPE_TABLETOP_OK) return 1;
     const size_t m = (size_t)last_.n_not_plane;
     ope_cluster_params cp;
     ope_cluster_default_params(&cp);
     std::vector<ope_cloud *> clouds(m + 1, nullptr);
-    std::vector<int32_t> idx(m + 1), off(m + 2);
+    if (idx) idx->assign(m + 1, 0);
+    if (off) off->assign(m + 2, 0);
     size_t k = 0;
-    if (ope_euclidean_clusters_cloud(ctx, notPlane.h, &cp, m, &k, clouds.data(), idx.data(), off.data()) != OPE_OK) {
+    if (ope_euclidean_clusters_cloud(ctx, notPlane.h, &cp, m, &k, clouds.data(), idx ? idx->data() : nullptr, off ? off->data() : nullptr) != OPE_OK) {
       compat::log_error("getSegmentedObjectsOnPlane", ctx);
-      return true;
+      deviceFailed_ = true;
+      return 0;
     }
-    deviceClusters_.clear();
+    deviceClusters_.clear();   // (kept until here: they are the clusters of the last call that got this far)
     for (size_t c = 0; c < k && c < m; ++c) {
       auto h = std::make_shared<compat::CloudHandle>();
       h->h = clouds[c];
       deviceClusters_.push_back(h);
-      Cloud::Ptr cloudCluster(new Cloud);
-      gather(*cloudCluster, notPlaneIdx.data(), idx.data() + off[c], (size_t)(off[c + 1] - off[c]));
-      cloudClusterVector.push_back(cloudCluster);
     }
-    return true;
+    return 0;
   }
 
   compat::SACSegmentation<PointTObj> sacSeg;
@@ -184,6 +234,7 @@ class ObjectSegmentationPlane {
   compat::EuclideanClusterExtraction<PointTObj> euclideanClustExtraction;
   uint64_t seed_ = 12345;
   ope_tabletop_result last_{};
+  bool deviceFailed_ = false;
   std::vector<std::shared_ptr<compat::CloudHandle>> deviceClusters_;
 };
 

@@ -12,6 +12,8 @@
 #pragma once
 
 #include <cstdio>
+#include <cstring>
+#include <memory>
 #include <vector>
 
 #include "pcl_compat.hpp"
@@ -96,6 +98,68 @@ class RegMeshPcd {
       *cloudTemp = *cloudAlignedIcp;                                                                                    // :258
     }
     *out = *cloudTemp;   // :266
+    return out;
+  }
+
+  // :210-271 over frames that are on the device (ObjectSegmentationPlane::deviceClusters()): the same sequence through the C
+  // ABI.  Normals (k = 12) are attached to the clouds as they come, the accumulated cloud is ope_cloud_concat (transform, append
+  // and re-sort on the device; colours carried when every frame has them) and never leaves the device: one download of its
+  // points and one of its colours at the end (white without colours).  The frames stay the caller's.  Empty on failure.
+  Cloud::Ptr registerPointClouds(const std::vector<std::shared_ptr<compat::CloudHandle>> &cloudVector, float /*maxCorrDist*/, float corrRejThresh,
+                                 int maxIter) {
+    corrRejThreshNormAngle = corrRejThresh;     // :227
+    pairs_.clear();
+    Cloud::Ptr out(new Cloud);
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || cloudVector.empty()) return out;
+    for (const auto &c : cloudVector)
+      if (!c || !c->h) return out;
+    ope_icp_params p;
+    ope_icp_default_params(&p);
+    p.max_iterations = maxIter;                          // :179
+    p.transformation_epsilon = 1e-8;                     // :182
+    p.euclidean_fitness_epsilon = 1e-8;                  // :184
+    p.corr_mode = OPE_CORR_NORMAL_SHOOTING;              // :139-145,:187
+    p.k_normal_shooting = 20;                            // :144
+    p.use_surface_normal_rej = 1;                        // :148-158,:190
+    p.surface_normal_thr = corrRejThresh;                // :158
+    p.estimator = OPE_EST_POINT_TO_PLANE_LM;             // :162,:193
+    const float vp[3] = {0.f, 0.f, 0.f};
+    auto fail = [&](const char *where) { compat::log_error(where, ctx); return Cloud::Ptr(new Cloud); };
+    std::shared_ptr<compat::CloudHandle> acc = cloudVector[0];
+    for (size_t i = 0; i + 1 < cloudVector.size(); ++i) {
+      std::printf("ICP between frame %zu and %zu\n", i, i + 1);
+      ope_cloud *tgt = cloudVector[i + 1]->h;
+      if (ope_normals(ctx, acc->h, 12, vp, nullptr, nullptr) != OPE_OK || ope_normals(ctx, tgt, 12, vp, nullptr, nullptr) != OPE_OK)   // :72-90
+        return fail("registerPointClouds (normals)");
+      compat::IndexHandle index;
+      if (ope_index_build(ctx, tgt, nullptr, &index.h) != OPE_OK) return fail("registerPointClouds (index)");
+      Pair pr{compat::Matrix4f::Identity(), 0, false, 0.0};
+      ope_icp_result res;
+      if (ope_icp_run(ctx, acc->h, index.h, nullptr, &p, pr.T.m, &res) != OPE_OK) return fail("registerPointClouds (icp)");              // :196
+      if (ope_fitness(ctx, acc->h, index.h, pr.T.m, DBL_MAX, &pr.fitness, nullptr, nullptr) != OPE_OK) return fail("registerPointClouds (fitness)");
+      std::printf("ICP converged with score: %g\n", pr.fitness);                                                                        // :198
+      pr.iterations = res.iterations;
+      pr.converged = res.converged != 0;
+      pairs_.push_back(pr);
+      auto next = std::make_shared<compat::CloudHandle>();
+      if (ope_cloud_concat(ctx, acc->h, pr.T.m, tgt, &next->h) != OPE_OK) return fail("registerPointClouds (concat)");                   // :203, :254
+      acc = next;
+    }
+    const size_t n = ope_cloud_size(acc->h);
+    std::vector<float> xyz(3 * n + 3);
+    std::vector<uint32_t> rgb(n + 1, 0x00ffffffu);
+    if (ope_cloud_download(ctx, acc->h, xyz.data()) != OPE_OK) return fail("registerPointClouds (download)");
+    if (ope_cloud_has_rgb(acc->h) && ope_cloud_download_rgb(ctx, acc->h, rgb.data()) != OPE_OK) return fail("registerPointClouds (download)");
+    out->points.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      PointTReg &q = out->points[k];
+      q.x = xyz[3 * k]; q.y = xyz[3 * k + 1]; q.z = xyz[3 * k + 2];
+      std::memcpy(&q.rgb, &rgb[k], 4);
+    }
+    out->width = (uint32_t)n;
+    out->height = 1;
+    out->is_dense = true;
     return out;
   }
 

@@ -406,6 +406,11 @@ ABI = [
     ("ope_depth_to_cloud", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(DepthParams), _fp, _fp, C.POINTER(_vp), _ip,
                                       C.POINTER(C.c_size_t)]),
     ("ope_depth_last_stats", C.c_int, [_vp, C.POINTER(DepthStats)]),
+    ("ope_cloud_set_rgb", C.c_int, [_vp, _vp, _vp]),
+    ("ope_cloud_has_rgb", C.c_int, [_vp]),
+    ("ope_cloud_download_rgb", C.c_int, [_vp, _vp, _vp]),
+    ("ope_depth_to_cloud_rgb", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.POINTER(DepthParams), _fp, _fp,
+                                          C.POINTER(_vp), _ip, C.POINTER(C.c_size_t)]),
 ]
 
 _lib = None
@@ -939,10 +944,12 @@ class Context:
                            Cloud(self, hp, r.n_plane) if ok else None, Cloud(self, hn, r.n_not_plane) if ok else None,
                            r.iterations_first, r.iterations_second, r.launches, r.host_syncs)
 
-    def depth_to_cloud(self, depth, params: "DepthParams | None" = None, lo=None, hi=None, want_pixels: bool = False):
+    def depth_to_cloud(self, depth, params: "DepthParams | None" = None, lo=None, hi=None, want_pixels: bool = False, bgr=None):
         """ope_depth_to_cloud: a (rows, cols) uint16 depth image -> the frame's Cloud (rgbd2Pcl, optionally cropped to lo .. hi).
         Rows may be strided (a view with a row pitch); samples within a row must be contiguous.  Returns the Cloud, or
-        (Cloud, pixel indices row * cols + col) with want_pixels."""
+        (Cloud, pixel indices row * cols + col) with want_pixels.
+        bgr: a (rows, cols, 3) uint8 image, channels B, G, R (rows may be strided too): ope_depth_to_cloud_rgb, the same cloud
+        carrying r << 16 | g << 8 | b of every point's pixel (Cloud.download_rgb)."""
         depth = np.asarray(depth)
         if depth.dtype != np.uint16 or depth.ndim != 2:
             raise ValueError("depth_to_cloud: expected a 2-D uint16 image")
@@ -960,8 +967,18 @@ class Context:
         pix = np.empty(max(rows * cols, 1), np.int32) if want_pixels else None
         n = C.c_size_t(0)
         h = _vp()
-        self._chk(lib().ope_depth_to_cloud(self.h, _vp(depth.ctypes.data), rows, cols, stride, C.byref(p), _p(lo, _fp), _p(hi, _fp),
-                                           C.byref(h), _p(pix, _ip), C.byref(n)))
+        if bgr is not None:
+            bgr = np.asarray(bgr)
+            if bgr.dtype != np.uint8 or bgr.shape != (rows, cols, 3):
+                raise ValueError("depth_to_cloud: bgr is a (rows, cols, 3) uint8 image of the depth image's size")
+            if rows * cols and (bgr.strides[2] != 1 or bgr.strides[1] != 3 or (rows > 1 and bgr.strides[0] < 3 * cols)):
+                bgr = np.ascontiguousarray(bgr)
+            bstride = bgr.strides[0] if rows > 1 and rows * cols else 3 * cols
+            self._chk(lib().ope_depth_to_cloud_rgb(self.h, _vp(depth.ctypes.data), rows, cols, stride, _vp(bgr.ctypes.data), bstride, C.byref(p),
+                                                   _p(lo, _fp), _p(hi, _fp), C.byref(h), _p(pix, _ip), C.byref(n)))
+        else:
+            self._chk(lib().ope_depth_to_cloud(self.h, _vp(depth.ctypes.data), rows, cols, stride, C.byref(p), _p(lo, _fp), _p(hi, _fp),
+                                               C.byref(h), _p(pix, _ip), C.byref(n)))
         c = Cloud(self, h, n.value)
         return (c, pix[: n.value].copy()) if want_pixels else c
 
@@ -1340,6 +1357,26 @@ class Cloud:
         if len(nrm) != self.n:
             raise ValueError("normals length mismatch")
         self.ctx._chk(lib().ope_cloud_set_normals(self.ctx.h, self.h, _p(nrm, _fp)))
+
+    def set_rgb(self, rgb):
+        """ope_cloud_set_rgb: n uint32 words r << 16 | g << 8 | b in the cloud's original order; None detaches the colours."""
+        if rgb is None:
+            self.ctx._chk(lib().ope_cloud_set_rgb(self.ctx.h, self.h, None))
+            return
+        rgb = np.ascontiguousarray(rgb, np.uint32).reshape(-1)
+        if len(rgb) != self.n:
+            raise ValueError("rgb length mismatch")
+        self.ctx._chk(lib().ope_cloud_set_rgb(self.ctx.h, self.h, _vp(rgb.ctypes.data)))
+
+    @property
+    def has_rgb(self) -> bool:
+        return bool(lib().ope_cloud_has_rgb(self.h))
+
+    def download_rgb(self) -> np.ndarray:
+        """ope_cloud_download_rgb: the colour words in original order (OpeError when the cloud has none)."""
+        out = np.empty(self.n, np.uint32)
+        self.ctx._chk(lib().ope_cloud_download_rgb(self.ctx.h, self.h, _vp(out.ctypes.data)))
+        return out
 
     def free(self):
         if self.h:

@@ -92,9 +92,18 @@ def register_point_clouds(ope, ctx, frames, max_corr_dist: float = 0.005, corr_r
     `aligned + target` is ope_cloud_concat (transform, append and re-sort on the device) and the result is fetched once
     at the end.  on_device=False goes through get_icp_normal pair by pair (host clouds in and out, as the reference's
     function signature has it); both give the same numbers.
+
+    The frames may also be device-resident Clouds (all of them): nothing is uploaded, the Clouds stay the caller's (they come
+    back with the normals of this run attached), and when every one of them carries colours the accumulated cloud carries
+    them through ope_cloud_concat: `rgb` is then one download at the end, beside the one of the points.
     """
     if len(frames) == 0:
         raise ValueError("register_point_clouds: no frames")
+    if all(isinstance(f, ope.Cloud) for f in frames):
+        if colors is not None and (len(colors) != len(frames) or any(len(c) != f.n for c, f in zip(colors, frames))):
+            raise ValueError("register_point_clouds: colors must match the frames point for point")
+        return _register_device_clouds(ope, ctx, list(frames), max_corr_dist, corr_rej_thresh, max_iterations, colors, k_normals,
+                                       estimator, use_max_corr_dist_in_icp)
     if colors is not None and (len(colors) != len(frames) or any(len(c) != len(f) for c, f in zip(colors, frames))):
         raise ValueError("register_point_clouds: colors must match the frames point for point")
     res = RegistrationResult(np.ascontiguousarray(frames[0], np.float32))
@@ -136,6 +145,92 @@ def register_point_clouds(ope, ctx, frames, max_corr_dist: float = 0.005, corr_r
     return res
 
 
+def _register_device_clouds(ope, ctx, clouds, max_corr_dist, corr_rej_thresh, max_iterations, colors, k_normals, estimator,
+                            use_max_corr_dist_in_icp) -> RegistrationResult:
+    """register_point_clouds over Clouds: the device loop of the array form without its uploads."""
+    p = icp_params_with_normals(ope, corr_rej_thresh, max_iterations, max_corr_dist if use_max_corr_dist_in_icp else None, estimator)
+    res = RegistrationResult(None)
+    acc, own = clouds[0], False
+    try:
+        for tgt in clouds[1:]:
+            index = None
+            try:
+                ctx.normals(acc, k_normals, fetch=False)     # :72-84
+                ctx.normals(tgt, k_normals, fetch=False)     # :86-90
+                index = ctx.build_index(tgt)
+                out = ctx.icp(acc, index, p)                 # :196
+                fit, _, _ = ctx.fitness(acc, index, out.T)   # :198
+                res.pairs.append(PairResult(out.T, out.iterations, out.converged, fit, acc.n, tgt.n))
+                nxt = ctx.concat(acc, out.T, tgt)            # :203 transformPointCloud, :254 += target (colours with the points)
+            finally:
+                if index is not None:
+                    index.free()
+            if own:
+                acc.free()
+            acc, own = nxt, True
+        res.cloud = ctx.download(acc)
+        if colors is not None:
+            res.rgb = np.concatenate([np.ascontiguousarray(c, np.uint32) for c in colors])
+        elif acc.has_rgb:
+            res.rgb = acc.download_rgb()
+    finally:
+        if own:
+            acc.free()
+    return res
+
+
+def segment_object_device(ope, ctx, frame):
+    """BuildModel's per-frame segmentation (main.cpp:181-182) of a device frame: getSegmentedObjectsOnPlane, then cluster 0.
+    Returns the cluster as a Cloud (coloured when the frame is).  ValueError when the frame has no plane or no cluster, where the
+    reference's `.at(0)` throws."""
+    seg = ctx.tabletop_segment(frame)
+    if seg.status != ope.TABLETOP_OK:
+        raise ValueError("no supporting plane in the frame (tabletop status %d)" % seg.status)
+    try:
+        clusters, _ = ctx.euclidean_clusters_cloud(seg.not_plane)
+    finally:
+        seg.plane.free()
+        seg.not_plane.free()
+    if not clusters:
+        raise ValueError("no cluster on the plane")
+    for c in clusters[1:]:
+        c.free()
+    return clusters[0]
+
+
+def build_model_from_images(ope, ctx, depths, bgrs, limits, out_path: str | None = None, params=None, max_corr_dist: float = 0.005,
+                            corr_rej_thresh: float = 0.7, max_iterations: int = 500, **kw) -> RegistrationResult:
+    """BuildModel from the sensor's images (main.cpp:171-225 behind DataGrabber::rgbd2Pcl(rgb, depth)), the `--scan` mode of the
+    build_model program: per frame the coloured ingest with the crop `limits` = (xmin, xmax, ymin, ymax, zmin, zmax)
+    (ope_depth_to_cloud_rgb), the table and cluster 0 on the device; then the sequential registration over the clusters and
+    `FIELDS x y z rgb`.  No host cloud exists between the images and the model.  depths: (rows, cols) uint16 images; bgrs:
+    (rows, cols, 3) uint8, channels B, G, R; params: DepthParams (default: the Kinect preset).  ValueError, naming the frame,
+    when a frame has no plane or no cluster."""
+    from . import pcd
+
+    if len(depths) == 0 or len(depths) != len(bgrs):
+        raise ValueError("build_model_from_images: one colour image per depth image, at least one pair")
+    lim = np.asarray(limits, np.float32).reshape(3, 2)
+    lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+    objects = []
+    try:
+        for i, (d, c) in enumerate(zip(depths, bgrs)):
+            frame = ctx.depth_to_cloud(d, params, lo, hi, bgr=c)
+            try:
+                objects.append(segment_object_device(ope, ctx, frame))
+            except ValueError as e:
+                raise ValueError("build_model_from_images: frame %d: %s" % (i, e)) from None
+            finally:
+                frame.free()
+        res = register_point_clouds(ope, ctx, objects, max_corr_dist, corr_rej_thresh, max_iterations, **kw)
+    finally:
+        for o in objects:
+            o.free()
+    if out_path is not None:
+        pcd.write_pcd(out_path, res.cloud, res.rgb)
+    return res
+
+
 def build_model_from_directory(ope, ctx, pcd_dir: str, out_path: str | None = None, limits=None, segment=None,
                                max_corr_dist: float = 0.005, corr_rej_thresh: float = 0.7, max_iterations: int = 500,
                                **kw) -> RegistrationResult:
@@ -148,7 +243,9 @@ def build_model_from_directory(ope, ctx, pcd_dir: str, out_path: str | None = No
     The reference walks the directory in `boost::filesystem::directory_iterator` order, which is unspecified; here
     the files are taken in name order.  Between crop and registration the reference cuts the object off its
     supporting plane (`ObjectSegmentationPlane`, main.cpp:186): that step is outside this path (SURVEY.md §8f-4
-    ranks it after the file loop) and enters as the optional `segment(xyz, rgb) -> (xyz, rgb)` hook.
+    ranks it after the file loop) and enters as the optional `segment(xyz, rgb) -> (xyz, rgb)` hook.  segment="device" runs
+    it on the device instead (segment_object_device): the frame is uploaded once with its colours, cropped, segmented and
+    registered as a Cloud, and the colours come back with the model.
     """
     import os
     from . import pcd
@@ -156,6 +253,37 @@ def build_model_from_directory(ope, ctx, pcd_dir: str, out_path: str | None = No
     names = sorted(n for n in os.listdir(pcd_dir) if n.lower().endswith(".pcd"))
     if not names:
         raise ValueError(f"build_model_from_directory: no .pcd files in {pcd_dir!r}")
+    if isinstance(segment, str):
+        if segment != "device":
+            raise ValueError("build_model_from_directory: segment is a callable or \"device\"")
+        objects = []
+        try:
+            for name in names:
+                xyz, rgb = pcd.read_pcd(os.path.join(pcd_dir, name))
+                frame = ctx.upload(xyz)
+                try:
+                    if rgb is not None:
+                        frame.set_rgb(rgb)
+                    if limits is not None:
+                        lim = np.asarray(limits, np.float32).reshape(3, 2)
+                        cropped, _ = ctx.pass_through_cloud(frame, lim[:, 0], lim[:, 1])
+                    else:
+                        cropped, _ = ctx.remove_nan_cloud(frame)
+                    try:
+                        objects.append(segment_object_device(ope, ctx, cropped))
+                    except ValueError as e:
+                        raise ValueError("build_model_from_directory: %s: %s" % (name, e)) from None
+                    finally:
+                        cropped.free()
+                finally:
+                    frame.free()
+            res = register_point_clouds(ope, ctx, objects, max_corr_dist, corr_rej_thresh, max_iterations, **kw)
+        finally:
+            for o in objects:
+                o.free()
+        if out_path is not None:
+            pcd.write_pcd(out_path, res.cloud, res.rgb)
+        return res
     frames, colors = [], []
     for name in names:
         xyz, rgb = pcd.read_pcd(os.path.join(pcd_dir, name))

@@ -24,8 +24,8 @@ int icp_accumulate_blocks_per_cu(bool, bool, bool);
 int icp_accumulate_cert_blocks_per_cu(bool, bool, bool);
 int chunk_plan(hipStream_t, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *, uint32_t, void *, size_t &);
 void fill_iota(hipStream_t, uint32_t *, uint32_t);
-hipError_t morton_order_device(hipStream_t, const float *, size_t, const float[3], const float[3], float4 *, int32_t *);
-hipError_t concat_device(hipStream_t, const CloudView &, const float *, const CloudView &, float *, float[3], float[3]);
+hipError_t concat_device(hipStream_t, const CloudView &, const float *, const CloudView &, float *, float[3], float[3], const uint32_t *,
+                         const uint32_t *, uint32_t *);
 hipError_t build_bvh_device(hipStream_t, const float4 *, const float4 *, size_t, int, const float[3], const float[3], int *, float4 **,
                             float4 **, float4 **, float4 **, bool);
 void launch_icp_accumulate_grid(hipStream_t, int, bool, const CloudView &, const BvhView &, const GridView &, const IcpState *, double *, int32_t *,
@@ -627,6 +627,40 @@ int ope_cloud_set_normals(ope_ctx *ctx, ope_cloud *cloud, const float *normals_x
   return OPE_OK;
 }
 
+int ope_cloud_set_rgb(ope_ctx *ctx, ope_cloud *cloud, const uint32_t *rgb) {
+  if (!ctx || !cloud) return set_err(ctx, OPE_EINVAL, "ope_cloud_set_rgb: bad argument");
+  OPE_HIP(ctx, hipSetDevice(ctx->device));
+  if (!rgb) {   // detach
+    if (cloud->d_rgb) (void)hipFree(cloud->d_rgb);
+    cloud->d_rgb = nullptr;
+    return OPE_OK;
+  }
+  { const int rch = cloud->ensure_host(); if (rch != OPE_OK) return rch; }
+  const size_t n = cloud->n;
+  std::vector<uint32_t> packed(n);
+  for (size_t i = 0; i < n; ++i) packed[i] = rgb[(size_t)cloud->perm[i]];
+  if (!cloud->d_rgb) OPE_HIP(ctx, hipMalloc((void **)&cloud->d_rgb, 4 * std::max<size_t>(n, 1)));
+  if (n) OPE_HIP(ctx, h2d_copy(ctx->stream, cloud->d_rgb, packed.data(), 4 * n));
+  return OPE_OK;
+}
+
+int ope_cloud_has_rgb(const ope_cloud *cloud) { return cloud && cloud->d_rgb ? 1 : 0; }
+
+int ope_cloud_download_rgb(ope_ctx *ctx, const ope_cloud *cloud, uint32_t *out) {
+  if (!ctx || !cloud || (cloud->n && !out)) return set_err(ctx, OPE_EINVAL, "ope_cloud_download_rgb: bad argument");
+  if (!cloud->d_rgb) return set_err(ctx, OPE_EINVAL, "ope_cloud_download_rgb: the cloud has no colours");
+  const int rc = cloud->ensure_host();
+  if (rc != OPE_OK) return rc;
+  const size_t n = cloud->n;
+  if (n == 0) return OPE_OK;
+  OPE_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<uint32_t> sorted(n);
+  OPE_HIP(ctx, hipMemcpyAsync(sorted.data(), cloud->d_rgb, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
+  OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < n; ++i) out[(size_t)cloud->perm[i]] = sorted[i];
+  return OPE_OK;
+}
+
 size_t ope_cloud_size(const ope_cloud *cloud) { return cloud ? cloud->n : 0; }
 
 void ope_cloud_free(ope_cloud *cloud) {
@@ -637,6 +671,7 @@ void ope_cloud_free(ope_cloud *cloud) {
   if (cloud->ctx && cloud->ctx->fixed_src == cloud) { cloud->ctx->fixed_src = nullptr; cloud->ctx->n_fixed = 0; }   // fixed correspondences index a cloud that is gone
   if (cloud->d_xyzw) (void)hipFree(cloud->d_xyzw);
   if (cloud->d_nrm) (void)hipFree(cloud->d_nrm);
+  if (cloud->d_rgb) (void)hipFree(cloud->d_rgb);
   delete cloud;
 }
 
@@ -674,7 +709,11 @@ int ope_cloud_concat(ope_ctx *ctx, const ope_cloud *a, const float T_a[16], cons
   float rows[12];
   float *d_rows = nullptr, *d_raw = nullptr;
   int32_t *d_perm = nullptr;
+  uint32_t *d_rgb_raw = nullptr;
+  const bool coloured = a->d_rgb && b->d_rgb;   // operator+= keeps rgb (regmeshpcd.cpp:254); colours on one side only are dropped
   hipError_t e = hipMalloc((void **)&c->d_xyzw, sizeof(float4) * std::max<size_t>(n, 1));
+  if (e == hipSuccess && coloured) e = hipMalloc((void **)&c->d_rgb, 4 * std::max<size_t>(n, 1));
+  if (e == hipSuccess && coloured && n) e = hipMalloc((void **)&d_rgb_raw, 4 * n);
   if (e == hipSuccess && n) e = hipMalloc((void **)&d_raw, 12 * n);
   if (e == hipSuccess && n) e = hipMalloc((void **)&d_perm, 4 * n);
   if (e == hipSuccess && T_a) {
@@ -683,16 +722,17 @@ int ope_cloud_concat(ope_ctx *ctx, const ope_cloud *a, const float T_a[16], cons
     if (e == hipSuccess) e = h2d_copy(ctx->stream, d_rows, rows, sizeof rows);
   }
   float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  if (e == hipSuccess && n) e = concat_device(ctx->stream, a->view(), d_rows, b->view(), d_raw, lo, hi);
+  if (e == hipSuccess && n) e = concat_device(ctx->stream, a->view(), d_rows, b->view(), d_raw, lo, hi, coloured ? a->d_rgb : nullptr,
+                                                coloured ? b->d_rgb : nullptr, d_rgb_raw);
   if (e == hipSuccess && n) {
     if (c->n_valid == 0) { for (int d = 0; d < 3; ++d) lo[d] = hi[d] = 0.f; }
     std::memcpy(c->bb_lo, lo, sizeof lo);
     std::memcpy(c->bb_hi, hi, sizeof hi);
     float inv[3];
     for (int d = 0; d < 3; ++d) inv[d] = (hi[d] > lo[d]) ? 1023.999f / (hi[d] - lo[d]) : 0.f;
-    e = morton_order_device(ctx->stream, d_raw, n, lo, inv, c->d_xyzw, d_perm);
+    e = morton_order_device(ctx->stream, d_raw, n, lo, inv, c->d_xyzw, d_perm, d_rgb_raw, d_rgb_raw ? c->d_rgb : nullptr);
   }
-  for (void *p : {(void *)d_rows, (void *)d_raw, (void *)d_perm})
+  for (void *p : {(void *)d_rows, (void *)d_raw, (void *)d_perm, (void *)d_rgb_raw})
     if (p) (void)hipFree(p);
   if (e != hipSuccess) {
     ope_cloud_free(c);

@@ -371,17 +371,19 @@ __global__ __launch_bounds__(kCcBlock) void cc_morton_key_kernel(const float4 *_
   vals[j] = j;
 }
 
-struct ClusterOut { float4 *xyzw, *nrm; };
+struct ClusterOut { float4 *xyzw, *nrm; uint32_t *rgb; };
 
 __global__ __launch_bounds__(kCcBlock) void cc_cloud_scatter_kernel(const unsigned long long *__restrict__ skey, const uint32_t *__restrict__ sval,
                                                                     const uint32_t *__restrict__ roff, const float4 *__restrict__ raw,
                                                                     const int32_t *__restrict__ idx, const uint32_t *__restrict__ pos_by_o,
-                                                                    const float4 *__restrict__ nrm, const ClusterOut *__restrict__ outs, uint32_t total) {
+                                                                    const float4 *__restrict__ nrm, const uint32_t *__restrict__ rgb,
+                                                                    const ClusterOut *__restrict__ outs, uint32_t total) {
   const uint32_t q = blockIdx.x * kCcBlock + threadIdx.x;
   if (q >= total) return;
   const uint32_t k = (uint32_t)(skey[q] >> 31), j = sval[q], pos = q - roff[k];
   outs[k].xyzw[pos] = raw[j];
   if (nrm) outs[k].nrm[pos] = nrm[pos_by_o[idx[j]]];
+  if (rgb) outs[k].rgb[pos] = rgb[pos_by_o[idx[j]]];   // the colour payload of the input, by its sorted position
 }
 
 int bits_for(unsigned long long v) {   // bits that hold every value <= v
@@ -623,7 +625,8 @@ int ope_euclidean_clusters_cloud(ope_ctx *ctx, const ope_cloud *cloud, const ope
     c->host_valid = false;
     e = hipMalloc((void **)&c->d_xyzw, sizeof(float4) * std::max<size_t>(c->n, 1));
     if (e == hipSuccess && cloud->d_nrm) e = hipMalloc((void **)&c->d_nrm, sizeof(float4) * std::max<size_t>(c->n, 1));
-    outs[k] = ClusterOut{c->d_xyzw, c->d_nrm};
+    if (e == hipSuccess && cloud->d_rgb) e = hipMalloc((void **)&c->d_rgb, 4 * std::max<size_t>(c->n, 1));
+    outs[k] = ClusterOut{c->d_xyzw, c->d_nrm, c->d_rgb};
   }
   auto *d_outs = (ClusterOut *)tmp.get(sizeof(ClusterOut) * kw, e);
   auto *raw = (float4 *)tmp.get(16ull * total, e);
@@ -644,7 +647,7 @@ int ope_euclidean_clusters_cloud(ope_ctx *ctx, const ope_cloud *cloud, const ope
   }
   if (e == hipSuccess)
     CC_LAUNCH(cc_cloud_scatter_kernel, 48.0 * total, dim3(grid_of(total)), dim3(kCcBlock), 0, st, mkey2, mval2, d_roff, raw, d_idx, d_pos,
-              cloud->d_nrm, d_outs, total);
+              cloud->d_nrm, (const uint32_t *)cloud->d_rgb, d_outs, total);
   std::vector<uint32_t> h_bb(8 * kw);
   if (e == hipSuccess) e = hipMemcpyAsync(h_bb.data(), bb, 32ull * kw, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);

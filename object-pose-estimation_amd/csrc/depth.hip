@@ -24,12 +24,11 @@
 
 namespace ope {
 
-hipError_t morton_order_device(hipStream_t, const float *, size_t, const float[3], const float[3], float4 *, int32_t *);
-
 namespace {
 
 constexpr int kTile = 64;        // rows and columns of a tile; a wave's lanes are the tile's rows
 constexpr int kTilePitch = 33;   // words per tile row in LDS: 32 hold the 64 samples, 1 pads (column reads hit 64 banks)
+constexpr int kBgrPitch = 49;    // the colour tile: 48 words hold a row's 64 x 3 bytes, 1 pads (odd: a column read hits 64 banks)
 constexpr int kDepthBlock = 256;
 constexpr int kColsPerWave = kTile / (kDepthBlock / 64);
 // What morton_order_device is booked as in ope_depth_stats: its key kernel, its one rocPRIM sort call (however many kernels
@@ -37,8 +36,10 @@ constexpr int kColsPerWave = kTile / (kDepthBlock / 64);
 constexpr int kMortonLaunches = 3, kMortonSyncs = 1;
 
 struct DepthJob {
-  const uint16_t *img;   // rows x pitch samples, pitch a multiple of kTile
-  uint32_t rows, cols, pitch, row_tiles, col_tiles;
+  // the frame on the device, row_bytes per image row: pitch depth samples (pitch a multiple of kTile) and, for a coloured
+  // frame, the row's pitch BGR pixels behind them (bgr_off = 2 * pitch; both parts start on a multiple of 64 bytes)
+  const unsigned char *img;
+  uint32_t rows, cols, pitch, row_tiles, col_tiles, row_bytes, bgr_off;
   float f_row, c_row, f_col, c_col, scale;
   double z_max;
   int crop;
@@ -87,10 +88,17 @@ __device__ __forceinline__ void block_commit(uint32_t klo[3], uint32_t khi[3], u
 // SCATTER = false: seg_count[col * row_tiles + row_tile] = survivors of that segment (and the valid pixels' count and, for a
 // cropped call, their box: the Morton box of the uncropped cloud).  SCATTER = true: the points, their pixel indices, the kept
 // points' box.
-template <bool SCATTER>
+// RGB (scatter pass of ope_depth_to_cloud_rgb): the tile's 64 x 64 BGR pixels, 192 bytes per tile row, come in as 16-byte loads (12
+// lanes read one tile row) and lie in LDS at an odd pitch of words; a wave reads the three bytes of (row = lane, one column) as the
+// two words they can span, 64 different banks each, and shifts them out (the column, so the shift, is the same for the wave).
+// rgb[o] = r << 16 | g << 8 | b beside the point (datagrabber.cpp:48-51: bytes 0, 1, 2 are b, g, r).
+template <bool SCATTER, bool RGB>
 __global__ __launch_bounds__(kDepthBlock) void depth_tile_kernel(DepthJob job, uint32_t *__restrict__ seg_count, const uint32_t *__restrict__ seg_off,
-                                                                 float *__restrict__ raw, int32_t *__restrict__ pix, uint32_t *__restrict__ res) {
+                                                                 float *__restrict__ raw, int32_t *__restrict__ pix, uint32_t *__restrict__ rgb,
+                                                                 uint32_t *__restrict__ res) {
+  static_assert(SCATTER || !RGB, "colours are written with the points");
   __shared__ uint32_t s_tile[kTile][kTilePitch];
+  __shared__ uint32_t s_bgr[RGB ? kTile : 1][kBgrPitch];
   const uint32_t tr = blockIdx.x / job.col_tiles, tc = blockIdx.x - tr * job.col_tiles;
   {
     const uint32_t k = threadIdx.x & 15u, r0 = threadIdx.x >> 4;
@@ -98,10 +106,21 @@ __global__ __launch_bounds__(kDepthBlock) void depth_tile_kernel(DepthJob job, u
     for (int step = 0; step < kTile / 16; ++step) {
       const uint32_t r = r0 + 16u * step, grow = tr * kTile + r;
       uint2 v = make_uint2(0u, 0u);   // rows past the image: depth 0, dropped
-      if (grow < job.rows) v = *reinterpret_cast<const uint2 *>(job.img + (size_t)grow * job.pitch + (size_t)tc * kTile + 4u * k);
+      if (grow < job.rows) v = *reinterpret_cast<const uint2 *>(job.img + (size_t)grow * job.row_bytes + (size_t)tc * (2 * kTile) + 8u * k);
       s_tile[r][2 * k] = v.x;
       s_tile[r][2 * k + 1] = v.y;
     }
+  }
+  if (RGB) {
+    constexpr uint32_t kVecPerRow = 3 * kTile / 16;   // 12 loads of 16 bytes per tile row
+    for (uint32_t i = threadIdx.x; i < kTile * kVecPerRow; i += kDepthBlock) {
+      const uint32_t r = i / kVecPerRow, k = i - r * kVecPerRow, grow = tr * kTile + r;
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);   // rows past the image: never read back (their depth is 0)
+      if (grow < job.rows)
+        v = *reinterpret_cast<const uint4 *>(job.img + (size_t)grow * job.row_bytes + job.bgr_off + (size_t)tc * (3 * kTile) + 16u * k);
+      s_bgr[r][4 * k] = v.x; s_bgr[r][4 * k + 1] = v.y; s_bgr[r][4 * k + 2] = v.z; s_bgr[r][4 * k + 3] = v.w;
+    }
+    if (threadIdx.x < kTile) s_bgr[threadIdx.x][kBgrPitch - 1] = 0u;   // the pad word: read as the upper word of the last column, shifted out
   }
   if (!SCATTER && blockIdx.x == 0 && threadIdx.x == 0) seg_count[(size_t)job.cols * job.row_tiles] = 0u;   // the scan's last slot
   __syncthreads();
@@ -143,6 +162,11 @@ __global__ __launch_bounds__(kDepthBlock) void depth_tile_kernel(DepthJob job, u
         const size_t o = (size_t)seg_off[seg] + rank;
         raw[3 * o] = x; raw[3 * o + 1] = y; raw[3 * o + 2] = z;
         pix[o] = (int32_t)(row * job.cols + col);
+        if (RGB) {
+          const uint32_t byte = 3u * c_local, w = byte >> 2;
+          const unsigned long long two = ((unsigned long long)s_bgr[lane][w + 1] << 32) | s_bgr[lane][w];
+          rgb[o] = (uint32_t)(two >> (8u * (byte & 3u))) & 0x00ffffffu;
+        }
         if (fin) {
           const float v[3] = {x, y, z};
 #pragma unroll
@@ -192,19 +216,25 @@ extern "C" int ope_depth_last_stats(const ope_ctx *ctx, ope_depth_stats *out) {
   return OPE_OK;
 }
 
-extern "C" int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t rows, size_t cols, size_t row_stride_bytes,
-                                  const ope_depth_params *params, const float lo[3], const float hi[3], ope_cloud **out, int32_t *out_pixel,
-                                  size_t *n_out) {
-  if (!ctx || !depth || !params || !out) return set_err(ctx, OPE_EINVAL, "ope_depth_to_cloud: bad argument");
+// ope_depth_to_cloud (bgr == nullptr) and ope_depth_to_cloud_rgb: one path.  A coloured frame differs in the bytes of a staged row
+// (2 + 3 per padded pixel instead of 2), in the scatter pass's instantiation and in the colour stream of the Morton gather.
+static int depth_to_cloud_impl(ope_ctx *ctx, const char *fn, const uint16_t *depth, size_t rows, size_t cols, size_t row_stride_bytes,
+                               const unsigned char *bgr, size_t bgr_stride_bytes, const ope_depth_params *params, const float lo[3],
+                               const float hi[3], ope_cloud **out, int32_t *out_pixel, size_t *n_out) {
+  const std::string who = std::string(fn) + ": ";
+  // (a NULL ctx is refused last: every other case is then told apart by its message without a context, ope_last_error(NULL))
+  if (!depth || !params || !out) return set_err(ctx, OPE_EINVAL, who + "bad argument");
   if (rows == 0 || cols == 0 || rows > (size_t)0x7fffffff || cols > (size_t)0x7fffffff || rows * cols > (size_t)0x7fffffff)
-    return set_err(ctx, OPE_EINVAL, "ope_depth_to_cloud: rows * cols must be 1 .. 2^31 - 1");
-  if (row_stride_bytes < 2 * cols || (row_stride_bytes & 1u)) return set_err(ctx, OPE_EINVAL, "ope_depth_to_cloud: row_stride_bytes must be even and >= 2 * cols");
+    return set_err(ctx, OPE_EINVAL, who + "rows * cols must be 1 .. 2^31 - 1");
+  if (row_stride_bytes < 2 * cols || (row_stride_bytes & 1u)) return set_err(ctx, OPE_EINVAL, who + "row_stride_bytes must be even and >= 2 * cols");
   if (!positive_finite(params->scale) || !positive_finite(params->f_row) || !positive_finite(params->f_col))
-    return set_err(ctx, OPE_EINVAL, "ope_depth_to_cloud: scale, f_row and f_col must be positive and finite");
+    return set_err(ctx, OPE_EINVAL, who + "scale, f_row and f_col must be positive and finite");
   if (!std::isfinite(params->c_row) || !std::isfinite(params->c_col))   // (no point would be finite: n_valid < n)
-    return set_err(ctx, OPE_EINVAL, "ope_depth_to_cloud: c_row and c_col must be finite");
-  if (2 * ((cols + kTile - 1) / kTile * kTile) > kStageChunk) return set_err(ctx, OPE_EINVAL, "ope_depth_to_cloud: one padded image row must fit the 32 MB staging block");
-  if ((lo == nullptr) != (hi == nullptr)) return set_err(ctx, OPE_EINVAL, "ope_depth_to_cloud: give both lo and hi, or neither");
+    return set_err(ctx, OPE_EINVAL, who + "c_row and c_col must be finite");
+  const size_t px_bytes = bgr ? 5 : 2;   // of a staged pixel: the depth sample and, for a coloured frame, its three colour bytes
+  if (px_bytes * ((cols + kTile - 1) / kTile * kTile) > kStageChunk) return set_err(ctx, OPE_EINVAL, who + "one padded image row must fit the 32 MB staging block");
+  if ((lo == nullptr) != (hi == nullptr)) return set_err(ctx, OPE_EINVAL, who + "give both lo and hi, or neither");
+  if (!ctx) return set_err(ctx, OPE_EINVAL, who + "bad argument: ctx is NULL");
   *out = nullptr;
   if (n_out) *n_out = 0;
   OPE_HIP(ctx, hipSetDevice(ctx->device));
@@ -225,11 +255,13 @@ extern "C" int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t ro
   job.z_max = params->z_max;
   job.crop = lo != nullptr;
   for (int d = 0; d < 3; ++d) { job.lo[d] = lo ? lo[d] : 0.f; job.hi[d] = hi ? hi[d] : 0.f; }
-  const size_t n_pix = rows * cols, n_seg = cols * (size_t)job.row_tiles, row_bytes = 2 * (size_t)job.pitch;
+  const size_t n_pix = rows * cols, n_seg = cols * (size_t)job.row_tiles, row_bytes = px_bytes * (size_t)job.pitch;
+  job.row_bytes = (uint32_t)row_bytes;
+  job.bgr_off = 2 * job.pitch;
   const unsigned n_tiles = job.row_tiles * job.col_tiles;
 
-  uint16_t *d_img = nullptr;
-  uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_res = nullptr;
+  unsigned char *d_img = nullptr;
+  uint32_t *d_cnt = nullptr, *d_off = nullptr, *d_res = nullptr, *d_rgb_raw = nullptr;
   float *d_raw = nullptr;
   int32_t *d_pix = nullptr, *d_perm = nullptr;
   void *d_tmp = nullptr;
@@ -242,10 +274,13 @@ extern "C" int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t ro
   if (e == hipSuccess) e = tmp_malloc(st, (void **)&d_res, sizeof res);
   if (e == hipSuccess) e = tmp_malloc(st, (void **)&d_raw, 12 * n_pix);
   if (e == hipSuccess) e = tmp_malloc(st, (void **)&d_pix, 4 * n_pix);
+  if (e == hipSuccess && bgr) e = tmp_malloc(st, (void **)&d_rgb_raw, 4 * n_pix);
   if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tb, d_cnt, d_off, 0u, n_seg + 1, rocprim::plus<uint32_t>(), st);
   if (e == hipSuccess) e = tmp_malloc(st, &d_tmp, std::max<size_t>(tb, 16));
   // the image, 2 bytes per pixel: its rows packed at the device pitch into the pinned block, one copy (images of more than the
-  // block's 32 MB: one copy and one synchronisation per block, the block is refilled next)
+  // block's 32 MB: one copy and one synchronisation per block, the block is refilled next).  A coloured frame travels the same
+  // way at 5 bytes per pixel: every staged row is the depth row followed by its colour row, so the two images share the
+  // block, the copy and, above 32 MB, the blocks (6.7 M pixels per block instead of 16.7 M).
   {
     unsigned char *blk = nullptr;
     size_t cap = 0;
@@ -257,7 +292,9 @@ extern "C" int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t ro
       if (r0) { e = hipStreamSynchronize(st); ++S.host_syncs; }
       for (size_t r = 0; e == hipSuccess && r < cnt; ++r)
         std::memcpy(blk + r * row_bytes, reinterpret_cast<const unsigned char *>(depth) + (r0 + r) * row_stride_bytes, 2 * cols);
-      if (e == hipSuccess) e = hipMemcpyAsync(reinterpret_cast<unsigned char *>(d_img) + r0 * row_bytes, blk, cnt * row_bytes, hipMemcpyHostToDevice, st);
+      for (size_t r = 0; bgr && e == hipSuccess && r < cnt; ++r)
+        std::memcpy(blk + r * row_bytes + job.bgr_off, bgr + (r0 + r) * bgr_stride_bytes, 3 * cols);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_img + r0 * row_bytes, blk, cnt * row_bytes, hipMemcpyHostToDevice, st);
       ++S.launches;
     }
   }
@@ -269,15 +306,19 @@ extern "C" int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t ro
   }
   if (e == hipSuccess) {
     job.img = d_img;
-    hipLaunchKernelGGL(depth_tile_kernel<false>, dim3(n_tiles), dim3(kDepthBlock), 0, st, job, d_cnt, (const uint32_t *)nullptr, (float *)nullptr,
-                       (int32_t *)nullptr, d_res);
+    hipLaunchKernelGGL((depth_tile_kernel<false, false>), dim3(n_tiles), dim3(kDepthBlock), 0, st, job, d_cnt, (const uint32_t *)nullptr, (float *)nullptr,
+                       (int32_t *)nullptr, (uint32_t *)nullptr, d_res);
     e = hipGetLastError();
     size_t t1 = std::max<size_t>(tb, 16);
     if (e == hipSuccess) e = rocprim::exclusive_scan(d_tmp, t1, d_cnt, d_off, 0u, n_seg + 1, rocprim::plus<uint32_t>(), st);
     S.launches += 2;
   }
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(depth_tile_kernel<true>, dim3(n_tiles), dim3(kDepthBlock), 0, st, job, (uint32_t *)nullptr, d_off, d_raw, d_pix, d_res);
+    if (bgr)
+      hipLaunchKernelGGL((depth_tile_kernel<true, true>), dim3(n_tiles), dim3(kDepthBlock), 0, st, job, (uint32_t *)nullptr, d_off, d_raw, d_pix, d_rgb_raw, d_res);
+    else
+      hipLaunchKernelGGL((depth_tile_kernel<true, false>), dim3(n_tiles), dim3(kDepthBlock), 0, st, job, (uint32_t *)nullptr, d_off, d_raw, d_pix,
+                         (uint32_t *)nullptr, d_res);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(&total, d_off + n_seg, 4, hipMemcpyDeviceToHost, st);
@@ -297,6 +338,7 @@ extern "C" int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t ro
     c->n_valid = res[kKeptFinite];
     c->host_valid = false;
     e = hipMalloc((void **)&c->d_xyzw, sizeof(float4) * std::max<size_t>(total, 1));
+    if (e == hipSuccess && bgr) e = hipMalloc((void **)&c->d_rgb, 4 * std::max<size_t>(total, 1));   // (an empty cloud has colours too)
   }
   if (e == hipSuccess) {
     if (c->n_valid > 0)
@@ -311,17 +353,33 @@ extern "C" int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t ro
     for (int d = 0; d < 3; ++d) inv[d] = (mhi[d] > mlo[d]) ? 1023.999f / (mhi[d] - mlo[d]) : 0.f;
     if (total) e = tmp_malloc(st, (void **)&d_perm, 4 * (size_t)total);
     if (e == hipSuccess && total && out_pixel) e = hipMemcpyAsync(out_pixel, d_pix, 4 * (size_t)total, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && total) e = morton_order_device(st, d_raw, total, mlo, inv, c->d_xyzw, d_perm);   // (synchronises)
+    if (e == hipSuccess && total) e = morton_order_device(st, d_raw, total, mlo, inv, c->d_xyzw, d_perm, d_rgb_raw, c->d_rgb);   // (synchronises)
     else if (total) (void)hipStreamSynchronize(st);
     S.launches += kMortonLaunches + (out_pixel ? 1 : 0);
     S.host_syncs += kMortonSyncs;
   }
-  for (void *p : {(void *)d_img, (void *)d_cnt, (void *)d_off, (void *)d_res, (void *)d_raw, (void *)d_pix, (void *)d_perm, d_tmp}) tmp_free(st, p);
+  for (void *p : {(void *)d_img, (void *)d_cnt, (void *)d_off, (void *)d_res, (void *)d_raw, (void *)d_pix, (void *)d_perm, (void *)d_rgb_raw, d_tmp}) tmp_free(st, p);
   if (e != hipSuccess) {
     if (c) ope_cloud_free(c);
-    return set_err(ctx, OPE_EHIP, std::string("ope_depth_to_cloud: ") + hipGetErrorString(e));
+    return set_err(ctx, OPE_EHIP, who + hipGetErrorString(e));
   }
   *out = c;
   if (n_out) *n_out = total;
   return OPE_OK;
+}
+
+extern "C" int ope_depth_to_cloud(ope_ctx *ctx, const uint16_t *depth, size_t rows, size_t cols, size_t row_stride_bytes,
+                                  const ope_depth_params *params, const float lo[3], const float hi[3], ope_cloud **out, int32_t *out_pixel,
+                                  size_t *n_out) {
+  return depth_to_cloud_impl(ctx, "ope_depth_to_cloud", depth, rows, cols, row_stride_bytes, nullptr, 0, params, lo, hi, out, out_pixel, n_out);
+}
+
+extern "C" int ope_depth_to_cloud_rgb(ope_ctx *ctx, const uint16_t *depth, size_t rows, size_t cols, size_t depth_stride_bytes,
+                                      const unsigned char *bgr, size_t bgr_stride_bytes, const ope_depth_params *params, const float lo[3],
+                                      const float hi[3], ope_cloud **out, int32_t *out_pixel, size_t *n_out) {
+  // the colour image's own cases first: they need no context (the message goes where ope_last_error(NULL) finds it)
+  if (!bgr) return set_err(ctx, OPE_EINVAL, "ope_depth_to_cloud_rgb: bgr is NULL");
+  if (cols <= (size_t)0x7fffffff && bgr_stride_bytes < 3 * cols) return set_err(ctx, OPE_EINVAL, "ope_depth_to_cloud_rgb: bgr_stride_bytes must be >= 3 * cols");
+  return depth_to_cloud_impl(ctx, "ope_depth_to_cloud_rgb", depth, rows, cols, depth_stride_bytes, bgr, bgr_stride_bytes, params, lo, hi, out, out_pixel,
+                             n_out);
 }

@@ -295,6 +295,10 @@ struct ope_cloud {
   size_t n = 0, n_valid = 0;
   float4 *d_xyzw = nullptr;
   float4 *d_nrm = nullptr;
+  // Optional colour payload, one word per point in the SORTED order beside d_xyzw: the 32 bits of PointXYZRGB::rgb
+  // (r << 16 | g << 8 | b, top byte as given).  Non-null means "has colours", for an empty cloud too.  Every entry point that makes a
+  // cloud from clouds carries it in the launches that move the points.
+  uint32_t *d_rgb = nullptr;
   // Host mirrors (original order xyz; sorted position -> original index).  Clouds made on the device (ope_cloud_concat)
   // materialise them on first use: ensure_host().
   mutable std::vector<float, default_init_allocator<float>> h_xyz;   // original order, n*3
@@ -527,6 +531,9 @@ class TraceRange {
       return ::ope::set_err((ctx), OPE_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
   } while (0)
 
+// sampling.hip: the Morton order of n raw points (input order) into d_xyzw / d_perm; d_rgb_raw -> d_rgb the colour words, by the same gather
+hipError_t morton_order_device(hipStream_t stream, const float *d_raw, size_t n, const float lo[3], const float inv[3], float4 *d_xyzw,
+                               int32_t *d_perm, const uint32_t *d_rgb_raw = nullptr, uint32_t *d_rgb = nullptr);
 // sampling.hip: a new cloud from n_sel ORIGINAL indices (device array) of a device-resident cloud
 int select_cloud_device(ope_ctx *ctx, const ope_cloud *cloud, const int32_t *d_idx, size_t n_sel, ope_cloud **out);
 // the same for order-preserving filters: keep = one byte per ORIGINAL index (device); no re-sort (sampling.hip)

@@ -366,19 +366,22 @@ __global__ __launch_bounds__(256) void morton_key_kernel(const float *__restrict
 }
 
 __global__ __launch_bounds__(256) void morton_gather_kernel(const float *__restrict__ raw, const uint32_t *__restrict__ order,
-                                                             uint32_t n, float4 *__restrict__ xyzw, int32_t *__restrict__ perm) {
+                                                             uint32_t n, float4 *__restrict__ xyzw, int32_t *__restrict__ perm,
+                                                             const uint32_t *__restrict__ rgb_raw, uint32_t *__restrict__ rgb) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint32_t o = order[i];
   perm[i] = (int32_t)o;
   xyzw[i] = make_float4(raw[3 * (size_t)o], raw[3 * (size_t)o + 1], raw[3 * (size_t)o + 2], __int_as_float((int)o));
+  if (rgb) rgb[i] = rgb_raw[o];   // the colour payload follows its point (ope_cloud::d_rgb)
 }
 
 // d_raw: n*3 floats in input order (device).  Outputs: d_xyzw (n float4, sorted), d_perm (n, sorted position -> input index).
 // The order is that of the keys (Morton code, then input index): a STABLE sort of the 31-bit codes with the indices as
 // values (four radix passes over 8 bytes per point; round 2 sorted 64-bit code-and-index keys in eight).
+// d_rgb_raw / d_rgb (both or neither): the colour words in input order, gathered into sorted order by the same launch.
 hipError_t morton_order_device(hipStream_t stream, const float *d_raw, size_t n, const float lo[3], const float inv[3],
-                               float4 *d_xyzw, int32_t *d_perm) {
+                               float4 *d_xyzw, int32_t *d_perm, const uint32_t *d_rgb_raw, uint32_t *d_rgb) {
   if (n == 0) return hipSuccess;
   uint32_t *d_keys = nullptr, *d_keys2 = nullptr, *d_vals = nullptr, *d_vals2 = nullptr;
   void *d_tmp = nullptr;
@@ -395,7 +398,7 @@ hipError_t morton_order_device(hipStream_t stream, const float *d_raw, size_t n,
     if (e == hipSuccess) e = tmp_malloc(stream, &d_tmp, tb);
     if (e == hipSuccess) e = rocprim::radix_sort_pairs(d_tmp, tb, d_keys, d_keys2, d_vals, d_vals2, n, 0, 31, stream);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(morton_gather_kernel, dim3(nb), dim3(256), 0, stream, d_raw, d_vals2, (uint32_t)n, d_xyzw, d_perm);
+      hipLaunchKernelGGL(morton_gather_kernel, dim3(nb), dim3(256), 0, stream, d_raw, d_vals2, (uint32_t)n, d_xyzw, d_perm, d_rgb_raw, d_rgb);
       e = hipStreamSynchronize(stream);
     }
   }
@@ -437,6 +440,7 @@ __device__ __forceinline__ void block_bbox_commit(const float v[3], bool fin, ui
 // pcl::transformPointCloud (float, ((r0 x + r1 y) + r2 z) + t, non-finite points passed through) followed by
 // operator+= (BuildModel regmeshpcd.cpp:203,254).
 __global__ __launch_bounds__(256) void concat_kernel(CloudView a, const float *__restrict__ T_rows, CloudView b, float *__restrict__ raw,
+                                                     const uint32_t *__restrict__ rgb_a, const uint32_t *__restrict__ rgb_b, uint32_t *__restrict__ rgb_raw,
                                                      uint32_t *__restrict__ mn, uint32_t *__restrict__ mx) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   const uint32_t n = a.n + b.n;
@@ -455,14 +459,16 @@ __global__ __launch_bounds__(256) void concat_kernel(CloudView a, const float *_
       fin = isfinite(x) && isfinite(y) && isfinite(z);
     }
     raw[3 * (size_t)o] = x; raw[3 * (size_t)o + 1] = y; raw[3 * (size_t)o + 2] = z;
+    if (rgb_raw) rgb_raw[o] = from_a ? rgb_a[i] : rgb_b[i - a.n];
   }
   // bounding box of the finite points: order-preserving integer keys, one atomic per block and word
   const float v[3] = {x, y, z};
   block_bbox_commit(v, fin, mn, mx, nullptr);
 }
 
+// rgb_a, rgb_b (sorted order, as the clouds hold them) and d_rgb_raw (original order of the result): all three or none
 hipError_t concat_device(hipStream_t stream, const CloudView &a, const float *d_T_rows, const CloudView &b, float *d_raw, float lo[3],
-                         float hi[3]) {
+                         float hi[3], const uint32_t *rgb_a, const uint32_t *rgb_b, uint32_t *d_rgb_raw) {
   const uint32_t n = a.n + b.n;
   uint32_t *d_mm = nullptr;
   hipError_t e = tmp_malloc(stream, (void **)&d_mm, 32);
@@ -470,7 +476,7 @@ hipError_t concat_device(hipStream_t stream, const CloudView &a, const float *d_
   if (e == hipSuccess) e = h2d_copy(stream, d_mm, init, sizeof init);
   uint32_t res[8];
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(concat_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a, d_T_rows, b, d_raw, d_mm, d_mm + 4);
+    hipLaunchKernelGGL(concat_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a, d_T_rows, b, d_raw, rgb_a, rgb_b, d_rgb_raw, d_mm, d_mm + 4);
     e = hipMemcpyAsync(res, d_mm, sizeof res, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
   }
@@ -499,8 +505,8 @@ __global__ __launch_bounds__(256) void inverse_perm_kernel(CloudView c, uint32_t
 }
 
 __global__ __launch_bounds__(256) void select_gather_kernel(CloudView c, const uint32_t *__restrict__ inv, const int32_t *__restrict__ idx, uint32_t n_sel,
-                                                            float *__restrict__ raw, uint32_t *__restrict__ mn, uint32_t *__restrict__ mx,
-                                                            uint32_t *__restrict__ n_finite) {
+                                                            float *__restrict__ raw, const uint32_t *__restrict__ rgb_old, uint32_t *__restrict__ rgb_raw,
+                                                            uint32_t *__restrict__ mn, uint32_t *__restrict__ mx, uint32_t *__restrict__ n_finite) {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
   float v[3] = {0.f, 0.f, 0.f};
   bool fin = false;
@@ -510,6 +516,7 @@ __global__ __launch_bounds__(256) void select_gather_kernel(CloudView c, const u
     fin = p < c.n_valid;
     v[0] = q.x; v[1] = q.y; v[2] = q.z;
     raw[3 * (size_t)j] = q.x; raw[3 * (size_t)j + 1] = q.y; raw[3 * (size_t)j + 2] = q.z;
+    if (rgb_raw) rgb_raw[j] = rgb_old[p];
   }
   block_bbox_commit(v, fin, mn, mx, n_finite);
 }
@@ -528,11 +535,15 @@ int select_cloud_device(ope_ctx *ctx, const ope_cloud *cloud, const int32_t *d_i
   c->ctx = ctx;
   c->n = n_sel;
   c->host_valid = false;
-  uint32_t *d_inv = nullptr, *d_mm = nullptr;
+  uint32_t *d_inv = nullptr, *d_mm = nullptr, *d_rgb_raw = nullptr;
   float *d_raw = nullptr;
   int32_t *d_perm = nullptr;
   const CloudView cv = cloud->view();
   hipError_t e = hipMalloc((void **)&c->d_xyzw, sizeof(float4) * std::max<size_t>(n_sel, 1));
+  // colours travel in the launches that move the points: the gather below and the Morton gather (an empty selection of a
+  // coloured cloud is an empty coloured cloud)
+  if (e == hipSuccess && cloud->d_rgb) e = hipMalloc((void **)&c->d_rgb, 4 * std::max<size_t>(n_sel, 1));
+  if (e == hipSuccess && n_sel && cloud->d_rgb) e = tmp_malloc(ctx->stream, (void **)&d_rgb_raw, 4 * n_sel);
   if (e == hipSuccess && n_sel) e = tmp_malloc(ctx->stream, (void **)&d_inv, 4 * std::max<size_t>(cloud->n, 1));
   if (e == hipSuccess && n_sel) e = tmp_malloc(ctx->stream, (void **)&d_raw, 12 * n_sel);
   if (e == hipSuccess && n_sel) e = tmp_malloc(ctx->stream, (void **)&d_perm, 4 * n_sel);
@@ -542,7 +553,7 @@ int select_cloud_device(ope_ctx *ctx, const ope_cloud *cloud, const int32_t *d_i
     e = h2d_copy(ctx->stream, d_mm, res, sizeof res);
     hipLaunchKernelGGL(inverse_perm_kernel, dim3((unsigned)((cloud->n + 255) / 256)), dim3(256), 0, ctx->stream, cv, d_inv);
     hipLaunchKernelGGL(select_gather_kernel, dim3((unsigned)((n_sel + 255) / 256)), dim3(256), 0, ctx->stream, cv, d_inv, d_idx, (uint32_t)n_sel, d_raw,
-                       d_mm, d_mm + 4, d_mm + 8);
+                       (const uint32_t *)cloud->d_rgb, d_rgb_raw, d_mm, d_mm + 4, d_mm + 8);
     if (e == hipSuccess) e = hipMemcpyAsync(res, d_mm, sizeof res, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   }
@@ -555,7 +566,7 @@ int select_cloud_device(ope_ctx *ctx, const ope_cloud *cloud, const int32_t *d_i
     std::memcpy(c->bb_lo, lo, sizeof lo);
     std::memcpy(c->bb_hi, hi, sizeof hi);
     for (int d = 0; d < 3; ++d) inv3[d] = (hi[d] > lo[d]) ? 1023.999f / (hi[d] - lo[d]) : 0.f;
-    e = morton_order_device(ctx->stream, d_raw, n_sel, lo, inv3, c->d_xyzw, d_perm);
+    e = morton_order_device(ctx->stream, d_raw, n_sel, lo, inv3, c->d_xyzw, d_perm, d_rgb_raw, d_rgb_raw ? c->d_rgb : nullptr);
     if (e == hipSuccess && cloud->d_nrm) {
       e = hipMalloc((void **)&c->d_nrm, sizeof(float4) * n_sel);
       if (e == hipSuccess) {
@@ -565,7 +576,7 @@ int select_cloud_device(ope_ctx *ctx, const ope_cloud *cloud, const int32_t *d_i
       }
     }
   }
-  for (void *p : {(void *)d_inv, (void *)d_raw, (void *)d_perm, (void *)d_mm}) tmp_free(ctx->stream, p);
+  for (void *p : {(void *)d_inv, (void *)d_raw, (void *)d_perm, (void *)d_mm, (void *)d_rgb_raw}) tmp_free(ctx->stream, p);
   if (e != hipSuccess) {
     ope_cloud_free(c);
     return set_err(ctx, OPE_EHIP, std::string("cloud selection: ") + hipGetErrorString(e));
@@ -589,7 +600,7 @@ __global__ __launch_bounds__(256) void keep_flags_kernel(CloudView c, const unsi
 }
 __global__ __launch_bounds__(256) void compact_kernel(CloudView c, const uint32_t *__restrict__ f_sorted, const uint32_t *__restrict__ r_orig,
                                                       const uint32_t *__restrict__ r_sorted, float4 *__restrict__ xyzw_out, float4 *__restrict__ nrm_out,
-                                                      int32_t *__restrict__ idx_out, uint32_t *__restrict__ mn, uint32_t *__restrict__ mx,
+                                                      const uint32_t *__restrict__ rgb_in, uint32_t *__restrict__ rgb_out, int32_t *__restrict__ idx_out, uint32_t *__restrict__ mn, uint32_t *__restrict__ mx,
                                                       uint32_t *__restrict__ n_finite) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   float v[3] = {0.f, 0.f, 0.f};
@@ -599,6 +610,7 @@ __global__ __launch_bounds__(256) void compact_kernel(CloudView c, const uint32_
     const uint32_t o = (uint32_t)__float_as_int(q.w), o_new = r_orig[o], dst = r_sorted[p];
     xyzw_out[dst] = make_float4(q.x, q.y, q.z, __int_as_float((int)o_new));
     if (nrm_out) nrm_out[dst] = c.nrm[p];
+    if (rgb_out) rgb_out[dst] = rgb_in[p];
     if (idx_out) idx_out[o_new] = (int32_t)o;
     fin = p < c.n_valid;
     v[0] = q.x; v[1] = q.y; v[2] = q.z;
@@ -613,6 +625,7 @@ int compact_cloud_device(ope_ctx *ctx, const ope_cloud *cloud, const unsigned ch
   hipStream_t st = ctx->stream;
   uint32_t *d_fo = nullptr, *d_fs = nullptr, *d_ro = nullptr, *d_rs = nullptr, *d_mm = nullptr;
   float4 *d_x = nullptr, *d_n = nullptr;
+  uint32_t *d_c = nullptr;
   void *d_tmp = nullptr;
   size_t tb = 0;
   uint32_t res[12] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0, 0u, 0u, 0u, 0, 0u, 0, 0, 0};
@@ -642,12 +655,14 @@ int compact_cloud_device(ope_ctx *ctx, const ope_cloud *cloud, const unsigned ch
     c->host_valid = false;
     e = hipMalloc((void **)&d_x, sizeof(float4) * std::max<size_t>(count, 1));
     if (e == hipSuccess && cloud->d_nrm) e = hipMalloc((void **)&d_n, sizeof(float4) * std::max<size_t>(count, 1));
+    if (e == hipSuccess && cloud->d_rgb) e = hipMalloc((void **)&d_c, 4 * std::max<size_t>(count, 1));
     c->d_xyzw = d_x;
     c->d_nrm = d_n;
+    c->d_rgb = d_c;
   }
   if (e == hipSuccess && n) {
     e = h2d_copy(st, d_mm, res, sizeof res);
-    hipLaunchKernelGGL(compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cloud->view(), d_fs, d_ro, d_rs, d_x, d_n, d_idx_out, d_mm, d_mm + 4,
+    hipLaunchKernelGGL(compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cloud->view(), d_fs, d_ro, d_rs, d_x, d_n, (const uint32_t *)cloud->d_rgb, d_c, d_idx_out, d_mm, d_mm + 4,
                        d_mm + 8);
     if (e == hipSuccess) e = hipMemcpyAsync(res, d_mm, sizeof res, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);

@@ -87,3 +87,35 @@ def render_depth(points, params, rows: int, cols: int) -> np.ndarray:
     np.minimum.at(img, r[ok] * cols + c[ok], d[ok])
     img[img == 65536] = 0
     return img.astype(np.uint16).reshape(rows, cols)
+
+
+def write_ppm8(path: str, bgr) -> None:
+    """A (rows, cols, 3) uint8 image in OpenCV's channel order B, G, R as a binary PPM ("P6", maxval 255; the file's samples are
+    R, G, B)."""
+    bgr = np.asarray(bgr)
+    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError("write_ppm8: expected a (rows, cols, 3) uint8 image")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (bgr.shape[1], bgr.shape[0]))
+        f.write(np.ascontiguousarray(bgr[:, :, ::-1]).tobytes())
+
+
+def read_ppm8(path: str) -> np.ndarray:
+    """A binary PPM ("P6", maxval <= 255) as a (rows, cols, 3) uint8 image with the channels B, G, R, as cv::imread gives it.
+    ValueError for anything else."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:2] != b"P6":
+        raise ValueError("read_ppm8: not a binary PPM (P6)")
+    # the header is a PGM's but for the magic number: read it as one
+    import re
+    m = re.match(rb"P6(?:\s+|#[^\n]*\n)+(\d{1,9})(?:\s+|#[^\n]*\n)+(\d{1,9})(?:\s+|#[^\n]*\n)+(\d{1,9})\s", data)
+    if not m:
+        raise ValueError("read_ppm8: malformed header")
+    cols, rows, maxval = (int(v) for v in m.groups())
+    if cols < 1 or rows < 1 or not 1 <= maxval <= 255:
+        raise ValueError("read_ppm8: bad size or maxval (8-bit samples only)")
+    if len(data) - m.end() < 3 * rows * cols:
+        raise ValueError("read_ppm8: truncated file")
+    rgb = np.frombuffer(data, np.uint8, 3 * rows * cols, m.end()).reshape(rows, cols, 3)
+    return np.ascontiguousarray(rgb[:, :, ::-1])
