@@ -98,6 +98,10 @@ int ope_cloud_upload(ope_ctx *ctx, const void *base, size_t n, size_t stride_byt
                      ptrdiff_t normal_off, ope_cloud **out);
 /* Attach / replace normals (n*3 packed floats, original order). */
 int ope_cloud_set_normals(ope_ctx *ctx, ope_cloud *cloud, const float *normals_xyz);
+/* The normals attached to a cloud (ope_cloud_set_normals, ope_normals, ope_mls_smooth_cloud with compute_normals), in ORIGINAL
+ * order: out_normals n*3 floats, out_curvature n floats (the fourth component the device keeps beside a normal: 0 after
+ * ope_cloud_set_normals); either may be NULL.  OPE_EINVAL when the cloud carries none. */
+int ope_cloud_download_normals(ope_ctx *ctx, const ope_cloud *cloud, float *out_normals, float *out_curvature);
 /* The colour payload of a cloud: one word per point, the 32 bits of pcl::PointXYZRGB::rgb (r << 16 | g << 8 | b, top byte as
  * given), kept on the device beside the points.  ope_cloud_set_rgb attaches / replaces it from n words in ORIGINAL order; NULL
  * detaches it (the cloud is then what it was before: nothing else about a cloud depends on its colours).  ope_cloud_has_rgb: 1 or
@@ -106,7 +110,7 @@ int ope_cloud_set_normals(ope_ctx *ctx, ope_cloud *cloud, const float *normals_x
  * points (no further launch or synchronisation): ope_cloud_select (repeats and any order), ope_cloud_concat (below), the _cloud
  * forms of the filters (ope_remove_nan_cloud, ope_pass_through_cloud, ope_statistical_outlier_removal_cloud,
  * ope_uniform_sampling_cloud: the chosen point's colour), plane / not_plane of ope_plane_segment and ope_tabletop_segment, out of
- * ope_prism_extract, the clusters of ope_euclidean_clusters_cloud, and ope_depth_to_cloud_rgb makes it.  An empty cloud made from a
+ * ope_prism_extract, the clusters of ope_euclidean_clusters_cloud, ope_mls_smooth_cloud, and ope_depth_to_cloud_rgb makes it.  An empty cloud made from a
  * coloured one has colours.  NOT carried: *aligned of ope_track_pose (the moved model; the tracker reads no colours). */
 int ope_cloud_set_rgb(ope_ctx *ctx, ope_cloud *cloud, const uint32_t *rgb);
 int ope_cloud_has_rgb(const ope_cloud *cloud);
@@ -880,6 +884,46 @@ typedef struct {
   int64_t kept;     /* points of the cloud (valid and inside the crop) */
 } ope_depth_stats;
 int ope_depth_last_stats(const ope_ctx *ctx, ope_depth_stats *out);
+
+/* ---------------- moving least squares (ProcessingPcd::getSmooth) ---------------- */
+/* pcl::MovingLeastSquares::process with upsampling NONE (BuildModel/src/processingpcd.cpp:80-108: polynomial fit, radius search,
+ * normals off; regmeshpcd.cpp:264-266 with radius 0.02), DESIGN.md 4.14.  For every finite input point q, in ascending ORIGINAL
+ * index: its neighbours are the finite points p of the same cloud with fp32 ((dx*dx + dy*dy) + dz*dz) <= (float)radius *
+ * (float)radius, q included, however many.  Fewer than 3: q is DROPPED.  Otherwise, in fp64: centroid, unnormalised covariance,
+ * pcl::eigen33's smallest eigenpair (n, lambda), the plane through the centroid, q projected on it, curvature
+ * |lambda / trace| (0 for a zero trace).  With polynomial_fit and at least (order + 1)(order + 2) / 2 neighbours: the weighted
+ * least-squares polynomial of that order over the neighbours' plane coordinates about the projected point, weights
+ * exp(-d^2 / sqr_gauss_param), solved by Cholesky; if c[0] is finite the point moves by c[0] n and, with compute_normals, the normal
+ * becomes n - c[order + 1] u - c[1] v (neither normalised nor oriented); otherwise the projection and n stand.
+ * Two deviations from PCL: non-finite input points are dropped and are nobody's neighbour (PCL's behaviour on them is undefined);
+ * a Cholesky pivot that is <= 0 or not finite makes the fit fail like a non-finite c[0] (Eigen goes on with garbage).
+ * radius > 0; order 0, 1 or 2 (3 and 4 belong to MLS upsampling, which is not built): anything else OPE_EINVAL, nothing launched.
+ * sqr_gauss_param 0 means radius * radius, as setSearchRadius sets it. */
+typedef struct {
+  double radius;
+  int polynomial_fit;       /* 1 */
+  int order;                /* 2 */
+  double sqr_gauss_param;   /* 0 */
+  int compute_normals;      /* 0 */
+} ope_mls_params;
+void ope_mls_default_params(ope_mls_params *p);
+/* Host outputs, each with room for ope_cloud_size(cloud) points; any may be NULL except n_out.  out_xyz: the smoothed points
+ * (x y z); out_normals (x y z) and out_curvature: as above (the plane's normal when compute_normals is 0); out_idx: the ORIGINAL
+ * index of each output point (getCorrespondingIndices), ascending.  An empty cloud gives OPE_OK and *n_out = 0. */
+int ope_mls_smooth(ope_ctx *ctx, const ope_cloud *cloud, const ope_mls_params *params, float *out_xyz, float *out_normals,
+                   float *out_curvature, int32_t *out_idx, size_t *n_out);
+/* The same with the result left on the device: *out is a new cloud of the smoothed points (free it with ope_cloud_free), the
+ * input's colours carried (copyMissingFields) and, when compute_normals is set, the normals attached (w = curvature).  An empty
+ * result is an empty cloud, coloured if the input was.  out_idx is optional. */
+int ope_mls_smooth_cloud(ope_ctx *ctx, const ope_cloud *cloud, const ope_mls_params *params, ope_cloud **out, int32_t *out_idx,
+                         size_t *n_out);
+/* What the last ope_mls_smooth / ope_mls_smooth_cloud of this context did.  n_plane_only: output points that stand at their plane
+ * projection (no fit asked for, too few neighbours for the order, or a failed fit); n_dropped = n_in - n_out; neighbours_total:
+ * neighbourhood sizes summed over the finite input points, the dropped ones included. */
+typedef struct {
+  int64_t n_in, n_out, n_plane_only, n_dropped, neighbours_total;
+} ope_mls_stats;
+int ope_mls_last_stats(const ope_ctx *ctx, ope_mls_stats *out);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,10 @@
 //
 //   build_model --scan <kinect|astra|euclid> --limits x0 x1 y0 y1 z0 z1 <out.pcd> <corrRejThresh> <maxIter> <depth0.pgm> <rgb0.ppm> [...]
 //
+// `--smooth R` anywhere on a --scan line (opt-in) applies getSmooth with radius R to the finished, device-resident model before its
+// download, the line the reference keeps at regmeshpcd.cpp:264-266.  Without --scan the model is a host cloud: --smooth is a usage
+// error there (status 2).
+//
 // Depth images are 16-bit binary PGM, colour images 8-bit binary PPM (depth_io.hpp).  A frame without a supporting plane or
 // without a cluster ends the program with a message and status 5 (the reference's cloudClusterVector.at(0) throws).
 // Prints one `pair <k> iterations <n> converged <0|1> fitness <f> T <16 floats, column-major>` line per registration.
@@ -30,7 +34,8 @@ static int usage(const char *prog) {
   std::fprintf(stderr,
                "usage: %s <out.pcd> <corrRejThresh> <maxIter> <frame0.pcd> <frame1.pcd> [...]\n"
                "       %s --scan <kinect|astra|euclid> --limits x0 x1 y0 y1 z0 z1 <out.pcd> <corrRejThresh> <maxIter> <depth0.pgm> <rgb0.ppm> "
-               "[<depth1.pgm> <rgb1.ppm> ...]\n",
+               "[<depth1.pgm> <rgb1.ppm> ...]\n"
+               "       --smooth R anywhere on a --scan line: smooth the finished model (moving least squares, radius R) before it is written\n",
                prog, prog);
   return 2;
 }
@@ -45,7 +50,7 @@ static void print_pairs(const ope::RegMeshPcd &reg) {
 }
 
 // build_model --scan: argv[2] the sensor, argv[3] "--limits", argv[4..9] the box, argv[10..12] out / thresh / iterations, then the pairs
-static int scan_main(int argc, char **argv) {
+static int scan_main(int argc, char **argv, float smooth) {
   if (argc < 15 || (argc - 13) % 2 != 0 || std::strcmp(argv[3], "--limits") != 0) return usage(argv[0]);
   const std::string sensor = argv[2];
   if (sensor != "kinect" && sensor != "astra" && sensor != "euclid") return usage(argv[0]);
@@ -78,6 +83,7 @@ static int scan_main(int argc, char **argv) {
   }
   std::printf("Finished segmentation of %zu point clouds!\n", cloudVectorSeg.size());
   ope::RegMeshPcd regMeshPcd;
+  regMeshPcd.setSmoothRadius(smooth);
   auto cloudAligned = regMeshPcd.registerPointClouds(cloudVectorSeg, 0.005f, corrRejThresh, maxIter);   // :207
   if (cloudAligned->empty()) return 6;
   print_pairs(regMeshPcd);
@@ -87,7 +93,19 @@ static int scan_main(int argc, char **argv) {
 }
 
 int main(int argc, char **argv) {
-  if (argc > 1 && std::strcmp(argv[1], "--scan") == 0) return scan_main(argc, argv);
+  float smooth = 0.f;   // --smooth R, taken out of the line
+  for (int i = 1; i < argc; ++i)
+    if (std::strcmp(argv[i], "--smooth") == 0) {
+      char *end = nullptr;
+      if (i + 1 >= argc) return usage(argv[0]);
+      smooth = std::strtof(argv[i + 1], &end);
+      if (end == argv[i + 1] || *end || !(smooth > 0.f)) return usage(argv[0]);
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2;
+      break;
+    }
+  if (argc > 1 && std::strcmp(argv[1], "--scan") == 0) return scan_main(argc, argv, smooth);
+  if (smooth > 0.f) return usage(argv[0]);
   if (argc < 6) return usage(argv[0]);
   const std::string out_path = argv[1];
   const float corrRejThresh = (float)std::atof(argv[2]);

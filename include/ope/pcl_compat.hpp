@@ -772,6 +772,72 @@ struct PointIndices {
   std::vector<int> indices;
 };
 
+// pcl::MovingLeastSquares with upsampling NONE (ProcessingPcd::getSmooth, BuildModel/src/processingpcd.cpp:80-108): ope_mls_smooth.
+// The output point takes the smoothed xyz; its normal and curvature fields (if OutT has them) are written only when
+// setComputeNormals(true), as in PCL; every other field OutT shares with InT (here: rgb) is copied from the input point
+// (copyMissingFields).  getCorrespondingIndices: the input index of each output point.
+template <class InT, class OutT> class MovingLeastSquares {
+ public:
+  MovingLeastSquares() { ope_mls_default_params(&p_); }
+  void setInputCloud(const typename PointCloud<InT>::ConstPtr &c) { input_ = c; }
+  void setComputeNormals(bool on) { p_.compute_normals = on ? 1 : 0; }
+  void setPolynomialFit(bool on) { p_.polynomial_fit = on ? 1 : 0; }
+  void setPolynomialOrder(int order) { p_.order = order; }
+  template <class Tree> void setSearchMethod(const Tree &) {}   // accepted, unused: the device walks its own tree
+  void setSearchRadius(double r) { p_.radius = r; p_.sqr_gauss_param = r * r; }
+  void setSqrGaussParam(double g) { p_.sqr_gauss_param = g; }
+  PointIndices::Ptr getCorrespondingIndices() const { return corresponding_; }
+  void process(PointCloud<OutT> &out) {
+    PointCloud<OutT> tmp;
+    corresponding_ = std::make_shared<PointIndices>();
+    ope_ctx *ctx = default_context();
+    if (ctx && input_ && !input_->empty()) {
+      auto dev = upload(*input_, false);
+      const size_t cap = input_->size();
+      std::vector<float> xyz(3 * cap), nrm(3 * cap), curv(cap);
+      std::vector<int32_t> idx(cap);
+      size_t n = 0;
+      if (dev->h && ope_mls_smooth(ctx, dev->h, &p_, xyz.data(), nrm.data(), curv.data(), idx.data(), &n) != OPE_OK) { log_error("MovingLeastSquares", ctx); n = 0; }
+      tmp.points.resize(n);
+      corresponding_->indices.assign(idx.begin(), idx.begin() + n);
+      constexpr ptrdiff_t rgb_in = point_traits<InT>::rgb_offset, rgb_out = point_traits<OutT>::rgb_offset, n_out = point_traits<OutT>::normal_offset;
+      for (size_t i = 0; i < n; ++i) {
+        OutT &o = tmp.points[i];
+        o.x = xyz[3 * i]; o.y = xyz[3 * i + 1]; o.z = xyz[3 * i + 2];
+        if (rgb_in >= 0 && rgb_out >= 0)
+          std::memcpy(reinterpret_cast<unsigned char *>(&o) + rgb_out, reinterpret_cast<const unsigned char *>(&input_->points[idx[i]]) + rgb_in, 4);
+        if (n_out >= 0 && p_.compute_normals) {
+          std::memcpy(reinterpret_cast<unsigned char *>(&o) + n_out, &nrm[3 * i], 12);
+          set_curvature(o, curv[i]);
+        }
+      }
+      tmp.width = (uint32_t)n;
+    }
+    out = std::move(tmp);
+  }
+ private:
+  static void set_curvature(PointXYZRGBNormal &o, float c) { o.curvature = c; }
+  static void set_curvature(Normal &o, float c) { o.curvature = c; }
+  template <class T> static void set_curvature(T &, float) {}
+  typename PointCloud<InT>::ConstPtr input_;
+  ope_mls_params p_;
+  PointIndices::Ptr corresponding_;
+};
+
+// pcl::copyPointCloud between point types: the fields both have (xyz; rgb when both carry it)
+template <class A, class B> inline void copyPointCloud(const PointCloud<A> &in, PointCloud<B> &out) {
+  PointCloud<B> tmp;
+  tmp.points.resize(in.size());
+  constexpr ptrdiff_t ra = point_traits<A>::rgb_offset, rb = point_traits<B>::rgb_offset;
+  for (size_t i = 0; i < in.size(); ++i) {
+    tmp.points[i].x = in.points[i].x; tmp.points[i].y = in.points[i].y; tmp.points[i].z = in.points[i].z;
+    if (ra >= 0 && rb >= 0)
+      std::memcpy(reinterpret_cast<unsigned char *>(&tmp.points[i]) + rb, reinterpret_cast<const unsigned char *>(&in.points[i]) + ra, 4);
+  }
+  tmp.width = in.width; tmp.height = in.height; tmp.is_dense = in.is_dense;
+  out = std::move(tmp);
+}
+
 // ObjectSegmentationPlane::getClusters (objectsegmentationplane.cpp:79-93): the clusters of ope_euclidean_clusters, each as
 // ORIGINAL indices ascending, by size descending then smallest index (PCL's order; see ope.h for the one documented difference)
 template <class PointT> class EuclideanClusterExtraction {

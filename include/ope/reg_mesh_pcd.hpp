@@ -146,6 +146,15 @@ class RegMeshPcd {
       if (ope_cloud_concat(ctx, acc->h, pr.T.m, tgt, &next->h) != OPE_OK) return fail("registerPointClouds (concat)");                   // :203, :254
       acc = next;
     }
+    if (smoothRadius_ > 0.f) {   // :264-266 getSmooth(cloudTemp, radius): on the device, before the one download
+      ope_mls_params mp;
+      ope_mls_default_params(&mp);
+      mp.radius = smoothRadius_;
+      auto smooth = std::make_shared<compat::CloudHandle>();
+      size_t kept = 0;
+      if (ope_mls_smooth_cloud(ctx, acc->h, &mp, &smooth->h, nullptr, &kept) != OPE_OK) return fail("registerPointClouds (smooth)");
+      acc = smooth;
+    }
     const size_t n = ope_cloud_size(acc->h);
     std::vector<float> xyz(3 * n + 3);
     std::vector<uint32_t> rgb(n + 1, 0x00ffffffu);
@@ -163,7 +172,11 @@ class RegMeshPcd {
     return out;
   }
 
+  // opt-in: the device overload of registerPointClouds smooths the finished model with this radius (0: off, the default)
+  void setSmoothRadius(float radius) { smoothRadius_ = radius; }
+
  private:
+  float smoothRadius_ = 0.f;
   // NormalEstimation<PointXYZRGB, PointXYZRGBNormal>(k = 12), then copyPointCloud of xyz / rgb into it (:72-90)
   static CloudN::Ptr withNormals(const Cloud::Ptr &c) {
     CloudN::Ptr n(new CloudN);

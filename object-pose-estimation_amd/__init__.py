@@ -291,6 +291,27 @@ class DepthStats(C.Structure):
     ]
 
 
+class MlsParams(C.Structure):
+    """ope_mls_params: pcl::MovingLeastSquares with upsampling NONE (ProcessingPcd::getSmooth)."""
+    _fields_ = [
+        ("radius", C.c_double),
+        ("polynomial_fit", C.c_int),
+        ("order", C.c_int),
+        ("sqr_gauss_param", C.c_double),
+        ("compute_normals", C.c_int),
+    ]
+
+
+class MlsStats(C.Structure):
+    _fields_ = [
+        ("n_in", C.c_int64),
+        ("n_out", C.c_int64),
+        ("n_plane_only", C.c_int64),
+        ("n_dropped", C.c_int64),
+        ("neighbours_total", C.c_int64),
+    ]
+
+
 SENSOR_KINECT, SENSOR_ASTRA, SENSOR_EUCLID = 0, 1, 2
 SENSORS = {"kinect": SENSOR_KINECT, "astra": SENSOR_ASTRA, "euclid": SENSOR_EUCLID}
 
@@ -411,6 +432,11 @@ ABI = [
     ("ope_cloud_download_rgb", C.c_int, [_vp, _vp, _vp]),
     ("ope_depth_to_cloud_rgb", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.POINTER(DepthParams), _fp, _fp,
                                           C.POINTER(_vp), _ip, C.POINTER(C.c_size_t)]),
+    ("ope_cloud_download_normals", C.c_int, [_vp, _vp, _fp, _fp]),
+    ("ope_mls_default_params", None, [C.POINTER(MlsParams)]),
+    ("ope_mls_smooth", C.c_int, [_vp, _vp, C.POINTER(MlsParams), _fp, _fp, _fp, _ip, C.POINTER(C.c_size_t)]),
+    ("ope_mls_smooth_cloud", C.c_int, [_vp, _vp, C.POINTER(MlsParams), C.POINTER(_vp), _ip, C.POINTER(C.c_size_t)]),
+    ("ope_mls_last_stats", C.c_int, [_vp, C.POINTER(MlsStats)]),
 ]
 
 _lib = None
@@ -463,6 +489,16 @@ def default_depth_params(sensor="kinect", **kw) -> DepthParams:
     code = SENSORS[sensor] if isinstance(sensor, str) else int(sensor)
     if lib().ope_depth_sensor_params(code, C.byref(p)) != OPE_OK:
         raise ValueError(f"unknown sensor {sensor!r}")
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_mls_params(**kw) -> MlsParams:
+    p = MlsParams()
+    lib().ope_mls_default_params(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -1271,6 +1307,36 @@ class Context:
         self._chk(lib().ope_statistical_outlier_removal(self.h, cloud.h, mean_k, stddev_mul, _p(out, _ip), C.byref(n), _p(dist, _fp)))
         return (out[: n.value].copy(), dist[: cloud.n].copy()) if return_distances else out[: n.value].copy()
 
+    def mls_smooth(self, cloud: "Cloud", radius: float, order: int = 2, polynomial_fit: bool = True, compute_normals: bool = False,
+                   sqr_gauss_param: float | None = None, as_cloud: bool = False):
+        """pcl::MovingLeastSquares, upsampling NONE (ProcessingPcd::getSmooth).  as_cloud=False: (xyz, idx) or, with
+        compute_normals, (xyz, idx, normals, curvature), idx the ORIGINAL index of each output point.  as_cloud=True: (Cloud, idx),
+        the smoothed points left on the device with the input's colours and, with compute_normals, the normals attached."""
+        p = default_mls_params(radius=float(radius), order=int(order), polynomial_fit=int(bool(polynomial_fit)),
+                               compute_normals=int(bool(compute_normals)),
+                               sqr_gauss_param=0.0 if sqr_gauss_param is None else float(sqr_gauss_param))
+        cap = max(cloud.n, 1)
+        idx = np.empty(cap, np.int32)
+        n = C.c_size_t(0)
+        if as_cloud:
+            h = _vp()
+            self._chk(lib().ope_mls_smooth_cloud(self.h, cloud.h, C.byref(p), C.byref(h), _p(idx, _ip), C.byref(n)))
+            return Cloud(self, h, n.value), idx[: n.value].copy()
+        xyz = np.empty((cap, 3), np.float32)
+        nrm = np.empty((cap, 3), np.float32) if compute_normals else None
+        curv = np.empty(cap, np.float32) if compute_normals else None
+        self._chk(lib().ope_mls_smooth(self.h, cloud.h, C.byref(p), _p(xyz, _fp), _p(nrm, _fp), _p(curv, _fp), _p(idx, _ip), C.byref(n)))
+        m = n.value
+        if compute_normals:
+            return xyz[:m].copy(), idx[:m].copy(), nrm[:m].copy(), curv[:m].copy()
+        return xyz[:m].copy(), idx[:m].copy()
+
+    def mls_stats(self) -> dict:
+        """ope_mls_last_stats: n_in, n_out, n_plane_only, n_dropped, neighbours_total of the last mls_smooth."""
+        s = MlsStats()
+        self._chk(lib().ope_mls_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in MlsStats._fields_}
+
     def sacia(self, src: "Cloud", src_feat, tgt: "Cloud", tgt_index: "Index", tgt_feat, params: SaciaParams | None = None,
               forced_samples=None):
         p = params or default_sacia_params()
@@ -1357,6 +1423,13 @@ class Cloud:
         if len(nrm) != self.n:
             raise ValueError("normals length mismatch")
         self.ctx._chk(lib().ope_cloud_set_normals(self.ctx.h, self.h, _p(nrm, _fp)))
+
+    def download_normals(self):
+        """ope_cloud_download_normals: (normals (n, 3), curvature (n,)) in original order (OpeError when the cloud carries none)."""
+        nrm = np.empty((self.n, 3), np.float32)
+        curv = np.empty(self.n, np.float32)
+        self.ctx._chk(lib().ope_cloud_download_normals(self.ctx.h, self.h, _p(nrm, _fp), _p(curv, _fp)))
+        return nrm, curv
 
     def set_rgb(self, rgb):
         """ope_cloud_set_rgb: n uint32 words r << 16 | g << 8 | b in the cloud's original order; None detaches the colours."""

@@ -81,7 +81,7 @@ def get_icp_normal(ope, ctx, source_xyz, target_xyz, corr_rej_thresh: float = 0.
 
 def register_point_clouds(ope, ctx, frames, max_corr_dist: float = 0.005, corr_rej_thresh: float = 0.7,
                           max_iterations: int = 500, colors=None, on_device: bool = True, k_normals: int = 12,
-                          estimator: str = "lm", use_max_corr_dist_in_icp: bool = False) -> RegistrationResult:
+                          estimator: str = "lm", use_max_corr_dist_in_icp: bool = False, smooth_radius: float | None = None) -> RegistrationResult:
     """Sequential accumulate-and-register over N frames (regmeshpcd.cpp:210-271).
 
     cloudTemp = frame 0; for every next frame: align cloudTemp to it, then cloudTemp = aligned + frame.
@@ -96,14 +96,19 @@ def register_point_clouds(ope, ctx, frames, max_corr_dist: float = 0.005, corr_r
     The frames may also be device-resident Clouds (all of them): nothing is uploaded, the Clouds stay the caller's (they come
     back with the normals of this run attached), and when every one of them carries colours the accumulated cloud carries
     them through ope_cloud_concat: `rgb` is then one download at the end, beside the one of the points.
+
+    smooth_radius (device-resident frames only; default None: off): the line the reference keeps commented at
+    regmeshpcd.cpp:264-266, getSmooth of the finished model (Context.mls_smooth, on the device, before the one download).
     """
     if len(frames) == 0:
         raise ValueError("register_point_clouds: no frames")
+    if smooth_radius is not None and not all(isinstance(f, ope.Cloud) for f in frames):
+        raise ValueError("register_point_clouds: smooth_radius needs device-resident frames")
     if all(isinstance(f, ope.Cloud) for f in frames):
         if colors is not None and (len(colors) != len(frames) or any(len(c) != f.n for c, f in zip(colors, frames))):
             raise ValueError("register_point_clouds: colors must match the frames point for point")
         return _register_device_clouds(ope, ctx, list(frames), max_corr_dist, corr_rej_thresh, max_iterations, colors, k_normals,
-                                       estimator, use_max_corr_dist_in_icp)
+                                       estimator, use_max_corr_dist_in_icp, smooth_radius)
     if colors is not None and (len(colors) != len(frames) or any(len(c) != len(f) for c, f in zip(colors, frames))):
         raise ValueError("register_point_clouds: colors must match the frames point for point")
     res = RegistrationResult(np.ascontiguousarray(frames[0], np.float32))
@@ -146,7 +151,7 @@ def register_point_clouds(ope, ctx, frames, max_corr_dist: float = 0.005, corr_r
 
 
 def _register_device_clouds(ope, ctx, clouds, max_corr_dist, corr_rej_thresh, max_iterations, colors, k_normals, estimator,
-                            use_max_corr_dist_in_icp) -> RegistrationResult:
+                            use_max_corr_dist_in_icp, smooth_radius=None) -> RegistrationResult:
     """register_point_clouds over Clouds: the device loop of the array form without its uploads."""
     p = icp_params_with_normals(ope, corr_rej_thresh, max_iterations, max_corr_dist if use_max_corr_dist_in_icp else None, estimator)
     res = RegistrationResult(None)
@@ -168,9 +173,17 @@ def _register_device_clouds(ope, ctx, clouds, max_corr_dist, corr_rej_thresh, ma
             if own:
                 acc.free()
             acc, own = nxt, True
+        kept = None
+        if smooth_radius is not None:                        # :264-266 getSmooth(cloudTemp, radius), on the device
+            nxt, kept = ctx.mls_smooth(acc, smooth_radius, as_cloud=True)
+            if own:
+                acc.free()
+            acc, own = nxt, True
         res.cloud = ctx.download(acc)
         if colors is not None:
             res.rgb = np.concatenate([np.ascontiguousarray(c, np.uint32) for c in colors])
+            if kept is not None:
+                res.rgb = res.rgb[kept]
         elif acc.has_rgb:
             res.rgb = acc.download_rgb()
     finally:
@@ -199,13 +212,14 @@ def segment_object_device(ope, ctx, frame):
 
 
 def build_model_from_images(ope, ctx, depths, bgrs, limits, out_path: str | None = None, params=None, max_corr_dist: float = 0.005,
-                            corr_rej_thresh: float = 0.7, max_iterations: int = 500, **kw) -> RegistrationResult:
+                            corr_rej_thresh: float = 0.7, max_iterations: int = 500, smooth_radius: float | None = None, **kw) -> RegistrationResult:
     """BuildModel from the sensor's images (main.cpp:171-225 behind DataGrabber::rgbd2Pcl(rgb, depth)), the `--scan` mode of the
     build_model program: per frame the coloured ingest with the crop `limits` = (xmin, xmax, ymin, ymax, zmin, zmax)
     (ope_depth_to_cloud_rgb), the table and cluster 0 on the device; then the sequential registration over the clusters and
     `FIELDS x y z rgb`.  No host cloud exists between the images and the model.  depths: (rows, cols) uint16 images; bgrs:
     (rows, cols, 3) uint8, channels B, G, R; params: DepthParams (default: the Kinect preset).  ValueError, naming the frame,
-    when a frame has no plane or no cluster."""
+    when a frame has no plane or no cluster.  smooth_radius (default None: off): getSmooth of the finished model on the device
+    before it is fetched and written (regmeshpcd.cpp:264-266), `build_model --scan --smooth R`."""
     from . import pcd
 
     if len(depths) == 0 or len(depths) != len(bgrs):
@@ -222,7 +236,7 @@ def build_model_from_images(ope, ctx, depths, bgrs, limits, out_path: str | None
                 raise ValueError("build_model_from_images: frame %d: %s" % (i, e)) from None
             finally:
                 frame.free()
-        res = register_point_clouds(ope, ctx, objects, max_corr_dist, corr_rej_thresh, max_iterations, **kw)
+        res = register_point_clouds(ope, ctx, objects, max_corr_dist, corr_rej_thresh, max_iterations, smooth_radius=smooth_radius, **kw)
     finally:
         for o in objects:
             o.free()

@@ -750,6 +750,25 @@ int ope_cloud_download(ope_ctx *ctx, const ope_cloud *cloud, float *out_xyz) {
   return OPE_OK;
 }
 
+int ope_cloud_download_normals(ope_ctx *ctx, const ope_cloud *cloud, float *out_normals, float *out_curvature) {
+  if (!ctx || !cloud) return set_err(ctx, OPE_EINVAL, "ope_cloud_download_normals: bad argument");
+  if (!cloud->d_nrm) return set_err(ctx, OPE_EINVAL, "ope_cloud_download_normals: the cloud carries no normals");
+  const int rc = cloud->ensure_host();
+  if (rc != OPE_OK) return rc;
+  const size_t n = cloud->n;
+  if (n == 0) return OPE_OK;
+  OPE_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<float> sorted(4 * n);
+  OPE_HIP(ctx, hipMemcpyAsync(sorted.data(), cloud->d_nrm, sizeof(float4) * n, hipMemcpyDeviceToHost, ctx->stream));
+  OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < n; ++i) {
+    const size_t o = (size_t)cloud->perm[i];
+    if (out_normals) std::memcpy(out_normals + 3 * o, &sorted[4 * i], 12);
+    if (out_curvature) out_curvature[o] = sorted[4 * i + 3];
+  }
+  return OPE_OK;
+}
+
 // ------------------------------------------------------------------------------------------ index
 void ope_index_default_params(ope_index_params *p) {
   if (p) { p->leaf_size = 16; p->grid = 1; p->grid_fill = 0.f; p->grid_max_cells = 0; }

@@ -77,6 +77,74 @@ __device__ void eigen33_smallest(const float mat[9], float *eigenvalue, float ev
   evec[0] = vx / s; evec[1] = vy / s; evec[2] = vz / s;
 }
 
+// The same algorithm with Scalar = double (MovingLeastSquares calls pcl::eigen33 on a Matrix3d, mls.hip).  The fp32 path above keeps
+// its own libm (bit parity with the CPU oracle); here atan2 / cos / sin are the device library's fp64 functions.
+__device__ inline void compute_roots2(double b, double c, double roots[3]) {
+  roots[0] = 0.0;
+  double d = b * b - 4.0 * c;
+  if (d < 0.0) d = 0.0;
+  const double sd = sqrt(d);
+  roots[2] = 0.5 * (b + sd);
+  roots[1] = 0.5 * (b - sd);
+}
+
+__device__ inline void compute_roots(const double m[9], double roots[3]) {
+  const double c0 = m[0] * m[4] * m[8] + 2.0 * m[1] * m[2] * m[5] - m[0] * m[5] * m[5] - m[4] * m[2] * m[2] - m[8] * m[1] * m[1];
+  const double c1 = m[0] * m[4] - m[1] * m[1] + m[0] * m[8] - m[2] * m[2] + m[4] * m[8] - m[5] * m[5];
+  const double c2 = m[0] + m[4] + m[8];
+  if (fabs(c0) < 2.220446049250313e-16) {
+    compute_roots2(c2, c1, roots);
+    return;
+  }
+  const double s_inv3 = 1.0 / 3.0;
+  const double s_sqrt3 = sqrt(3.0);
+  const double c2_over_3 = c2 * s_inv3;
+  double a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
+  if (a_over_3 > 0.0) a_over_3 = 0.0;
+  const double half_b = 0.5 * (c0 + c2_over_3 * (2.0 * c2_over_3 * c2_over_3 - c1));
+  double q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
+  if (q > 0.0) q = 0.0;
+  const double rho = sqrt(-a_over_3);
+  const double theta = atan2(sqrt(-q), half_b) * s_inv3;
+  const double cos_theta = cos(theta), sin_theta = sin(theta);
+  roots[0] = c2_over_3 + 2.0 * rho * cos_theta;
+  roots[1] = c2_over_3 - rho * (cos_theta + s_sqrt3 * sin_theta);
+  roots[2] = c2_over_3 - rho * (cos_theta - s_sqrt3 * sin_theta);
+  double t;
+  if (roots[0] >= roots[1]) { t = roots[0]; roots[0] = roots[1]; roots[1] = t; }
+  if (roots[1] >= roots[2]) {
+    t = roots[1]; roots[1] = roots[2]; roots[2] = t;
+    if (roots[0] >= roots[1]) { t = roots[0]; roots[0] = roots[1]; roots[1] = t; }
+  }
+  if (roots[0] <= 0.0) compute_roots2(c2, c1, roots);
+}
+
+__device__ inline void eigen33_smallest(const double mat[9], double *eigenvalue, double evec[3]) {
+  double scale = 0.0;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) scale = fmax(scale, fabs(mat[i]));
+  if (scale <= 2.2250738585072014e-308) scale = 1.0;
+  double sm[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) sm[i] = mat[i] / scale;
+  double roots[3];
+  compute_roots(sm, roots);
+  *eigenvalue = roots[0] * scale;
+  sm[0] -= roots[0]; sm[4] -= roots[0]; sm[8] -= roots[0];
+  const double v1[3] = {sm[1] * sm[5] - sm[2] * sm[4], sm[2] * sm[3] - sm[0] * sm[5], sm[0] * sm[4] - sm[1] * sm[3]};
+  const double v2[3] = {sm[1] * sm[8] - sm[2] * sm[7], sm[2] * sm[6] - sm[0] * sm[8], sm[0] * sm[7] - sm[1] * sm[6]};
+  const double v3[3] = {sm[4] * sm[8] - sm[5] * sm[7], sm[5] * sm[6] - sm[3] * sm[8], sm[3] * sm[7] - sm[4] * sm[6]};
+  const double l1 = v1[0] * v1[0] + v1[1] * v1[1] + v1[2] * v1[2];
+  const double l2 = v2[0] * v2[0] + v2[1] * v2[1] + v2[2] * v2[2];
+  const double l3 = v3[0] * v3[0] + v3[1] * v3[1] + v3[2] * v3[2];
+  double vx, vy, vz, l;
+  if (l1 >= l2 && l1 >= l3) { vx = v1[0]; vy = v1[1]; vz = v1[2]; l = l1; }
+  else if (l2 >= l1 && l2 >= l3) { vx = v2[0]; vy = v2[1]; vz = v2[2]; l = l2; }
+  else { vx = v3[0]; vy = v3[1]; vz = v3[2]; l = l3; }
+  const double s = sqrt(l);
+  evec[0] = vx / s; evec[1] = vy / s; evec[2] = vz / s;
+}
+
 // computeMeanAndCovarianceMatrix, single pass in fp32: one neighbour P added to the nine running sums
 #define OPE_ACCUMULATE_NEIGHBOUR(P)                                       \
   accu[0] += P.x * P.x; accu[1] += P.x * P.y; accu[2] += P.x * P.z;       \
