@@ -17,7 +17,7 @@ namespace ope {
 void launch_icp_accumulate(hipStream_t, int, int, bool, bool, const CloudView &, const BvhView &, const BvhView &,
                            const IcpState *, double *, int32_t *, float *, uint32_t *, uint32_t *, const uint32_t *,
                            uint32_t *, const uint32_t *, bool, int, double *, const uint32_t *, float *, const uint32_t *, hipEvent_t, hipEvent_t, bool,
-                           uint32_t *, uint32_t, float4 *, uint32_t *, uint32_t *, uint32_t, uint32_t, float *);
+                           uint32_t *, uint32_t, float4 *, uint32_t *, uint32_t *, uint32_t, uint32_t, float *, uint32_t *, uint32_t);
 void plan_heavy(hipStream_t, const uint32_t *, uint32_t, float, float, uint32_t, uint32_t *);
 void plan_slots(hipStream_t, const uint32_t *, uint32_t, const uint32_t *, uint32_t *);
 int icp_accumulate_blocks_per_cu(bool, bool, bool);
@@ -62,7 +62,12 @@ static thread_local std::string g_global_err;
 
 constexpr double kGridMaxTreeShare = 0.03, kGridMinTreeShare = 0.015;
 constexpr size_t kGridMinQueries = 0;
-constexpr float kHeavyLoadFactor = 1.5f;   // launches that fill the GPU: group walks for chunks beyond this multiple of a wave's fair share (C3, slots listed by duration: 1.0 183 us, 1.2 166, 1.45 153, 1.7 157; without the list 1.45 was 174)
+// Launches that fill the GPU: group walks for chunks beyond this multiple of a wave's fair share.  Launches dealt from the slot
+// queue (icp_kernels.hip: deal_next; C3 kernel us, four runs each): 1.5 155-163, 1.2 144-152, 1.0 140-143, 0.8 156-159, 0.6 189-192.
+constexpr float kHeavyLoadFactor = 1.0f;
+// ... and under the static deal (certifying launches, the grid kernel's tree part), where handing over more chunks lengthens
+// the launch (C3, slots listed by duration: 1.0 183 us, 1.2 166, 1.45 153, 1.7 157; without the list 1.45 was 174)
+constexpr float kHeavyLoadFactorStatic = 1.5f;
 constexpr float kHeavyMaxChunksPerWave = 1.8f;   // beyond this the launch is throughput-bound: no 8-lane group walks
 
 int set_err(ope_ctx *ctx, int code, const std::string &msg) {
@@ -256,7 +261,7 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
       const bool repart = it_done <= 4 || it_done % kPlanPeriod == 0 || it_done == ctx->force_plan_at;
       if (grid_plan(ctx->stream, repart, ctx->d_qclass, (uint32_t)ctx->run_src->n_valid, ctx->d_qorder, ctx->d_work_counter + 8, cost_r,
                     ctx->d_chunk_keys, ctx->d_chunk_cost_sorted, ctx->d_chunk_ids, ctx->d_chunk_order, nch,
-                    (uint32_t)ctx->acc_blocks * (kAccBlock / 64), -1.0f /* no factor override */, kHeavyLoadFactor, ctx->d_part_tmp, ctx->part_tmp_bytes) != 0)
+                    (uint32_t)ctx->acc_blocks * (kAccBlock / 64), -1.0f /* no factor override */, kHeavyLoadFactorStatic, ctx->d_part_tmp, ctx->part_tmp_bytes) != 0)
         return set_err(ctx, OPE_EHIP, "grid plan step failed");
       ctx->plan_valid = true;
       if (it_done == 1 || it_done >= 8) {   // after launch 0 (decided before launch 2, see grid_probe_poll), then with the later plans
@@ -305,7 +310,9 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
     //   1.3 (500 k queries)       168 / 138 / 132 / 156   2.5 (C3)          177 / 261 / 232 / 254  <- none is best
     const float chunks_per_wave = (float)nch / (float)(ctx->n_cu * 4 * kAccWavesPerSimd);
     const float heavy_factor = chunks_per_wave > kHeavyMaxChunksPerWave ? 0.0f : std::min(7.0f, std::max(2.0f, 1.2f + 1.5f * chunks_per_wave));
-    const float load_factor = chunks_per_wave > kHeavyMaxChunksPerWave ? kHeavyLoadFactor : 0.0f;
+    // (the plan serves the launches from the next one on: certifying launches keep the static deal)
+    const bool static_deal = ctx->cert_run && ctx->cert_seen && ctx->run_params.corr_mode == OPE_CORR_NEAREST && !ctx->run_params.use_reciprocal;
+    const float load_factor = chunks_per_wave > kHeavyMaxChunksPerWave ? (static_deal ? kHeavyLoadFactorStatic : kHeavyLoadFactor) : 0.0f;
     // (a one-launch plan — costs bucketed at 16 per octave, counting sort, same rules on the buckets — took 2.5 us per
     // iteration off the driver's twenty-step window and put 5-9 us on its search kernel: the coarser order is the worse
     // schedule while the costs still move; a one-block rocprim::block_radix_sort of the 15 625 keys took 63 us on its single
@@ -352,7 +359,9 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
                         (ctx->plan_valid && ctx->plan_cur_slots) ? ctx->d_plan_slots[ctx->plan_cur] : nullptr,
                         p.corr_mode == OPE_CORR_NORMAL_SHOOTING ? ctx->d_knn_rk : nullptr, ctx->d_plan_out + 8 * ctx->plan_cur,
                         timed ? ctx->prof_events[2 * ctx->prof_used] : nullptr, timed ? ctx->prof_events[2 * ctx->prof_used + 1] : nullptr,
-                        ctx->measuring_flag, ctx->chain_on ? chain_ptr(ctx) : nullptr, ctx->chain_seq, certify ? ctx->d_cert_q : nullptr, ctx->d_cert_pos, ctx->d_pace, ++ctx->launch_no, ctx->wait_ticks, ctx->d_cert_l);
+                        ctx->measuring_flag, ctx->chain_on ? chain_ptr(ctx) : nullptr, ctx->chain_seq, certify ? ctx->d_cert_q : nullptr, ctx->d_cert_pos, ctx->d_pace, ++ctx->launch_no, ctx->wait_ticks, ctx->d_cert_l,
+                        ctx->d_deal, ctx->deal_parity);
+  ctx->deal_parity ^= 1u;   // this launch has cleared the other set of queue counters for the next one
   if (timed) ++ctx->prof_used;
   return OPE_OK;
 }
@@ -410,6 +419,7 @@ int ope_ctx_create(ope_ctx **out, int device_ordinal) {
   if (hipMalloc(&ctx->d_state, sizeof(IcpState)) != hipSuccess ||
       hipMalloc(&ctx->d_partials, sizeof(double) * kNumSumsMax * kAccMaxBlocks) != hipSuccess ||
       hipMalloc((void **)&ctx->d_work_counter, 256) != hipSuccess ||
+      hipMalloc((void **)&ctx->d_deal, kDealBytes) != hipSuccess || hipMemset(ctx->d_deal, 0, kDealBytes) != hipSuccess ||
       hipMalloc((void **)&ctx->d_lm_stats, sizeof(double) * 96) != hipSuccess ||
       hipMalloc((void **)&ctx->d_plan_out, 64) != hipSuccess || hipMemset(ctx->d_plan_out, 0, 64) != hipSuccess ||
       hipStreamCreateWithFlags(&ctx->plan_stream, hipStreamNonBlocking) != hipSuccess ||
@@ -457,6 +467,7 @@ void ope_ctx_destroy(ope_ctx *ctx) {
   if (ctx->d_state) (void)hipFree(ctx->d_state);
   if (ctx->d_partials) (void)hipFree(ctx->d_partials);
   if (ctx->d_work_counter) (void)hipFree(ctx->d_work_counter);
+  if (ctx->d_deal) (void)hipFree(ctx->d_deal);
   if (ctx->d_lm_stats) (void)hipFree(ctx->d_lm_stats);
   if (ctx->d_fixed) (void)hipFree(ctx->d_fixed);
   tmp_release_stream(ctx->stream);   // the cached temporaries of this context's stream
@@ -1278,6 +1289,9 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
   if (ctx->d_sums_ext)
     OPE_HIP(ctx, hipMemsetAsync(ctx->d_sums_ext, 0, sizeof(double) * (p.estimator == OPE_EST_POINT_TO_PLANE_LLS ? kNumSumsMax : kNumSums), ctx->stream));
   OPE_HIP(ctx, hipMemsetAsync(ctx->d_work_counter, 0, 256, ctx->stream));
+  // the slot queue's counters: both sets, once per run (the launches keep them clear from here on, icp_kernels.hip: deal_next)
+  OPE_HIP(ctx, hipMemsetAsync(ctx->d_deal, 0, kDealBytes, ctx->stream));
+  ctx->deal_parity = 0;
   OPE_HIP(ctx, hipMemsetAsync(ctx->d_lm_stats, 0, sizeof(double) * 96, ctx->stream));
   ctx->measuring_flag = false;
   // partial-sum rows of blocks that do not exist in this run must read as zero

@@ -75,6 +75,39 @@ __device__ __forceinline__ void acc_launch_end(uint32_t *chain) {
   if (threadIdx.x == 0) __hip_atomic_fetch_add(chain, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- the slot queue of the tree accumulate kernel: which wave takes which slot of a planned launch, and when.
+// The plan lists the launch's slots in descending order of expected duration.  Wave w takes entry w (no atomic); every later
+// entry is popped from one of n_stripes counters, stripe c serving the entries n_waves + c + k n_stripes, k = 0, 1, ... — each
+// stripe is itself descending, so whatever the durations turn out to be, the longest slots start first and a wave that drew a
+// long one simply comes back late, to an empty queue (longest-first list scheduling within the stripe's waves: they end within
+// one of the cheapest slots of max(longest slot, their fair share)).  Wave w pops from stripe w % n_stripes only and leaves
+// when a pop comes back past the end of the list: every stripe has waves of its own (n_stripes <= n_waves), so no entry is
+// left behind, and nobody waits for anybody.  (Moving on to the next stripes for up to four failed pops — stealing — was
+// measured: C3 launches of 142-145 us against 140-143 without; the stripes are interleaved samples of one sorted list and run
+// dry within a slot of each other, and the failed pops are round trips at the very end of the launch.)
+// Why stripes: all waves popping from ONE word was tried first — 24 k returning atomics on one address took 130 us of a
+// 150 us launch (atomics execute at the memory side, one after the other per address).  Spread over 64 lines of 128 bytes the
+// same pops are 64 queues of a few hundred, served in parallel, each pop issued a whole chunk (20-140 us) before its value
+// is needed.
+// The counters come in two sets: a launch pops from set `parity` and clears the other for the launch after it (launches of
+// this kernel follow each other on one stream; ope_icp_begin clears both).  The clearing happens before anything can end the
+// launch early, so a launch that finds nothing to do leaves the sets as consistent as one that ran.
+__device__ __forceinline__ uint32_t deal_pop(uint32_t *counters, uint32_t stripe, uint32_t lane_id) {
+  uint32_t k = 0u;
+  if (lane_id == 0u) k = __hip_atomic_fetch_add(counters + stripe * kDealLineWords, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return k;   // lane 0 holds the ticket
+}
+constexpr uint32_t kDealNone = 0xffffffffu;
+// k: the ticket popped from `stripe` while the last slot was walked.  Returns the next entry of the list, or kDealNone.
+__device__ __forceinline__ uint32_t deal_next(uint32_t k, uint32_t stripe, uint32_t n_stripes, uint32_t n_waves, uint32_t n_slots) {
+  const uint32_t slot = n_waves + stripe + k * n_stripes;   // (k <= pops of one launch: far from 2^32 / n_stripes)
+  return slot < n_slots ? slot : kDealNone;
+}
+__device__ __forceinline__ void deal_clear_other_set(uint32_t *deal, uint32_t parity) {
+  if (blockIdx.x == 0 && threadIdx.x < kDealStripes)
+    __hip_atomic_store(deal + (size_t)(parity ^ 1u) * kDealStripes * kDealLineWords + threadIdx.x * kDealLineWords, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // One query's contribution to the wave's running sums {n, Σs, Σt, Σ t sᵀ, Σd²} (+ 27 normal-equation sums with the
 // point-to-plane estimator): 16-lane row sums by DPP, then one ds_add_f64 per row and component into `acc` (LDS).
 // t: the matched target point, tn: its normal (point-to-plane only); lanes with ok == false contribute zeros.
@@ -234,7 +267,9 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
     uint32_t *__restrict__ hint, const uint32_t *__restrict__ chunk_order, uint32_t *__restrict__ chunk_cost,
     const uint32_t *__restrict__ plan_info, double *__restrict__ S_atomic, const uint32_t *__restrict__ slot_list,
     float *__restrict__ knn_rk, const uint32_t *__restrict__ plan_out, uint32_t measuring_launch, uint32_t *chain_arg, uint32_t chain_seq,
-    float4 *__restrict__ cert_q, uint32_t *__restrict__ cert_pos, uint32_t *pace, uint32_t launch_no, uint32_t wait_ticks, float *__restrict__ cert_l) {
+    float4 *__restrict__ cert_q, uint32_t *__restrict__ cert_pos, uint32_t *pace, uint32_t launch_no, uint32_t wait_ticks, float *__restrict__ cert_l,
+    uint32_t *deal, uint32_t deal_parity) {
+  deal_clear_other_set(deal, deal_parity);   // (before anything can end the launch: see deal_next)
   // pace (host-visible): "launch launch_no has started", i.e. every launch before it is over — the host keeps a bounded lead
   // over the GPU by it (api.hip: pace_wait), which is what lets it notice, a few launches late at most, that the update step
   // has asked for certifying launches (IcpState::cert_mode -> host_cert)
@@ -297,58 +332,71 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
   const bool p2p = NRM && st->estimator == OPE_EST_POINT_TO_PLANE_LLS;
 
   const uint32_t lane_id = threadIdx.x & 63u;
-  // Static, cost-aware work distribution.  Query cost is very uneven (a clutter point far from the model
-  // walks 10-40x more nodes than a surface point) and the kernel ends with its slowest wave, so the
-  // 64-query chunks of the Morton order are dealt to the waves in "snake" order over a list sorted by
-  // the cost each chunk measured in an earlier iteration (heaviest chunks first, each wave's later
-  // chunks progressively lighter): longest-processing-time-first scheduling with no atomics.  (A
-  // device-wide ticket counter was tried first: ~24 k returning atomics on one word cost 130 us.)
-  // The n_heavy costliest chunks (clutter: long private walks) are split into eight slots each and walked
-  // by 8-lane groups (bvh_traverse_oct); all other chunks take one slot and one lane per query.
+  // Cost-aware work distribution.  Query cost is very uneven (a clutter point far from the model walks 10-40x more nodes
+  // than a surface point) and the kernel ends with its slowest wave.  The 64-query chunks of the Morton order are therefore
+  // taken longest first, from a list sorted by the cost each chunk measured in an earlier launch (the plan steps, api.hip).
+  // The n_heavy costliest chunks (clutter: long private walks) are split into eight slots each and walked by 8-lane groups
+  // (bvh_traverse_oct); all other chunks take one slot and one lane per query.
+  // Who takes which entry of that list:
+  //  - planned launches of every instantiation but the certifying one: from the striped device queue above (deal_next).
+  //    Durations move with the pose and with what shares the SIMD (a far chunk is 115 us alone, 146 us under load): a wave
+  //    that drew a long slot simply comes back late, to an empty queue.
+  //  - the certifying instantiation, and launches without a plan (first launches of a run, deterministic_sums, large
+  //    normal-shooting launches): a static deal with no atomics.  The plan's costliest per-lane chunks, which each outlast
+  //    the share of work a wave has in a balanced launch (plan_out[5] of them; with the merged list its first plan_out[7]
+  //    entries), get a wave to themselves; everything else goes to the other waves in "snake" order (heaviest first, each
+  //    wave's later slots progressively lighter).  A certified chunk is over in a microsecond or two, less than the round
+  //    trip of the pop that would fetch its successor (vector memory returns in order: the walk's loads queue up behind the
+  //    pop), and 4 chunks per wave of them made the settled launches 43-46 us where the static deal has 40-42.  Under
+  //    deterministic_sums the natural chunk order is part of what the mode promises.
   const uint32_t n_waves = gridDim.x * (BLOCK / 64);
-  const uint32_t wave_id = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+  const uint32_t wave_id = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)));
   const uint32_t n_chunks = (src.n_valid + 63u) / 64u;
   // measuring_launch (a kernel argument: the host knows it when it launches): the launch before a plan step — every chunk takes the per-lane walk, so that the
   // costs the plan sorts are all of one kind and none is older than one launch
   const bool measuring = chunk_order && measuring_launch != 0u;
   // plan_out: what the plan step computed for this chunk order ([0] chunks walked by groups, [5] / [7] chunks with a wave to
-  // themselves); plan_info: the launch's flags
+  // themselves in the static deal); plan_info: the launch's flags
   const uint32_t n_heavy = (OCT_OK && chunk_order && !measuring) ? min(plan_out[0], n_chunks) : 0u;
-  // The plan's costliest per-lane chunks each outlast the share of work a wave has in a balanced launch (plan_info[5] of
-  // them, ranks n_heavy .. n_heavy + n_alone - 1): each gets a wave to itself (waves 0 .. n_alone - 1) and that wave
-  // takes nothing else; all other slots are dealt to the remaining waves in snake order.
   // With group walks in the plan the slots come as a list in descending order of expected duration (plan_slots_kernel:
-  // the eight slots of a group-walked chunk merged in among the per-lane chunks they are as long as), its first
-  // plan_info[7] entries being the ones that get a wave to themselves.
+  // the eight slots of a group-walked chunk merged in among the per-lane chunks they are as long as); without, the list
+  // is the group-walked chunks' slots followed by the other chunks in the plan's order.
   const bool listed = OCT_OK && slot_list != nullptr && chunk_order != nullptr && !measuring && n_heavy > 0u;
-  const uint32_t n_alone = !chunk_order ? 0u
-                           : listed   ? min(plan_out[7], n_waves / 2u)
-                                      : min(min(plan_out[5] + (measuring ? min(plan_out[0], n_chunks) : 0u), n_chunks - n_heavy), n_waves / 2u);
-  const uint32_t n_snake = listed ? (n_chunks + 7u * n_heavy - n_alone) : (8u * n_heavy + (n_chunks - n_heavy - n_alone));
-  const uint32_t snake_waves = n_waves - n_alone;
-  for (uint32_t round = 0;; ++round) {
-    bool oct = false;
-    uint32_t ord, sub = 0;
-    uint32_t slot;
-    if (wave_id < n_alone) {
-      if (round > 0) break;
-      slot = wave_id;
-      ord = n_heavy + wave_id;
-    } else {
-      if (round * snake_waves >= n_snake) break;
-      const uint32_t w = wave_id - n_alone;
-      slot = round * snake_waves + ((round & 1u) ? (snake_waves - 1u - w) : w);
-      if (slot >= n_snake) continue;
-      oct = slot < 8u * n_heavy;
-      ord = oct ? (slot >> 3) : (n_heavy + n_alone + (slot - 8u * n_heavy));
-      sub = slot & 7u;
-      slot += n_alone;
-    }
+  const uint32_t n_slots = n_chunks + 7u * n_heavy;
+  const bool dealt = chunk_order != nullptr && !CERT;
+  uint32_t *const deal_set = deal + (size_t)deal_parity * kDealStripes * kDealLineWords;
+  const uint32_t n_stripes = min(kDealStripes, n_waves);
+  const uint32_t stripe = wave_id % n_stripes;
+  // the static deal: entry of the list that this wave takes in round r (the queue's first entry is its round 0: wave w, entry w)
+  const uint32_t n_alone = (dealt || !chunk_order) ? 0u
+                           : listed             ? min(plan_out[7], n_waves / 2u)
+                                                : min(min(plan_out[5] + (measuring ? min(plan_out[0], n_chunks) : 0u), n_chunks - n_heavy), n_waves / 2u);
+  const uint32_t n_snake = n_slots - n_alone, snake_waves = n_waves - n_alone;
+  auto static_slot = [&](uint32_t r) -> uint32_t {
+    if (wave_id < n_alone) return r == 0u ? (listed ? wave_id : 8u * n_heavy + wave_id) : kDealNone;
+    const uint32_t w = wave_id - n_alone;
+    const uint32_t sn = r * snake_waves + ((r & 1u) ? (snake_waves - 1u - w) : w);
+    if (sn >= n_snake) return kDealNone;   // (only a launch's last round is short: nothing follows it)
+    return (listed || sn >= 8u * n_heavy) ? sn + n_alone : sn;
+  };
+  uint32_t round = 0u;
+  uint32_t slot = static_slot(0u);
+  while (slot != kDealNone) {
+    // the ticket for the NEXT slot goes out behind this chunk's first loads (source point, start leaf) and is looked at when the
+    // chunk is done: its round trip hides behind the walk.  (Vector memory returns in order: issued in front of those loads it
+    // would hold them up by the difference between an atomic's round trip and a load's.)
+    uint32_t ticket_v = 0u;
+    bool oct;
+    uint32_t ord, sub;
     if (listed) {
       const uint32_t e = slot_list[slot];
       oct = (e >> 31) != 0u;
       sub = (e >> 28) & 7u;
       ord = e & 0x0fffffffu;
+    } else {
+      oct = slot < 8u * n_heavy;
+      ord = oct ? (slot >> 3) : (n_heavy + (slot - 8u * n_heavy));
+      sub = slot & 7u;
     }
     const uint32_t chunk = chunk_order ? chunk_order[ord] : ord;
     const uint32_t base = chunk * 64u;
@@ -394,6 +442,7 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
       // (in a slot walked by 8-lane groups the eight lanes of a group carry the same query: one of them builds)
       const bool build = need && !stuck && owner && cert_worth_building(corr_d2[i], cst[18], cst[19], cst[17]);
       const uint32_t h = need ? hint[i] : 0u;   // start leaf of the walks (queries answered from their certificate need none)
+      if (dealt) ticket_v = deal_pop(deal_set, stripe, lane_id);
       const bool fast = need && !build && !(oct && __shfl((int)build, (int)(lane_id & ~7u), 64) != 0);   // (a group whose query builds does not walk as well)
       NearestVisitor v{fast ? best_init : -INFINITY, kNoPos, 0};
       const unsigned long long fmask = __ballot(fast);
@@ -440,6 +489,7 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
       NearestVisitor v{active ? cst[15] : -INFINITY, kNoPos, 0};
       // start at the leaf that held this query's nearest neighbour one iteration ago (0 = none yet)
       const uint32_t h = active ? hint[i] : 0u;
+      if (dealt) ticket_v = deal_pop(deal_set, stripe, lane_id);
       if (OCT_OK && oct) {
         if (active) bvh_traverse_oct(tgt, x, y, z, v, &s_stk[0][threadIdx.x & ~7u], BLOCK, h);
       } else {
@@ -488,6 +538,7 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
         }
       }
       const uint32_t h0 = active ? hint[i] : 0u;
+      if (dealt) ticket_v = deal_pop(deal_set, stripe, lane_id);
       bool todo = active;
       for (;;) {
         if (todo) {
@@ -525,6 +576,7 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
       ok = active && v.count > 0 && !(min_dist > max_dist_unsq);
       match = v.count > 0 ? (store_pos ? (int)pos : __float_as_int(tgt.pts[pos].w)) : -1;
     } else {
+      if (dealt) ticket_v = deal_pop(deal_set, stripe, lane_id);
       float *ld = reinterpret_cast<float *>(s_dyn) + threadIdx.x;
       uint32_t *lp = reinterpret_cast<uint32_t *>(s_dyn + sizeof(float) * BLOCK * kKnnMaxK) + threadIdx.x;
       KnnVisitor v{ld, lp, BLOCK, kk, 0, active ? INFINITY : -INFINITY};
@@ -566,6 +618,11 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
     add_query_sums<NRM>(s_red[threadIdx.x >> 6], (lds_cfloat_ptr)s_const, lane_id, ok, p2p, x, y, z, tgt.pts[ok ? pos : 0],
                         (NRM && p2p) ? tgt.nrm[ok ? pos : 0] : make_float4(0.f, 0.f, 0.f, 0.f), d2);
     if (lane_id == 0 && !oct) chunk_cost[chunk] = (uint32_t)((__builtin_amdgcn_s_memtime() - t_begin) >> 4);
+    if (dealt) {
+      slot = deal_next((uint32_t)__builtin_amdgcn_readfirstlane((int)ticket_v), stripe, n_stripes, n_waves, n_slots);
+    } else {
+      slot = static_slot(++round);
+    }
   }
 
   // wave slots -> block partial, fixed order
@@ -1340,7 +1397,7 @@ void launch_icp_accumulate(hipStream_t stream, int nblocks, int mode, bool nrm, 
                            const uint32_t *chunk_order, uint32_t *chunk_cost, const uint32_t *plan_info, bool packet,
                            int k_normal_shooting, double *S_atomic, const uint32_t *slot_list, float *knn_rk, const uint32_t *plan_out,
                            hipEvent_t e0, hipEvent_t e1, bool measuring, uint32_t *chain, uint32_t chain_seq, float4 *cert_q, uint32_t *cert_pos,
-                           uint32_t *pace, uint32_t launch_no, uint32_t wait_ticks, float *cert_l) {
+                           uint32_t *pace, uint32_t launch_no, uint32_t wait_ticks, float *cert_l, uint32_t *deal, uint32_t deal_parity) {
   const uint32_t mflag = measuring ? 1u : 0u;
   // e0 / e1 (ope_icp_profile): the launch's own start and stop time stamps, taken by the dispatch itself (hipExtLaunchKernelGGL).
   // Round 3 measured what a hipEventRecord before and after every launch costs the loop it times: 7-11 us per iteration (two
@@ -1349,10 +1406,10 @@ void launch_icp_accumulate(hipStream_t stream, int nblocks, int mode, bool nrm, 
   do {                                                                                                                        \
     if (e0 != nullptr)                                                                                                        \
       hipExtLaunchKernelGGL(KERNEL, dim3(nblocks), dim3(BLK), LDS, stream, e0, e1, 0, src, tgt, srcix, st, partials, corr_match, \
-                            corr_d2, work_counter, hint, chunk_order, chunk_cost, plan_info, S_atomic, slot_list, knn_rk, plan_out, mflag, chain, chain_seq, cert_q, cert_pos, pace, launch_no, wait_ticks, cert_l); \
+                            corr_d2, work_counter, hint, chunk_order, chunk_cost, plan_info, S_atomic, slot_list, knn_rk, plan_out, mflag, chain, chain_seq, cert_q, cert_pos, pace, launch_no, wait_ticks, cert_l, deal, deal_parity); \
     else                                                                                                                      \
       hipLaunchKernelGGL(KERNEL, dim3(nblocks), dim3(BLK), LDS, stream, src, tgt, srcix, st, partials, corr_match, corr_d2,   \
-                         work_counter, hint, chunk_order, chunk_cost, plan_info, S_atomic, slot_list, knn_rk, plan_out, mflag, chain, chain_seq, cert_q, cert_pos, pace, launch_no, wait_ticks, cert_l); \
+                         work_counter, hint, chunk_order, chunk_cost, plan_info, S_atomic, slot_list, knn_rk, plan_out, mflag, chain, chain_seq, cert_q, cert_pos, pace, launch_no, wait_ticks, cert_l, deal, deal_parity); \
   } while (0)
 #define OPE_LAUNCH_ACC(M, N, R, BLK, LDS) OPE_KLAUNCH((icp_accumulate_kernel<M, N, R>), BLK, LDS)
   const bool certify = cert_q != nullptr && mode == 0 && !recip;   // the certifying instantiation (api.hip decides when)

@@ -125,6 +125,11 @@ constexpr int kAccBlock = 512;       // threads per block of the accumulate kern
 // only 768 of the 1024 blocks are resident at a time (C3: 230 -> 197 us, C2: 78 -> 68 us).
 constexpr int kAccWavesPerSimd = 6;
 constexpr int kAccMaxBlocks = 1024;  // partials rows; the update kernel reduces them with 1024 threads
+// The slot queue of the tree accumulate kernel (icp_kernels.hip: deal_next): kDealStripes counters, each on a 128-byte line
+// of its own, two sets (a launch uses one and clears the other for the launch after it).
+constexpr uint32_t kDealStripes = 64;
+constexpr uint32_t kDealLineWords = 32;
+constexpr size_t kDealBytes = sizeof(uint32_t) * 2 * kDealStripes * kDealLineWords;
 
 }  // namespace ope
 
@@ -160,6 +165,8 @@ struct ope_ctx {
   uint32_t *d_chunk_cost = nullptr, *d_chunk_cost_sorted = nullptr, *d_chunk_ids = nullptr, *d_chunk_order = nullptr;
   uint32_t *d_slot_list = nullptr;   // the launch's slots in descending order of expected duration (plan_slots_kernel)
   bool slot_list_valid = false;
+  uint32_t *d_deal = nullptr;        // the slot queue's counters (kDealBytes), cleared by ope_icp_begin
+  uint32_t deal_parity = 0;          // the set the next tree launch pops from
   void *d_plan_tmp = nullptr;
   size_t plan_tmp_bytes = 0, chunk_cap = 0;
   bool plan_valid = false;
