@@ -897,7 +897,7 @@ int ope_depth_last_stats(const ope_ctx *ctx, ope_depth_stats *out);
  * becomes n - c[order + 1] u - c[1] v (neither normalised nor oriented); otherwise the projection and n stand.
  * Two deviations from PCL: non-finite input points are dropped and are nobody's neighbour (PCL's behaviour on them is undefined);
  * a Cholesky pivot that is <= 0 or not finite makes the fit fail like a non-finite c[0] (Eigen goes on with garbage).
- * radius > 0; order 0, 1 or 2 (3 and 4 belong to MLS upsampling, which is not built): anything else OPE_EINVAL, nothing launched.
+ * radius > 0; order 0, 1 or 2 (3 and 4 belong to MLS upsampling: ope_mls_upsample below): anything else OPE_EINVAL, nothing launched.
  * sqr_gauss_param 0 means radius * radius, as setSearchRadius sets it. */
 typedef struct {
   double radius;
@@ -924,6 +924,62 @@ typedef struct {
   int64_t n_in, n_out, n_plane_only, n_dropped, neighbours_total;
 } ope_mls_stats;
 int ope_mls_last_stats(const ope_ctx *ctx, ope_mls_stats *out);
+
+/* ---------------- moving least squares, upsampled (RegMeshPcd::generateMesh) ---------------- */
+/* pcl::MovingLeastSquares::process with upsampling VOXEL_GRID_DILATION (BuildModel/src/regmeshpcd.cpp:275-292: order 4, radius 0.03,
+ * voxel 0.002; PCL 1.7.x surface/impl/mls.hpp), DESIGN.md 4.15.  Nothing is produced per input point in this mode; instead:
+ *  a. every finite input point with 3 or more neighbours (as for ope_mls_smooth) keeps its MLSResult: the query projected on its
+ *     plane (mean), the plane's normal n, the axes v = unitOrthogonal(n) and u = n x v when polynomial_fit is set and it has at least
+ *     nr_coeff = (order + 1)(order + 2) / 2 neighbours (both zero otherwise, as 1.7 leaves them), the Cholesky solution c, the
+ *     neighbour count m and the curvature.  Points with fewer than 3 neighbours are invalid.
+ *  b. MLSVoxelGrid: bmin / bmax the float box of the finite points; data_size = uint64(1.5 * max extent / voxel_size); per finite point
+ *     cell = int((p - bmin) / voxel_size) in float; key = (cell0 * data_size + cell1) * data_size + cell2; the grid is the set of distinct
+ *     keys in ascending order.  Each of dilation_iterations rounds replaces the set by the union of the 27 neighbours (itself
+ *     included) of every voxel.  data_size 0 (all points within 2/3 of a voxel) decodes every key to cell (0, 0, 0).
+ *  c. per voxel in key order: position = float(cell) * voxel_size + bmin (multiply, then add, in float); j = the nearest finite input
+ *     point in fp32 ((dx*dx + dy*dy) + dz*dz); the voxel is skipped when j is invalid; u_disp, v_disp = the float dot products of
+ *     (position - q_j) with j's axes cast to float; projectPointToMLSSurface: result = mean + u u_disp + v v_disp + n n_disp in
+ *     double, cast to float, where n_disp is the polynomial of order `order` in (u_disp, v_disp) when polynomial_fit is set, j has at
+ *     least 5 nr_coeff neighbours, the fit did not fail and c[0] is finite, and 0 otherwise; with compute_normals the normal is
+ *     n - d_u u - d_v v normalised (d_u, d_v the polynomial's partial derivatives there), otherwise j's plane normal; the curvature
+ *     is j's.  The voxel is skipped when the result lies farther from q_j than the voxel's position did (both distances in float).
+ *     Survivors come out in key order; out_idx is j (getCorrespondingIndices), and the colour word is that of point j.
+ * Three deviations from PCL: non-finite input points are dropped, are nobody's neighbour and nobody's nearest point; a Cholesky
+ * pivot that is <= 0 or not finite makes the fit count as failed (Eigen goes on with garbage); a dilation neighbour with a cell
+ * component outside [0, data_size) is dropped (PCL lets the unsigned key wrap).  Equal fp32 distances of the nearest search go to the
+ * lowest original index (FLANN's choice there is implementation-defined).
+ * radius > 0; order 0..4; voxel_size > 0 and finite; dilation_iterations 0..8; data_size <= 2^21: anything else OPE_EINVAL, nothing
+ * launched.  sqr_gauss_param 0 means radius * radius.  The sequence of launches and host waits depends on the parameters only. */
+typedef struct {
+  double radius;
+  int polynomial_fit;        /* 1 */
+  int order;                 /* 2 (generateMesh: 4) */
+  double sqr_gauss_param;    /* 0 */
+  int compute_normals;       /* 0 */
+  float voxel_size;          /* 1.0 (generateMesh: 0.002) */
+  int dilation_iterations;   /* 0 */
+} ope_mls_upsample_params;
+void ope_mls_upsample_default_params(ope_mls_upsample_params *p);
+/* Host outputs, each with room for `capacity` points; any may be NULL except n_out.  out_normals (x y z) and out_curvature as above.
+ * The size of the result is not known beforehand: when it exceeds `capacity` (and an output array was given) nothing is copied,
+ * the call returns OPE_EINVAL and *n_out is set to the size the arrays need, so that a second call with that capacity succeeds
+ * (all arrays NULL and capacity 0 only count: OPE_OK).  An empty cloud gives OPE_OK and *n_out = 0. */
+int ope_mls_upsample(ope_ctx *ctx, const ope_cloud *cloud, const ope_mls_upsample_params *params, float *out_xyz, float *out_normals,
+                     float *out_curvature, int32_t *out_idx, size_t capacity, size_t *n_out);
+/* The same with the result left on the device: *out is a new cloud of the upsampled points, Morton-ordered like an upload (its
+ * ORIGINAL order is the key order), with the colour word of point j for every output and, when compute_normals is set, the normals
+ * attached (w = curvature).  out_idx (optional, room for `capacity`) is in key order; too small a capacity: as above. */
+int ope_mls_upsample_cloud(ope_ctx *ctx, const ope_cloud *cloud, const ope_mls_upsample_params *params, ope_cloud **out, int32_t *out_idx,
+                           size_t capacity, size_t *n_out);
+/* What the last ope_mls_upsample / ope_mls_upsample_cloud of this context did.  n_valid: input points with an MLSResult; n_voxels:
+ * the grid after the dilation; n_invalid_nearest: voxels skipped because their nearest point is invalid; n_polynomial: voxels (with
+ * a valid nearest point) whose projection applied the polynomial; n_rejected_farther: voxels dropped by the keep rule; n_out =
+ * n_voxels - n_invalid_nearest - n_rejected_farther.  launches and host_syncs are BOOKED along the call's fixed path, as for
+ * ope_depth_last_stats (the temporary index build counts as one launch, a rocPRIM call as one). */
+typedef struct {
+  int64_t n_in, n_valid, n_voxels, n_invalid_nearest, n_polynomial, n_rejected_farther, n_out, data_size, launches, host_syncs;
+} ope_mls_upsample_stats;
+int ope_mls_upsample_last_stats(const ope_ctx *ctx, ope_mls_upsample_stats *out);
 
 #ifdef __cplusplus
 }

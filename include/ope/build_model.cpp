@@ -12,6 +12,10 @@
 // download, the line the reference keeps at regmeshpcd.cpp:264-266.  Without --scan the model is a host cloud: --smooth is a usage
 // error there (status 2).
 //
+// `--mesh-cloud OUT.pcd` anywhere on either line (opt-in) also runs the head of generateMesh on the aligned cloud, as main.cpp:227-235
+// does after saving it (copyPointCloud to PointXYZ, then regmeshpcd.cpp:275-303: MLS upsampling, normals k = 20), and writes the cloud
+// the triangulation would get, `FIELDS x y z rgb normal_x normal_y normal_z curvature`, to OUT.pcd.
+//
 // Depth images are 16-bit binary PGM, colour images 8-bit binary PPM (depth_io.hpp).  A frame without a supporting plane or
 // without a cluster ends the program with a message and status 5 (the reference's cloudClusterVector.at(0) throws).
 // Prints one `pair <k> iterations <n> converged <0|1> fitness <f> T <16 floats, column-major>` line per registration.
@@ -35,7 +39,8 @@ static int usage(const char *prog) {
                "usage: %s <out.pcd> <corrRejThresh> <maxIter> <frame0.pcd> <frame1.pcd> [...]\n"
                "       %s --scan <kinect|astra|euclid> --limits x0 x1 y0 y1 z0 z1 <out.pcd> <corrRejThresh> <maxIter> <depth0.pgm> <rgb0.ppm> "
                "[<depth1.pgm> <rgb1.ppm> ...]\n"
-               "       --smooth R anywhere on a --scan line: smooth the finished model (moving least squares, radius R) before it is written\n",
+               "       --smooth R anywhere on a --scan line: smooth the finished model (moving least squares, radius R) before it is written\n"
+               "       --mesh-cloud OUT.pcd anywhere: also write the upsampled cloud with normals that generateMesh hands to the triangulation\n",
                prog, prog);
   return 2;
 }
@@ -49,8 +54,20 @@ static void print_pairs(const ope::RegMeshPcd &reg) {
   }
 }
 
+// main.cpp:227-235 up to the triangulation: the aligned cloud as PointXYZ, generateMesh's upsampling and normals, saved to `path`
+template <class CloudT> static int write_mesh_cloud(ope::RegMeshPcd &reg, const CloudT &aligned, const std::string &path) {
+  if (path.empty()) return 0;
+  pcl::PointCloud<pcl::PointXYZ>::Ptr cloudAlignedXYZ(new pcl::PointCloud<pcl::PointXYZ>);
+  pcl::copyPointCloud(aligned, *cloudAlignedXYZ);                               // :232
+  auto cloudWithNormals = reg.generateMeshCloud(cloudAlignedXYZ);               // :233 -> regmeshpcd.cpp:275-303
+  if (cloudWithNormals->empty()) return 6;
+  if (pcl::io::savePCDFile(path, *cloudWithNormals, true) != 0) return 4;
+  std::printf("Saved %zu upsampled points with normals to %s.\n", cloudWithNormals->size(), path.c_str());
+  return 0;
+}
+
 // build_model --scan: argv[2] the sensor, argv[3] "--limits", argv[4..9] the box, argv[10..12] out / thresh / iterations, then the pairs
-static int scan_main(int argc, char **argv, float smooth) {
+static int scan_main(int argc, char **argv, float smooth, const std::string &mesh_cloud) {
   if (argc < 15 || (argc - 13) % 2 != 0 || std::strcmp(argv[3], "--limits") != 0) return usage(argv[0]);
   const std::string sensor = argv[2];
   if (sensor != "kinect" && sensor != "astra" && sensor != "euclid") return usage(argv[0]);
@@ -89,10 +106,19 @@ static int scan_main(int argc, char **argv, float smooth) {
   print_pairs(regMeshPcd);
   if (pcl::io::savePCDFile(out_path, *cloudAligned, true) != 0) return 4;   // :221
   std::printf("Saved %zu data points to %s.\n", cloudAligned->size(), out_path.c_str());
-  return 0;
+  return write_mesh_cloud(regMeshPcd, *cloudAligned, mesh_cloud);
 }
 
 int main(int argc, char **argv) {
+  std::string mesh_cloud;   // --mesh-cloud OUT.pcd, taken out of the line
+  for (int i = 1; i < argc; ++i)
+    if (std::strcmp(argv[i], "--mesh-cloud") == 0) {
+      if (i + 1 >= argc || !argv[i + 1][0]) return usage(argv[0]);
+      mesh_cloud = argv[i + 1];
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2;
+      break;
+    }
   float smooth = 0.f;   // --smooth R, taken out of the line
   for (int i = 1; i < argc; ++i)
     if (std::strcmp(argv[i], "--smooth") == 0) {
@@ -104,7 +130,7 @@ int main(int argc, char **argv) {
       argc -= 2;
       break;
     }
-  if (argc > 1 && std::strcmp(argv[1], "--scan") == 0) return scan_main(argc, argv, smooth);
+  if (argc > 1 && std::strcmp(argv[1], "--scan") == 0) return scan_main(argc, argv, smooth, mesh_cloud);
   if (smooth > 0.f) return usage(argv[0]);
   if (argc < 6) return usage(argv[0]);
   const std::string out_path = argv[1];
@@ -122,5 +148,5 @@ int main(int argc, char **argv) {
   print_pairs(regMeshPcd);
   if (pcl::io::savePCDFile(out_path, *cloudAligned, true) != 0) return 4;   // main.cpp:221
   std::printf("Saved %zu data points to %s.\n", cloudAligned->size(), out_path.c_str());
-  return 0;
+  return write_mesh_cloud(regMeshPcd, *cloudAligned, mesh_cloud);
 }

@@ -772,12 +772,14 @@ struct PointIndices {
   std::vector<int> indices;
 };
 
-// pcl::MovingLeastSquares with upsampling NONE (ProcessingPcd::getSmooth, BuildModel/src/processingpcd.cpp:80-108): ope_mls_smooth.
-// The output point takes the smoothed xyz; its normal and curvature fields (if OutT has them) are written only when
+// pcl::MovingLeastSquares.  Upsampling NONE (ProcessingPcd::getSmooth, BuildModel/src/processingpcd.cpp:80-108): ope_mls_smooth,
+// orders 0 to 2.  Upsampling VOXEL_GRID_DILATION (RegMeshPcd::generateMesh, regmeshpcd.cpp:275-292): ope_mls_upsample, orders 0 to 4.
+// The output point takes the new xyz; its normal and curvature fields (if OutT has them) are written only when
 // setComputeNormals(true), as in PCL; every other field OutT shares with InT (here: rgb) is copied from the input point
-// (copyMissingFields).  getCorrespondingIndices: the input index of each output point.
+// (copyMissingFields).  getCorrespondingIndices: the input index of each output point (when upsampling, the nearest input point).
 template <class InT, class OutT> class MovingLeastSquares {
  public:
+  enum UpsamplingMethod { NONE, VOXEL_GRID_DILATION };
   MovingLeastSquares() { ope_mls_default_params(&p_); }
   void setInputCloud(const typename PointCloud<InT>::ConstPtr &c) { input_ = c; }
   void setComputeNormals(bool on) { p_.compute_normals = on ? 1 : 0; }
@@ -786,6 +788,9 @@ template <class InT, class OutT> class MovingLeastSquares {
   template <class Tree> void setSearchMethod(const Tree &) {}   // accepted, unused: the device walks its own tree
   void setSearchRadius(double r) { p_.radius = r; p_.sqr_gauss_param = r * r; }
   void setSqrGaussParam(double g) { p_.sqr_gauss_param = g; }
+  void setUpsamplingMethod(UpsamplingMethod m) { method_ = m; }
+  void setDilationVoxelSize(float v) { voxel_size_ = v; }
+  void setDilationIterations(int n) { dilation_iterations_ = n; }
   PointIndices::Ptr getCorrespondingIndices() const { return corresponding_; }
   void process(PointCloud<OutT> &out) {
     PointCloud<OutT> tmp;
@@ -793,11 +798,26 @@ template <class InT, class OutT> class MovingLeastSquares {
     ope_ctx *ctx = default_context();
     if (ctx && input_ && !input_->empty()) {
       auto dev = upload(*input_, false);
-      const size_t cap = input_->size();
+      size_t cap = method_ == NONE ? input_->size() : std::max<size_t>(8 * input_->size(), (size_t)1 << 16);   // upsampling: a guess, the call says what it needs
       std::vector<float> xyz(3 * cap), nrm(3 * cap), curv(cap);
       std::vector<int32_t> idx(cap);
       size_t n = 0;
-      if (dev->h && ope_mls_smooth(ctx, dev->h, &p_, xyz.data(), nrm.data(), curv.data(), idx.data(), &n) != OPE_OK) { log_error("MovingLeastSquares", ctx); n = 0; }
+      int rc = OPE_OK;
+      if (dev->h && method_ == NONE) {
+        rc = ope_mls_smooth(ctx, dev->h, &p_, xyz.data(), nrm.data(), curv.data(), idx.data(), &n);
+      } else if (dev->h) {
+        ope_mls_upsample_params u;
+        ope_mls_upsample_default_params(&u);
+        u.radius = p_.radius; u.polynomial_fit = p_.polynomial_fit; u.order = p_.order; u.sqr_gauss_param = p_.sqr_gauss_param;
+        u.compute_normals = p_.compute_normals; u.voxel_size = voxel_size_; u.dilation_iterations = dilation_iterations_;
+        rc = ope_mls_upsample(ctx, dev->h, &u, xyz.data(), nrm.data(), curv.data(), idx.data(), cap, &n);
+        if (rc == OPE_EINVAL && n > cap) {
+          cap = n;
+          xyz.resize(3 * cap); nrm.resize(3 * cap); curv.resize(cap); idx.resize(cap);
+          rc = ope_mls_upsample(ctx, dev->h, &u, xyz.data(), nrm.data(), curv.data(), idx.data(), cap, &n);
+        }
+      }
+      if (rc != OPE_OK) { log_error("MovingLeastSquares", ctx); n = 0; }
       tmp.points.resize(n);
       corresponding_->indices.assign(idx.begin(), idx.begin() + n);
       constexpr ptrdiff_t rgb_in = point_traits<InT>::rgb_offset, rgb_out = point_traits<OutT>::rgb_offset, n_out = point_traits<OutT>::normal_offset;
@@ -821,6 +841,9 @@ template <class InT, class OutT> class MovingLeastSquares {
   template <class T> static void set_curvature(T &, float) {}
   typename PointCloud<InT>::ConstPtr input_;
   ope_mls_params p_;
+  UpsamplingMethod method_ = NONE;
+  float voxel_size_ = 1.0f;        // PCL's defaults
+  int dilation_iterations_ = 0;
   PointIndices::Ptr corresponding_;
 };
 

@@ -1,7 +1,8 @@
 // reg_mesh_pcd.hpp — BuildModel's RegMeshPcd (BuildModel/include/regmeshpcd.h:27-49, src/regmeshpcd.cpp:8-271) on the
 // façade: getIcp (stock point-to-point ICP), getIcpNormal (normals k = 12, normal shooting k = 20, surface-normal
 // rejector, point-to-plane LM estimator, eps 1e-8 / 1e-8) and registerPointClouds (sequential accumulate-and-register).
-// generateMesh (:273-343) is surface reconstruction, out of scope.
+// generateMeshCloud is generateMesh up to the cloud it hands to the triangulation (:275-303: MLS upsampling by voxel-grid dilation,
+// then normals k = 20); the greedy triangulation and the VTK smoothing (:305-343) are sequential surface reconstruction, out of scope.
 //
 // Kept from the reference on purpose:
 //   * p_maxCorrDist only reaches a stand-alone determineCorrespondences call whose result is discarded (:140-159); the ICP
@@ -165,6 +166,52 @@ class RegMeshPcd {
       PointTReg &q = out->points[k];
       q.x = xyz[3 * k]; q.y = xyz[3 * k + 1]; q.z = xyz[3 * k + 2];
       std::memcpy(&q.rgb, &rgb[k], 4);
+    }
+    out->width = (uint32_t)n;
+    out->height = 1;
+    out->is_dense = true;
+    return out;
+  }
+
+  // :275-303  what generateMesh hands to the greedy triangulation: the cloud upsampled by MovingLeastSquares (order 4, radius 0.03,
+  // VOXEL_GRID_DILATION with voxels of 0.002 and no dilation round) with the normals of NormalEstimation k = 20 on it.  On the device;
+  // the result stays there (normals attached, w = curvature).  Null on failure.
+  std::shared_ptr<compat::CloudHandle> generateMeshCloud(const std::shared_ptr<compat::CloudHandle> &p_cloud) {
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || !p_cloud || !p_cloud->h) return nullptr;
+    ope_mls_upsample_params mp;
+    ope_mls_upsample_default_params(&mp);
+    mp.radius = 0.03;                 // :280
+    mp.polynomial_fit = 1;            // :281
+    mp.order = 4;                     // :282
+    mp.voxel_size = 0.002f;           // :286
+    auto up = std::make_shared<compat::CloudHandle>();
+    size_t n = 0;
+    if (ope_mls_upsample_cloud(ctx, p_cloud->h, &mp, &up->h, nullptr, 0, &n) != OPE_OK) { compat::log_error("generateMeshCloud (upsampling)", ctx); return nullptr; }
+    const float vp[3] = {0.f, 0.f, 0.f};
+    if (n && ope_normals(ctx, up->h, 20, vp, nullptr, nullptr) != OPE_OK) { compat::log_error("generateMeshCloud (normals)", ctx); return nullptr; }   // :291-298
+    return up;
+  }
+  // the same from and to the host: the PointXYZRGBNormal cloud of concatenateFields (:303), rgb left at its default as there
+  CloudN::Ptr generateMeshCloud(const compat::PointCloud<compat::PointXYZ>::Ptr &p_cloud) {
+    CloudN::Ptr out(new CloudN);
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || !p_cloud || p_cloud->empty()) return out;
+    const auto up = generateMeshCloud(compat::upload(*p_cloud, false));
+    if (!up) return out;
+    const size_t n = ope_cloud_size(up->h);
+    if (n == 0) return out;
+    std::vector<float> xyz(3 * n), nrm(3 * n), curv(n);
+    if (ope_cloud_download(ctx, up->h, xyz.data()) != OPE_OK || ope_cloud_download_normals(ctx, up->h, nrm.data(), curv.data()) != OPE_OK) {
+      compat::log_error("generateMeshCloud (download)", ctx);
+      return out;
+    }
+    out->points.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      PN &q = out->points[k];
+      q.x = xyz[3 * k]; q.y = xyz[3 * k + 1]; q.z = xyz[3 * k + 2];
+      q.normal_x = nrm[3 * k]; q.normal_y = nrm[3 * k + 1]; q.normal_z = nrm[3 * k + 2];
+      q.curvature = curv[k];
     }
     out->width = (uint32_t)n;
     out->height = 1;

@@ -312,6 +312,34 @@ class MlsStats(C.Structure):
     ]
 
 
+class MlsUpsampleParams(C.Structure):
+    """ope_mls_upsample_params: pcl::MovingLeastSquares with upsampling VOXEL_GRID_DILATION (RegMeshPcd::generateMesh)."""
+    _fields_ = [
+        ("radius", C.c_double),
+        ("polynomial_fit", C.c_int),
+        ("order", C.c_int),
+        ("sqr_gauss_param", C.c_double),
+        ("compute_normals", C.c_int),
+        ("voxel_size", C.c_float),
+        ("dilation_iterations", C.c_int),
+    ]
+
+
+class MlsUpsampleStats(C.Structure):
+    _fields_ = [
+        ("n_in", C.c_int64),
+        ("n_valid", C.c_int64),
+        ("n_voxels", C.c_int64),
+        ("n_invalid_nearest", C.c_int64),
+        ("n_polynomial", C.c_int64),
+        ("n_rejected_farther", C.c_int64),
+        ("n_out", C.c_int64),
+        ("data_size", C.c_int64),
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+    ]
+
+
 SENSOR_KINECT, SENSOR_ASTRA, SENSOR_EUCLID = 0, 1, 2
 SENSORS = {"kinect": SENSOR_KINECT, "astra": SENSOR_ASTRA, "euclid": SENSOR_EUCLID}
 
@@ -437,6 +465,10 @@ ABI = [
     ("ope_mls_smooth", C.c_int, [_vp, _vp, C.POINTER(MlsParams), _fp, _fp, _fp, _ip, C.POINTER(C.c_size_t)]),
     ("ope_mls_smooth_cloud", C.c_int, [_vp, _vp, C.POINTER(MlsParams), C.POINTER(_vp), _ip, C.POINTER(C.c_size_t)]),
     ("ope_mls_last_stats", C.c_int, [_vp, C.POINTER(MlsStats)]),
+    ("ope_mls_upsample_default_params", None, [C.POINTER(MlsUpsampleParams)]),
+    ("ope_mls_upsample", C.c_int, [_vp, _vp, C.POINTER(MlsUpsampleParams), _fp, _fp, _fp, _ip, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_mls_upsample_cloud", C.c_int, [_vp, _vp, C.POINTER(MlsUpsampleParams), C.POINTER(_vp), _ip, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_mls_upsample_last_stats", C.c_int, [_vp, C.POINTER(MlsUpsampleStats)]),
 ]
 
 _lib = None
@@ -499,6 +531,16 @@ def default_depth_params(sensor="kinect", **kw) -> DepthParams:
 def default_mls_params(**kw) -> MlsParams:
     p = MlsParams()
     lib().ope_mls_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_mls_upsample_params(**kw) -> MlsUpsampleParams:
+    p = MlsUpsampleParams()
+    lib().ope_mls_upsample_default_params(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -1330,6 +1372,44 @@ class Context:
         if compute_normals:
             return xyz[:m].copy(), idx[:m].copy(), nrm[:m].copy(), curv[:m].copy()
         return xyz[:m].copy(), idx[:m].copy()
+
+    def mls_upsample(self, cloud: "Cloud", radius: float, order: int = 2, voxel_size: float = 1.0, dilation_iterations: int = 0,
+                     compute_normals: bool = False, as_cloud: bool = False, polynomial_fit: bool = True,
+                     sqr_gauss_param: float | None = None):
+        """pcl::MovingLeastSquares, upsampling VOXEL_GRID_DILATION (RegMeshPcd::generateMesh).  as_cloud=False: (xyz, idx, normals,
+        curvature), idx the ORIGINAL index of the input point nearest to each output point, normals the plane's unless
+        compute_normals.  as_cloud=True: (Cloud, idx), the new points left on the device with their nearest points' colours and, with
+        compute_normals, the normals attached."""
+        p = default_mls_upsample_params(radius=float(radius), order=int(order), polynomial_fit=int(bool(polynomial_fit)),
+                                        compute_normals=int(bool(compute_normals)), voxel_size=float(voxel_size),
+                                        dilation_iterations=int(dilation_iterations),
+                                        sqr_gauss_param=0.0 if sqr_gauss_param is None else float(sqr_gauss_param))
+        n = C.c_size_t(0)
+        cap = max(8 * cloud.n, 1 << 16)   # a guess; the call says what it needs when that is too small
+        for _ in range(2):
+            idx = np.empty(cap, np.int32)
+            if as_cloud:
+                h = _vp()
+                rc = lib().ope_mls_upsample_cloud(self.h, cloud.h, C.byref(p), C.byref(h), _p(idx, _ip), cap, C.byref(n))
+            else:
+                xyz = np.empty((cap, 3), np.float32)
+                nrm = np.empty((cap, 3), np.float32)
+                curv = np.empty(cap, np.float32)
+                rc = lib().ope_mls_upsample(self.h, cloud.h, C.byref(p), _p(xyz, _fp), _p(nrm, _fp), _p(curv, _fp), _p(idx, _ip), cap, C.byref(n))
+            if rc != OPE_EINVAL or n.value <= cap:
+                break
+            cap = n.value
+        self._chk(rc)
+        m = n.value
+        if as_cloud:
+            return Cloud(self, h, m), idx[:m].copy()
+        return xyz[:m].copy(), idx[:m].copy(), nrm[:m].copy(), curv[:m].copy()
+
+    def mls_upsample_stats(self) -> dict:
+        """ope_mls_upsample_last_stats: what the last mls_upsample did (include/ope.h)."""
+        s = MlsUpsampleStats()
+        self._chk(lib().ope_mls_upsample_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in MlsUpsampleStats._fields_}
 
     def mls_stats(self) -> dict:
         """ope_mls_last_stats: n_in, n_out, n_plane_only, n_dropped, neighbours_total of the last mls_smooth."""

@@ -36,6 +36,7 @@ class RegistrationResult:
     cloud: np.ndarray                      # accumulated, registered cloud (frame of the last input)
     pairs: list = field(default_factory=list)
     rgb: np.ndarray | None = None          # packed colours of `cloud`, when the frames came with colours
+    mesh_cloud: tuple | None = None        # (xyz, normals, curvature) of generate_mesh_cloud(cloud), when asked for
 
 
 def icp_params_with_normals(ope, corr_rej_thresh: float, max_iterations: int, max_corr_dist: float | None = None, estimator: str = "lm"):
@@ -192,6 +193,31 @@ def _register_device_clouds(ope, ctx, clouds, max_corr_dist, corr_rej_thresh, ma
     return res
 
 
+def generate_mesh_cloud(ope, ctx, cloud, keep_on_device: bool = False):
+    """RegMeshPcd::generateMesh up to the cloud it hands to the triangulation (regmeshpcd.cpp:275-303): MovingLeastSquares upsampling
+    (order 4, radius 0.03, VOXEL_GRID_DILATION, voxels of 0.002, no dilation round), then NormalEstimation k = 20 on the result.
+    cloud: (n, 3) array or a Cloud (left as it is).  Returns (xyz, normals, curvature), or with keep_on_device the new Cloud with
+    its normals attached.  The triangulation and the VTK smoothing (:305-343) are not built."""
+    own = not isinstance(cloud, ope.Cloud)
+    src = ctx.upload(np.ascontiguousarray(cloud, np.float32)) if own else cloud
+    try:
+        up, _ = ctx.mls_upsample(src, 0.03, order=4, voxel_size=0.002, as_cloud=True)   # :278-288
+    finally:
+        if own:
+            src.free()
+    if up.n:
+        ctx.normals(up, 20, fetch=False)                                                   # :291-298
+    if keep_on_device:
+        return up
+    try:
+        if up.n == 0:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.float32)
+        nrm, curv = up.download_normals()
+        return ctx.download(up), nrm, curv
+    finally:
+        up.free()
+
+
 def segment_object_device(ope, ctx, frame):
     """BuildModel's per-frame segmentation (main.cpp:181-182) of a device frame: getSegmentedObjectsOnPlane, then cluster 0.
     Returns the cluster as a Cloud (coloured when the frame is).  ValueError when the frame has no plane or no cluster, where the
@@ -212,14 +238,17 @@ def segment_object_device(ope, ctx, frame):
 
 
 def build_model_from_images(ope, ctx, depths, bgrs, limits, out_path: str | None = None, params=None, max_corr_dist: float = 0.005,
-                            corr_rej_thresh: float = 0.7, max_iterations: int = 500, smooth_radius: float | None = None, **kw) -> RegistrationResult:
+                            corr_rej_thresh: float = 0.7, max_iterations: int = 500, smooth_radius: float | None = None, mesh_cloud=False,
+                            **kw) -> RegistrationResult:
     """BuildModel from the sensor's images (main.cpp:171-225 behind DataGrabber::rgbd2Pcl(rgb, depth)), the `--scan` mode of the
     build_model program: per frame the coloured ingest with the crop `limits` = (xmin, xmax, ymin, ymax, zmin, zmax)
     (ope_depth_to_cloud_rgb), the table and cluster 0 on the device; then the sequential registration over the clusters and
     `FIELDS x y z rgb`.  No host cloud exists between the images and the model.  depths: (rows, cols) uint16 images; bgrs:
     (rows, cols, 3) uint8, channels B, G, R; params: DepthParams (default: the Kinect preset).  ValueError, naming the frame,
     when a frame has no plane or no cluster.  smooth_radius (default None: off): getSmooth of the finished model on the device
-    before it is fetched and written (regmeshpcd.cpp:264-266), `build_model --scan --smooth R`."""
+    before it is fetched and written (regmeshpcd.cpp:264-266), `build_model --scan --smooth R`.  mesh_cloud (default False: off):
+    True also runs generate_mesh_cloud on the aligned cloud (main.cpp:227-235) and returns it in the result; a path writes it there
+    as well, after the aligned cloud, `build_model --mesh-cloud OUT.pcd`."""
     from . import pcd
 
     if len(depths) == 0 or len(depths) != len(bgrs):
@@ -242,6 +271,10 @@ def build_model_from_images(ope, ctx, depths, bgrs, limits, out_path: str | None
             o.free()
     if out_path is not None:
         pcd.write_pcd(out_path, res.cloud, res.rgb)
+    if mesh_cloud:
+        res.mesh_cloud = generate_mesh_cloud(ope, ctx, res.cloud)
+        if isinstance(mesh_cloud, (str, bytes)) or hasattr(mesh_cloud, "__fspath__"):
+            pcd.write_pcd_normals(mesh_cloud, *res.mesh_cloud)
     return res
 
 

@@ -9,6 +9,8 @@
 //   mls_fit_kernel    walk B: the weighted moments sum w u^a v^b (a + b <= 2 * order) and right-hand sums sum w f u^a v^b
 //                     (a + b <= order) about the projected query in the plane's Darboux frame; P W P^T is made of the moments;
 //                     Eigen's unblocked lower Cholesky and its two triangular solves, in the lane.
+// The upsampling (mls_upsample.hip) runs the same two walks in record mode for orders 0 to 4 (mls_fit_records): nothing
+// moves, every point with 3 or more neighbours gets its MLSResult under its original index.
 // Results go to the point's ORIGINAL index; a flag per original index, one rocPRIM scan and one scatter put the survivors in
 // ascending original index (PCL's output order) with their indices and colour words.  The sequence of launches does not depend
 // on the points.  The host waits once for what it needs to go on (the count, the bounding box and the statistics) and once more at the
@@ -24,21 +26,13 @@
 #include <vector>
 
 #include "feature_math.hpp"
+#include "mls_shared.hpp"
 
 namespace ope {
 
 hipError_t self_leaves(hipStream_t, const BvhView &, size_t, uint32_t *);   // features.hip
 
 constexpr int kMlsBlock = 256;
-
-// what walk A leaves for walk B, per SORTED position
-struct MlsPlane {
-  double pt[3];   // the query projected on its plane
-  double n[3];    // the plane's normal (smallest eigenvector)
-};
-
-// words of the statistics block
-enum { kMlsMin = 0, kMlsMax = 4, kMlsFinite = 8, kMlsFit = 9, kMlsNeighbours = 10 /* 64 bits */, kMlsWords = 12 };
 
 struct MlsPlaneVisitor {
   float r2;
@@ -152,9 +146,9 @@ struct MlsFitVisitor {
 // false: a pivot that is <= 0 or not finite (Eigen would go on; here the fit counts as failed, like a non-finite c[0]).
 template <int N>
 __device__ __forceinline__ bool mls_llt_solve(double (&A)[N][N], double (&b)[N]) {
-  // every loop has constant bounds and a guard, so that all of them unroll at once and every index is a constant (orders 0 and 1
-  // then live in registers; the 6 x 6 system of order 2 stays a 288-byte private array); a failed pivot only
-  // poisons what follows, and the result is not used
+  // every loop has constant bounds and a guard, so that all of them unroll at once and every index is a constant (the system then
+  // lives in registers for every order, the 15 x 15 of order 4 included: DESIGN.md 4.14, 4.15); a failed pivot only poisons what
+  // follows, and the result is not used
   bool ok = true;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -204,28 +198,47 @@ template <int ORDER, int I, int J>
 struct MlsPair {
   static constexpr int slot = mls_slot(2 * ORDER, mls_term_a(ORDER, I) + mls_term_a(ORDER, J), mls_term_b(ORDER, I) + mls_term_b(ORDER, J));
 };
+// (a class member, like MlsPair::slot, is a constant expression by force; a call of the constexpr functions in the subscript is one only
+// if the optimiser folds their loops, and where it did not the subscript was computed at run time, the visitor stayed in private stack
+// and every accumulator was stored there again for every neighbour of the walk)
+template <int ORDER, int J>
+struct MlsTerm {
+  static constexpr int slot = mls_slot(ORDER, mls_term_a(ORDER, J), mls_term_b(ORDER, J));
+};
 template <int ORDER, int N, int... K>
 __device__ __forceinline__ void mls_fill_system(const double *mom, const double *rhs, double (&A)[N][N], double (&c)[N],
                                                 std::integer_sequence<int, K...>) {
   ((A[K / N][K % N] = mom[MlsPair<ORDER, K / N, K % N>::slot]), ...);
-  ((c[K % N] = rhs[mls_slot(ORDER, mls_term_a(ORDER, K % N), mls_term_b(ORDER, K % N))]), ...);
+  ((c[K % N] = rhs[MlsTerm<ORDER, K % N>::slot]), ...);
 }
 
-template <int ORDER>
+// RECORD (the upsampling, mls_upsample.hip): nothing moves; every point with 3 or more neighbours gets its MLSResult under its original
+// index, and `compute_normals` carries polynomial_fit instead (without it, or below nr_coeff neighbours, the record has no axes).
+template <int ORDER, bool RECORD = false>
 __global__ __launch_bounds__(kMlsBlock) void mls_fit_kernel(CloudView q, BvhView tgt, float r2, double sgp, int compute_normals,
                                                              const uint32_t *__restrict__ self_leaf, const MlsPlane *__restrict__ plane,
                                                              const int32_t *__restrict__ cnt, float *__restrict__ pos_orig,
-                                                             float4 *__restrict__ nrm_orig, uint32_t *__restrict__ stats) {
+                                                             float4 *__restrict__ nrm_orig, uint32_t *__restrict__ stats,
+                                                             MlsRecord *__restrict__ rec = nullptr) {
   using V = MlsFitVisitor<ORDER>;
   constexpr int NR = V::NR;
   __shared__ float s_stk[kMaxDepth + 1][kMlsBlock];
   float *stk = &s_stk[0][threadIdx.x];
   uint32_t local_fit = 0;
   for (uint32_t i = blockIdx.x * kMlsBlock + threadIdx.x; i < q.n_valid; i += gridDim.x * kMlsBlock) {
-    if (cnt[i] < (NR > 3 ? NR : 3)) continue;   // dropped by the plane kernel, or too few neighbours for this order: its projection stands
+    if (cnt[i] < (RECORD || NR <= 3 ? 3 : NR)) continue;   // dropped by the plane kernel, or too few neighbours for this order: its projection stands
     const float4 s = q.xyzw[i];
     const uint32_t orig = (uint32_t)__float_as_int(s.w);
     const MlsPlane pl = plane[i];
+    if constexpr (RECORD) {
+      MlsRecord *r = rec + orig;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) { r->mean[d] = pl.pt[d]; r->n[d] = pl.n[d]; }
+      r->m = cnt[i];
+      r->curvature = reinterpret_cast<const float *>(nrm_orig + orig)[3];
+      r->flags = 0u;
+      if (!compute_normals || cnt[i] < NR) continue;
+    }
     const double nx = pl.n[0], ny = pl.n[1], nz = pl.n[2];
     // Eigen's unitOrthogonal (3-vectors), then u = n x v
     double vx, vy, vz;
@@ -250,7 +263,16 @@ __global__ __launch_bounds__(kMlsBlock) void mls_fit_kernel(CloudView q, BvhView
     // (P W P^T)(i, j) = sum w u^(a_i + a_j) v^(b_i + b_j); P W f = the right-hand sums
     double A[NR][NR], c[NR];
     mls_fill_system<ORDER>(v.mom, v.rhs, A, c, std::make_integer_sequence<int, NR * NR>());
-    if (!mls_llt_solve<NR>(A, c) || !isfinite(c[0])) continue;   // the plane kernel's projection stands
+    const bool solved = mls_llt_solve<NR>(A, c);
+    if constexpr (RECORD) {
+      MlsRecord *r = rec + orig;
+#pragma unroll
+      for (int k = 0; k < NR; ++k) r->c[k] = c[k];
+      r->flags = kMlsRecAxes | (solved ? kMlsRecSolved : 0u);
+      local_fit += solved ? 1u : 0u;
+      continue;
+    }
+    if (!solved || !isfinite(c[0])) continue;   // the plane kernel's projection stands
     ++local_fit;
     const double ox = pl.pt[0] + c[0] * nx, oy = pl.pt[1] + c[0] * ny, oz = pl.pt[2] + c[0] * nz;
     pos_orig[3 * (size_t)orig] = (float)ox; pos_orig[3 * (size_t)orig + 1] = (float)oy; pos_orig[3 * (size_t)orig + 2] = (float)oz;
@@ -313,6 +335,60 @@ __global__ __launch_bounds__(256) void mls_normals_gather_kernel(const float4 *_
                                                                   float4 *__restrict__ nrm_sorted) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p < n) nrm_sorted[p] = nrm_out[perm[p]];
+}
+
+hipError_t mls_bbox(hipStream_t s, const float *d_pos, const uint32_t *d_flag, uint32_t n, uint32_t *d_stats) {
+  hipLaunchKernelGGL(mls_bbox_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, d_pos, d_flag, n, d_stats);
+  return hipGetLastError();
+}
+
+hipError_t mls_normals_gather(hipStream_t s, const float4 *d_nrm_out, const int32_t *d_perm, uint32_t n, float4 *d_nrm_sorted) {
+  hipLaunchKernelGGL(mls_normals_gather_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, d_nrm_out, d_perm, n, d_nrm_sorted);
+  return hipGetLastError();
+}
+
+template <int ORDER>
+static void mls_launch_records(hipStream_t s, unsigned nblocks, const ope_cloud *cloud, const ope_index *ix, float r2, double sgp, int polynomial_fit,
+                               const uint32_t *d_self, const MlsPlane *d_plane, const int32_t *d_cnt, float4 *d_nrm, uint32_t *d_stats,
+                               MlsRecord *d_rec) {
+  hipLaunchKernelGGL((mls_fit_kernel<ORDER, true>), dim3(nblocks), dim3(kMlsBlock), 0, s, cloud->view(), ix->view(), r2, sgp, polynomial_fit, d_self,
+                     d_plane, d_cnt, (float *)nullptr, d_nrm, d_stats, d_rec);
+}
+
+hipError_t mls_fit_records(ope_ctx *ctx, const ope_cloud *cloud, const ope_index *ix, const uint32_t *d_self, float r2, double sgp,
+                           int polynomial_fit, int order, uint32_t *d_flag, MlsRecord *d_rec, uint32_t *d_stats) {
+  const size_t n = cloud->n, nv = cloud->n_valid;
+  hipStream_t s = ctx->stream;
+  MlsPlane *d_plane = nullptr;
+  int32_t *d_cnt = nullptr;
+  float *d_pos = nullptr;
+  float4 *d_nrm = nullptr;
+  hipError_t e = tmp_malloc(s, (void **)&d_plane, sizeof(MlsPlane) * nv);
+  if (e == hipSuccess) e = tmp_malloc(s, (void **)&d_cnt, 4 * nv);
+  if (e == hipSuccess) e = tmp_malloc(s, (void **)&d_pos, 12 * n);
+  if (e == hipSuccess) e = tmp_malloc(s, (void **)&d_nrm, 16 * n);
+  if (e == hipSuccess) {
+    const unsigned nblocks = (unsigned)std::min<size_t>((nv + kMlsBlock - 1) / kMlsBlock, 8192);
+    KernelTimer kt_a(ctx, "mls_plane_kernel", 0.0), kt_b(ctx, "mls_fit_kernel", 0.0, /*start_now=*/false);
+    hipLaunchKernelGGL(mls_plane_kernel, dim3(nblocks), dim3(kMlsBlock), 0, s, cloud->view(), ix->view(), r2, d_self, d_plane, d_cnt, d_pos, d_nrm,
+                       d_flag, d_stats);
+    kt_a.stop();
+    e = hipGetLastError();
+    if (e == hipSuccess) {
+      kt_b.start();
+      switch (order) {
+        case 0: mls_launch_records<0>(s, nblocks, cloud, ix, r2, sgp, polynomial_fit, d_self, d_plane, d_cnt, d_nrm, d_stats, d_rec); break;
+        case 1: mls_launch_records<1>(s, nblocks, cloud, ix, r2, sgp, polynomial_fit, d_self, d_plane, d_cnt, d_nrm, d_stats, d_rec); break;
+        case 2: mls_launch_records<2>(s, nblocks, cloud, ix, r2, sgp, polynomial_fit, d_self, d_plane, d_cnt, d_nrm, d_stats, d_rec); break;
+        case 3: mls_launch_records<3>(s, nblocks, cloud, ix, r2, sgp, polynomial_fit, d_self, d_plane, d_cnt, d_nrm, d_stats, d_rec); break;
+        default: mls_launch_records<4>(s, nblocks, cloud, ix, r2, sgp, polynomial_fit, d_self, d_plane, d_cnt, d_nrm, d_stats, d_rec); break;
+      }
+      kt_b.stop();
+      e = hipGetLastError();
+    }
+  }
+  for (void *q : {(void *)d_plane, (void *)d_cnt, (void *)d_pos, (void *)d_nrm}) tmp_free(s, q);
+  return e;
 }
 
 // what a call leaves on the device (temporaries of the context's stream; mls_release gives them back)

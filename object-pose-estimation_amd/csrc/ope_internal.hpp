@@ -282,6 +282,7 @@ struct ope_ctx {
   ope_depth_stats depth_stats{};   // what the last ope_depth_to_cloud did (depth.hip)
 
   ope_mls_stats mls_stats{};   // what the last ope_mls_smooth* call did (mls.hip)
+  ope_mls_upsample_stats mls_upsample_stats{};   // what the last ope_mls_upsample* call did (mls_upsample.hip)
 
   // what the last ope_coarse_pose_batch computed (ope_coarse_batch_features): segment 0 the model, 1..n the clusters;
   // key points (original indices), normals (x y z) and FPFH rows, packed by segment from coarse_key_off

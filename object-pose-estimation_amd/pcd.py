@@ -9,8 +9,8 @@ from __future__ import annotations
 import numpy as np
 
 
-def read_pcd(path: str):
-    """Returns (xyz float32 (n,3), rgb uint32 (n,) or None)."""
+def read_pcd_fields(path: str):
+    """The points as a numpy structured array, one field per PCD field."""
     with open(path, "rb") as f:
         header = {}
         while True:
@@ -43,6 +43,13 @@ def read_pcd(path: str):
                 data[name] = raw[:, i]
         else:
             raise ValueError(f"unsupported PCD DATA kind {kind!r} (binary_compressed is not used by the reference data)")
+    return data
+
+
+def read_pcd(path: str):
+    """Returns (xyz float32 (n,3), rgb uint32 (n,) or None)."""
+    data = read_pcd_fields(path)
+    fields = data.dtype.names
     xyz = np.stack([data["x"], data["y"], data["z"]], axis=1).astype(np.float32)
     rgb = None
     if "rgb" in fields:
@@ -63,6 +70,25 @@ def write_pcd(path: str, xyz, rgb=None) -> None:
     rec[:, :3] = xyz
     if rgb is not None:
         rec[:, 3] = np.ascontiguousarray(rgb, np.uint32).view(np.float32)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def write_pcd_normals(path: str, xyz, normals, curvature, rgb=None) -> None:
+    """Binary PCD v0.7 of a PointXYZRGBNormal cloud, `FIELDS x y z rgb normal_x normal_y normal_z curvature` (rgb 0 when not given),
+    like pcl::io::savePCDFile(..., binary=true)."""
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    n = len(xyz)
+    header = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb normal_x normal_y normal_z curvature\n"
+              f"SIZE {' '.join(['4'] * 8)}\nTYPE {' '.join(['F'] * 8)}\nCOUNT {' '.join(['1'] * 8)}\nWIDTH {n}\nHEIGHT 1\n"
+              f"VIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA binary\n")
+    rec = np.zeros((n, 8), np.float32)
+    rec[:, :3] = xyz
+    if rgb is not None:
+        rec[:, 3] = np.ascontiguousarray(rgb, np.uint32).view(np.float32)
+    rec[:, 4:7] = np.ascontiguousarray(normals, np.float32).reshape(n, 3)
+    rec[:, 7] = np.ascontiguousarray(curvature, np.float32).reshape(n)
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())
