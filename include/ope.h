@@ -808,6 +808,42 @@ typedef struct {
 int ope_tabletop_segment(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_params *params, ope_tabletop_result *out,
                          ope_cloud **plane, ope_cloud **not_plane, int32_t *prism_idx, int32_t *plane_idx, int32_t *not_plane_idx);
 
+/* ObjectSegmentationPlane::getSegmentedObjectsExceptPlane between its crop and getClusters (objectsegmentationplane.cpp:296-319):
+ * the dominant plane is fitted and its inliers removed, over and over, until at most keep_fraction of the input's points are left.
+ *     m = n0 = the cloud's points (non-finite ones included)
+ *     while ((double)m > keep_fraction * (double)n0) {      the test is made BEFORE each fit
+ *       [max_planes > 0 and that many planes peeled: stop OPE_PEEL_MAX_PLANES]
+ *       a fresh ope_plane_segment fit of the remainder, re-indexed 0..m-1 in ascending original order, the same parameters and seed
+ *       no model, or a model without inliers: stop OPE_PEEL_NO_INLIERS
+ *       the remainder loses the inliers (ExtractIndices negative, order kept) }
+ * The rounds run on one packed point array that shrinks in place of a cloud per plane; one cloud is built, at the end. */
+typedef struct {
+  double keep_fraction;   /* 0.3 (objectsegmentationplane.cpp:300) */
+  int32_t max_planes;     /* 0: no cap, as the reference; > 0: stop after that many planes */
+} ope_peel_params;
+void ope_peel_default_params(ope_peel_params *p);
+enum { OPE_PEEL_FRACTION = 0, OPE_PEEL_NO_INLIERS = 1, OPE_PEEL_MAX_PLANES = 2 };
+typedef struct {
+  int32_t n_planes;       /* planes peeled (all of them, also beyond cap_planes) */
+  int32_t n_rest;         /* points of the remainder */
+  int32_t stop;           /* OPE_PEEL_*: why the loop ended (the fraction test comes first: it wins over the cap) */
+  int64_t launches, host_syncs;
+} ope_peel_result;
+/*   plane / peel: NULL takes the defaults;
+ *   coeffs (4 floats per plane), counts (inliers per plane), iterations (RANSAC iterations per plane): each optional, written
+ *   for the first min(n_planes, cap_planes) planes;
+ *   label (optional, one entry per point, ORIGINAL order): the round that took the point, -1 for the remainder;
+ *   rest_idx (optional, room for every point): the remainder as ORIGINAL indices of `cloud`, ascending; entries past n_rest are
+ *   unspecified;  rest (optional): a new device cloud, exactly ope_cloud_select(cloud, rest_idx[0 .. n_rest)), colours and normals
+ *   carried, built once from the input cloud and booked as every selection of this section.
+ * OPE_EINVAL, nothing launched: what ope_plane_segment refuses of `plane`, keep_fraction negative or not finite, max_planes < 0,
+ * more than 2^31 - 1 points.  An empty cloud: 0 planes, OPE_PEEL_FRACTION, an empty remainder.
+ * Per peeled plane the call enqueues a fixed number of launches and synchronises twice; neither depends on the points or on the
+ * iterations.  ope_plane_last_stats / ope_plane_last_hypotheses describe the LAST fit of the call (indices of its remainder). */
+int ope_plane_peel(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_params *plane, const ope_peel_params *peel, size_t cap_planes,
+                   float *coeffs, int32_t *counts, int64_t *iterations, int32_t *label, int32_t *rest_idx, ope_cloud **rest,
+                   ope_peel_result *out);
+
 /* ---------------- ingest: the sensor's depth image -> the frame's cloud ---------------- */
 /* DataGrabber::rgbd2Pcl (DetectAndLocalize/src/datagrabber.cpp:65-118, called once per frame at rosinterface.cpp:422) with
  * depthToMeter (:121-174), optionally followed by getPassThrough (rosinterface.cpp:212), on the device: the caller hands over

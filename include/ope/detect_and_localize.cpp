@@ -22,6 +22,12 @@
 // fit, prism, second fit and clusters on the device), then the clusters as --candidates takes them.  Prints
 // `segment plane <n>`, `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
 //
+//   detect_and_localize --frame <model.pcd> <frame.pcd> --except-plane [--limits x0 x1 y0 y1 z0 z1] [--seed N] [--self-occluded]
+// A frame without a single table (a floor, a wall, a shelf side): ope::ObjectSegmentationPlane::getSegmentedObjectsExceptPlane, its
+// crop (getFiltered) set to the -l limits, planes peeled on the device until at most 30 % of the cropped points are left, the
+// clusters of the remainder as --candidates takes them.  Prints `segment planes <k> sizes <c0> <c1> ... rest <m>`,
+// `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
+//
 //   detect_and_localize --track <model.pcd> --frame <a.pcd> [<b.pcd> ...] [--frame ...] [--seed N] [--self-occluded] [--time]
 //   detect_and_localize --track-loop <model.pcd> --frame ... (same)
 // DetectAndLocalize's per-frame policy (rosinterface.cpp:226-313) over a sequence of camera frames, one --frame per frame with
@@ -229,6 +235,7 @@ int main(int argc, char **argv) {
   int candidates = 0;   // 1: estimateFinalPoseCandidates, 2: the reference's loop
   bool segment = false; // --segment: the clusters come from getClusters over the one scene file (the non-plane cloud)
   bool frame = false;   // --frame: the clusters come from getSegmentedObjectsOnPlane over the one scene file (a camera frame)
+  bool except_plane = false;   // --except-plane (with --frame): from getSegmentedObjectsExceptPlane instead
   float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -237,9 +244,11 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--candidates-loop")) candidates = 2;
     else if (!std::strcmp(argv[i], "--segment")) { segment = true; candidates = 1; }
     else if (!std::strcmp(argv[i], "--frame")) { frame = true; candidates = 1; }
+    else if (!std::strcmp(argv[i], "--except-plane")) except_plane = true;
     else if (!std::strcmp(argv[i], "--limits") && i + 6 < argc) { for (int d = 0; d < 6; ++d) limits[d] = std::strtof(argv[++i], nullptr); }
     else files.push_back(argv[i]);
   }
+  if (except_plane && !frame) { std::fprintf(stderr, "--except-plane goes with --frame\n"); return 2; }
   if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded] [--candidates | --candidates-loop | --segment | --frame]\n", argv[0]); return 2; }
   typedef ope::PoseEstimator::PointT PointT;
   pcl::PointCloud<PointT>::Ptr cloudSourceOriginal(new pcl::PointCloud<PointT>), cloudSource(new pcl::PointCloud<PointT>);
@@ -285,7 +294,20 @@ int main(int argc, char **argv) {
       }
       std::printf("\n");
     }
-    if (frame) {
+    if (frame && except_plane) {
+      pcl::PointCloud<PointT>::Ptr cloudTarget(new pcl::PointCloud<PointT>);
+      if (segment || files.size() != 2 || pcl::io::loadPCDFile(files[1], *cloudTarget) != 0) return 3;
+      ope::ObjectSegmentationPlane objSegPlane;
+      objSegPlane.setFilterLimits(limits[0], limits[1], limits[2], limits[3], limits[4], limits[5]);
+      clusters = objSegPlane.getSegmentedObjectsExceptPlane(cloudTarget);
+      if (objSegPlane.deviceFailed()) return 5;
+      std::printf("segment planes %d sizes", objSegPlane.lastPeel().n_planes);
+      for (int32_t c : objSegPlane.lastPeelCounts()) std::printf(" %d", c);
+      std::printf(" rest %d\n", objSegPlane.lastPeel().n_rest);
+      std::printf("segment clusters %zu sizes", clusters.size());
+      for (const auto &c : clusters) std::printf(" %zu", c->size());
+      std::printf("\n");
+    } else if (frame) {
       // rosinterface.cpp:212-213: the pass-through crop, then the table-top segmentation
       pcl::PointCloud<PointT>::Ptr cloudTarget(new pcl::PointCloud<PointT>), cloudPlane;
       if (segment || files.size() != 2 || pcl::io::loadPCDFile(files[1], *cloudTarget) != 0) return 3;

@@ -12,6 +12,7 @@
 // getMinMax3D, and the extremes of a planar set are attained at its hull's vertices.
 #pragma once
 
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -27,6 +28,32 @@ class ObjectSegmentationPlane {
 
   void setSeed(uint64_t s) { seed_ = s; }
   const ope_tabletop_result &lastResult() const { return last_; }
+  // getSegmentedObjectsExceptPlane's last peel: the planes' inlier counts in peeling order, and the call's result
+  const std::vector<int32_t> &lastPeelCounts() const { return peelCounts_; }
+  const ope_peel_result &lastPeel() const { return lastPeel_; }
+  // getFiltered's limits.  The default is DetectAndLocalize's literals (objectsegmentationplane.cpp:17: -0.5 0.5, -0.5 0.3, 0.5 1.6);
+  // BuildModel's file has -0.4 0.6, -0.5 0.5, 0.7 1.4 (BuildModel objectsegmentationplane.cpp:17).
+  void setFilterLimits(float p_minX, float p_maxX, float p_minY, float p_maxY, float p_minZ, float p_maxZ) {
+    filterLo_[0] = p_minX; filterLo_[1] = p_minY; filterLo_[2] = p_minZ;
+    filterHi_[0] = p_maxX; filterHi_[1] = p_maxY; filterHi_[2] = p_maxZ;
+  }
+
+  // :8-33: the fixed pass-through (the reference's down-sampling after it is commented out)
+  Cloud::Ptr getFiltered(Cloud::Ptr p_cloudInput) {
+    Cloud::Ptr cloudOutput(new Cloud);
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || !p_cloudInput || p_cloudInput->empty()) return cloudOutput;
+    auto frame = compat::upload(*p_cloudInput, false);
+    std::vector<int32_t> idx(p_cloudInput->size());
+    size_t n = 0;
+    if (!frame->h || ope_pass_through(ctx, frame->h, filterLo_, filterHi_, idx.data(), &n) != OPE_OK) { compat::log_error("getFiltered", ctx); return cloudOutput; }
+    cloudOutput->points.resize(n);
+    for (size_t j = 0; j < n; ++j) cloudOutput->points[j] = p_cloudInput->points[(size_t)idx[j]];
+    cloudOutput->width = (uint32_t)n;
+    cloudOutput->height = 1;
+    cloudOutput->is_dense = true;
+    return cloudOutput;
+  }
 
   // objectsegmentationplane.cpp:36-55
   bool getPlaneIndicesAndCoeffSAC(Cloud::Ptr p_cloudInput, compat::PointIndices::Ptr p_indices, compat::ModelCoefficients::Ptr p_modelCoeff) {
@@ -137,6 +164,46 @@ class ObjectSegmentationPlane {
     return segmentDeviceFrame(ctx, p_frame.h, n, point, hand_back, cloudClusterVector, p_cloudPlane);
   }
 
+  // :286-358.  The clusters of what is left when the planes are peeled off the cropped frame; deviceClusters() holds them as they
+  // were left on the device.  The host clouds are gathered from the input through the index lists, so every field of the point
+  // type (the colour) is carried.  No .pcd file is written: the reference's savePCDFile per cluster (:342-348) is a debugging
+  // leftover with a path of its author's machine.
+  std::vector<Cloud::Ptr> getSegmentedObjectsExceptPlane(Cloud::Ptr p_cloudInput) {
+    std::vector<Cloud::Ptr> cloudClusterVector;
+    resetPeel();
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || !p_cloudInput) return cloudClusterVector;
+    auto frame = compat::upload(*p_cloudInput, false);
+    if (!frame->h) { deviceFailed_ = true; return cloudClusterVector; }
+    exceptPlaneDeviceFrame(ctx, frame->h, p_cloudInput->size(), [&](size_t i) { return p_cloudInput->points[i]; }, cloudClusterVector);
+    return cloudClusterVector;
+  }
+
+  // The same for a frame that is already on the device: it is not uploaded.  The host clouds are built from ONE download of the
+  // frame's xyz, white unless the frame carries colours (then each takes them from the device cluster it mirrors).
+  std::vector<Cloud::Ptr> getSegmentedObjectsExceptPlane(const compat::CloudHandle &p_frame) {
+    std::vector<Cloud::Ptr> cloudClusterVector;
+    resetPeel();
+    ope_ctx *ctx = compat::default_context();
+    if (!ctx || !p_frame.h) return cloudClusterVector;
+    const size_t n = ope_cloud_size(p_frame.h);
+    std::vector<float> xyz(3 * n + 3);
+    if (ope_cloud_download(ctx, p_frame.h, xyz.data()) != OPE_OK) {
+      compat::log_error("getSegmentedObjectsExceptPlane", ctx);
+      deviceFailed_ = true;
+      return cloudClusterVector;
+    }
+    auto point = [&](size_t i) {
+      const uint32_t white = 0x00ffffffu;
+      PointTObj q;
+      q.x = xyz[3 * i]; q.y = xyz[3 * i + 1]; q.z = xyz[3 * i + 2];
+      std::memcpy(&q.rgb, &white, 4);
+      return q;
+    };
+    exceptPlaneDeviceFrame(ctx, p_frame.h, n, point, cloudClusterVector);
+    return cloudClusterVector;
+  }
+
   // The same without any host cloud: only deviceClusters() is filled (BuildModel's scan loop hands cluster 0 straight to the
   // registration).  false without a plane, or when a device call failed (deviceFailed() tells the two apart); true with
   // deviceClusters() empty when nothing on the plane is a cluster.
@@ -157,6 +224,65 @@ class ObjectSegmentationPlane {
   const std::vector<std::shared_ptr<compat::CloudHandle>> &deviceClusters() const { return deviceClusters_; }
 
  private:
+  void resetPeel() {
+    lastPeel_ = ope_peel_result{};
+    peelCounts_.clear();
+    deviceClusters_.clear();
+    deviceFailed_ = false;
+  }
+
+  // getSegmentedObjectsExceptPlane on a frame of n points that is on the device: the crop (:292), the peel (:296-319) and
+  // getClusters (:324), each handing a device cloud to the next; only index lists come back.  point(i): the host point of frame
+  // index i.  A failed device call sets deviceFailed_ and leaves no clusters.
+  template <class PointAt>
+  void exceptPlaneDeviceFrame(ope_ctx *ctx, const ope_cloud *frame, size_t n, PointAt point, std::vector<Cloud::Ptr> &cloudClusterVector) {
+    auto fail = [&]() { compat::log_error("getSegmentedObjectsExceptPlane", ctx); deviceFailed_ = true; };
+    compat::CloudHandle filtered, rest;
+    std::vector<int32_t> cropIdx(n + 1), restIdx;
+    size_t nCrop = 0;
+    if (ope_pass_through_cloud(ctx, frame, filterLo_, filterHi_, &filtered.h, cropIdx.data(), &nCrop) != OPE_OK) return fail();
+    ope_plane_params p;
+    ope_plane_default_params(&p);
+    p.seed = seed_;
+    const size_t capPlanes = 64;   // (more planes than this are peeled all the same; only their counts are not kept)
+    peelCounts_.assign(capPlanes, 0);
+    restIdx.assign(nCrop + 1, 0);
+    if (ope_plane_peel(ctx, filtered.h, &p, nullptr, capPlanes, nullptr, peelCounts_.data(), nullptr, nullptr, restIdx.data(), &rest.h, &lastPeel_) !=
+        OPE_OK) {
+      peelCounts_.clear();
+      return fail();
+    }
+    peelCounts_.resize(std::min<size_t>((size_t)lastPeel_.n_planes, capPlanes));
+    const size_t m = (size_t)lastPeel_.n_rest;
+    ope_cluster_params cp;
+    ope_cluster_default_params(&cp);
+    std::vector<ope_cloud *> clouds(m + 1, nullptr);
+    std::vector<int32_t> idx(m + 1, 0), off(m + 2, 0);
+    size_t k = 0;
+    if (ope_euclidean_clusters_cloud(ctx, rest.h, &cp, m, &k, clouds.data(), idx.data(), off.data()) != OPE_OK) return fail();
+    std::vector<uint32_t> rgb;
+    for (size_t c = 0; c < k && c < m; ++c) {
+      auto h = std::make_shared<compat::CloudHandle>();
+      h->h = clouds[c];
+      deviceClusters_.push_back(h);
+      // the cluster's points by index (:330-337), through remainder and crop back to the frame
+      const size_t cnt = (size_t)(off[c + 1] - off[c]);
+      Cloud::Ptr cloudCluster(new Cloud);
+      cloudCluster->points.resize(cnt);
+      for (size_t j = 0; j < cnt; ++j) cloudCluster->points[j] = point((size_t)cropIdx[(size_t)restIdx[(size_t)idx[(size_t)off[c] + j]]]);
+      if (cnt && ope_cloud_has_rgb(h->h)) {
+        rgb.resize(cnt);
+        if (ope_cloud_download_rgb(ctx, h->h, rgb.data()) == OPE_OK)
+          for (size_t j = 0; j < cnt; ++j) std::memcpy(&cloudCluster->points[j].rgb, &rgb[j], 4);
+        else compat::log_error("getSegmentedObjectsExceptPlane", ctx);
+      }
+      cloudCluster->width = (uint32_t)cnt;
+      cloudCluster->height = 1;
+      cloudCluster->is_dense = true;
+      cloudClusterVector.push_back(cloudCluster);
+    }
+  }
+
   // Steps 2-8 on a frame of n points that is on the device.  point(i): the host point of frame index i, from which the output
   // clouds are gathered; hand_back(): what is returned when there is no plane.
   template <class PointAt, class HandBack>
@@ -234,6 +360,9 @@ class ObjectSegmentationPlane {
   compat::EuclideanClusterExtraction<PointTObj> euclideanClustExtraction;
   uint64_t seed_ = 12345;
   ope_tabletop_result last_{};
+  float filterLo_[3] = {-0.5f, -0.5f, 0.5f}, filterHi_[3] = {0.5f, 0.3f, 1.6f};
+  ope_peel_result lastPeel_{};
+  std::vector<int32_t> peelCounts_;
   bool deviceFailed_ = false;
   std::vector<std::shared_ptr<compat::CloudHandle>> deviceClusters_;
 };

@@ -1,7 +1,7 @@
 // segmentation_check.cpp — ope::ObjectSegmentationPlane and the façade classes under it from a file, for
 // tests/test_gpu_tabletop_pipeline.py:
 //
-//   segmentation_check <frame.pcd>
+//   segmentation_check <frame.pcd> [--except-plane]
 //
 // Prints, floats as their 32 bits in hex and point lists as an FNV-1a hash of their xyz bytes:
 //   sac found <0|1> coeff <a> <b> <c> <d> inliers <n> hash <h>      getPlaneIndicesAndCoeffSAC (pcl::SACSegmentation)
@@ -10,6 +10,10 @@
 //   prism <n> hash <h>                                              pcl::ExtractPolygonalPrismData over the four corners (:174-214)
 //   objects <0|1> plane <n> <h> clusters <k>                        getSegmentedObjectsOnPlane
 //   cluster <i> <n> <h>                                             ... each cluster
+// and with --except-plane, after them (the colours hashed as well: <hc> is the FNV-1a hash of the clusters' rgb words):
+//   filtered <n> <h>                                                getFiltered
+//   except planes <k> sizes <c0> ... rest <m> clusters <k>          getSegmentedObjectsExceptPlane
+//   except cluster <i> <n> <h> <hc>                                 ... each cluster
 #include <cinttypes>
 #include <cstdio>
 #include <cstring>
@@ -34,8 +38,19 @@ static uint64_t hash_xyz(const Cloud &c) {
   return h;
 }
 
+static uint64_t hash_rgb(const Cloud &c) {
+  uint64_t h = 1469598103934665603ull;
+  for (const PointTObj &p : c.points) {
+    unsigned char b[4];
+    std::memcpy(b, &p.rgb, 4);
+    for (unsigned char v : b) { h ^= v; h *= 1099511628211ull; }
+  }
+  return h;
+}
+
 int main(int argc, char **argv) {
-  if (argc != 2) { std::fprintf(stderr, "usage: %s <frame.pcd>\n", argv[0]); return 2; }
+  const bool except = argc == 3 && std::strcmp(argv[2], "--except-plane") == 0;
+  if (argc != 2 && !except) { std::fprintf(stderr, "usage: %s <frame.pcd> [--except-plane]\n", argv[0]); return 2; }
   Cloud::Ptr frame(new Cloud);
   if (pcl::io::loadPCDFile(argv[1], *frame) != 0) return 3;
   ope::ObjectSegmentationPlane seg;
@@ -83,5 +98,17 @@ int main(int argc, char **argv) {
   const bool ok = seg.getSegmentedObjectsOnPlane(frame, clusters, cloudPlane);
   std::printf("objects %d plane %zu %016" PRIx64 " clusters %zu\n", ok ? 1 : 0, cloudPlane->size(), hash_xyz(*cloudPlane), clusters.size());
   for (size_t i = 0; i < clusters.size(); ++i) std::printf("cluster %zu %zu %016" PRIx64 "\n", i, clusters[i]->size(), hash_xyz(*clusters[i]));
+  if (except) {
+    Cloud::Ptr filtered = seg.getFiltered(frame);
+    std::printf("filtered %zu %016" PRIx64 "\n", filtered->size(), hash_xyz(*filtered));
+    std::vector<Cloud::Ptr> objects = seg.getSegmentedObjectsExceptPlane(frame);
+    if (seg.deviceFailed()) return 5;
+    std::printf("except planes %d sizes", seg.lastPeel().n_planes);
+    for (int32_t c : seg.lastPeelCounts()) std::printf(" %d", c);
+    std::printf(" rest %d clusters %zu\n", seg.lastPeel().n_rest, objects.size());
+    if (objects.size() != seg.deviceClusters().size()) return 6;
+    for (size_t i = 0; i < objects.size(); ++i)
+      std::printf("except cluster %zu %zu %016" PRIx64 " %016" PRIx64 "\n", i, objects[i]->size(), hash_xyz(*objects[i]), hash_rgb(*objects[i]));
+  }
   return 0;
 }

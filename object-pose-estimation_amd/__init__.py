@@ -269,6 +269,26 @@ class TabletopResult(C.Structure):
 TABLETOP_OK, TABLETOP_NO_PLANE_FIRST, TABLETOP_NO_PLANE_SECOND = 0, 1, 2
 
 
+class PeelParams(C.Structure):
+    _fields_ = [
+        ("keep_fraction", C.c_double),
+        ("max_planes", C.c_int32),
+    ]
+
+
+class PeelResult(C.Structure):
+    _fields_ = [
+        ("n_planes", C.c_int32),
+        ("n_rest", C.c_int32),
+        ("stop", C.c_int32),
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+    ]
+
+
+PEEL_FRACTION, PEEL_NO_INLIERS, PEEL_MAX_PLANES = 0, 1, 2
+
+
 class DepthParams(C.Structure):
     """ope_depth_params: the reference applies its cx / fx to the ROW and its cy / fy to the COLUMN (datagrabber.cpp:86,170-171)."""
     _fields_ = [
@@ -451,6 +471,9 @@ ABI = [
     ("ope_prism_extract", C.c_int, [_vp, _vp, _fp, C.c_size_t, C.c_double, C.c_double, _ip, C.POINTER(C.c_size_t), C.POINTER(_vp), _fp]),
     ("ope_tabletop_segment", C.c_int, [_vp, _vp, C.POINTER(PlaneParams), C.POINTER(TabletopResult), C.POINTER(_vp), C.POINTER(_vp), _ip, _ip,
                                         _ip]),
+    ("ope_peel_default_params", None, [C.POINTER(PeelParams)]),
+    ("ope_plane_peel", C.c_int, [_vp, _vp, C.POINTER(PlaneParams), C.POINTER(PeelParams), C.c_size_t, _fp, _ip, C.POINTER(C.c_int64), _ip, _ip,
+                                 C.POINTER(_vp), C.POINTER(PeelResult)]),
     ("ope_depth_sensor_params", C.c_int, [C.c_int, C.POINTER(DepthParams)]),
     ("ope_depth_to_cloud", C.c_int, [_vp, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(DepthParams), _fp, _fp, C.POINTER(_vp), _ip,
                                       C.POINTER(C.c_size_t)]),
@@ -638,6 +661,18 @@ class PlaneOut:
     plane: "Cloud | None"
     not_plane: "Cloud | None"
     stats: dict
+
+
+@dataclass
+class PeelOut:
+    coeffs: np.ndarray         # (k, 4) the peeled planes, in peeling order
+    counts: np.ndarray         # (k,) their inliers
+    iterations: np.ndarray     # (k,) the iterations RANSAC would have run for each
+    rest_idx: np.ndarray       # the remainder, ORIGINAL indices ascending
+    rest: "Cloud | None"
+    labels: "np.ndarray | None"  # (n,) the round that took each point, -1 for the remainder
+    stop: int                  # PEEL_FRACTION / PEEL_NO_INLIERS / PEEL_MAX_PLANES
+    stats: dict                # n_planes, n_rest, launches, host_syncs
 
 
 @dataclass
@@ -1021,6 +1056,50 @@ class Context:
                            li[: r.n_plane].copy() if ok else None, ni[: r.n_not_plane].copy() if ok else None,
                            Cloud(self, hp, r.n_plane) if ok else None, Cloud(self, hn, r.n_not_plane) if ok else None,
                            r.iterations_first, r.iterations_second, r.launches, r.host_syncs)
+
+    def plane_peel(self, cloud, params: "PlaneParams | None" = None, keep_fraction: float = 0.3, max_planes: int = 0, want_cloud: bool = False,
+                   want_labels: bool = False) -> "PeelOut":
+        """ope_plane_peel: the loop of getSegmentedObjectsExceptPlane (objectsegmentationplane.cpp:296-319) on a Cloud (or an (n, 3)
+        array, uploaded first): fit the dominant plane and remove its inliers until at most keep_fraction of the points are left."""
+        if not isinstance(cloud, Cloud):
+            cloud = self.upload(cloud)
+        p = params if params is not None else default_plane_params()
+        q = PeelParams(float(keep_fraction), int(max_planes))
+        r = PeelResult()
+        n1 = max(cloud.n, 1)
+        rest_idx = np.empty(n1, np.int32)
+        lab = np.empty(n1, np.int32) if want_labels else None
+        h = _vp()
+        cap = 32
+        while True:   # (a second call only for more planes than the first one had room for)
+            coeffs, counts, its = np.zeros((cap, 4), np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.int64)
+            self._chk(lib().ope_plane_peel(self.h, cloud.h, C.byref(p), C.byref(q), cap, _p(coeffs, _fp), _p(counts, _ip),
+                                           its.ctypes.data_as(C.POINTER(C.c_int64)), _p(lab, _ip) if lab is not None else None,
+                                           _p(rest_idx, _ip), C.byref(h) if want_cloud else None, C.byref(r)))
+            if r.n_planes <= cap:
+                break
+            if want_cloud:
+                Cloud(self, h, r.n_rest).free()
+                h = _vp()
+            cap = r.n_planes
+        k = r.n_planes
+        stats = dict(n_planes=k, n_rest=r.n_rest, launches=r.launches, host_syncs=r.host_syncs)
+        return PeelOut(coeffs[:k].copy(), counts[:k].copy(), its[:k].copy(), rest_idx[: r.n_rest].copy(),
+                       Cloud(self, h, r.n_rest) if want_cloud else None, lab[: cloud.n].copy() if lab is not None else None, r.stop, stats)
+
+    def except_plane_segment(self, cloud, params: "PlaneParams | None" = None, keep_fraction: float = 0.3, max_planes: int = 0,
+                             tolerance: float = 0.05, min_size: int = 300, max_size: int = 100000, want_clouds: bool = False):
+        """getSegmentedObjectsExceptPlane after its crop (objectsegmentationplane.cpp:296-324): plane_peel, then euclidean_clusters
+        of the remainder.  Returns (clusters, peel): the clusters as int32 arrays of indices into the INPUT cloud, ascending, in
+        euclidean_clusters' order; with want_clouds, (cluster clouds, clusters, peel)."""
+        if not isinstance(cloud, Cloud):
+            cloud = self.upload(cloud)
+        peel = self.plane_peel(cloud, params, keep_fraction, max_planes, want_cloud=True)
+        if want_clouds:
+            clouds, local = self.euclidean_clusters_cloud(peel.rest, tolerance, min_size, max_size)
+            return clouds, [peel.rest_idx[c] for c in local], peel
+        local = self.euclidean_clusters(peel.rest, tolerance, min_size, max_size)
+        return [peel.rest_idx[c] for c in local], peel
 
     def depth_to_cloud(self, depth, params: "DepthParams | None" = None, lo=None, hi=None, want_pixels: bool = False, bgr=None):
         """ope_depth_to_cloud: a (rows, cols) uint16 depth image -> the frame's Cloud (rgbd2Pcl, optionally cropped to lo .. hi).

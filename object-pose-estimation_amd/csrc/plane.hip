@@ -17,6 +17,8 @@
 //   6. indices, count and coefficients come back (second synchronisation); the two clouds are cloud selections.
 // ope_prism_extract: one lane takes the hull's plane, one launch tests every point, a scan and a scatter pack the survivors.
 // ope_tabletop_segment chains them.  No launch count depends on the number of points or on the iterations the replay kept.
+// ope_plane_peel (getSegmentedObjectsExceptPlane's loop, :296-319) runs steps 2-5 round after round on one packed
+// point array: pl_peel_kernel, in step 5's last place, packs what a round leaves into the other half of a double buffer.
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -139,18 +141,19 @@ __global__ __launch_bounds__(64) void pl_draw_kernel(const float4 *__restrict__ 
   meta[0] = made;
 }
 
-// 3. countWithinDistance of every hypothesis in one pass: fabsf(dist) < threshold, the comparison in double
-__global__ __launch_bounds__(kPlBlock) void pl_score_kernel(CloudView c, const float4 *__restrict__ hyp, const uint32_t *__restrict__ meta, double thr,
-                                                            uint32_t *__restrict__ cnt) {
+// 3. countWithinDistance of every hypothesis in one pass: fabsf(dist) < threshold, the comparison in double.  The counts do not
+// depend on the order of the points: pts is the cloud's stored array, or (the peel) a packed array of n points.
+__global__ __launch_bounds__(kPlBlock) void pl_score_kernel(const float4 *__restrict__ pts, uint32_t n, const float4 *__restrict__ hyp,
+                                                            const uint32_t *__restrict__ meta, double thr, uint32_t *__restrict__ cnt) {
   __shared__ float4 s_h[kMaxHyp];
   __shared__ uint32_t s_c[kMaxHyp];
   const uint32_t H = min(meta[0], (uint32_t)kMaxHyp), t = threadIdx.x;
   for (uint32_t i = t; i < H; i += kPlBlock) { s_h[i] = hyp[i]; s_c[i] = 0u; }
   __syncthreads();
-  for (uint32_t base = blockIdx.x * kPlBlock; base < c.n; base += gridDim.x * kPlBlock) {
+  for (uint32_t base = blockIdx.x * kPlBlock; base < n; base += gridDim.x * kPlBlock) {
     const uint32_t p = base + t;
-    const bool on = p < c.n;
-    const float4 q = on ? c.xyzw[p] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool on = p < n;
+    const float4 q = on ? pts[p] : make_float4(0.f, 0.f, 0.f, 0.f);
     for (uint32_t h = 0; h < H; ++h) {
       const float d = fabsf(plane_dist(s_h[h], q.x, q.y, q.z));
       const unsigned long long b = __ballot(on && (double)d < thr);
@@ -220,6 +223,36 @@ __global__ __launch_bounds__(kPlBlock) void pl_index_kernel(uint32_t n, const ui
   if (o >= n) return;
   if (flags[o]) idx[rank[o]] = (int32_t)o;
   else if (rest) rest[o - rank[o]] = (int32_t)o;
+}
+
+// ---- the peel.  Before its first round: orig = 0..n-1, every label -1
+__global__ __launch_bounds__(kPlBlock) void pl_peel_init_kernel(uint32_t n, int32_t *__restrict__ orig, int32_t *__restrict__ label) {
+  const uint32_t o = blockIdx.x * kPlBlock + threadIdx.x;
+  if (o >= n) return;
+  orig[o] = (int32_t)o;
+  if (label) label[o] = -1;
+}
+
+// The peel's step, from a round's last flags / rank over its m points: the unflagged points and their original indices packed
+// into the other half of the double buffer, ascending (what ExtractIndices' negative keeps, in order); label[original index] =
+// round for the flagged ones; shuffled_indices_ = 0..m-1 again for the next round's draws; the next m left in *d_m.  One point
+// per lane: 16 B loads and stores of the points, every other stream 4 B per lane and coalesced but the label's scatter.
+__global__ __launch_bounds__(kPlBlock) void pl_peel_kernel(const float4 *__restrict__ pts, const int32_t *__restrict__ orig, uint32_t m,
+                                                           const uint32_t *__restrict__ flags, const uint32_t *__restrict__ rank, int32_t round,
+                                                           float4 *__restrict__ pts_next, int32_t *__restrict__ orig_next,
+                                                           int32_t *__restrict__ label, int32_t *__restrict__ shuf, uint32_t *__restrict__ d_m) {
+  const uint32_t o = blockIdx.x * kPlBlock + threadIdx.x;
+  if (o == 0) *d_m = m - rank[m];
+  if (o >= m) return;
+  const uint32_t r = rank[o];
+  const int32_t g = orig[o];
+  if (flags[o]) {
+    if (label) label[g] = round;
+  } else {
+    pts_next[o - r] = pts[o];
+    orig_next[o - r] = g;
+  }
+  shuf[o] = (int32_t)o;
 }
 
 // ---- prism.  hp: {a b c d} of the hull's plane, {a' b' c' 0} its normal normalised once more (projectPoints), k1 k2 (int bits)
@@ -356,10 +389,53 @@ hipError_t scan_flags(ope_ctx *ctx, void *d_tmp, size_t tb, const uint32_t *flag
   return rocprim::exclusive_scan(d_tmp, tb, flags, rank, 0u, n + 1, rocprim::plus<uint32_t>(), ctx->stream);
 }
 
-// steps 1-6 without the clouds.  samples: host triples or null.  Adds to ctx->plane_stats' launches and syncs; sets the rest.
-int plane_fit(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *cloud, const ope_plane_params &p, const int32_t *samples,
-              size_t n_samples, int32_t *out_idx, Fit &fit) {
-  const uint32_t n = (uint32_t)cloud->n;
+// the temporaries of one fit of at most n points and H hypotheses; the peel keeps one set for all its rounds
+struct FitBufs {
+  float4 *pts_o = nullptr, *packed = nullptr, *d_coeff = nullptr;
+  int32_t *shuf = nullptr, *idx = nullptr, *rest = nullptr, *d_inj = nullptr;
+  unsigned char *d_back = nullptr;   // one block read back at the first synchronisation: hyp (H float4) | samp (3H) | cnt (H) | meta (4 words)
+  size_t back_bytes = 0, tb = 0;
+  uint32_t *flags = nullptr, *rank = nullptr;
+  void *d_tmp = nullptr;
+};
+
+hipError_t fit_alloc(CallTmp &tmp, hipStream_t st, uint32_t n, uint32_t H, bool injected, size_t n_samples, bool index, FitBufs &B) {
+  hipError_t e = hipSuccess;
+  const size_t n1 = std::max<size_t>(n, 1);
+  B.pts_o = (float4 *)tmp.get(16 * n1, e);
+  B.shuf = (int32_t *)tmp.get(4 * n1, e);
+  B.back_bytes = 16ull * H + 12ull * H + 4ull * H + 16;
+  B.d_back = (unsigned char *)tmp.get(B.back_bytes, e);
+  B.flags = (uint32_t *)tmp.get(4 * (n1 + 1), e);
+  B.rank = (uint32_t *)tmp.get(4 * (n1 + 1), e);
+  B.packed = (float4 *)tmp.get(16 * n1, e);
+  if (index) {
+    B.idx = (int32_t *)tmp.get(4 * n1, e);
+    B.rest = (int32_t *)tmp.get(4 * n1, e);
+  }
+  B.d_coeff = (float4 *)tmp.get(16, e);
+  if (injected) B.d_inj = (int32_t *)tmp.get(12 * std::max<size_t>(n_samples, 1), e);
+  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, B.tb, B.flags, B.rank, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st);
+  B.tb = std::max<size_t>(B.tb, 16);
+  B.d_tmp = tmp.get(B.tb, e);
+  return e;
+}
+
+// what a round of the peel runs in place of pl_index_kernel (pl_peel_kernel's arguments)
+struct PeelStep {
+  float4 *pts_next;
+  const int32_t *orig;
+  int32_t *orig_next, *label;
+  int32_t round;
+  uint32_t *d_m;
+  uint32_t m_next;   // out: *d_m, read back at the second synchronisation
+};
+
+// steps 1-6 without the clouds, on n points.  cloud: the points' source (step 1 restores its original order into B.pts_o); NULL
+// (the peel after its first round): B.pts_o holds them already and B.shuf is 0..n-1.  samples: host triples or null.  peel: the
+// step that takes pl_index_kernel's place.  Adds to ctx->plane_stats' launches and syncs; sets the rest.
+int fit_run(ope_ctx *ctx, const char *who, const FitBufs &B, const ope_cloud *cloud, uint32_t n, const ope_plane_params &p, const int32_t *samples,
+            size_t n_samples, int32_t *out_idx, PeelStep *peel, Fit &fit) {
   const uint32_t H = (uint32_t)p.max_iterations + 1u;
   const hipStream_t st = ctx->stream;
   ope_plane_stats &S = ctx->plane_stats;
@@ -368,22 +444,19 @@ int plane_fit(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *clou
   S.found = 0;
   ctx->plane_samples.clear(); ctx->plane_counts.clear(); ctx->plane_coeffs.clear();
   hipError_t e = hipSuccess;
-  const size_t n1 = std::max<size_t>(n, 1);
-  auto *pts_o = (float4 *)tmp.get(16 * n1, e);
-  auto *shuf = (int32_t *)tmp.get(4 * n1, e);
-  // one block read back at the first synchronisation: hyp (H float4) | samp (3H) | cnt (H) | meta (4 words)
-  const size_t back_bytes = 16ull * H + 12ull * H + 4ull * H + 16;
-  auto *d_back = (unsigned char *)tmp.get(back_bytes, e);
-  auto *flags = (uint32_t *)tmp.get(4 * (n1 + 1), e), *rank = (uint32_t *)tmp.get(4 * (n1 + 1), e);
-  auto *packed = (float4 *)tmp.get(16 * n1, e);
-  auto *idx = (int32_t *)tmp.get(4 * n1, e), *rest = (int32_t *)tmp.get(4 * n1, e);
-  auto *d_coeff = (float4 *)tmp.get(16, e);
-  int32_t *d_inj = nullptr;
-  if (samples) d_inj = (int32_t *)tmp.get(12 * std::max<size_t>(n_samples, 1), e);
-  size_t tb = 0;
-  if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tb, flags, rank, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st);
-  void *d_tmp = tmp.get(std::max<size_t>(tb, 16), e);
-  if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
+  float4 *pts_o = B.pts_o, *packed = B.packed, *d_coeff = B.d_coeff;
+  int32_t *shuf = B.shuf, *idx = B.idx, *rest = B.rest, *d_inj = B.d_inj;
+  unsigned char *d_back = B.d_back;
+  const size_t back_bytes = B.back_bytes;
+  uint32_t *flags = B.flags, *rank = B.rank;
+  void *d_tmp = B.d_tmp;
+  size_t tb = B.tb;
+  if (peel) {   // fewer points than the buffers were sized for: a query (nothing is launched) that the scan still fits
+    e = rocprim::exclusive_scan(nullptr, tb, flags, rank, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st);
+    if (e != hipSuccess || tb > B.tb)
+      return set_err(ctx, OPE_EHIP, std::string(who) + (e != hipSuccess ? hipGetErrorString(e) : "the scan's temporary storage grew with fewer points"));
+    tb = B.tb;
+  }
   auto *hyp = (float4 *)d_back;
   auto *samp = (int32_t *)(d_back + 16ull * H);
   auto *cnt = (uint32_t *)(d_back + 28ull * H);
@@ -400,12 +473,12 @@ int plane_fit(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *clou
   if (e == hipSuccess) e = hipMemsetAsync(d_back, 0, back_bytes, st);
   ++S.launches;
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  const CloudView cv = cloud->view();
-  PL_LAUNCH(pl_orig_kernel, 36.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, cv, pts_o, shuf);
+  if (cloud) PL_LAUNCH(pl_orig_kernel, 36.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, cloud->view(), pts_o, shuf);
   PL_LAUNCH(pl_draw_kernel, 0.0, dim3(1), dim3(64), 0, st, pts_o, n, shuf, (uint32_t)(p.seed & 0xffffffffull), H, d_inj, (uint32_t)n_samples, hyp, samp,
             meta);
   const unsigned score_blocks = (unsigned)std::min<size_t>(grid_of(n), (size_t)ctx->n_cu * 8);
-  PL_LAUNCH(pl_score_kernel, 16.0 * n, dim3(score_blocks), dim3(kPlBlock), 0, st, cv, hyp, meta, p.distance_threshold, cnt);
+  PL_LAUNCH(pl_score_kernel, 16.0 * n, dim3(score_blocks), dim3(kPlBlock), 0, st, cloud ? (const float4 *)cloud->d_xyzw : (const float4 *)pts_o, n, hyp, meta,
+            p.distance_threshold, cnt);
   // ---- the first synchronisation: hypotheses and counts
   std::vector<unsigned char> back(back_bytes);
   e = hipGetLastError();
@@ -469,18 +542,30 @@ int plane_fit(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *clou
     PL_LAUNCH(pl_flag_kernel, 20.0 * n, dim3(grid_of((size_t)n + 1)), dim3(kPlBlock), 0, st, pts_o, n, c_final, p.distance_threshold, flags);
     e = scan_flags(ctx, d_tmp, tb, flags, rank, n);
   }
-  if (e == hipSuccess) PL_LAUNCH(pl_index_kernel, 16.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, n, flags, rank, idx, rest);
+  if (e == hipSuccess && !peel) PL_LAUNCH(pl_index_kernel, 16.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, n, flags, rank, idx, rest);
+  if (e == hipSuccess && peel)
+    PL_LAUNCH(pl_peel_kernel, 52.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, pts_o, peel->orig, n, flags, rank, peel->round, peel->pts_next,
+              peel->orig_next, peel->label, shuf, peel->d_m);
   // ---- the second synchronisation: coefficients, count (and the indices, whose number the host does not know yet)
   uint32_t n_in = 0;
   if (e == hipSuccess) e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(fit.coeff, d_coeff, 16, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(&n_in, rank + n, 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && peel) e = hipMemcpyAsync(&peel->m_next, peel->d_m, 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && out_idx) e = hipMemcpyAsync(out_idx, idx, 4ull * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   ++S.host_syncs;
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
   fit.n_in = n_in;
   return OPE_OK;
+}
+
+int plane_fit(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *cloud, const ope_plane_params &p, const int32_t *samples,
+              size_t n_samples, int32_t *out_idx, Fit &fit) {
+  FitBufs B;
+  const hipError_t e = fit_alloc(tmp, ctx->stream, (uint32_t)cloud->n, (uint32_t)p.max_iterations + 1u, samples != nullptr, n_samples, true, B);
+  if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
+  return fit_run(ctx, who, B, cloud, (uint32_t)cloud->n, p, samples, n_samples, out_idx, nullptr, fit);
 }
 
 // a selection, counted
@@ -583,6 +668,89 @@ int ope_plane_segment(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_para
     if (rc != OPE_OK && plane && *plane) { ope_cloud_free(*plane); *plane = nullptr; }
   }
   return rc;
+}
+
+void ope_peel_default_params(ope_peel_params *p) {
+  if (!p) return;
+  p->keep_fraction = 0.3;
+  p->max_planes = 0;
+}
+
+int ope_plane_peel(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_params *plane, const ope_peel_params *peel, size_t cap_planes,
+                   float *coeffs, int32_t *counts, int64_t *iterations, int32_t *label, int32_t *rest_idx, ope_cloud **rest,
+                   ope_peel_result *out) {
+  static const char *who = "ope_plane_peel: ";
+  if (!ctx) return OPE_EINVAL;
+  ctx->plane_stats = ope_plane_stats{};
+  ctx->plane_stats.best = -1;
+  ctx->plane_samples.clear(); ctx->plane_counts.clear(); ctx->plane_coeffs.clear();
+  if (rest) *rest = nullptr;
+  if (out) std::memset(out, 0, sizeof *out);
+  if (!cloud || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
+  ope_plane_params p;
+  { const int rc = check_plane_params(ctx, who, plane, p); if (rc != OPE_OK) return rc; }
+  ope_peel_params q;
+  ope_peel_default_params(&q);
+  if (peel) q = *peel;
+  if (!std::isfinite(q.keep_fraction) || q.keep_fraction < 0.0) return set_err(ctx, OPE_EINVAL, std::string(who) + "keep_fraction must be >= 0 and finite");
+  if (q.max_planes < 0) return set_err(ctx, OPE_EINVAL, std::string(who) + "max_planes must be >= 0");
+  if (cloud->n > (size_t)0x7fffffff) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 2^31 - 1 points");
+  OPE_HIP(ctx, hipSetDevice(ctx->device));
+  TraceRange r(ctx, "plane_peel");
+  CallTmp tmp{ctx->stream, {}};
+  const hipStream_t st = ctx->stream;
+  const uint32_t n0 = (uint32_t)cloud->n;
+  const size_t n1 = std::max<size_t>(n0, 1);
+  // every temporary, once: a fit's buffers for n0 points, the other half of the points' double buffer, both halves of the
+  // original indices, the labels, the remainder's size
+  FitBufs B;
+  hipError_t e = fit_alloc(tmp, st, n0, (uint32_t)p.max_iterations + 1u, false, 0, false, B);
+  float4 *pts_cur = B.pts_o, *pts_nxt = (float4 *)tmp.get(16 * n1, e);
+  int32_t *orig_cur = (int32_t *)tmp.get(4 * n1, e), *orig_nxt = (int32_t *)tmp.get(4 * n1, e);
+  int32_t *d_label = label ? (int32_t *)tmp.get(4 * n1, e) : nullptr;
+  uint32_t *d_m = (uint32_t *)tmp.get(16, e);
+  if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
+  if (n0) PL_LAUNCH(pl_peel_init_kernel, 8.0 * n0, dim3(grid_of(n0)), dim3(kPlBlock), 0, st, n0, orig_cur, d_label);
+  uint32_t m = n0;
+  int32_t n_planes = 0, stop = OPE_PEEL_FRACTION;
+  // objectsegmentationplane.cpp:300-319.  The host knows m from the round's second synchronisation; no cloud is built per round.
+  while ((double)m > q.keep_fraction * (double)n0) {
+    if (q.max_planes > 0 && n_planes >= q.max_planes) { stop = OPE_PEEL_MAX_PLANES; break; }
+    PeelStep step{pts_nxt, orig_cur, orig_nxt, d_label, n_planes, d_m, m};
+    Fit fit;
+    B.pts_o = pts_cur;
+    const int rc = fit_run(ctx, who, B, n_planes == 0 ? cloud : nullptr, m, p, nullptr, 0, nullptr, &step, fit);
+    if (rc != OPE_OK) return rc;
+    if (!fit.found || fit.n_in == 0) { stop = OPE_PEEL_NO_INLIERS; break; }   // (:308-312; nothing was flagged: this half still holds the remainder)
+    if ((size_t)n_planes < cap_planes) {
+      if (coeffs) std::memcpy(coeffs + 4 * (size_t)n_planes, fit.coeff, 16);
+      if (counts) counts[n_planes] = (int32_t)fit.n_in;
+      if (iterations) iterations[n_planes] = ctx->plane_stats.iterations;
+    }
+    ++n_planes;
+    if (step.m_next != m - fit.n_in) return set_err(ctx, OPE_EHIP, std::string(who) + "the remainder's size on the device and the inlier count disagree");
+    m = step.m_next;
+    std::swap(pts_cur, pts_nxt);
+    std::swap(orig_cur, orig_nxt);
+  }
+  // the remainder as indices, the labels, and the one cloud of the call
+  if ((rest_idx && m) || (label && n0)) {
+    if (rest_idx && m) e = hipMemcpyAsync(rest_idx, orig_cur, 4ull * m, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && label && n0) e = hipMemcpyAsync(label, d_label, 4ull * n0, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    ++ctx->plane_stats.host_syncs;
+    if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
+  }
+  if (rest) {
+    const int rc = select_counted(ctx, cloud, orig_cur, m, rest);
+    if (rc != OPE_OK) return rc;
+  }
+  out->n_planes = n_planes;
+  out->n_rest = (int32_t)m;
+  out->stop = stop;
+  out->launches = ctx->plane_stats.launches;
+  out->host_syncs = ctx->plane_stats.host_syncs;
+  return OPE_OK;
 }
 
 int ope_plane_last_stats(const ope_ctx *ctx, ope_plane_stats *out) {
