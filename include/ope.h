@@ -729,6 +729,61 @@ typedef struct {
 } ope_cluster_stats;
 int ope_cluster_last_stats(const ope_ctx *ctx, ope_cluster_stats *out);
 
+/* ---------------- segmentation: smoothness-constrained region growing ---------------- */
+/* SegmentationRegionGrow::getSegmentRegGrow (segmentationregiongrow.cpp:9-82): pcl::RegionGrowing over normals, the reference's
+ * answer to a frame without a table whose objects no plane model separates. */
+typedef struct {
+  int32_t number_of_neighbours;   /* setNumberOfNeighbours: 15 (segmentationregiongrow.cpp:31) */
+  int32_t normals_k;              /* setKSearch of the NormalEstimation: 30 (:25); used only when no normals are passed */
+  double smoothness_threshold;    /* setSmoothnessThreshold: 10.0 / 180.0 * M_PI (:35) */
+  double curvature_threshold;     /* setCurvatureThreshold: 1.0 (:36) */
+  int32_t min_size, max_size;     /* setMinClusterSize / setMaxClusterSize: 500, 1000000 (:28-29) */
+} ope_region_params;
+void ope_region_default_params(ope_region_params *p);
+/* What RegionGrowing::extract returns (PCL 1.7/1.8 region_growing.hpp, smooth mode, residual test off) while no curvature exceeds
+ * the threshold, restated so that it runs in parallel:
+ *   N(u) = the number_of_neighbours nearest finite points of u, u included: the list ope_knn_search returns;
+ *   u -> v  iff  v is in N(u) and !(fabsf(n_v . n_u) < c), the dot product (x*x' + y*y') + z*z' in float without contraction and
+ *            c = (float)cos((double)(float)smoothness_threshold); a NaN product is not < c: a NaN normal passes, as in PCL;
+ *   rank: by curvature ascending, equal curvatures by ORIGINAL index ascending (PCL's std::sort leaves that order
+ *            implementation-defined), a NaN curvature after every other;
+ *   region(v) = the point of smallest rank among those that reach v along the edges, v included: PCL's sequential flood from
+ *            the lowest-ranked unlabelled seed, which with the reference's threshold (1.0 >= every curvature) refuses no seed.
+ *  - a non-finite point is in no region;
+ *  - a region with fewer than min_size or more than max_size points is dropped whole;
+ *  - regions come in seed order (the rank of their seed), NOT by size; the points of a region are ORIGINAL indices, ascending.
+ * normals (n x 3) / curvature (n): host arrays in ORIGINAL order, both or neither.  Passed: used as given (setInputNormals), the
+ * cloud's own are left alone.  Neither: the call runs ope_normals(cloud, normals_k, viewpoint 0 0 0) and leaves its result attached
+ * to the cloud, as that call does.
+ * *n_clusters, out_idx, out_offsets, out_label: the conventions of ope_euclidean_clusters.  An empty cloud gives 0 clusters.
+ * A point with curvature > (float)curvature_threshold makes PCL's flood depend on which points end up as seeds; that rule is not
+ * built: the call counts such points in the launch that reads the curvatures and, if there is one, returns OPE_EINVAL with
+ * *n_clusters = 0 and out_idx, out_offsets, out_label (and out_clouds) untouched.
+ * OPE_EINVAL, nothing launched: number_of_neighbours outside 1..32; normals_k outside 3..32 when no normals are passed; a threshold
+ * that is not finite or a negative smoothness_threshold; min_size < 1; max_size < min_size; only one of normals / curvature;
+ * more than (2^31 - 1) / 32 points.
+ * Synchronous.  Kernel launches booked: 19 + 5 per batch of four propagation sweeps (batches go out until a sweep changes nothing),
+ * + 1 with normals passed in; host synchronisations: 2 + 1 per batch (+ the staged upload of passed normals).  Not booked: the
+ * build of the cloud's own search tree and, when the call estimates the normals, ope_normals with its one synchronisation.
+ * Neither count depends on the number of regions. */
+int ope_region_grow(ope_ctx *ctx, ope_cloud *cloud, const ope_region_params *params, const float *normals, const float *curvature,
+                    size_t max_clusters, size_t *n_clusters, int32_t *out_idx, int32_t *out_offsets, int32_t *out_label);
+/* The same, with each written region also as a new device cloud, exactly what ope_cloud_select(cloud, indices of region k)
+ * builds, normals (the cloud's own) and colours carried: the batched path of ope_euclidean_clusters_cloud (4 more launches, one
+ * more synchronisation).  out_clouds: max_clusters entries; out_idx / out_offsets optional. */
+int ope_region_grow_cloud(ope_ctx *ctx, ope_cloud *cloud, const ope_region_params *params, const float *normals, const float *curvature,
+                          size_t max_clusters, size_t *n_clusters, ope_cloud **out_clouds, int32_t *out_idx, int32_t *out_offsets);
+/* What the last ope_region_grow* call of this context did. */
+typedef struct {
+  int64_t launches;                    /* kernel launches enqueued (a rocPRIM sort or scan, a memset and a copy count as one) */
+  int64_t host_syncs;
+  int64_t sweeps;                      /* propagation rounds until one changed nothing (that one included) */
+  int64_t one_way_edges;               /* edges u -> v without v -> u */
+  int64_t regions_before_size_filter;
+  int64_t refused_curvature;           /* points with curvature > curvature_threshold (non-zero: the call was refused) */
+} ope_region_stats;
+int ope_region_last_stats(const ope_ctx *ctx, ope_region_stats *out);
+
 /* ---------------- segmentation: RANSAC plane fit, polygonal prism, table-top ---------------- */
 /* pcl::SACSegmentation with SACMODEL_PLANE, SAC_RANSAC (getPlaneIndicesAndCoeffSAC, objectsegmentationplane.cpp:36-55).
  * The reference also calls setAxis / setEpsAngle (:44-45); they have no effect on SACMODEL_PLANE in PCL (only the

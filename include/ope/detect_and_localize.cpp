@@ -22,6 +22,11 @@
 // fit, prism, second fit and clusters on the device), then the clusters as --candidates takes them.  Prints
 // `segment plane <n>`, `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
 //
+//   detect_and_localize --frame <model.pcd> <frame.pcd> --region-grow [--seed N] [--self-occluded]
+// A frame whose objects no plane model separates (curved, many-faced, standing free): ope::SegmentationRegionGrow::getSegmentRegGrow
+// (the z crop over [0, 1.2], normals with k = 30, region growing over them on the device), every cluster as --candidates takes
+// them.  Prints `segment crop <n> sweeps <s>`, `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
+//
 //   detect_and_localize --frame <model.pcd> <frame.pcd> --except-plane [--limits x0 x1 y0 y1 z0 z1] [--seed N] [--self-occluded]
 // A frame without a single table (a floor, a wall, a shelf side): ope::ObjectSegmentationPlane::getSegmentedObjectsExceptPlane, its
 // crop (getFiltered) set to the -l limits, planes peeled on the device until at most 30 % of the cropped points are left, the
@@ -59,6 +64,7 @@
 #include "object_tracker.hpp"
 #include "pcd_io.hpp"
 #include "pose_estimator.hpp"
+#include "segmentation_region_grow.hpp"
 
 namespace pcl = ope::compat;
 
@@ -236,6 +242,7 @@ int main(int argc, char **argv) {
   bool segment = false; // --segment: the clusters come from getClusters over the one scene file (the non-plane cloud)
   bool frame = false;   // --frame: the clusters come from getSegmentedObjectsOnPlane over the one scene file (a camera frame)
   bool except_plane = false;   // --except-plane (with --frame): from getSegmentedObjectsExceptPlane instead
+  bool region_grow = false;    // --region-grow (with --frame): from SegmentationRegionGrow::getSegmentRegGrow instead
   float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -245,10 +252,12 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--segment")) { segment = true; candidates = 1; }
     else if (!std::strcmp(argv[i], "--frame")) { frame = true; candidates = 1; }
     else if (!std::strcmp(argv[i], "--except-plane")) except_plane = true;
+    else if (!std::strcmp(argv[i], "--region-grow")) region_grow = true;
     else if (!std::strcmp(argv[i], "--limits") && i + 6 < argc) { for (int d = 0; d < 6; ++d) limits[d] = std::strtof(argv[++i], nullptr); }
     else files.push_back(argv[i]);
   }
   if (except_plane && !frame) { std::fprintf(stderr, "--except-plane goes with --frame\n"); return 2; }
+  if (region_grow && (!frame || except_plane)) { std::fprintf(stderr, "--region-grow goes with --frame and without --except-plane\n"); return 2; }
   if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded] [--candidates | --candidates-loop | --segment | --frame]\n", argv[0]); return 2; }
   typedef ope::PoseEstimator::PointT PointT;
   pcl::PointCloud<PointT>::Ptr cloudSourceOriginal(new pcl::PointCloud<PointT>), cloudSource(new pcl::PointCloud<PointT>);
@@ -304,6 +313,17 @@ int main(int argc, char **argv) {
       std::printf("segment planes %d sizes", objSegPlane.lastPeel().n_planes);
       for (int32_t c : objSegPlane.lastPeelCounts()) std::printf(" %d", c);
       std::printf(" rest %d\n", objSegPlane.lastPeel().n_rest);
+      std::printf("segment clusters %zu sizes", clusters.size());
+      for (const auto &c : clusters) std::printf(" %zu", c->size());
+      std::printf("\n");
+    } else if (frame && region_grow) {
+      pcl::PointCloud<PointT>::Ptr cloudTarget(new pcl::PointCloud<PointT>);
+      if (segment || files.size() != 2 || pcl::io::loadPCDFile(files[1], *cloudTarget) != 0) return 3;
+      ope::SegmentationRegionGrow segRegGrow;
+      segRegGrow.getSegmentRegGrow(cloudTarget);
+      if (segRegGrow.deviceFailed()) return 5;
+      clusters = segRegGrow.getClusters();
+      std::printf("segment crop %zu sweeps %lld\n", segRegGrow.lastCropSize(), (long long)segRegGrow.lastStats().sweeps);
       std::printf("segment clusters %zu sizes", clusters.size());
       for (const auto &c : clusters) std::printf(" %zu", c->size());
       std::printf("\n");

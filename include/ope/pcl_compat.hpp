@@ -888,6 +888,46 @@ template <class PointT> class EuclideanClusterExtraction {
   ope_cluster_params p_{0.0, 1, 0x7fffffff};   // PCL's defaults: no tolerance set (extract refuses), min 1, max INT_MAX
 };
 
+// pcl::RegionGrowing over normals (ope_region_grow), with the setters SegmentationRegionGrow::getSegmentRegGrow calls
+// (segmentationregiongrow.cpp:28-39).  Smooth mode, the residual test off: PCL's defaults, which the reference leaves alone.
+// extract on a cloud with a curvature above the threshold logs ope_region_grow's refusal and returns no clusters.
+template <class PointT, class NormalT = Normal> class RegionGrowing {
+ public:
+  RegionGrowing() { p_.number_of_neighbours = 30; p_.normals_k = 30; p_.smoothness_threshold = 30.0 / 180.0 * M_PI; p_.curvature_threshold = 0.05;
+                    p_.min_size = 1; p_.max_size = 0x7fffffff; }   // PCL's defaults
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &c) { input_ = c; }
+  void setInputNormals(const typename PointCloud<NormalT>::ConstPtr &n) { normals_ = n; }
+  template <class Tree> void setSearchMethod(const Tree &) {}   // accepted, unused: the device walks its own tree
+  void setNumberOfNeighbours(unsigned int k) { p_.number_of_neighbours = (int32_t)k; }
+  void setSmoothnessThreshold(float t) { p_.smoothness_threshold = t; }
+  void setCurvatureThreshold(float c) { p_.curvature_threshold = c; }
+  void setMinClusterSize(int n) { p_.min_size = n; }
+  void setMaxClusterSize(int n) { p_.max_size = n; }
+  void extract(std::vector<PointIndices> &clusters) {
+    clusters.clear();
+    ope_ctx *ctx = default_context();
+    if (!ctx || !input_ || input_->empty() || !normals_ || normals_->size() != input_->size()) return;
+    auto dev = upload(*input_, false);
+    if (!dev->h) return;
+    const size_t n = input_->size();
+    std::vector<float> nrm(3 * n), curv(n);
+    for (size_t i = 0; i < n; ++i) {
+      const NormalT &q = normals_->points[i];
+      nrm[3 * i] = q.normal_x; nrm[3 * i + 1] = q.normal_y; nrm[3 * i + 2] = q.normal_z;
+      curv[i] = q.curvature;
+    }
+    std::vector<int32_t> idx(n), off(n + 1);
+    size_t k = 0;
+    if (ope_region_grow(ctx, dev->h, &p_, nrm.data(), curv.data(), n, &k, idx.data(), off.data(), nullptr) != OPE_OK) { log_error("RegionGrowing", ctx); return; }
+    clusters.resize(k);
+    for (size_t c = 0; c < k; ++c) clusters[c].indices.assign(idx.begin() + off[c], idx.begin() + off[c + 1]);
+  }
+ private:
+  typename PointCloud<PointT>::ConstPtr input_;
+  typename PointCloud<NormalT>::ConstPtr normals_;
+  ope_region_params p_;
+};
+
 // ------------------------------------------------------------------------------------------ table-top segmentation
 // The classes ObjectSegmentationPlane uses (objectsegmentationplane.cpp:36-71, 95-107, 169-214), with its call shapes.
 struct ModelCoefficients {

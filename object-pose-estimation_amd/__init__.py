@@ -229,6 +229,28 @@ class ClusterStats(C.Structure):
     ]
 
 
+class RegionParams(C.Structure):
+    _fields_ = [
+        ("number_of_neighbours", C.c_int32),
+        ("normals_k", C.c_int32),
+        ("smoothness_threshold", C.c_double),
+        ("curvature_threshold", C.c_double),
+        ("min_size", C.c_int32),
+        ("max_size", C.c_int32),
+    ]
+
+
+class RegionStats(C.Structure):
+    _fields_ = [
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+        ("sweeps", C.c_int64),
+        ("one_way_edges", C.c_int64),
+        ("regions_before_size_filter", C.c_int64),
+        ("refused_curvature", C.c_int64),
+    ]
+
+
 class PlaneParams(C.Structure):
     _fields_ = [
         ("distance_threshold", C.c_double),
@@ -463,6 +485,11 @@ ABI = [
     ("ope_euclidean_clusters_cloud", C.c_int, [_vp, _vp, C.POINTER(ClusterParams), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_vp),
                                                 _ip, _ip]),
     ("ope_cluster_last_stats", C.c_int, [_vp, C.POINTER(ClusterStats)]),
+    ("ope_region_default_params", None, [C.POINTER(RegionParams)]),
+    ("ope_region_grow", C.c_int, [_vp, _vp, C.POINTER(RegionParams), _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t), _ip, _ip, _ip]),
+    ("ope_region_grow_cloud", C.c_int, [_vp, _vp, C.POINTER(RegionParams), _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_vp),
+                                        _ip, _ip]),
+    ("ope_region_last_stats", C.c_int, [_vp, C.POINTER(RegionStats)]),
     ("ope_plane_default_params", None, [C.POINTER(PlaneParams)]),
     ("ope_plane_segment", C.c_int, [_vp, _vp, C.POINTER(PlaneParams), _ip, C.c_size_t, _fp, _ip, C.POINTER(C.c_size_t), C.POINTER(_vp),
                                      C.POINTER(_vp)]),
@@ -988,6 +1015,52 @@ class Context:
         s = ClusterStats()
         self._chk(lib().ope_cluster_last_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in ClusterStats._fields_}
+
+    def region_grow(self, cloud, params: "RegionParams | None" = None, normals=None, curvature=None, max_clusters: int | None = None,
+                    clouds: bool = False):
+        """ope_region_grow: pcl::RegionGrowing over normals (segmentationregiongrow.cpp:9-82) of a Cloud (or an (n, 3) array,
+        uploaded first).  normals (n, 3) / curvature (n,): both or neither; neither: estimated with params.normals_k and left on
+        the cloud.  Returns (clusters, labels, stats): the regions in seed order as int32 arrays of ORIGINAL indices, ascending;
+        labels (n,) the rank of each point's written region or -1; stats as region_stats().  With clouds=True the regions also
+        come as device clouds: (clouds, clusters, stats)."""
+        if not isinstance(cloud, Cloud):
+            cloud = self.upload(cloud)
+        p = params if params is not None else default_region_params()
+        n = cloud.n
+        nrm = cur = None
+        if normals is not None:
+            nrm = _f32(normals, 3)
+            if len(nrm) != n:
+                raise ValueError("normals length mismatch")
+        if curvature is not None:
+            cur = np.ascontiguousarray(curvature, np.float32).reshape(-1)
+            if len(cur) != n:
+                raise ValueError("curvature length mismatch")
+        pn = _p(nrm, _fp) if nrm is not None else None
+        pc = _p(cur, _fp) if cur is not None else None
+        cap = n if max_clusters is None else int(max_clusters)
+        idx = np.empty(max(n, 1), np.int32)
+        off = np.zeros(cap + 1, np.int32)
+        k = C.c_size_t(0)
+        if clouds:
+            hs = (_vp * max(cap, 1))()
+            self._chk(lib().ope_region_grow_cloud(self.h, cloud.h, C.byref(p), pn, pc, cap, C.byref(k), hs, _p(idx, _ip), _p(off, _ip)))
+        else:
+            lab = np.empty(max(n, 1), np.int32)
+            self._chk(lib().ope_region_grow(self.h, cloud.h, C.byref(p), pn, pc, cap, C.byref(k), _p(idx, _ip), _p(off, _ip), _p(lab, _ip)))
+        kw = min(k.value, cap)
+        self.last_cluster_count = k.value
+        indices = [idx[off[i]:off[i + 1]].copy() for i in range(kw)]
+        if clouds:
+            return [Cloud(self, _vp(hs[i]), len(indices[i])) for i in range(kw)], indices, self.region_stats()
+        return indices, lab[:n].copy(), self.region_stats()
+
+    def region_stats(self) -> dict:
+        """ope_region_last_stats: launches, host synchronisations, sweeps, one-way edges, regions before the size filter and the
+        points refused for their curvature, of the last region_grow."""
+        s = RegionStats()
+        self._chk(lib().ope_region_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in RegionStats._fields_}
 
     def plane_segment(self, cloud, params: "PlaneParams | None" = None, samples=None, want_clouds: bool = False) -> "PlaneOut":
         """ope_plane_segment: pcl::SACSegmentation (SACMODEL_PLANE, SAC_RANSAC; objectsegmentationplane.cpp:36-55) of a Cloud (or
@@ -1532,6 +1605,16 @@ def default_cluster_params(**kw) -> ClusterParams:
     """ope_cluster_default_params (tolerance 0.05, min 300, max 100000: objectsegmentationplane.cpp:85-87)."""
     p = ClusterParams()
     lib().ope_cluster_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_region_params(**kw) -> RegionParams:
+    """ope_region_default_params (15 neighbours, normals k 30, smoothness 10 degrees, curvature 1.0, sizes 500 .. 1000000:
+    segmentationregiongrow.cpp:25-36)."""
+    p = RegionParams()
+    lib().ope_region_default_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -558,6 +558,86 @@ int cluster_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *c
 }
 
 }  // namespace
+
+// The tail of the _cloud forms (ope_euclidean_clusters_cloud, ope_region_grow_cloud): the kw written clusters (host offsets `off`,
+// device offsets d_roff, packed ORIGINAL indices d_idx) as new device clouds, gathered, boxed, Morton-sorted and scattered in
+// batched launches.  d_pts_by_o / d_pos_by_o: the input cloud's points and sorted positions by original index.
+#define CB_LAUNCH(name, bytes, ...)                  \
+  do {                                               \
+    KernelTimer kt_(ctx, #name, (double)(bytes));    \
+    hipLaunchKernelGGL(name, __VA_ARGS__);           \
+    ++*launches;                                     \
+  } while (0)
+#define CB_PRIM(label, call)                          \
+  do {                                                \
+    if (e == hipSuccess) {                            \
+      KernelTimer kt_(ctx, label, 0.0);               \
+      e = (call);                                     \
+      ++*launches;                                    \
+    }                                                 \
+  } while (0)
+int clusters_build_clouds(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *cloud, size_t kw, const std::vector<uint32_t> &off,
+                          const int32_t *d_idx, const uint32_t *d_roff, const float4 *d_pts, const uint32_t *d_pos, ope_cloud **out_clouds,
+                          int64_t *launches, int64_t *host_syncs) {
+  const uint32_t total = off[kw];
+  // the new clouds, then every cluster's gather, box, Morton sort and scatter in batched launches
+  std::vector<ope_cloud *> made(kw, nullptr);
+  std::vector<ClusterOut> outs(kw);
+  hipError_t e = hipSuccess;
+  for (size_t k = 0; k < kw && e == hipSuccess; ++k) {
+    ope_cloud *c = new ope_cloud();
+    made[k] = c;
+    c->ctx = ctx;
+    c->n = off[k + 1] - off[k];
+    c->host_valid = false;
+    e = hipMalloc((void **)&c->d_xyzw, sizeof(float4) * std::max<size_t>(c->n, 1));
+    if (e == hipSuccess && cloud->d_nrm) e = hipMalloc((void **)&c->d_nrm, sizeof(float4) * std::max<size_t>(c->n, 1));
+    if (e == hipSuccess && cloud->d_rgb) e = hipMalloc((void **)&c->d_rgb, 4 * std::max<size_t>(c->n, 1));
+    outs[k] = ClusterOut{c->d_xyzw, c->d_nrm, c->d_rgb};
+  }
+  auto *d_outs = (ClusterOut *)tmp.get(sizeof(ClusterOut) * kw, e);
+  auto *raw = (float4 *)tmp.get(16ull * total, e);
+  auto *clof = (uint32_t *)tmp.get(4ull * total, e);
+  auto *bb = (uint32_t *)tmp.get(32ull * kw, e);
+  auto *mkey = (unsigned long long *)tmp.get(8ull * total, e), *mkey2 = (unsigned long long *)tmp.get(8ull * total, e);
+  auto *mval = (uint32_t *)tmp.get(4ull * total, e), *mval2 = (uint32_t *)tmp.get(4ull * total, e);
+  const int mbits = 31 + bits_for(cloud->n);
+  size_t tb = 0;
+  if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tb, mkey, mkey2, mval, mval2, total, 0, mbits, ctx->stream);
+  void *d_tmp = tmp.get(std::max<size_t>(tb, 16), e);
+  if (e == hipSuccess) { e = h2d_copy(ctx->stream, d_outs, outs.data(), sizeof(ClusterOut) * kw); ++*launches; }
+  const hipStream_t st = ctx->stream;
+  if (e == hipSuccess) {
+    CB_LAUNCH(cc_gather_box_kernel, 24.0 * total, dim3((unsigned)kw), dim3(kCcBlock), 0, st, d_idx, d_roff, d_pts, raw, clof, bb);
+    CB_LAUNCH(cc_morton_key_kernel, 32.0 * total, dim3(grid_of(total)), dim3(kCcBlock), 0, st, raw, clof, bb, total, mkey, mval);
+    CB_PRIM("cc_sort_morton", rocprim::radix_sort_pairs(d_tmp, tb, mkey, mkey2, mval, mval2, total, 0, mbits, st));
+  }
+  if (e == hipSuccess)
+    CB_LAUNCH(cc_cloud_scatter_kernel, 48.0 * total, dim3(grid_of(total)), dim3(kCcBlock), 0, st, mkey2, mval2, d_roff, raw, d_idx, d_pos,
+              cloud->d_nrm, (const uint32_t *)cloud->d_rgb, d_outs, total);
+  std::vector<uint32_t> h_bb(8 * kw);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_bb.data(), bb, 32ull * kw, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  ++*host_syncs;
+  if (e != hipSuccess) {
+    for (ope_cloud *c : made) ope_cloud_free(c);
+    return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
+  }
+  auto unkey = [](uint32_t k) { const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; std::memcpy(&f, &u, 4); return f; };
+  for (size_t k = 0; k < kw; ++k) {
+    ope_cloud *c = made[k];
+    c->n_valid = h_bb[8 * k + 6];
+    for (int d = 0; d < 3; ++d) {
+      c->bb_lo[d] = c->n_valid ? unkey(h_bb[8 * k + d]) : 0.f;
+      c->bb_hi[d] = c->n_valid ? unkey(h_bb[8 * k + 3 + d]) : 0.f;
+    }
+    out_clouds[k] = c;
+  }
+  return OPE_OK;
+}
+#undef CB_LAUNCH
+#undef CB_PRIM
+
 }  // namespace ope
 
 using namespace ope;
@@ -610,61 +690,10 @@ int ope_euclidean_clusters_cloud(ope_ctx *ctx, const ope_cloud *cloud, const ope
   const int32_t *d_idx; const uint32_t *d_roff, *d_pos; const float4 *d_pts;
   int rc = cluster_core(ctx, tmp, who, cloud, p, max_clusters, out_idx != nullptr, out_idx, out_offsets, nullptr, res, &d_idx, &d_roff, &d_pts, &d_pos);
   if (rc != OPE_OK) return rc;
-  const size_t kw = res.kw;
-  const uint32_t total = res.off[kw];
-  if (kw == 0) { *n_clusters = res.K; return OPE_OK; }
-  // the new clouds, then every cluster's gather, box, Morton sort and scatter in batched launches
-  std::vector<ope_cloud *> made(kw, nullptr);
-  std::vector<ClusterOut> outs(kw);
-  hipError_t e = hipSuccess;
-  for (size_t k = 0; k < kw && e == hipSuccess; ++k) {
-    ope_cloud *c = new ope_cloud();
-    made[k] = c;
-    c->ctx = ctx;
-    c->n = res.off[k + 1] - res.off[k];
-    c->host_valid = false;
-    e = hipMalloc((void **)&c->d_xyzw, sizeof(float4) * std::max<size_t>(c->n, 1));
-    if (e == hipSuccess && cloud->d_nrm) e = hipMalloc((void **)&c->d_nrm, sizeof(float4) * std::max<size_t>(c->n, 1));
-    if (e == hipSuccess && cloud->d_rgb) e = hipMalloc((void **)&c->d_rgb, 4 * std::max<size_t>(c->n, 1));
-    outs[k] = ClusterOut{c->d_xyzw, c->d_nrm, c->d_rgb};
-  }
-  auto *d_outs = (ClusterOut *)tmp.get(sizeof(ClusterOut) * kw, e);
-  auto *raw = (float4 *)tmp.get(16ull * total, e);
-  auto *clof = (uint32_t *)tmp.get(4ull * total, e);
-  auto *bb = (uint32_t *)tmp.get(32ull * kw, e);
-  auto *mkey = (unsigned long long *)tmp.get(8ull * total, e), *mkey2 = (unsigned long long *)tmp.get(8ull * total, e);
-  auto *mval = (uint32_t *)tmp.get(4ull * total, e), *mval2 = (uint32_t *)tmp.get(4ull * total, e);
-  const int mbits = 31 + bits_for(cloud->n);
-  size_t tb = 0;
-  if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, tb, mkey, mkey2, mval, mval2, total, 0, mbits, ctx->stream);
-  void *d_tmp = tmp.get(std::max<size_t>(tb, 16), e);
-  if (e == hipSuccess) { e = h2d_copy(ctx->stream, d_outs, outs.data(), sizeof(ClusterOut) * kw); ++ctx->cluster_stats.launches; }
-  const hipStream_t st = ctx->stream;
-  if (e == hipSuccess) {
-    CC_LAUNCH(cc_gather_box_kernel, 24.0 * total, dim3((unsigned)kw), dim3(kCcBlock), 0, st, d_idx, d_roff, d_pts, raw, clof, bb);
-    CC_LAUNCH(cc_morton_key_kernel, 32.0 * total, dim3(grid_of(total)), dim3(kCcBlock), 0, st, raw, clof, bb, total, mkey, mval);
-    CC_PRIM("cc_sort_morton", rocprim::radix_sort_pairs(d_tmp, tb, mkey, mkey2, mval, mval2, total, 0, mbits, st));
-  }
-  if (e == hipSuccess)
-    CC_LAUNCH(cc_cloud_scatter_kernel, 48.0 * total, dim3(grid_of(total)), dim3(kCcBlock), 0, st, mkey2, mval2, d_roff, raw, d_idx, d_pos,
-              cloud->d_nrm, (const uint32_t *)cloud->d_rgb, d_outs, total);
-  std::vector<uint32_t> h_bb(8 * kw);
-  if (e == hipSuccess) e = hipMemcpyAsync(h_bb.data(), bb, 32ull * kw, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  ++ctx->cluster_stats.host_syncs;
-  if (e != hipSuccess) {
-    for (ope_cloud *c : made) ope_cloud_free(c);
-    return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  }
-  auto unkey = [](uint32_t k) { const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; std::memcpy(&f, &u, 4); return f; };
-  for (size_t k = 0; k < kw; ++k) {
-    ope_cloud *c = made[k];
-    c->n_valid = h_bb[8 * k + 6];
-    for (int d = 0; d < 3; ++d) {
-      c->bb_lo[d] = c->n_valid ? unkey(h_bb[8 * k + d]) : 0.f;
-      c->bb_hi[d] = c->n_valid ? unkey(h_bb[8 * k + 3 + d]) : 0.f;
-    }
-    out_clouds[k] = c;
+  if (res.kw > 0) {
+    rc = clusters_build_clouds(ctx, tmp, who, cloud, res.kw, res.off, d_idx, d_roff, d_pts, d_pos, out_clouds, &ctx->cluster_stats.launches,
+                               &ctx->cluster_stats.host_syncs);
+    if (rc != OPE_OK) return rc;
   }
   *n_clusters = res.K;
   return OPE_OK;

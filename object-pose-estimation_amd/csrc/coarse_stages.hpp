@@ -45,6 +45,13 @@ struct CallTmp {
   ~CallTmp() { for (void *q : ps) tmp_free(st, q); }
 };
 
+// clusters.hip: the kw written clusters of a segmentation (host offsets `off`, device offsets d_roff, packed ORIGINAL indices d_idx
+// into `cloud`) as new device clouds, each what ope_cloud_select builds, in batched launches and one synchronisation (both are
+// added to *launches / *host_syncs).  d_pts_by_o / d_pos_by_o: the cloud's points and sorted positions by original index.
+int clusters_build_clouds(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *cloud, size_t kw, const std::vector<uint32_t> &off,
+                          const int32_t *d_idx, const uint32_t *d_roff, const float4 *d_pts_by_o, const uint32_t *d_pos_by_o,
+                          ope_cloud **out_clouds, int64_t *launches, int64_t *host_syncs);
+
 // Uniform sampling of nseg segments (d_segs, d_off: nseg + 1 point offsets, total points): one segmented radix sort, PCL's
 // survivor rule per voxel run, one scan.  *d_kp (total + 1 float4): the key points packed by segment (w = original index);
 // *d_key_off (nseg + 1): first slot of every segment.  key_off receives *d_key_off on the host: the call's one

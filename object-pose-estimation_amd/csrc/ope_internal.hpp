@@ -273,6 +273,7 @@ struct ope_ctx {
   double last_fpfh_mean_neighbours = 0.0;
 
   ope_cluster_stats cluster_stats{};   // what the last ope_euclidean_clusters* call did (clusters.hip)
+  ope_region_stats region_stats{};     // what the last ope_region_grow* call did (region_grow.hip)
 
   // the last ope_plane_segment (plane.hip): what it did, and its hypotheses in drawing order (ope_plane_last_hypotheses)
   ope_plane_stats plane_stats{};
