@@ -1072,6 +1072,58 @@ typedef struct {
 } ope_mls_upsample_stats;
 int ope_mls_upsample_last_stats(const ope_ctx *ctx, ope_mls_upsample_stats *out);
 
+/* ---------------- recognition: Viewpoint Feature Histograms and chi-square matching ---------------- */
+/* ObjectDetection (BuildModel/src/objectdetection.cpp): getVfhFeature computes k = 30 normals and one pcl::VFHEstimation signature
+ * of 308 bins per cloud; getObjectName takes the 15 nearest rows of a table of trained signatures by chi-square distance.
+ * The signature restates pcl::VFHEstimation::computeFeature of PCL 1.7.x with its defaults (normalize_bins_ on,
+ * normalize_distances_ off, size_component_ off): bins [0, 45) f1, [45, 90) f2, [90, 135) f3, [135, 180) f4 (zero under the
+ * defaults), [180, 308) the viewpoint component.  use_given_centroid / use_given_normal are setUseGivenCentroid /
+ * setUseGivenNormal with setCentroidToUse / setNormalToUse; they apply to every cluster of the call. */
+typedef struct {
+  int32_t normals_k;           /* 30 (objectdetection.cpp:17): NormalEstimation of a cloud that carries no normals */
+  float viewpoint[3];          /* 0 0 0 (setViewPoint) */
+  int32_t use_given_centroid;  /* 0 */
+  float centroid[3];
+  int32_t use_given_normal;    /* 0 */
+  float normal[3];
+} ope_vfh_params;
+void ope_vfh_default_params(ope_vfh_params *p);
+/* One signature per cluster, all clusters in the same launches: out308 has n x 308 floats.  counts_opt (n x 308 int32): the hits of
+ * every bin, whose replayed additions of hist_incr are the signature.  bins_opt (4 bytes per point, the clusters' points packed in
+ * call order, each cluster in its ORIGINAL order): the f1, f2, f3 bins of the point's pair with the centroid (0xFF each when
+ * computePairFeatures rejects the pair) and its viewpoint bin.
+ * A cluster that carries normals is taken with them; one that does not gets ope_normals(normals_k, viewpoint 0 0 0), left attached.
+ * An empty cluster gives a zero row (stats.empty_clouds).  OPE_EINVAL, nothing launched: n == 0, a NULL cluster, a cluster with a
+ * non-finite point, normals attached with ope_cloud_set_normals that are not finite, normals_k outside 3..32, non-finite
+ * parameters.  Normals written on the device (ope_normals, MLS) are checked in the first launch: OPE_EINVAL after the call's
+ * synchronisation if one is not finite, the outputs then undefined.
+ * Launches and host synchronisations do not depend on the number of clusters or their sizes (one synchronisation, at the end),
+ * except: one ope_normals per cluster without normals, and one more wait when the cluster table exceeds 4 KiB (~100 clusters). */
+int ope_vfh_batch(ope_ctx *ctx, size_t n, ope_cloud *const *clusters, const ope_vfh_params *params, float *out308, int32_t *counts_opt,
+                  unsigned char *bins_opt);
+/* What the last ope_vfh_batch / ope_vfh_match / ope_vfh_recognise of this context did. */
+typedef struct {
+  int64_t points;             /* of all clusters */
+  int64_t rejected_pairs;     /* points whose pair with the centroid computePairFeatures rejected */
+  int64_t normals_estimated;  /* clusters whose normals the call estimated */
+  int64_t empty_clouds;
+  int64_t launches;           /* kernels and memsets, booked along the call's path (ope_normals not included) */
+  int64_t host_syncs;
+} ope_vfh_stats;
+int ope_vfh_last_stats(const ope_ctx *ctx, ope_vfh_stats *out);
+/* A table of m trained signatures (rows: m x 308 finite floats), kept on the device.  OPE_EINVAL for m == 0. */
+typedef struct ope_vfh_db ope_vfh_db;
+int ope_vfh_db_create(ope_ctx *ctx, const float *rows, size_t m, ope_vfh_db **db);
+void ope_vfh_db_free(ope_vfh_db *db);
+size_t ope_vfh_db_size(const ope_vfh_db *db);
+/* The k nearest rows of every query (q x 308 finite floats) by flann::ChiSquareDistance, fp32 in dimension order: out_idx /
+ * out_dist are q x k, nearest first, equal distances by ascending row; past m: -1 / +inf.  1 <= k <= 16.  This is EXACT search:
+ * the reference's KDTreeIndexParams(1) with 512 checks is FLANN's approximate search over a randomised tree. */
+int ope_vfh_match(ope_ctx *ctx, const ope_vfh_db *db, const float *queries308, size_t q, int k, int32_t *out_idx, float *out_dist);
+/* ope_vfh_batch followed by ope_vfh_match with the signatures never leaving the device; out308_opt: the signatures as well. */
+int ope_vfh_recognise(ope_ctx *ctx, const ope_vfh_db *db, size_t n, ope_cloud *const *clusters, const ope_vfh_params *params, int k,
+                      float *out308_opt, int32_t *out_idx, float *out_dist);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,11 @@
 // clusters of the remainder as --candidates takes them.  Prints `segment planes <k> sizes <c0> <c1> ... rest <m>`,
 // `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
 //
+//   ... --recognise <train_dir>   (with --candidates, --candidates-loop, --segment or --frame)
+// Before the pose stage, ope::ObjectDetection::getObjectNames over every cluster in one call against the table under <train_dir>
+// (training_data.list / training_data.f32).  Prints `recognise <i> <name> <distance>` per cluster: the name getObjectName gives
+// and the distance it compares with 120 (the reference's "distance of 1-NN", read from neighbour [1]).  Nothing else changes.
+//
 //   detect_and_localize --track <model.pcd> --frame <a.pcd> [<b.pcd> ...] [--frame ...] [--seed N] [--self-occluded] [--time]
 //   detect_and_localize --track-loop <model.pcd> --frame ... (same)
 // DetectAndLocalize's per-frame policy (rosinterface.cpp:226-313) over a sequence of camera frames, one --frame per frame with
@@ -60,6 +65,7 @@
 #include <chrono>
 
 #include "data_grabber.hpp"
+#include "object_detection.hpp"
 #include "object_segmentation_plane.hpp"
 #include "object_tracker.hpp"
 #include "pcd_io.hpp"
@@ -243,9 +249,11 @@ int main(int argc, char **argv) {
   bool frame = false;   // --frame: the clusters come from getSegmentedObjectsOnPlane over the one scene file (a camera frame)
   bool except_plane = false;   // --except-plane (with --frame): from getSegmentedObjectsExceptPlane instead
   bool region_grow = false;    // --region-grow (with --frame): from SegmentationRegionGrow::getSegmentRegGrow instead
+  std::string recognise;       // --recognise <train_dir>: name every cluster before the pose stage
   float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
+    else if (!std::strcmp(argv[i], "--recognise") && i + 1 < argc) recognise = argv[++i];
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--candidates")) candidates = 1;
     else if (!std::strcmp(argv[i], "--candidates-loop")) candidates = 2;
@@ -258,6 +266,7 @@ int main(int argc, char **argv) {
   }
   if (except_plane && !frame) { std::fprintf(stderr, "--except-plane goes with --frame\n"); return 2; }
   if (region_grow && (!frame || except_plane)) { std::fprintf(stderr, "--region-grow goes with --frame and without --except-plane\n"); return 2; }
+  if (!recognise.empty() && !candidates) { std::fprintf(stderr, "--recognise goes with --candidates, --candidates-loop, --segment or --frame\n"); return 2; }
   if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded] [--candidates | --candidates-loop | --segment | --frame]\n", argv[0]); return 2; }
   typedef ope::PoseEstimator::PointT PointT;
   pcl::PointCloud<PointT>::Ptr cloudSourceOriginal(new pcl::PointCloud<PointT>), cloudSource(new pcl::PointCloud<PointT>);
@@ -352,6 +361,14 @@ int main(int argc, char **argv) {
     for (size_t k = 1; !segment && !frame && k < files.size(); ++k) {
       clusters.emplace_back(new pcl::PointCloud<PointT>);
       if (pcl::io::loadPCDFile(files[k], *clusters.back()) != 0) return 3;
+    }
+    if (!recognise.empty()) {
+      ope::ObjectDetection objDetection;
+      if (!objDetection.loadTrainData(recognise)) return 6;
+      std::vector<std::string> names;
+      std::vector<float> dist;
+      if (!clusters.empty() && !objDetection.getObjectNames(clusters, names, &dist)) return 5;
+      for (size_t i = 0; i < names.size(); ++i) std::printf("recognise %zu %s %.9g\n", i, names[i].c_str(), (double)dist[i]);
     }
     double fitnessScore = 10.0, alignedStrength = 0.0;
     int selected = -1;

@@ -44,6 +44,7 @@ struct alignas(16) PointXYZRGBNormal {
   float rgb = 0.f, curvature = 0.f, pad_[2] = {0, 0};
 };
 struct FPFHSignature33 { float histogram[33]; };
+struct VFHSignature308 { float histogram[308]; };
 struct Correspondence { int index_query = 0; int index_match = -1; float distance = FLT_MAX; };
 typedef std::vector<Correspondence> Correspondences;
 static_assert(sizeof(PointXYZ) == 16 && sizeof(Normal) == 32 && sizeof(PointXYZRGB) == 32 &&
@@ -926,6 +927,46 @@ template <class PointT, class NormalT = Normal> class RegionGrowing {
   typename PointCloud<PointT>::ConstPtr input_;
   typename PointCloud<NormalT>::ConstPtr normals_;
   ope_region_params p_;
+};
+
+// pcl::VFHEstimation with the call shapes ObjectDetection::getVfhFeature uses (objectdetection.cpp:24-27) and PCL's given centroid /
+// normal: one signature per cloud (ope_vfh_batch of one cluster).  The bin layout and normalisation are PCL's defaults; the
+// setters that would change them (setNormalizeBins, setNormalizeDistance, setFillSizeComponent) do not exist here.
+template <class PointInT, class PointNT = Normal, class PointOutT = VFHSignature308> class VFHEstimation {
+ public:
+  VFHEstimation() { ope_vfh_default_params(&p_); }
+  void setInputCloud(const typename PointCloud<PointInT>::ConstPtr &c) { input_ = c; }
+  void setInputNormals(const typename PointCloud<PointNT>::ConstPtr &n) { normals_ = n; }
+  template <class Tree> void setSearchMethod(const Tree &) {}   // accepted, unused: VFH takes the whole cloud
+  void setViewPoint(float x, float y, float z) { p_.viewpoint[0] = x; p_.viewpoint[1] = y; p_.viewpoint[2] = z; }
+  void setUseGivenCentroid(bool use) { p_.use_given_centroid = use ? 1 : 0; }
+  void setUseGivenNormal(bool use) { p_.use_given_normal = use ? 1 : 0; }
+  template <class V3> void setCentroidToUse(const V3 &c) { p_.centroid[0] = c.v[0]; p_.centroid[1] = c.v[1]; p_.centroid[2] = c.v[2]; }
+  template <class V3> void setNormalToUse(const V3 &n) { p_.normal[0] = n.v[0]; p_.normal[1] = n.v[1]; p_.normal[2] = n.v[2]; }
+  void compute(PointCloud<PointOutT> &out) {
+    out.clear();
+    ope_ctx *ctx = default_context();
+    if (!ctx || !input_ || !normals_ || normals_->size() != input_->size()) return;
+    auto dev = upload(*input_, false);
+    if (!dev->h) return;
+    const size_t n = input_->size();
+    std::vector<float> nrm(3 * n + 3);
+    for (size_t i = 0; i < n; ++i) {
+      const PointNT &q = normals_->points[i];
+      nrm[3 * i] = q.normal_x; nrm[3 * i + 1] = q.normal_y; nrm[3 * i + 2] = q.normal_z;
+    }
+    ope_cloud *cl = dev->h;
+    PointOutT sig;
+    if (ope_cloud_set_normals(ctx, cl, nrm.data()) != OPE_OK || ope_vfh_batch(ctx, 1, &cl, &p_, sig.histogram, nullptr, nullptr) != OPE_OK) {
+      log_error("VFHEstimation", ctx);
+      return;
+    }
+    out.push_back(sig);   // "We only output _1_ signature"
+  }
+ private:
+  typename PointCloud<PointInT>::ConstPtr input_;
+  typename PointCloud<PointNT>::ConstPtr normals_;
+  ope_vfh_params p_;
 };
 
 // ------------------------------------------------------------------------------------------ table-top segmentation

@@ -251,6 +251,28 @@ class RegionStats(C.Structure):
     ]
 
 
+class VfhParams(C.Structure):
+    _fields_ = [
+        ("normals_k", C.c_int32),
+        ("viewpoint", C.c_float * 3),
+        ("use_given_centroid", C.c_int32),
+        ("centroid", C.c_float * 3),
+        ("use_given_normal", C.c_int32),
+        ("normal", C.c_float * 3),
+    ]
+
+
+class VfhStats(C.Structure):
+    _fields_ = [
+        ("points", C.c_int64),
+        ("rejected_pairs", C.c_int64),
+        ("normals_estimated", C.c_int64),
+        ("empty_clouds", C.c_int64),
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+    ]
+
+
 class PlaneParams(C.Structure):
     _fields_ = [
         ("distance_threshold", C.c_double),
@@ -490,6 +512,14 @@ ABI = [
     ("ope_region_grow_cloud", C.c_int, [_vp, _vp, C.POINTER(RegionParams), _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_vp),
                                         _ip, _ip]),
     ("ope_region_last_stats", C.c_int, [_vp, C.POINTER(RegionStats)]),
+    ("ope_vfh_default_params", None, [C.POINTER(VfhParams)]),
+    ("ope_vfh_batch", C.c_int, [_vp, C.c_size_t, C.POINTER(_vp), C.POINTER(VfhParams), _fp, _ip, _vp]),
+    ("ope_vfh_last_stats", C.c_int, [_vp, C.POINTER(VfhStats)]),
+    ("ope_vfh_db_create", C.c_int, [_vp, _fp, C.c_size_t, C.POINTER(_vp)]),
+    ("ope_vfh_db_free", None, [_vp]),
+    ("ope_vfh_db_size", C.c_size_t, [_vp]),
+    ("ope_vfh_match", C.c_int, [_vp, _vp, _fp, C.c_size_t, C.c_int, _ip, _fp]),
+    ("ope_vfh_recognise", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(VfhParams), C.c_int, _fp, _ip, _fp]),
     ("ope_plane_default_params", None, [C.POINTER(PlaneParams)]),
     ("ope_plane_segment", C.c_int, [_vp, _vp, C.POINTER(PlaneParams), _ip, C.c_size_t, _fp, _ip, C.POINTER(C.c_size_t), C.POINTER(_vp),
                                      C.POINTER(_vp)]),
@@ -1062,6 +1092,67 @@ class Context:
         self._chk(lib().ope_region_last_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in RegionStats._fields_}
 
+    # ---- recognition (vfh.hip)
+    def _vfh_clusters(self, clusters):
+        cl = [c if isinstance(c, Cloud) else self.upload(c) for c in clusters]
+        hs = (_vp * max(len(cl), 1))(*[c.h for c in cl])
+        return cl, hs
+
+    def vfh(self, clusters, params: "VfhParams | None" = None, want_counts: bool = False, want_bins: bool = False):
+        """ope_vfh_batch: one pcl::VFHEstimation signature (308 bins, PCL's defaults) per cluster, every cluster in the same
+        launches.  clusters: Clouds (or (n, 3) arrays, uploaded first); a cloud without normals gets the k = params.normals_k
+        estimate, left on it.  Returns the (n, 308) float32 signatures; with want_counts / want_bins a tuple (signatures, counts
+        (n, 308) int32 or None, bins (total points, 4) uint8 or None): per point the f1, f2, f3 bins (255: rejected pair) and the
+        viewpoint bin, clusters packed in call order, each in its original order."""
+        cl, hs = self._vfh_clusters(clusters)
+        n = len(cl)
+        p = params if params is not None else default_vfh_params()
+        out = np.zeros((n, 308), np.float32)
+        counts = np.zeros((n, 308), np.int32) if want_counts else None
+        bins = np.zeros((max(sum(c.n for c in cl), 1), 4), np.uint8) if want_bins else None
+        self._chk(lib().ope_vfh_batch(self.h, n, hs, C.byref(p), _p(out, _fp), _p(counts, _ip), _p(bins, _vp)))
+        if not (want_counts or want_bins):
+            return out
+        return out, counts, (bins[:sum(c.n for c in cl)] if bins is not None else None)
+
+    def vfh_db(self, rows) -> "VfhDb":
+        """ope_vfh_db_create: a table of trained signatures (m, 308) kept on the device."""
+        rows = _f32(rows, 308)
+        h = _vp()
+        self._chk(lib().ope_vfh_db_create(self.h, _p(rows, _fp), len(rows), C.byref(h)))
+        return VfhDb(self, h, len(rows))
+
+    def vfh_match(self, db: "VfhDb | None", queries, k: int = 15):
+        """ope_vfh_match: the k nearest rows of every query (q, 308) by chi-square distance, exact; (indices (q, k) int32,
+        distances (q, k) float32), -1 / +inf past the table's size."""
+        qs = _f32(queries, 308)
+        kk = max(int(k), 1)
+        idx = np.zeros((len(qs), kk), np.int32)
+        dist = np.zeros((len(qs), kk), np.float32)
+        self._chk(lib().ope_vfh_match(self.h, db.h if db is not None else None, _p(qs, _fp), len(qs), int(k), _p(idx, _ip), _p(dist, _fp)))
+        return idx, dist
+
+    def vfh_recognise(self, db: "VfhDb | None", clusters, k: int = 15, params: "VfhParams | None" = None, want_signatures: bool = False):
+        """ope_vfh_recognise: vfh + vfh_match of every cluster with the signatures never leaving the device; (indices, distances)
+        or, with want_signatures, (indices, distances, signatures)."""
+        cl, hs = self._vfh_clusters(clusters)
+        n = len(cl)
+        p = params if params is not None else default_vfh_params()
+        kk = max(int(k), 1)
+        idx = np.zeros((n, kk), np.int32)
+        dist = np.zeros((n, kk), np.float32)
+        sig = np.zeros((n, 308), np.float32) if want_signatures else None
+        self._chk(lib().ope_vfh_recognise(self.h, db.h if db is not None else None, n, hs, C.byref(p), int(k), _p(sig, _fp), _p(idx, _ip),
+                                          _p(dist, _fp)))
+        return (idx, dist, sig) if want_signatures else (idx, dist)
+
+    def vfh_stats(self) -> dict:
+        """ope_vfh_last_stats: points, rejected pairs, clouds whose normals were estimated, empty clouds, launches and host
+        synchronisations of the last vfh / vfh_match / vfh_recognise."""
+        s = VfhStats()
+        self._chk(lib().ope_vfh_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in VfhStats._fields_}
+
     def plane_segment(self, cloud, params: "PlaneParams | None" = None, samples=None, want_clouds: bool = False) -> "PlaneOut":
         """ope_plane_segment: pcl::SACSegmentation (SACMODEL_PLANE, SAC_RANSAC; objectsegmentationplane.cpp:36-55) of a Cloud (or
         an (n, 3) array, uploaded first).  samples: (k, 3) ORIGINAL indices taken instead of the draws."""
@@ -1620,6 +1711,19 @@ def default_region_params(**kw) -> RegionParams:
     return p
 
 
+def default_vfh_params(**kw) -> VfhParams:
+    """ope_vfh_default_params (normals_k 30, viewpoint 0 0 0, no given centroid or normal); viewpoint / centroid / normal take
+    3-sequences."""
+    p = VfhParams()
+    lib().ope_vfh_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k in ("viewpoint", "centroid", "normal"):
+            setattr(p, k, (C.c_float * 3)(*[float(x) for x in v]))
+        else:
+            setattr(p, k, v)
+    return p
+
+
 def default_plane_params(**kw) -> PlaneParams:
     """ope_plane_default_params (threshold 0.01, 50 iterations, probability 0.99, optimised coefficients, seed 12345)."""
     p = PlaneParams()
@@ -1702,6 +1806,24 @@ class Cloud:
         try:
             if self.ctx.h:
                 self.free()
+        except Exception:
+            pass
+
+
+class VfhDb:
+    """A device-resident table of VFH signatures (ope_vfh_db)."""
+
+    def __init__(self, ctx: Context, h, m: int):
+        self.ctx, self.h, self.m = ctx, h, m
+
+    def free(self):
+        if getattr(self, "h", None):
+            lib().ope_vfh_db_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 

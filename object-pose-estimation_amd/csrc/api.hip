@@ -635,6 +635,9 @@ int ope_cloud_set_normals(ope_ctx *ctx, ope_cloud *cloud, const float *normals_x
   }
   if (!cloud->d_nrm) OPE_HIP(ctx, hipMalloc((void **)&cloud->d_nrm, sizeof(float4) * std::max<size_t>(n, 1)));
   if (n) OPE_HIP(ctx, h2d_copy(ctx->stream, cloud->d_nrm, packed.data(), sizeof(float4) * n));
+  cloud->nrm_nonfinite = 0;
+  for (size_t i = 0; i < 3 * n; ++i)
+    if (!std::isfinite(normals_xyz[i])) { cloud->nrm_nonfinite = 1; break; }
   return OPE_OK;
 }
 

@@ -475,6 +475,7 @@ static int normals_impl(ope_ctx *ctx, ope_cloud *cloud, const ope_index *index, 
   static const float origin[3] = {0.f, 0.f, 0.f};
   const float *v = vp ? vp : origin;
   if (!cloud->d_nrm) OPE_HIP(ctx, hipMalloc((void **)&cloud->d_nrm, sizeof(float4) * n));
+  cloud->nrm_nonfinite = -1;
   const bool want_host = out_normals || out_curvature;   // both null: the normals only stay attached to the cloud
   std::vector<float> packed(want_host ? n * 4 : 0);
   if (cloud->n_valid > 0) {

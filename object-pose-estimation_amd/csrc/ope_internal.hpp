@@ -274,6 +274,7 @@ struct ope_ctx {
 
   ope_cluster_stats cluster_stats{};   // what the last ope_euclidean_clusters* call did (clusters.hip)
   ope_region_stats region_stats{};     // what the last ope_region_grow* call did (region_grow.hip)
+  ope_vfh_stats vfh_stats{};           // what the last ope_vfh_* call did (vfh.hip)
 
   // the last ope_plane_segment (plane.hip): what it did, and its hypotheses in drawing order (ope_plane_last_hypotheses)
   ope_plane_stats plane_stats{};
@@ -306,6 +307,7 @@ struct ope_cloud {
   size_t n = 0, n_valid = 0;
   float4 *d_xyzw = nullptr;
   float4 *d_nrm = nullptr;
+  int nrm_nonfinite = -1;   // what the host knows of d_nrm: 1 some component is not finite, 0 none is (ope_cloud_set_normals), -1 written on the device
   // Optional colour payload, one word per point in the SORTED order beside d_xyzw: the 32 bits of PointXYZRGB::rgb
   // (r << 16 | g << 8 | b, top byte as given).  Non-null means "has colours", for an empty cloud too.  Every entry point that makes a
   // cloud from clouds carries it in the launches that move the points.

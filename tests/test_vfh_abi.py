@@ -1,0 +1,85 @@
+"""CPU-side checks of the recognition entry points (ope_vfh_*): declared, exported and bound; the ctypes structs lay out exactly
+as the C compiler lays out ope_vfh_params / ope_vfh_stats; the defaults are the reference's (objectdetection.cpp:17, PCL's
+VFHEstimation constructor); the ABI version stays 5."""
+import ctypes
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT, load_pkg
+
+HEADER = os.path.join(ROOT, "include", "ope.h")
+ENTRIES = ("ope_vfh_default_params", "ope_vfh_batch", "ope_vfh_last_stats", "ope_vfh_db_create", "ope_vfh_db_free", "ope_vfh_db_size",
+           "ope_vfh_match", "ope_vfh_recognise")
+
+
+@pytest.fixture(scope="module")
+def ope():
+    pkg = load_pkg()
+    pkg.build_library()
+    return pkg
+
+
+@pytest.mark.parametrize("name", ENTRIES)
+def test_vfh_entry_is_declared_exported_and_bound(ope, name):
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert re.search(r"\b(int|void|size_t)\s+" + name + r"\s*\(", src)
+    assert hasattr(ctypes.CDLL(ope.LIB_PATH), name)
+    assert name in {n for n, _, _ in ope.ABI}
+
+
+PROBE = r"""
+#include <stddef.h>
+#include <stdio.h>
+#include "ope.h"
+#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
+int main(void) {
+  printf("sizeof_p %zu\nsizeof_s %zu\n", sizeof(ope_vfh_params), sizeof(ope_vfh_stats));
+  O(ope_vfh_params, "p", normals_k); O(ope_vfh_params, "p", viewpoint); O(ope_vfh_params, "p", use_given_centroid);
+  O(ope_vfh_params, "p", centroid); O(ope_vfh_params, "p", use_given_normal); O(ope_vfh_params, "p", normal);
+  O(ope_vfh_stats, "s", points); O(ope_vfh_stats, "s", rejected_pairs); O(ope_vfh_stats, "s", normals_estimated);
+  O(ope_vfh_stats, "s", empty_clouds); O(ope_vfh_stats, "s", launches); O(ope_vfh_stats, "s", host_syncs);
+  return 0;
+}
+"""
+
+
+def test_vfh_layouts_match_the_c_compiler(ope, tmp_path):
+    c = tmp_path / "probe.c"
+    c.write_text(PROBE)
+    exe = tmp_path / "probe"
+    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
+    want = dict(line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
+    want = {k: int(v) for k, v in want.items()}
+    structs = {"p": ope.VfhParams, "s": ope.VfhStats}
+    got = {"sizeof_" + t: ctypes.sizeof(S) for t, S in structs.items()}
+    for t, S in structs.items():
+        for name, _ in S._fields_:
+            got[t + "." + name] = getattr(S, name).offset
+    assert got == want
+
+
+def test_vfh_binding_has_the_header_s_argument_counts(ope):
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    table = {n: a for n, _, a in ope.ABI}
+    for name in ENTRIES:
+        args = re.search(r"\b" + name + r"\s*\(([^)]*)\)", src).group(1)
+        assert len(args.split(",")) == len(table[name]), name
+
+
+def test_vfh_defaults(ope):
+    p = ope.default_vfh_params()
+    assert p.normals_k == 30                               # normEst.setKSearch (30) (objectdetection.cpp:17)
+    assert list(p.viewpoint) == [0.0, 0.0, 0.0]            # vpx_ = vpy_ = vpz_ = 0
+    assert (p.use_given_centroid, p.use_given_normal) == (0, 0)
+    assert list(p.centroid) == [0.0, 0.0, 0.0] and list(p.normal) == [0.0, 0.0, 0.0]
+    q = ope.default_vfh_params(use_given_centroid=1, centroid=(1, 2, 3))
+    assert q.use_given_centroid == 1 and list(q.centroid) == [1.0, 2.0, 3.0]
+
+
+def test_vfh_leaves_the_abi_version_alone(ope):
+    assert ope.lib().ope_abi_version() == 5
+    for name in ("vfh", "vfh_db", "vfh_match", "vfh_recognise", "vfh_stats"):
+        assert callable(getattr(ope.Context, name))
