@@ -18,8 +18,8 @@ void launch_icp_accumulate(hipStream_t, int, int, bool, bool, const CloudView &,
                            const IcpState *, double *, int32_t *, float *, uint32_t *, uint32_t *, const uint32_t *,
                            uint32_t *, const uint32_t *, bool, int, double *, const uint32_t *, float *, const uint32_t *, hipEvent_t, hipEvent_t, bool,
                            uint32_t *, uint32_t, float4 *, uint32_t *, uint32_t *, uint32_t, uint32_t, float *, uint32_t *, uint32_t);
-void plan_heavy(hipStream_t, const uint32_t *, uint32_t, float, float, uint32_t, uint32_t *);
-void plan_slots(hipStream_t, const uint32_t *, uint32_t, const uint32_t *, uint32_t *);
+void plan_heavy(hipStream_t, const uint32_t *, uint32_t, float, float, uint32_t, uint32_t, float, uint32_t *);
+void plan_slots(hipStream_t, const uint32_t *, uint32_t, const uint32_t *, uint32_t, float, uint32_t *);
 int icp_accumulate_blocks_per_cu(bool, bool, bool);
 int icp_accumulate_cert_blocks_per_cu(bool, bool, bool);
 int chunk_plan(hipStream_t, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *, uint32_t, void *, size_t &);
@@ -64,6 +64,8 @@ constexpr double kGridMaxTreeShare = 0.03, kGridMinTreeShare = 0.015;
 constexpr size_t kGridMinQueries = 0;
 // Launches that fill the GPU: group walks for chunks beyond this multiple of a wave's fair share.  Launches dealt from the slot
 // queue (icp_kernels.hip: deal_next; C3 kernel us, four runs each): 1.5 155-163, 1.2 144-152, 1.0 140-143, 0.8 156-159, 0.6 189-192.
+// With the 4-lane frontier walk in those slots (2.2x the wave-time of the per-lane walk instead of 3.4x; value in it/s, four runs each):
+// 1.2 6314-6443, 1.0 7158-7258, 0.8 7066-7211, 0.6 6577-6715, parent 6667-6751: the optimum did not move.
 constexpr float kHeavyLoadFactor = 1.0f;
 // ... and under the static deal (certifying launches, the grid kernel's tree part), where handing over more chunks lengthens
 // the launch (C3, slots listed by duration: 1.0 183 us, 1.2 166, 1.45 153, 1.7 157; without the list 1.45 was 174)
@@ -302,8 +304,9 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
   }
   const bool plan_step = !no_plan && nch > 1 && it_done >= 1 && plan_step_after(ctx, it_done);
   if (plan_step) {
-    // Chunks costlier than `factor` x the median chunk are walked by 8-lane groups: a third of the dependent trips for
-    // ~2.7x the lane-cycles.  That trade pays while the launch is bound by its slowest wave, i.e. while there are few
+    // Chunks costlier than `factor` x the median chunk are walked by lane groups (the figures below: 8-lane look-ahead groups, a
+    // third of the dependent trips for ~2.7x the lane-cycles; the plain instantiations now walk them frontier-first in 4-lane
+    // groups, half the chain for 2.2x: C2 59 -> 49 us).  That trade pays while the launch is bound by its slowest wave, i.e. while there are few
     // chunks per resident wave; once the waves are busy for several rounds the extra lane-cycles only lengthen the launch.
     // Measured (model 100 k, steady state, kernel us at factor none / 2 / 3 / 5):
     //   0.25 chunks per wave (C2)  98 / 62 / 62 / 80      0.3 (a 1/8 shard) 130 / 70 / 69 / 100      0.6  154 / 79 / 99 / 139
@@ -332,9 +335,12 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
     if (chunk_plan(ps, cost_r, ctx->d_plan_sorted[nxt], ctx->d_chunk_ids, ctx->d_plan_order[nxt], nch, ctx->d_plan_tmp, tb) != 0)
       return set_err(ctx, OPE_EHIP, "chunk plan sort failed");
     uint32_t *out = ctx->d_plan_out + 8 * nxt;
-    plan_heavy(ps, ctx->d_plan_sorted[nxt], nch, heavy_factor, load_factor, (uint32_t)ctx->acc_blocks * (kAccBlock / 64), out);
+    // the plain instantiations walk those chunks frontier-first in kFrontLanes slots, the certifying one in eight look-ahead slots
+    const uint32_t group_slots = static_deal ? 8u : (uint32_t)kFrontLanes;
+    const float slot_share = static_deal ? kOctSlotShare : kFrontSlotShare;
+    plan_heavy(ps, ctx->d_plan_sorted[nxt], nch, heavy_factor, load_factor, (uint32_t)ctx->acc_blocks * (kAccBlock / 64), group_slots, slot_share, out);
     const bool slots = ctx->run_params.corr_mode == OPE_CORR_NEAREST && !ctx->run_params.use_reciprocal;
-    if (slots) plan_slots(ps, ctx->d_plan_sorted[nxt], nch, out, ctx->d_plan_slots[nxt]);
+    if (slots) plan_slots(ps, ctx->d_plan_sorted[nxt], nch, out, group_slots, slot_share, ctx->d_plan_slots[nxt]);
     OPE_HIP(ctx, hipEventRecord(ctx->ev_plan_done, ps));
     ctx->plan_pending = true;
     ctx->plan_pending_slots = slots;

@@ -670,6 +670,194 @@ __device__ __forceinline__ void bvh_traverse_oct(const BvhView &t, float qx, flo
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Frontier ("front") traversal: W consecutive lanes serve ONE query and open W pending nodes per trip.  A far query's
+// `best` is essentially final once its hint leaf is scanned, so the set of nodes its walk has to open — every node whose
+// box bound is below `best` — is fixed before the walk starts and the order of opening is free.  The per-lane walk opens
+// them one after the other; here each lane of the group does exactly the per-lane walk's node step (two children, two
+// obb_dist2) on a node of its own: no look-ahead, no speculative box test, a W-times shorter dependent chain.
+//   Pending set: a group-shared stack of node ids in the group's own W columns of the parked-bound array (`stk` points at
+//     the group's first column: W x (kMaxDepth + 2) words), its top group-uniform in a register.  No bounds are parked: an
+//     entry was admitted against an older `best`, which only lets more through.  Push and pop positions come from a
+//     ballot over the group's lanes and a popcount.  The LDS writes of one trip are read in a later instruction of the
+//     same wave: program order, no barrier.
+//   Trip: a lane without a node backs up to a sibling it kept to itself (below) or pops one; a lane with an inner node
+//     tests both children against the shared `best`, goes on with the nearer survivor and pushes the other; a lane at a
+//     leaf notes it in the group's leaf queue (W entries at the other end of the same region).
+//   Scan: when the queue is full, nothing is left to open, or the query has no candidate yet, lane g scans noted leaf g
+//     (scan_leaf_nearest) and best / pos / leaf are merged by a group minimum, the lowest lane winning an equal d2.
+//   Overflow loses nothing: a lane that finds the stack full keeps the second child as a bit of a private trail (bit k: the
+//     sibling of the k-th ancestor of this lane's node is pending, as in the per-lane walk) and opens it before it pops
+//     again.  No waits and no spinning: every trip opens a node, retires one, or notes a leaf.
+// Exact: every subtree is either entered or pruned against a `best` no smaller than the final one, every leaf reached is
+// scanned before the walk returns, and point distances use sq_dist3 — d2 is bit-equal to the oracle's (on exact fp32 ties
+// the index may be another of the tied points, as with every search here).  The visitor comes back identical in all W
+// lanes; v.leaf is the leaf that holds the best point.  CAP: entries of the pending stack (the stand-alone check cuts it).
+template <int W>
+__device__ __forceinline__ float group_min(float v) {
+#pragma unroll
+  for (int m = 1; m < W; m <<= 1) v = fminf(v, __shfl_xor(v, m, 64));
+  return v;
+}
+
+template <int W, int CAP = W * (kMaxDepth + 1)>
+__device__ __forceinline__ void bvh_traverse_front(const BvhView &t, float qx, float qy, float qz, NearestVisitor &v, float *stk,
+                                                   int stk_stride, uint32_t start_leaf) {
+  static_assert(W == 2 || W == 4 || W == 8, "lanes per query");
+  constexpr uint32_t TOT = W * (kMaxDepth + 2);   // words of the group's region: stack from entry 0 up, leaf queue from TOT - 1 down
+  static_assert(CAP >= 1 && CAP + W <= (int)TOT && 2 * kMaxDepth <= (int)TOT, "stack, queue and the start's bounds share the region");
+  constexpr uint32_t GM = (1u << W) - 1u;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t g = lane & (W - 1u), gsh = lane & ~(W - 1u);
+  const uint32_t below = (1u << g) - 1u;
+  const uint32_t leaf0 = 1u << t.depth;
+  const int D = t.depth;
+  uint32_t *const reg = reinterpret_cast<uint32_t *>(stk);
+  auto cell = [&](uint32_t e) -> uint32_t & { return reg[(e / W) * (uint32_t)stk_stride + (e % W)]; };
+  auto gballot = [&](bool p) -> uint32_t { return (uint32_t)(__ballot(p) >> gsh) & GM; };
+  // what one lane of the group wrote to the region, another reads: the wave's LDS accesses are served in program order, the
+  // fence keeps the compiler to that order (wavefront scope: no instruction)
+  auto group_fence = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); };
+
+  uint32_t node = 0, trail = 0;   // this lane's node (live) or the node its trail is relative to
+  bool live = false;
+  uint32_t top = 0, nq = 0;       // group-uniform: pending nodes, noted leaves
+  if (start_leaf != 0) {
+    // bounds of the D ancestor siblings, lane g taking levels g, g + W, ...: all fetched ahead of the leaf scan that gives
+    // the bound they are tested against, two in flight per lane, and kept at the far end of the region meanwhile
+    for (int k0 = (int)g; k0 < D; k0 += 2 * W) {
+      const int k1 = k0 + W;
+      const uint32_t s0 = (start_leaf >> k0) ^ 1u;
+      const uint32_t s1 = k1 < D ? ((start_leaf >> k1) ^ 1u) : s0;
+      v4f a0, b0, c0, a1, b1, c1;
+      load_node(t, s0, a0, b0, c0);
+      load_node(t, s1, a1, b1, c1);
+      cell(TOT - 1u - (uint32_t)k0) = __float_as_uint(obb_dist2(a0, b0, c0, qx, qy, qz));
+      if (k1 < D) cell(TOT - 1u - (uint32_t)k1) = __float_as_uint(obb_dist2(a1, b1, c1, qx, qy, qz));
+    }
+    group_fence();
+    // the start leaf, two points per lane and batch
+    {
+      const uint32_t j = start_leaf - leaf0;
+      const uint32_t s = (uint32_t)(((unsigned long long)j * t.n) >> t.depth);
+      const uint32_t e = (uint32_t)(((unsigned long long)(j + 1) * t.n) >> t.depth);
+      float dmin = INFINITY;
+      uint32_t ip = kNoPos;
+      for (uint32_t i = s; i < e; i += 2 * W) {
+        const uint32_t i0 = i + g, i1 = i + W + g;
+        const v4f p0 = ld16(t.pts + min(i0, e - 1)), p1 = ld16(t.pts + min(i1, e - 1));
+        const float d0 = (i0 < e) ? sq_dist3(__fsub_rn(qx, p0.x), __fsub_rn(qy, p0.y), __fsub_rn(qz, p0.z)) : INFINITY;
+        const float d1 = (i1 < e) ? sq_dist3(__fsub_rn(qx, p1.x), __fsub_rn(qy, p1.y), __fsub_rn(qz, p1.z)) : INFINITY;
+        if (d0 < dmin) { dmin = d0; ip = i0; }
+        if (d1 < dmin) { dmin = d1; ip = i1; }
+      }
+      const float dm = group_min<W>(dmin);
+      if (dm < v.best) {
+        const uint32_t w = (uint32_t)__builtin_ctz(gballot(dmin == dm));
+        v.best = dm;
+        v.pos = (uint32_t)__shfl((int)ip, (int)(gsh + w), 64);
+        v.leaf = start_leaf;
+      }
+    }
+    // the siblings that beat it become the pending set, shallow ones first (the deepest end up on top); what the stack
+    // cannot take goes to lane 0's trail, relative to the start leaf
+    uint32_t ov = 0;
+    for (int r = (D - 1) / W; r >= 0 && D > 0; --r) {
+      const int k = (int)g + r * W;
+      const bool want = k < D && __uint_as_float(cell(TOT - 1u - (uint32_t)min(k, D - 1))) < v.best;
+      const uint32_t pm = gballot(want);
+      if (pm != 0u) {
+        const uint32_t n = (uint32_t)__popc(pm), rr = n - 1u - (uint32_t)__popc(pm & below), room = (uint32_t)CAP - top;
+        const bool fits = rr < room;
+        if (want && fits) cell(top + rr) = (start_leaf >> k) ^ 1u;
+        ov |= gballot(want && !fits) << (r * W);
+        top += min(n, room);
+      }
+    }
+    group_fence();
+    if (g == 0u) { node = start_leaf; trail = ov; }
+  } else {
+    v4f a, b, c;
+    load_node(t, 1, a, b, c);
+    if (v.prune(obb_dist2(a, b, c, qx, qy, qz))) return;
+    if (g == 0u) { node = 1; live = true; }
+  }
+  bool work = top > 0u || gballot(live || trail != 0u) != 0u;
+  for (;;) {
+    // ---- trips: a query without a candidate has its first leaf scanned at once (nothing can be pruned before)
+    bool go = work && nq < (uint32_t)W && !(nq > 0u && v.pos == kNoPos);
+    while (__ballot(go) != 0ull) {
+      if (go) {
+        // a lane without a node: back up to a sibling it kept to itself, else pop
+        if (!live && trail != 0u) {
+          const int k = __builtin_ctz(trail);
+          node = (node >> k) ^ 1u;
+          trail = (trail >> k) & ~1u;
+          live = true;
+        }
+        const uint32_t wm = gballot(!live);
+        if (wm != 0u && top > 0u) {
+          const uint32_t rank = (uint32_t)__popc(wm & below);
+          if (!live && rank < top) { node = cell(top - 1u - rank); live = true; }   // (its trail is empty)
+          top -= min((uint32_t)__popc(wm), top);
+        }
+        // open: the per-lane walk's node step
+        uint32_t far = 0;
+        if (live && node < leaf0) {
+          v4f c0, c1, c2, c3, c4, c5;
+          load_node(t, 2 * node, c0, c1, c2);
+          load_node(t, 2 * node + 1, c3, c4, c5);
+          const float d0 = obb_dist2(c0, c1, c2, qx, qy, qz);
+          const float d1 = obb_dist2(c3, c4, c5, qx, qy, qz);
+          const bool right = d1 < d0;
+          const float dn = right ? d1 : d0;
+          const float df = right ? d0 : d1;
+          if (!v.prune(dn)) {
+            node = 2 * node + (right ? 1u : 0u);
+            trail <<= 1;
+            far = v.prune(df) ? 0u : (node ^ 1u);
+          } else {
+            live = false;
+          }
+        }
+        // push the second children
+        const uint32_t pm = gballot(far != 0u);
+        if (pm != 0u) {
+          const uint32_t rank = (uint32_t)__popc(pm & below), room = (uint32_t)CAP - top;
+          if (far != 0u) {
+            if (rank < room) cell(top + rank) = far;
+            else trail |= 1u;
+          }
+          top += min((uint32_t)__popc(pm), room);
+        }
+        // note the leaves reached (a lane that finds the queue full holds its leaf until the scan)
+        const bool at_leaf = live && node >= leaf0;
+        const uint32_t nm = gballot(at_leaf);
+        if (nm != 0u) {
+          const uint32_t rank = (uint32_t)__popc(nm & below), room = (uint32_t)W - nq;
+          if (at_leaf && rank < room) { cell(TOT - 1u - (nq + rank)) = node; live = false; }
+          nq += min((uint32_t)__popc(nm), room);
+        }
+        group_fence();
+        work = top > 0u || gballot(live || trail != 0u) != 0u;
+        go = work && nq < (uint32_t)W && !(nq > 0u && v.pos == kNoPos);
+      }
+    }
+    // ---- scan what the group has noted: lane g takes leaf g
+    if (nq > 0u) {
+      NearestVisitor w = v;
+      if (g < nq) scan_leaf_nearest(t, cell(TOT - 1u - g), qx, qy, qz, w);
+      const float m = group_min<W>(w.best);
+      const int from = (int)(gsh + (uint32_t)__builtin_ctz(gballot(w.best == m)));
+      v.best = m;
+      v.pos = (uint32_t)__shfl((int)w.pos, from, 64);
+      v.leaf = (uint32_t)__shfl((int)w.leaf, from, 64);
+      nq = 0u;
+    }
+    if (__ballot(work) == 0ull) return;
+  }
+}
+
 // k-nearest list of one lane, kept in LDS with a per-thread stride (bank-conflict free), ascending.
 // `worst` starts at +inf for plain k-NN, or just above r^2 for "the k nearest within radius r".
 struct KnnVisitor {

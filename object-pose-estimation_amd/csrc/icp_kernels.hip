@@ -335,8 +335,9 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
   // Cost-aware work distribution.  Query cost is very uneven (a clutter point far from the model walks 10-40x more nodes
   // than a surface point) and the kernel ends with its slowest wave.  The 64-query chunks of the Morton order are therefore
   // taken longest first, from a list sorted by the cost each chunk measured in an earlier launch (the plan steps, api.hip).
-  // The n_heavy costliest chunks (clutter: long private walks) are split into eight slots each and walked by 8-lane groups
-  // (bvh_traverse_oct); all other chunks take one slot and one lane per query.
+  // The n_heavy costliest chunks (clutter: long private walks) are split into GW slots each and walked by groups of GW lanes:
+  // kFrontLanes-lane frontier walks (bvh_traverse_front) in the plain instantiations, 8-lane look-ahead walks (bvh_traverse_oct) in
+  // the certifying one; all other chunks take one slot and one lane per query.
   // Who takes which entry of that list:
   //  - planned launches of every instantiation but the certifying one: from the striped device queue above (deal_next).
   //    Durations move with the pose and with what shares the SIMD (a far chunk is 115 us alone, 146 us under load): a wave
@@ -358,11 +359,13 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
   // plan_out: what the plan step computed for this chunk order ([0] chunks walked by groups, [5] / [7] chunks with a wave to
   // themselves in the static deal); plan_info: the launch's flags
   const uint32_t n_heavy = (OCT_OK && chunk_order && !measuring) ? min(plan_out[0], n_chunks) : 0u;
+  constexpr uint32_t GW = CERT ? 8u : (uint32_t)kFrontLanes;   // lanes per query = slots per chunk of a group-walked chunk
   // With group walks in the plan the slots come as a list in descending order of expected duration (plan_slots_kernel:
-  // the eight slots of a group-walked chunk merged in among the per-lane chunks they are as long as); without, the list
-  // is the group-walked chunks' slots followed by the other chunks in the plan's order.
-  const bool listed = OCT_OK && slot_list != nullptr && chunk_order != nullptr && !measuring && n_heavy > 0u;
-  const uint32_t n_slots = n_chunks + 7u * n_heavy;
+  // the slots of a group-walked chunk merged in among the per-lane chunks they are as long as); without — or with a list
+  // that was made for the other instantiation's slot count (plan_out[6]: a run that starts certifying between two plan steps) —
+  // the list is the group-walked chunks' slots followed by the other chunks in the plan's order.
+  const bool listed = OCT_OK && slot_list != nullptr && chunk_order != nullptr && !measuring && n_heavy > 0u && plan_out[6] == GW;
+  const uint32_t n_slots = n_chunks + (GW - 1u) * n_heavy;
   const bool dealt = chunk_order != nullptr && !CERT;
   uint32_t *const deal_set = deal + (size_t)deal_parity * kDealStripes * kDealLineWords;
   const uint32_t n_stripes = min(kDealStripes, n_waves);
@@ -373,11 +376,11 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
                                                 : min(min(plan_out[5] + (measuring ? min(plan_out[0], n_chunks) : 0u), n_chunks - n_heavy), n_waves / 2u);
   const uint32_t n_snake = n_slots - n_alone, snake_waves = n_waves - n_alone;
   auto static_slot = [&](uint32_t r) -> uint32_t {
-    if (wave_id < n_alone) return r == 0u ? (listed ? wave_id : 8u * n_heavy + wave_id) : kDealNone;
+    if (wave_id < n_alone) return r == 0u ? (listed ? wave_id : GW * n_heavy + wave_id) : kDealNone;
     const uint32_t w = wave_id - n_alone;
     const uint32_t sn = r * snake_waves + ((r & 1u) ? (snake_waves - 1u - w) : w);
     if (sn >= n_snake) return kDealNone;   // (only a launch's last round is short: nothing follows it)
-    return (listed || sn >= 8u * n_heavy) ? sn + n_alone : sn;
+    return (listed || sn >= GW * n_heavy) ? sn + n_alone : sn;
   };
   uint32_t round = 0u;
   uint32_t slot = static_slot(0u);
@@ -394,16 +397,16 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
       sub = (e >> 28) & 7u;
       ord = e & 0x0fffffffu;
     } else {
-      oct = slot < 8u * n_heavy;
-      ord = oct ? (slot >> 3) : (n_heavy + (slot - 8u * n_heavy));
-      sub = slot & 7u;
+      oct = slot < GW * n_heavy;
+      ord = oct ? (slot / GW) : (n_heavy + (slot - GW * n_heavy));
+      sub = slot % GW;
     }
     const uint32_t chunk = chunk_order ? chunk_order[ord] : ord;
     const uint32_t base = chunk * 64u;
     const unsigned long long t_begin = __builtin_amdgcn_s_memtime();
-    const uint32_t i = oct ? (base + sub * 8u + (lane_id >> 3)) : (base + lane_id);
+    const uint32_t i = oct ? (base + sub * (64u / GW) + (lane_id / GW)) : (base + lane_id);
     const bool active = i < src.n_valid;
-    const bool owner = active && (!oct || (lane_id & 7u) == 0u);  // the one lane that reports a query
+    const bool owner = active && (!oct || (lane_id & (GW - 1u)) == 0u);  // the one lane that reports a query
     // (the pointer keeps its LDS address space: through a generic pointer these became flat_loads, which take the
     // vector-memory path and wait on both counters)
     lds_cfloat_ptr cst = (lds_cfloat_ptr)s_const;
@@ -491,7 +494,7 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
       const uint32_t h = active ? hint[i] : 0u;
       if (dealt) ticket_v = deal_pop(deal_set, stripe, lane_id);
       if (OCT_OK && oct) {
-        if (active) bvh_traverse_oct(tgt, x, y, z, v, &s_stk[0][threadIdx.x & ~7u], BLOCK, h);
+        if (active) bvh_traverse_front<kFrontLanes>(tgt, x, y, z, v, &s_stk[0][threadIdx.x & ~(GW - 1u)], BLOCK, h);
       } else {
         // coherent chunks (a handful of start leaves for 64 queries) take one packet walk through the scalar cache
         // (PACKET instantiation: launches that fill the GPU); everything else the per-lane walk from its own leaf

@@ -115,6 +115,11 @@ struct P2pView {
 };
 
 constexpr float kOctSlotShare = 0.42f;   // one of a group-walked chunk's eight slots lasts about this share of the chunk's per-lane duration (measured: 0.39-0.53)
+// The frontier walk of the plain 1-NN instantiations (bvh_traverse.hpp: bvh_traverse_front): lanes per query = slots per chunk, and what
+// one of those slots lasts relative to the chunk's per-lane duration (measured on C3 from the chunk-cost buffer of a measuring launch
+// and the launch after it: mean 0.56-0.68, median 0.51-0.64; at 8 lanes 0.25-0.31, at 2 lanes the launch was 190 us against 136)
+constexpr int kFrontLanes = 4;
+constexpr float kFrontSlotShare = 0.55f;
 constexpr float kCertWorth = 24.0f;     // a query builds a certificate when the slack it can expect is worth this many launches of the scene's current displacement
 constexpr int kCertCand = 5;            // skip certificates: candidates kept per query (built by a (kCertCand + 1)-nearest walk)
 constexpr int kNumSums = 17;

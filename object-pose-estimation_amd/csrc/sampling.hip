@@ -115,14 +115,17 @@ __device__ __forceinline__ uint32_t count_costlier(const uint32_t *cost_sorted_d
 }
 
 // Plan of a launch from the chunk costs in descending order (one block of 256 threads).
-// plan_info[0] = n_heavy, the chunks walked by 8-lane groups (capped at n/4):
+// plan_info[0] = n_heavy, the chunks walked by lane groups (capped at n/4), each in `slots` slots that last `share` x the chunk's
+//   per-lane duration (8 and kOctSlotShare for the 8-lane look-ahead walk, kFrontLanes and kFrontSlotShare for the frontier walk;
+//   plan_info[6] = slots, so that a launch can tell whose list it was handed):
 //   factor > 0:      those costlier than factor x the median chunk (launches with few chunks per wave: latency-bound)
 //   load_factor > 0: those costlier than load_factor x (sum of all costs / waves), i.e. chunks that on their own far
 //                    outlast the share of work a wave has in a balanced launch (launches that fill the GPU)
 // plan_info[5] = n_alone, the next-costliest chunks that get a wave to themselves: those at or above the fair share L of
 //   the waves that are left, L = (work not yet given away) / (waves not yet given away), iterated to its fixed point.  A
-//   group-walked chunk counts as kOctWork x its per-lane cost (eight slots of about a third of the duration each).
-constexpr double kOctWork = 8.0 * kOctSlotShare;  // wave-time of a group-walked chunk relative to its per-lane walk
+//   group-walked chunk counts as group_work x its per-lane cost.
+__host__ __device__ constexpr double group_work(uint32_t slots, float share) { return (double)slots * (double)share; }  // wave-time of a group-walked chunk relative to its per-lane walk
+constexpr double kOctWork = group_work(8u, kOctSlotShare);   // (the grid kernel's tree part)
 __device__ __forceinline__ double block_sum_range(const uint32_t *v, uint32_t a, uint32_t b, double *s_sum) {
   double acc = 0.0;
   for (uint32_t i = a + threadIdx.x; i < b; i += 256) acc += (double)v[i];
@@ -136,7 +139,7 @@ __device__ __forceinline__ double block_sum_range(const uint32_t *v, uint32_t a,
   return s_sum[0];
 }
 __global__ __launch_bounds__(1024) void plan_heavy_kernel(const uint32_t *cost_sorted_desc, uint32_t n, float factor, float load_factor,
-                                                          uint32_t n_waves, uint32_t *plan_info) {
+                                                          uint32_t n_waves, uint32_t slots, float share, uint32_t *plan_info) {
   // prefix sums of the sorted costs at a stride of `per` entries (one pass, one block scan); thread 0 then answers every
   // "cost of the m costliest chunks" with one LDS read and fewer than `per` loads
   using scan_t = rocprim::block_scan<double, 1024>;
@@ -165,8 +168,9 @@ __global__ __launch_bounds__(1024) void plan_heavy_kernel(const uint32_t *cost_s
     else if (load_factor > 0.f) nh = count_costlier(cost_sorted_desc, n / 4, load_factor * (float)(total / (double)max(n_waves, 1u)));
   }
   const double heavy = sum_first(nh);
-  // the eight slots of a group-walked chunk are dealt like ordinary chunks; everything but the alone chunks is "the rest"
-  rest = kOctWork * heavy + (total - heavy);
+  // the slots of a group-walked chunk are dealt like ordinary chunks; everything but the alone chunks is "the rest"
+  const double gwork = group_work(slots, share);
+  rest = gwork * heavy + (total - heavy);
   for (int pass = 0; pass < 4; ++pass) {
     const uint32_t w_left = n_waves > k ? n_waves - k : 1u;
     const float fair = (float)(rest / (double)w_left);
@@ -179,10 +183,11 @@ __global__ __launch_bounds__(1024) void plan_heavy_kernel(const uint32_t *cost_s
     const uint32_t k_new = lo - nh;
     if (k_new == k) break;
     k = k_new;
-    rest = kOctWork * heavy + (total - heavy) - (sum_first(nh + k) - heavy);
+    rest = gwork * heavy + (total - heavy) - (sum_first(nh + k) - heavy);
   }
   plan_info[0] = nh;
   plan_info[5] = k;
+  plan_info[6] = slots;
   // for the merged slot list (plan_slots_kernel): how many of its leading entries get a wave to themselves — the k
   // per-lane chunks above, plus the slots of group-walked chunks that on their own reach the fair share (rare)
   const uint32_t w_left = n_waves > k ? n_waves - k : 1u;
@@ -190,48 +195,48 @@ __global__ __launch_bounds__(1024) void plan_heavy_kernel(const uint32_t *cost_s
   uint32_t lo = 0, hi = nh;
   while (lo < hi) {
     const uint32_t mid = (lo + hi) / 2;
-    if (kOctSlotShare * (float)cost_sorted_desc[mid] >= fair && fair > 0.f) lo = mid + 1; else hi = mid;
+    if (share * (float)cost_sorted_desc[mid] >= fair && fair > 0.f) lo = mid + 1; else hi = mid;
   }
-  plan_info[7] = min(k + 8u * lo, n_waves / 2u);
+  plan_info[7] = min(k + slots * lo, n_waves / 2u);
 }
 
 // The launch's slots in descending order of expected duration: a per-lane chunk of rank q counts its cost, each of the
-// eight slots of a group-walked chunk of rank i < n_heavy counts kOctSlotShare x the chunk's cost.  Both sequences are
+// `slots` slots of a group-walked chunk of rank i < n_heavy counts share x the chunk's cost.  Both sequences are
 // descending already, so every entry finds its place with one binary search in the other (ties: per-lane first).
-// Entry: rank in bits 0-27, slot in bits 28-30, bit 31 = walked by 8-lane groups.
+// Entry: rank in bits 0-27, slot in bits 28-30, bit 31 = walked by lane groups.
 __global__ __launch_bounds__(256) void plan_slots_kernel(const uint32_t *__restrict__ cost_sorted_desc, uint32_t n, const uint32_t *__restrict__ plan_info,
-                                                         uint32_t *__restrict__ slot_list) {
+                                                         uint32_t slots, float share, uint32_t *__restrict__ slot_list) {
   const uint32_t r = blockIdx.x * 256 + threadIdx.x;
   if (r >= n) return;
   const uint32_t nh = min(plan_info[0], n);
   const float c = (float)cost_sorted_desc[r];
   if (r < nh) {
-    const float key = kOctSlotShare * c;
+    const float key = share * c;
     uint32_t lo = nh, hi = n;   // first per-lane rank whose cost is below the key
     while (lo < hi) {
       const uint32_t mid = (lo + hi) / 2;
       if ((float)cost_sorted_desc[mid] >= key) lo = mid + 1; else hi = mid;
     }
-    const uint32_t base = 8u * r + (lo - nh);
-#pragma unroll
-    for (uint32_t j = 0; j < 8u; ++j) slot_list[base + j] = r | (j << 28) | 0x80000000u;
+    const uint32_t base = slots * r + (lo - nh);
+    for (uint32_t j = 0; j < slots; ++j) slot_list[base + j] = r | (j << 28) | 0x80000000u;
   } else {
     uint32_t lo = 0, hi = nh;   // first group-walked rank whose key is not above this cost
     while (lo < hi) {
       const uint32_t mid = (lo + hi) / 2;
-      if (kOctSlotShare * (float)cost_sorted_desc[mid] > c) lo = mid + 1; else hi = mid;
+      if (share * (float)cost_sorted_desc[mid] > c) lo = mid + 1; else hi = mid;
     }
-    slot_list[(r - nh) + 8u * lo] = r;
+    slot_list[(r - nh) + slots * lo] = r;
   }
 }
 
-void plan_slots(hipStream_t stream, const uint32_t *cost_sorted_desc, uint32_t n, const uint32_t *plan_info, uint32_t *slot_list) {
-  hipLaunchKernelGGL(plan_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cost_sorted_desc, n, plan_info, slot_list);
+void plan_slots(hipStream_t stream, const uint32_t *cost_sorted_desc, uint32_t n, const uint32_t *plan_info, uint32_t slots, float share,
+                uint32_t *slot_list) {
+  hipLaunchKernelGGL(plan_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cost_sorted_desc, n, plan_info, slots, share, slot_list);
 }
 
 void plan_heavy(hipStream_t stream, const uint32_t *cost_sorted_desc, uint32_t n, float factor, float load_factor, uint32_t n_waves,
-                uint32_t *plan_info) {
-  hipLaunchKernelGGL(plan_heavy_kernel, dim3(1), dim3(1024), 0, stream, cost_sorted_desc, n, factor, load_factor, n_waves, plan_info);
+                uint32_t slots, float share, uint32_t *plan_info) {
+  hipLaunchKernelGGL(plan_heavy_kernel, dim3(1), dim3(1024), 0, stream, cost_sorted_desc, n, factor, load_factor, n_waves, slots, share, plan_info);
 }
 
 // ---- plan step of the GRID accumulate kernel (icp_accumulate_grid_kernel): everything stays on the device
