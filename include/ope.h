@@ -481,6 +481,13 @@ int ope_voxel_grid_rgb(ope_ctx *ctx, const ope_cloud *cloud, const float leaf[3]
  * out_mean_dist (optional, n floats, ORIGINAL order): the per-point mean distances. */
 int ope_statistical_outlier_removal(ope_ctx *ctx, const ope_cloud *cloud, int mean_k, double stddev_mul, int32_t *out_idx,
                                     size_t *n_out, float *out_mean_dist);
+/* pcl::ConditionalRemoval with a ConditionAnd of six PackedRGBComparison (ProcessingPcd::getFilterRgb, BuildModel
+ * processingpcd.cpp:112-141: "r" GT lo[0], "r" LT hi[0], then "g" and "b" alike): a point survives iff lo[c] < channel_c < hi[c]
+ * for c = r, g, b of its colour word (ope_cloud_set_rgb; the top byte plays no part).  Strict integer comparisons, as
+ * PackedRGBComparison compares the uint8 with the value.  The coordinates play no part: a non-finite point passes or fails by its
+ * colour like any other.  ORIGINAL indices, ascending (out_idx has room for every point).  OPE_EINVAL for a cloud without
+ * colours. */
+int ope_color_filter(ope_ctx *ctx, const ope_cloud *cloud, const int32_t lo[3], const int32_t hi[3], int32_t *out_idx, size_t *n_out);
 
 /* Device-resident forms of the filters above: the survivors are handed on as a new cloud (*out, as ope_cloud_select of the
  * indices the host form returns would build it), so that crop -> outlier removal -> key points -> normals -> FPFH -> SAC-IA
@@ -492,6 +499,8 @@ int ope_pass_through_cloud(ope_ctx *ctx, const ope_cloud *cloud, const float lo[
 int ope_statistical_outlier_removal_cloud(ope_ctx *ctx, const ope_cloud *cloud, int mean_k, double stddev_mul, ope_cloud **out,
                                           int32_t *out_idx, size_t *n_out);
 int ope_uniform_sampling_cloud(ope_ctx *ctx, const ope_cloud *cloud, float leaf, ope_cloud **out, int32_t *out_idx, size_t *n_out);
+int ope_color_filter_cloud(ope_ctx *ctx, const ope_cloud *cloud, const int32_t lo[3], const int32_t hi[3], ope_cloud **out, int32_t *out_idx,
+                           size_t *n_out);
 
 typedef struct {
   int max_iterations;      /* 400  (poseestimator.cpp:55) */
@@ -783,6 +792,53 @@ typedef struct {
   int64_t refused_curvature;           /* points with curvature > curvature_threshold (non-zero: the call was refused) */
 } ope_region_stats;
 int ope_region_last_stats(const ope_ctx *ctx, ope_region_stats *out);
+
+/* ---------------- segmentation: colour-based region growing ---------------- */
+/* SegmentationRegionGrow::getSegmentRegGrowRgb (segmentationregiongrow.cpp:85-151): pcl::RegionGrowingRGB, the reference's answer to
+ * objects that neither a plane nor surface normals separate from what they touch. */
+typedef struct {
+  int32_t region_neighbour_number;  /* PCL's region_neighbour_number_, which the reference never changes: 100; 1..128 */
+  double distance_threshold;        /* setDistanceThreshold (0.1) (segmentationregiongrow.cpp:100) */
+  double point_color_threshold;     /* setPointColorThreshold (10) (:101) */
+  double region_color_threshold;    /* setRegionColorThreshold (10) (:102) */
+  int32_t min_size, max_size;       /* setMinClusterSize (700) (:103); PCL's default maximum, INT32_MAX */
+} ope_region_rgb_params;
+void ope_region_rgb_default_params(ope_region_rgb_params *p);
+/* What RegionGrowingRGB::extract returns (PCL 1.7/1.8 region_growing_rgb.hpp; normal, curvature and residual tests off, as its
+ * constructor leaves them) for a cloud with colours (ope_cloud_set_rgb).  With K = region_neighbour_number, N(u) the K nearest finite
+ * points of u (u included), cd the sum of the squared channel differences, and every threshold squared in float:
+ *  - point edges u -> v iff v is in N(u), v != u and !(cd(u, v) > point_color_threshold^2); segment(v) = the smallest ORIGINAL index
+ *    among the points that reach v, v included; segments are numbered by seed;
+ *  - a segment's colour is the truncated float mean of each channel; its neighbours are the K segments t nearest by
+ *    (min d2 over its own points' lists, t);
+ *  - merge A joins a segment to the first earlier segment that keeps it within distance_threshold^2 and whose colour differs by
+ *    less than region_color_threshold^2; merge B moves every region below min_size into the region of its nearest neighbour, in
+ *    order; regions are reordered by PCL's two-pointer pass over the empty ones, and those outside min_size..max_size are dropped.
+ * DESIGN.md 4.19 has the whole restatement.  A non-finite point is in no region.  out_idx, out_offsets, out_label, *n_clusters and
+ * max_clusters as ope_euclidean_clusters.  OPE_EINVAL, nothing launched: a cloud without colours, region_neighbour_number outside
+ * 1..128, a threshold that is negative or not finite, min_size < 1, max_size < min_size, more than (2^31 - 1) / 128 points.  An
+ * empty cloud gives 0 clusters.
+ * Kernel launches booked: 27 + 5 per batch of four sweeps (+ 5 for the _cloud form); host synchronisations: 4 + 1 per batch (+ 1
+ * for the _cloud form).  Neither count depends on the number of points, segments or regions. */
+int ope_region_grow_rgb(ope_ctx *ctx, const ope_cloud *cloud, const ope_region_rgb_params *params, size_t max_clusters, size_t *n_clusters,
+                        int32_t *out_idx, int32_t *out_offsets, int32_t *out_label);
+/* The same, with each written region also as a new device cloud, exactly what ope_cloud_select(cloud, indices of region k)
+ * builds (colours and normals carried); the caller frees them.  out_idx / out_offsets are optional here. */
+int ope_region_grow_rgb_cloud(ope_ctx *ctx, const ope_cloud *cloud, const ope_region_rgb_params *params, size_t max_clusters, size_t *n_clusters,
+                              ope_cloud **out_clouds, int32_t *out_idx, int32_t *out_offsets);
+/* What the last ope_region_grow_rgb* call of this context did. */
+typedef struct {
+  int64_t launches;
+  int64_t host_syncs;
+  int64_t sweeps;
+  int64_t one_way_edges;
+  int64_t segments;                    /* S */
+  int64_t segment_pairs;               /* directed pairs (s, t) with a distance, before the cut to the K nearest */
+  int64_t homogeneous_regions;         /* H, after merge A */
+  int64_t regions_absorbed;            /* merge B */
+  int64_t regions_before_size_filter;  /* non-empty regions after merge B */
+} ope_region_rgb_stats;
+int ope_region_rgb_last_stats(const ope_ctx *ctx, ope_region_rgb_stats *out);
 
 /* ---------------- segmentation: RANSAC plane fit, polygonal prism, table-top ---------------- */
 /* pcl::SACSegmentation with SACMODEL_PLANE, SAC_RANSAC (getPlaneIndicesAndCoeffSAC, objectsegmentationplane.cpp:36-55).

@@ -27,6 +27,12 @@
 // (the z crop over [0, 1.2], normals with k = 30, region growing over them on the device), every cluster as --candidates takes
 // them.  Prints `segment crop <n> sweeps <s>`, `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
 //
+//   detect_and_localize --frame <model.pcd> <frame.pcd> --region-grow-rgb [--seed N] [--self-occluded]
+// A frame whose objects differ from what they touch by colour alone (a coloured box against a wall, two flush parts):
+// ope::SegmentationRegionGrow::getSegmentRegGrowRgb (the z crop over [0, 1.1], colour-based region growing on the device), every
+// cluster as --candidates takes them.  Prints `segment crop <n> segments <s> absorbed <a>`, `segment clusters <n> sizes <s0> <s1>
+// ...`, then the --candidates lines.
+//
 //   detect_and_localize --frame <model.pcd> <frame.pcd> --except-plane [--limits x0 x1 y0 y1 z0 z1] [--seed N] [--self-occluded]
 // A frame without a single table (a floor, a wall, a shelf side): ope::ObjectSegmentationPlane::getSegmentedObjectsExceptPlane, its
 // crop (getFiltered) set to the -l limits, planes peeled on the device until at most 30 % of the cropped points are left, the
@@ -249,6 +255,7 @@ int main(int argc, char **argv) {
   bool frame = false;   // --frame: the clusters come from getSegmentedObjectsOnPlane over the one scene file (a camera frame)
   bool except_plane = false;   // --except-plane (with --frame): from getSegmentedObjectsExceptPlane instead
   bool region_grow = false;    // --region-grow (with --frame): from SegmentationRegionGrow::getSegmentRegGrow instead
+  bool region_grow_rgb = false;   // --region-grow-rgb (with --frame): from SegmentationRegionGrow::getSegmentRegGrowRgb instead
   std::string recognise;       // --recognise <train_dir>: name every cluster before the pose stage
   float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
@@ -261,11 +268,16 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--frame")) { frame = true; candidates = 1; }
     else if (!std::strcmp(argv[i], "--except-plane")) except_plane = true;
     else if (!std::strcmp(argv[i], "--region-grow")) region_grow = true;
+    else if (!std::strcmp(argv[i], "--region-grow-rgb")) region_grow_rgb = true;
     else if (!std::strcmp(argv[i], "--limits") && i + 6 < argc) { for (int d = 0; d < 6; ++d) limits[d] = std::strtof(argv[++i], nullptr); }
     else files.push_back(argv[i]);
   }
   if (except_plane && !frame) { std::fprintf(stderr, "--except-plane goes with --frame\n"); return 2; }
   if (region_grow && (!frame || except_plane)) { std::fprintf(stderr, "--region-grow goes with --frame and without --except-plane\n"); return 2; }
+  if (region_grow_rgb && (!frame || except_plane || region_grow)) {
+    std::fprintf(stderr, "--region-grow-rgb goes with --frame and without --except-plane and --region-grow\n");
+    return 2;
+  }
   if (!recognise.empty() && !candidates) { std::fprintf(stderr, "--recognise goes with --candidates, --candidates-loop, --segment or --frame\n"); return 2; }
   if (files.size() < 2) { std::fprintf(stderr, "usage: %s <model.pcd> <scene.pcd> [more scenes] [--seed N] [--self-occluded] [--candidates | --candidates-loop | --segment | --frame]\n", argv[0]); return 2; }
   typedef ope::PoseEstimator::PointT PointT;
@@ -333,6 +345,18 @@ int main(int argc, char **argv) {
       if (segRegGrow.deviceFailed()) return 5;
       clusters = segRegGrow.getClusters();
       std::printf("segment crop %zu sweeps %lld\n", segRegGrow.lastCropSize(), (long long)segRegGrow.lastStats().sweeps);
+      std::printf("segment clusters %zu sizes", clusters.size());
+      for (const auto &c : clusters) std::printf(" %zu", c->size());
+      std::printf("\n");
+    } else if (frame && region_grow_rgb) {
+      pcl::PointCloud<PointT>::Ptr cloudTarget(new pcl::PointCloud<PointT>);
+      if (segment || files.size() != 2 || pcl::io::loadPCDFile(files[1], *cloudTarget) != 0) return 3;
+      ope::SegmentationRegionGrow segRegGrow;
+      segRegGrow.getSegmentRegGrowRgb(cloudTarget);
+      if (segRegGrow.deviceFailed()) return 5;
+      clusters = segRegGrow.getClusters();
+      std::printf("segment crop %zu segments %lld absorbed %lld\n", segRegGrow.lastCropSize(), (long long)segRegGrow.lastRgbStats().segments,
+                  (long long)segRegGrow.lastRgbStats().regions_absorbed);
       std::printf("segment clusters %zu sizes", clusters.size());
       for (const auto &c : clusters) std::printf(" %zu", c->size());
       std::printf("\n");

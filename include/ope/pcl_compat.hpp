@@ -19,6 +19,7 @@
 // hasConverged() == false / the transform at identity (registration_mod.hpp:60-64,73-77).
 #pragma once
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -676,6 +677,16 @@ template <class PointT> class PassThrough {
   void setFilterLimits(float lo, float hi) { lo_ = lo; hi_ = hi; }
   void filter(PointCloud<PointT> &out) {
     PointCloud<PointT> tmp;
+    std::vector<int> idx;
+    filter(idx);
+    tmp.points.reserve(idx.size());
+    for (int i : idx) tmp.points.push_back(input_->points[i]);
+    tmp.width = (uint32_t)idx.size();
+    out = std::move(tmp);
+  }
+  // the indices of the survivors (segmentationregiongrow.cpp:95)
+  void filter(std::vector<int> &indices) {
+    indices.clear();
     ope_ctx *ctx = default_context();
     if (ctx && input_ && !input_->empty()) {
       float lo[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX}, hi[3] = {FLT_MAX, FLT_MAX, FLT_MAX};
@@ -685,11 +696,8 @@ template <class PointT> class PassThrough {
       std::vector<int32_t> idx(input_->size());
       size_t n = 0;
       if (dev->h && ope_pass_through(ctx, dev->h, lo, hi, idx.data(), &n) != OPE_OK) { log_error("PassThrough", ctx); n = 0; }
-      tmp.points.reserve(n);
-      for (size_t i = 0; i < n; ++i) tmp.points.push_back(input_->points[idx[i]]);
-      tmp.width = (uint32_t)n;
+      indices.assign(idx.begin(), idx.begin() + n);
     }
-    out = std::move(tmp);
   }
  private:
   typename PointCloud<PointT>::ConstPtr input_;
@@ -765,6 +773,90 @@ template <class PointT> class StatisticalOutlierRemoval {
   typename PointCloud<PointT>::ConstPtr input_;
   int mean_k_ = 1;      // PCL's defaults
   double mul_ = 0.0;
+};
+
+// pcl::ConditionalRemoval over a ConditionAnd of PackedRGBComparison, as far as ProcessingPcd::getFilterRgb uses them
+// (BuildModel processingpcd.cpp:112-141): GT and LT on the channels "r", "g", "b".  The conjunction is an open interval per
+// channel, which is what ope_color_filter takes.
+namespace ComparisonOps { enum CompareOp { GT, LT }; }
+
+template <class PointT> class PackedRGBComparison {
+ public:
+  typedef std::shared_ptr<PackedRGBComparison> Ptr;
+  // PCL compares the channel, a uint8 widened to double, with compare_val
+  PackedRGBComparison(const std::string &component_name, ComparisonOps::CompareOp op, double compare_val)
+      : channel_(component_name == "r" ? 0 : component_name == "g" ? 1 : component_name == "b" ? 2 : -1), op_(op), val_(compare_val) {
+    if (channel_ < 0) std::fprintf(stderr, "[ope::PackedRGBComparison] unrecognized component name '%s'\n", component_name.c_str());
+  }
+  bool isCapable() const { return channel_ >= 0; }
+  int channel_;
+  ComparisonOps::CompareOp op_;
+  double val_;
+};
+
+template <class PointT> class ConditionAnd {
+ public:
+  typedef std::shared_ptr<ConditionAnd> Ptr;
+  void addComparison(const typename PackedRGBComparison<PointT>::Ptr &c) {
+    if (!c || !c->isCapable()) { capable_ = false; return; }
+    // an integer channel: c > v iff c > floor(v), c < v iff c < ceil(v); limits beyond a byte decide nothing
+    const double v = c->val_ != c->val_ ? (c->op_ == ComparisonOps::GT ? 256.0 : -1.0) : std::fmin(std::fmax(c->val_, -1.0), 256.0);
+    if (c->op_ == ComparisonOps::GT) lo_[c->channel_] = std::max(lo_[c->channel_], (int32_t)std::floor(v));
+    else hi_[c->channel_] = std::min(hi_[c->channel_], (int32_t)std::ceil(v));
+  }
+  bool isCapable() const { return capable_; }
+  int32_t lo_[3] = {-1, -1, -1}, hi_[3] = {256, 256, 256};
+ private:
+  bool capable_ = true;
+};
+
+template <class PointT> class ConditionalRemoval {
+  static_assert(point_traits<PointT>::rgb_offset >= 0, "PackedRGBComparison needs a point type with a colour");
+ public:
+  explicit ConditionalRemoval(const typename ConditionAnd<PointT>::Ptr &condition) : condition_(condition) {}
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &c) { input_ = c; }
+  void setKeepOrganized(bool keep) { keep_organized_ = keep; }
+  // keep organized: the input's size, width and height; a failing point keeps its other fields and gets x = y = z = NaN
+  // (PCL's user_filter_value_), and is_dense goes false when any point failed.  Otherwise the finite passing points, in order.
+  void filter(PointCloud<PointT> &out) {
+    PointCloud<PointT> tmp;
+    ope_ctx *ctx = default_context();
+    if (ctx && input_ && condition_ && condition_->isCapable() && !input_->empty()) {
+      const size_t n_in = input_->size();
+      std::vector<uint32_t> rgb(n_in);
+      for (size_t i = 0; i < n_in; ++i)
+        std::memcpy(&rgb[i], reinterpret_cast<const unsigned char *>(&input_->points[i]) + point_traits<PointT>::rgb_offset, 4);
+      auto dev = upload(*input_, false);
+      std::vector<int32_t> idx(n_in);
+      size_t n = 0;
+      if (!dev->h || ope_cloud_set_rgb(ctx, dev->h, rgb.data()) != OPE_OK ||
+          ope_color_filter(ctx, dev->h, condition_->lo_, condition_->hi_, idx.data(), &n) != OPE_OK) {
+        log_error("ConditionalRemoval", ctx);
+        n = 0;
+      }
+      if (keep_organized_) {
+        tmp = *input_;
+        size_t next = 0;
+        for (size_t i = 0; i < n_in; ++i) {
+          if (next < n && (size_t)idx[next] == i) { ++next; continue; }
+          tmp.points[i].x = tmp.points[i].y = tmp.points[i].z = NAN;
+        }
+        if (n < n_in) tmp.is_dense = false;
+      } else {
+        tmp.points.reserve(n);
+        for (size_t i = 0; i < n; ++i) {
+          const PointT &p = input_->points[idx[i]];
+          if (std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z)) tmp.points.push_back(p);
+        }
+        tmp.width = (uint32_t)tmp.points.size();
+      }
+    }
+    out = std::move(tmp);
+  }
+ private:
+  typename ConditionAnd<PointT>::Ptr condition_;
+  typename PointCloud<PointT>::ConstPtr input_;
+  bool keep_organized_ = false;
 };
 
 struct PointIndices {
@@ -927,6 +1019,62 @@ template <class PointT, class NormalT = Normal> class RegionGrowing {
   typename PointCloud<PointT>::ConstPtr input_;
   typename PointCloud<NormalT>::ConstPtr normals_;
   ope_region_params p_;
+};
+
+// pcl::RegionGrowingRGB (ope_region_grow_rgb), with the setters SegmentationRegionGrow::getSegmentRegGrowRgb calls
+// (segmentationregiongrow.cpp:97-106).  The point type carries the colours.  With setIndices the call runs on the selected points
+// alone, as PCL's indexed search sees only those, and the clusters come back as indices into the input cloud.
+typedef std::shared_ptr<std::vector<int>> IndicesPtr;
+template <class PointT, class NormalT = Normal> class RegionGrowingRGB {
+  static_assert(point_traits<PointT>::rgb_offset >= 0, "RegionGrowingRGB needs a point type with a colour");
+ public:
+  RegionGrowingRGB() { ope_region_rgb_default_params(&p_); }   // what the reference sets (:100-103), until a setter changes it
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &c) { input_ = c; }
+  void setIndices(const IndicesPtr &indices) { indices_ = indices; }
+  template <class Tree> void setSearchMethod(const Tree &) {}   // accepted, unused: the device walks its own tree
+  void setDistanceThreshold(float t) { p_.distance_threshold = t; }
+  void setPointColorThreshold(float t) { p_.point_color_threshold = t; }
+  void setRegionColorThreshold(float t) { p_.region_color_threshold = t; }
+  void setMinClusterSize(int n) { p_.min_size = n; }
+  void setMaxClusterSize(int n) { p_.max_size = n; }
+  void setNumberOfRegionNeighbours(unsigned int k) { p_.region_neighbour_number = (int32_t)k; }
+  void extract(std::vector<PointIndices> &clusters) {
+    clusters.clear();
+    ope_ctx *ctx = default_context();
+    if (!ctx || !input_ || input_->empty()) return;
+    const size_t n_in = input_->size();
+    std::vector<uint32_t> rgb(n_in);
+    for (size_t i = 0; i < n_in; ++i)
+      std::memcpy(&rgb[i], reinterpret_cast<const unsigned char *>(&input_->points[i]) + point_traits<PointT>::rgb_offset, 4);
+    auto dev = upload(*input_, false);
+    if (!dev->h) return;
+    if (ope_cloud_set_rgb(ctx, dev->h, rgb.data()) != OPE_OK) { log_error("RegionGrowingRGB", ctx); return; }
+    CloudHandle sub;
+    const ope_cloud *cloud = dev->h;
+    size_t n = n_in;
+    if (indices_) {
+      std::vector<int32_t> sel(indices_->begin(), indices_->end());
+      for (int32_t i : sel)
+        if (i < 0 || (size_t)i >= n_in) { std::fprintf(stderr, "[ope::RegionGrowingRGB] an index lies outside the input cloud\n"); return; }
+      if (sel.empty()) return;
+      if (ope_cloud_select(ctx, dev->h, sel.data(), sel.size(), &sub.h) != OPE_OK) { log_error("RegionGrowingRGB", ctx); return; }
+      cloud = sub.h;
+      n = sel.size();
+    }
+    std::vector<int32_t> idx(n), off(n + 1);
+    size_t k = 0;
+    if (ope_region_grow_rgb(ctx, cloud, &p_, n, &k, idx.data(), off.data(), nullptr) != OPE_OK) { log_error("RegionGrowingRGB", ctx); return; }
+    clusters.resize(k);
+    for (size_t c = 0; c < k; ++c) {
+      clusters[c].indices.assign(idx.begin() + off[c], idx.begin() + off[c + 1]);
+      if (indices_)
+        for (int &i : clusters[c].indices) i = (*indices_)[(size_t)i];
+    }
+  }
+ private:
+  typename PointCloud<PointT>::ConstPtr input_;
+  IndicesPtr indices_;
+  ope_region_rgb_params p_;
 };
 
 // pcl::VFHEstimation with the call shapes ObjectDetection::getVfhFeature uses (objectdetection.cpp:24-27) and PCL's given centroid /

@@ -5,7 +5,7 @@
 //   getDownSampled    :45-59   pcl::VoxelGrid with a cubic leaf                  (ope_voxel_grid / ope_voxel_grid_rgb)
 //   getOutlierRemove  :62-78   pcl::StatisticalOutlierRemoval, meanK 30          (ope_statistical_outlier_removal)
 //   getSmooth         :81-108  pcl::MovingLeastSquares, polynomial fit, no normals (ope_mls_smooth)
-// getFilterRgb (:112-) is not built: the colour filter has no device entry point yet.
+//   getFilterRgb      :112-141 pcl::ConditionalRemoval over PackedRGBComparison, organized (ope_color_filter)
 #pragma once
 
 #include "pcl_compat.hpp"
@@ -68,6 +68,25 @@ class ProcessingPcd {
     mls.process(cloudNormal);
     compat::copyPointCloud(cloudNormal, *cloudSmooth);
     return cloudSmooth;
+  }
+
+  // min < channel < max for r, g and b (strict); the output keeps the input's size, width and height, a failing point its colour
+  // with x = y = z = NaN
+  Cloud::Ptr getFilterRgb(Cloud::Ptr p_cloud, int p_minR, int p_maxR, int p_minG, int p_maxG, int p_minB, int p_maxB) {
+    Cloud::Ptr cloudFiltered(new Cloud);
+    typedef compat::PackedRGBComparison<PointTProc> Comparison;
+    compat::ConditionAnd<PointTProc>::Ptr colorCond(new compat::ConditionAnd<PointTProc>());
+    colorCond->addComparison(Comparison::Ptr(new Comparison("r", compat::ComparisonOps::LT, p_maxR)));
+    colorCond->addComparison(Comparison::Ptr(new Comparison("r", compat::ComparisonOps::GT, p_minR)));
+    colorCond->addComparison(Comparison::Ptr(new Comparison("g", compat::ComparisonOps::LT, p_maxG)));
+    colorCond->addComparison(Comparison::Ptr(new Comparison("g", compat::ComparisonOps::GT, p_minG)));
+    colorCond->addComparison(Comparison::Ptr(new Comparison("b", compat::ComparisonOps::LT, p_maxB)));
+    colorCond->addComparison(Comparison::Ptr(new Comparison("b", compat::ComparisonOps::GT, p_minB)));
+    compat::ConditionalRemoval<PointTProc> condRem(colorCond);
+    condRem.setInputCloud(p_cloud);
+    condRem.setKeepOrganized(true);
+    condRem.filter(*cloudFiltered);
+    return cloudFiltered;
   }
 };
 

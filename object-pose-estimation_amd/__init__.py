@@ -251,6 +251,31 @@ class RegionStats(C.Structure):
     ]
 
 
+class RegionRgbParams(C.Structure):
+    _fields_ = [
+        ("region_neighbour_number", C.c_int32),
+        ("distance_threshold", C.c_double),
+        ("point_color_threshold", C.c_double),
+        ("region_color_threshold", C.c_double),
+        ("min_size", C.c_int32),
+        ("max_size", C.c_int32),
+    ]
+
+
+class RegionRgbStats(C.Structure):
+    _fields_ = [
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+        ("sweeps", C.c_int64),
+        ("one_way_edges", C.c_int64),
+        ("segments", C.c_int64),
+        ("segment_pairs", C.c_int64),
+        ("homogeneous_regions", C.c_int64),
+        ("regions_absorbed", C.c_int64),
+        ("regions_before_size_filter", C.c_int64),
+    ]
+
+
 class VfhParams(C.Structure):
     _fields_ = [
         ("normals_k", C.c_int32),
@@ -484,6 +509,8 @@ ABI = [
     ("ope_uniform_sampling", C.c_int, [_vp, _vp, C.c_float, _ip, C.POINTER(C.c_size_t)]),
     ("ope_remove_nan", C.c_int, [_vp, _vp, _ip, C.POINTER(C.c_size_t)]),
     ("ope_pass_through", C.c_int, [_vp, _vp, _fp, _fp, _ip, C.POINTER(C.c_size_t)]),
+    ("ope_color_filter", C.c_int, [_vp, _vp, _ip, _ip, _ip, C.POINTER(C.c_size_t)]),
+    ("ope_color_filter_cloud", C.c_int, [_vp, _vp, _ip, _ip, C.POINTER(_vp), _ip, C.POINTER(C.c_size_t)]),
     ("ope_voxel_grid", C.c_int, [_vp, _vp, _fp, _fp, C.POINTER(C.c_size_t)]),
     ("ope_voxel_grid_rgb", C.c_int, [_vp, _vp, _fp, _vp, _fp, _vp, C.POINTER(C.c_size_t)]),
     ("ope_statistical_outlier_removal", C.c_int, [_vp, _vp, C.c_int, C.c_double, _ip, C.POINTER(C.c_size_t), _fp]),
@@ -512,6 +539,10 @@ ABI = [
     ("ope_region_grow_cloud", C.c_int, [_vp, _vp, C.POINTER(RegionParams), _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_vp),
                                         _ip, _ip]),
     ("ope_region_last_stats", C.c_int, [_vp, C.POINTER(RegionStats)]),
+    ("ope_region_rgb_default_params", None, [C.POINTER(RegionRgbParams)]),
+    ("ope_region_grow_rgb", C.c_int, [_vp, _vp, C.POINTER(RegionRgbParams), C.c_size_t, C.POINTER(C.c_size_t), _ip, _ip, _ip]),
+    ("ope_region_grow_rgb_cloud", C.c_int, [_vp, _vp, C.POINTER(RegionRgbParams), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(_vp), _ip, _ip]),
+    ("ope_region_rgb_last_stats", C.c_int, [_vp, C.POINTER(RegionRgbStats)]),
     ("ope_vfh_default_params", None, [C.POINTER(VfhParams)]),
     ("ope_vfh_batch", C.c_int, [_vp, C.c_size_t, C.POINTER(_vp), C.POINTER(VfhParams), _fp, _ip, _vp]),
     ("ope_vfh_last_stats", C.c_int, [_vp, C.POINTER(VfhStats)]),
@@ -1092,6 +1123,38 @@ class Context:
         self._chk(lib().ope_region_last_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in RegionStats._fields_}
 
+    def region_grow_rgb(self, cloud: "Cloud", params: "RegionRgbParams | None" = None, max_clusters: int | None = None, clouds: bool = False):
+        """ope_region_grow_rgb: pcl::RegionGrowingRGB (segmentationregiongrow.cpp:85-151) of a Cloud with colours (set_rgb).
+        Returns (clusters, labels, stats): the regions in PCL's order as int32 arrays of ORIGINAL indices, ascending; labels (n,) the
+        index of each point's written region or -1; stats as region_rgb_stats().  With clouds=True the regions also come as device
+        clouds (colours and normals carried): (clouds, clusters, stats)."""
+        p = params if params is not None else default_region_rgb_params()
+        n = cloud.n
+        cap = n if max_clusters is None else int(max_clusters)
+        idx = np.empty(max(n, 1), np.int32)
+        off = np.zeros(cap + 1, np.int32)
+        k = C.c_size_t(0)
+        if clouds:
+            hs = (_vp * max(cap, 1))()
+            self._chk(lib().ope_region_grow_rgb_cloud(self.h, cloud.h, C.byref(p), cap, C.byref(k), hs, _p(idx, _ip), _p(off, _ip)))
+        else:
+            lab = np.empty(max(n, 1), np.int32)
+            self._chk(lib().ope_region_grow_rgb(self.h, cloud.h, C.byref(p), cap, C.byref(k), _p(idx, _ip), _p(off, _ip), _p(lab, _ip)))
+        kw = min(k.value, cap)
+        self.last_cluster_count = k.value
+        indices = [idx[off[i]:off[i + 1]].copy() for i in range(kw)]
+        if clouds:
+            return [Cloud(self, _vp(hs[i]), len(indices[i])) for i in range(kw)], indices, self.region_rgb_stats()
+        return indices, lab[:n].copy(), self.region_rgb_stats()
+
+    def region_rgb_stats(self) -> dict:
+        """ope_region_rgb_last_stats: launches, host synchronisations, sweeps, one-way edges, segments, directed segment pairs,
+        homogeneous regions, regions absorbed by the small-region merge and regions before the size filter, of the last
+        region_grow_rgb."""
+        s = RegionRgbStats()
+        self._chk(lib().ope_region_rgb_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in RegionRgbStats._fields_}
+
     # ---- recognition (vfh.hip)
     def _vfh_clusters(self, clusters):
         cl = [c if isinstance(c, Cloud) else self.upload(c) for c in clusters]
@@ -1568,6 +1631,21 @@ class Context:
         self._chk(lib().ope_pass_through(self.h, cloud.h, _p(lo, _fp), _p(hi, _fp), _p(out, _ip), C.byref(n)))
         return out[: n.value].copy()
 
+    def color_filter(self, cloud: "Cloud", lo, hi, as_cloud: bool = False):
+        """ProcessingPcd::getFilterRgb's condition (pcl::ConditionalRemoval over PackedRGBComparison): original indices, ascending, of
+        the points with lo[c] < channel_c < hi[c] for c = r, g, b (strict; the coordinates play no part).  as_cloud=True: (the
+        passing points as a new device cloud, colours and normals carried, those indices).  OpeError(OPE_EINVAL) for a cloud
+        without colours."""
+        lo = np.ascontiguousarray(lo, np.int32); hi = np.ascontiguousarray(hi, np.int32)
+        if lo.shape != (3,) or hi.shape != (3,):
+            raise ValueError("color_filter: lo and hi are 3-vectors (r, g, b)")
+        if as_cloud:
+            return self._filter_cloud(lib().ope_color_filter_cloud, cloud, (_p(lo, _ip), _p(hi, _ip)), True)
+        out = np.empty(max(cloud.n, 1), np.int32)
+        n = C.c_size_t(0)
+        self._chk(lib().ope_color_filter(self.h, cloud.h, _p(lo, _ip), _p(hi, _ip), _p(out, _ip), C.byref(n)))
+        return out[: n.value].copy()
+
     def voxel_grid(self, cloud: "Cloud", leaf, rgb=None):
         """pcl::VoxelGrid centroids (m,3) in ascending voxel index; OpeError(OPE_ERANGE) where PCL refuses the leaf.
         rgb (optional, n uint32 = the bits of PointXYZRGB::rgb, input order): also the voxels' colours -> (centroids, colours)."""
@@ -1706,6 +1784,15 @@ def default_region_params(**kw) -> RegionParams:
     segmentationregiongrow.cpp:25-36)."""
     p = RegionParams()
     lib().ope_region_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_region_rgb_params(**kw) -> RegionRgbParams:
+    """pcl::RegionGrowingRGB as SegmentationRegionGrow::getSegmentRegGrowRgb sets it (segmentationregiongrow.cpp:97-106)"""
+    p = RegionRgbParams()
+    lib().ope_region_rgb_default_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -5,6 +5,7 @@
 //   pcl::PassThrough::filter       BuildModel/src/processingpcd.cpp:8-36 (z, then y, then x: an axis-aligned box)
 //   pcl::VoxelGrid::filter         BuildModel/src/processingpcd.cpp:39-52
 //   pcl::StatisticalOutlierRemoval DetectAndLocalize/src/processingpcd.cpp:62-77 (getOutlierRemove, meanK 30)
+//   pcl::ConditionalRemoval        BuildModel/src/processingpcd.cpp:112-141 (getFilterRgb: PackedRGBComparison GT / LT per channel)
 //
 // Index filters return ORIGINAL indices in ascending order (PCL keeps the input order).  The cloud on the
 // device is Morton-sorted, so the keep flag of each point is scattered to its original position and a
@@ -35,6 +36,19 @@ __global__ __launch_bounds__(256) void box_flags_kernel(CloudView c, float lox, 
   // passthrough.hpp: "if (value > max || value < min) -> removed"; non-finite points (sorted last) never pass
   const bool keep = i < c.n_valid && !(p.x > hix || p.x < lox) && !(p.y > hiy || p.y < loy) && !(p.z > hiz || p.z < loz);
   flags_orig[(uint32_t)__float_as_int(p.w)] = keep ? 1 : 0;
+}
+
+// ProcessingPcd::getFilterRgb's condition: lo < channel < hi for r, g and b of the colour word (sorted order, beside the
+// points), strict integer comparisons as PackedRGBComparison makes them with GT / LT.  The coordinates play no part, so a
+// non-finite point passes or fails by its colour like any other.
+__global__ __launch_bounds__(256) void color_flags_kernel(CloudView c, const uint32_t *__restrict__ rgb, int lor, int log, int lob, int hir, int hig,
+                                                           int hib, unsigned char *__restrict__ flags_orig) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= c.n) return;
+  const uint32_t v = rgb[i];
+  const int r = (int)((v >> 16) & 255u), g = (int)((v >> 8) & 255u), b = (int)(v & 255u);
+  const bool keep = r > lor && r < hir && g > log && g < hig && b > lob && b < hib;
+  flags_orig[(uint32_t)__float_as_int(c.xyzw[i].w)] = keep ? 1 : 0;
 }
 
 __global__ __launch_bounds__(256) void grid_key_kernel(CloudView c, float invx, float invy, float invz, int min_bx, int min_by,
@@ -159,9 +173,24 @@ __global__ __launch_bounds__(256) void reject_pairs_kernel(int kind, const float
   keep[i] = ok ? 1 : 0;
 }
 
+// What an index filter keeps: the points inside the box lo..hi (PassThrough), or, with clo / chi set, the points whose colour
+// channels lie strictly between them (ope_color_filter; the cloud has colours).
+struct KeepRule {
+  const float *lo, *hi;
+  const int32_t *clo = nullptr, *chi = nullptr;
+};
+// the keep flag of every point by ORIGINAL index (n > 0)
+static void keep_flags(ope_ctx *ctx, const ope_cloud *cloud, const KeepRule &k, unsigned char *d_flags) {
+  const dim3 grid((unsigned)((cloud->n + 255) / 256));
+  if (k.clo)
+    hipLaunchKernelGGL(color_flags_kernel, grid, dim3(256), 0, ctx->stream, cloud->view(), cloud->d_rgb, k.clo[0], k.clo[1], k.clo[2], k.chi[0], k.chi[1],
+                       k.chi[2], d_flags);
+  else
+    hipLaunchKernelGGL(box_flags_kernel, grid, dim3(256), 0, ctx->stream, cloud->view(), k.lo[0], k.lo[1], k.lo[2], k.hi[0], k.hi[1], k.hi[2], d_flags);
+}
+
 // survivors' ORIGINAL indices in input order, left on the device (*d_out_ret, caller frees); count on the host
-static int box_filter_dev(ope_ctx *ctx, const ope_cloud *cloud, const float lo[3], const float hi[3], int32_t **d_out_ret, unsigned int *count_ret,
-                          const char *who) {
+static int box_filter_dev(ope_ctx *ctx, const ope_cloud *cloud, const KeepRule &rule, int32_t **d_out_ret, unsigned int *count_ret, const char *who) {
   *d_out_ret = nullptr;
   *count_ret = 0;
   const size_t n = cloud->n;
@@ -176,8 +205,7 @@ static int box_filter_dev(ope_ctx *ctx, const ope_cloud *cloud, const float lo[3
   if (e == hipSuccess) e = tmp_malloc(ctx->stream, (void **)&d_out, 4 * n);
   if (e == hipSuccess) e = tmp_malloc(ctx->stream, (void **)&d_count, 4);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(box_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, cloud->view(), lo[0], lo[1],
-                       lo[2], hi[0], hi[1], hi[2], d_flags);
+    keep_flags(ctx, cloud, rule, d_flags);
     rocprim::counting_iterator<int32_t> iota(0);
     size_t tb = 0;
     e = rocprim::select(nullptr, tb, iota, d_flags, d_out, d_count, n, ctx->stream);
@@ -196,12 +224,11 @@ static int box_filter_dev(ope_ctx *ctx, const ope_cloud *cloud, const float lo[3
   return OPE_OK;
 }
 
-static int box_filter(ope_ctx *ctx, const ope_cloud *cloud, const float lo[3], const float hi[3], int32_t *out_idx,
-                      size_t *n_out, const char *who) {
+static int box_filter(ope_ctx *ctx, const ope_cloud *cloud, const KeepRule &rule, int32_t *out_idx, size_t *n_out, const char *who) {
   *n_out = 0;
   int32_t *d_out = nullptr;
   unsigned int count = 0;
-  const int rc = box_filter_dev(ctx, cloud, lo, hi, &d_out, &count, who);
+  const int rc = box_filter_dev(ctx, cloud, rule, &d_out, &count, who);
   if (rc != OPE_OK) return rc;
   hipError_t e = hipSuccess;
   if (count) e = hipMemcpy(out_idx, d_out, 4 * (size_t)count, hipMemcpyDeviceToHost);
@@ -213,8 +240,8 @@ static int box_filter(ope_ctx *ctx, const ope_cloud *cloud, const float lo[3], c
 
 // the same with the survivors handed on as a device-resident cloud (and, optionally, their indices to the host): the flags
 // by original index go straight into the order-preserving compaction (sampling.hip), nothing is sorted again
-static int box_filter_cloud(ope_ctx *ctx, const ope_cloud *cloud, const float lo[3], const float hi[3], ope_cloud **out, int32_t *out_idx,
-                            size_t *n_out, const char *who) {
+static int box_filter_cloud(ope_ctx *ctx, const ope_cloud *cloud, const KeepRule &rule, ope_cloud **out, int32_t *out_idx, size_t *n_out,
+                            const char *who) {
   *out = nullptr;
   if (n_out) *n_out = 0;
   const size_t n = cloud->n;
@@ -226,9 +253,7 @@ static int box_filter_cloud(ope_ctx *ctx, const ope_cloud *cloud, const float lo
   int rc = OPE_OK;
   size_t count = 0;
   if (e == hipSuccess) {
-    if (n)
-      hipLaunchKernelGGL(box_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, cloud->view(), lo[0], lo[1], lo[2], hi[0], hi[1],
-                         hi[2], d_flags);
+    if (n) keep_flags(ctx, cloud, rule, d_flags);
     rc = compact_cloud_device(ctx, cloud, d_flags, out, d_idx, &count);
     if (rc == OPE_OK && out_idx && count) e = hipMemcpy(out_idx, d_idx, 4 * count, hipMemcpyDeviceToHost);
   }
@@ -312,13 +337,13 @@ using namespace ope;
 extern "C" int ope_remove_nan(ope_ctx *ctx, const ope_cloud *cloud, int32_t *out_idx, size_t *n_out) {
   if (!ctx || !cloud || !out_idx || !n_out) return set_err(ctx, OPE_EINVAL, "ope_remove_nan: bad argument");
   const float lo[3] = {-INFINITY, -INFINITY, -INFINITY}, hi[3] = {INFINITY, INFINITY, INFINITY};
-  return box_filter(ctx, cloud, lo, hi, out_idx, n_out, "ope_remove_nan");
+  return box_filter(ctx, cloud, KeepRule{lo, hi}, out_idx, n_out, "ope_remove_nan");
 }
 
 extern "C" int ope_pass_through(ope_ctx *ctx, const ope_cloud *cloud, const float lo[3], const float hi[3], int32_t *out_idx,
                                 size_t *n_out) {
   if (!ctx || !cloud || !lo || !hi || !out_idx || !n_out) return set_err(ctx, OPE_EINVAL, "ope_pass_through: bad argument");
-  return box_filter(ctx, cloud, lo, hi, out_idx, n_out, "ope_pass_through");
+  return box_filter(ctx, cloud, KeepRule{lo, hi}, out_idx, n_out, "ope_pass_through");
 }
 
 extern "C" int ope_voxel_grid(ope_ctx *ctx, const ope_cloud *cloud, const float leaf[3], float *out_xyz, size_t *n_out) {
@@ -539,13 +564,26 @@ extern "C" int ope_statistical_outlier_removal_cloud(ope_ctx *ctx, const ope_clo
 extern "C" int ope_pass_through_cloud(ope_ctx *ctx, const ope_cloud *cloud, const float lo[3], const float hi[3], ope_cloud **out, int32_t *out_idx,
                                       size_t *n_out) {
   if (!ctx || !cloud || !lo || !hi || !out) return set_err(ctx, OPE_EINVAL, "ope_pass_through_cloud: bad argument");
-  return box_filter_cloud(ctx, cloud, lo, hi, out, out_idx, n_out, "ope_pass_through_cloud");
+  return box_filter_cloud(ctx, cloud, KeepRule{lo, hi}, out, out_idx, n_out, "ope_pass_through_cloud");
+}
+
+extern "C" int ope_color_filter(ope_ctx *ctx, const ope_cloud *cloud, const int32_t lo[3], const int32_t hi[3], int32_t *out_idx, size_t *n_out) {
+  if (!ctx || !cloud || !lo || !hi || !out_idx || !n_out) return set_err(ctx, OPE_EINVAL, "ope_color_filter: bad argument");
+  if (!cloud->d_rgb) return set_err(ctx, OPE_EINVAL, "ope_color_filter: the cloud has no colours");
+  return box_filter(ctx, cloud, KeepRule{nullptr, nullptr, lo, hi}, out_idx, n_out, "ope_color_filter");
+}
+
+extern "C" int ope_color_filter_cloud(ope_ctx *ctx, const ope_cloud *cloud, const int32_t lo[3], const int32_t hi[3], ope_cloud **out, int32_t *out_idx,
+                                      size_t *n_out) {
+  if (!ctx || !cloud || !lo || !hi || !out) return set_err(ctx, OPE_EINVAL, "ope_color_filter_cloud: bad argument");
+  if (!cloud->d_rgb) return set_err(ctx, OPE_EINVAL, "ope_color_filter_cloud: the cloud has no colours");
+  return box_filter_cloud(ctx, cloud, KeepRule{nullptr, nullptr, lo, hi}, out, out_idx, n_out, "ope_color_filter_cloud");
 }
 
 extern "C" int ope_remove_nan_cloud(ope_ctx *ctx, const ope_cloud *cloud, ope_cloud **out, int32_t *out_idx, size_t *n_out) {
   if (!ctx || !cloud || !out) return set_err(ctx, OPE_EINVAL, "ope_remove_nan_cloud: bad argument");
   const float lo[3] = {-INFINITY, -INFINITY, -INFINITY}, hi[3] = {INFINITY, INFINITY, INFINITY};
-  return box_filter_cloud(ctx, cloud, lo, hi, out, out_idx, n_out, "ope_remove_nan_cloud");
+  return box_filter_cloud(ctx, cloud, KeepRule{lo, hi}, out, out_idx, n_out, "ope_remove_nan_cloud");
 }
 
 extern "C" int ope_reject_pairs(ope_ctx *ctx, int kind, const float *a, const float *b, size_t n, double threshold, unsigned char *keep) {

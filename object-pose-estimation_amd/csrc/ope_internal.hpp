@@ -279,6 +279,7 @@ struct ope_ctx {
 
   ope_cluster_stats cluster_stats{};   // what the last ope_euclidean_clusters* call did (clusters.hip)
   ope_region_stats region_stats{};     // what the last ope_region_grow* call did (region_grow.hip)
+  ope_region_rgb_stats region_rgb_stats{};   // what the last ope_region_grow_rgb* call did (region_grow_rgb.hip)
   ope_vfh_stats vfh_stats{};           // what the last ope_vfh_* call did (vfh.hip)
 
   // the last ope_plane_segment (plane.hip): what it did, and its hypotheses in drawing order (ope_plane_last_hypotheses)
