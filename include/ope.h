@@ -59,7 +59,7 @@ void ope_ctx_destroy(ope_ctx *ctx);
 int ope_ctx_set_stream(ope_ctx *ctx, void *hip_stream);
 int ope_ctx_sync(ope_ctx *ctx);
 /* Named roctx ranges (rocprofv3 --marker-trace) around the host side of the path: icp_iter {nn, reduce}, normals,
- * fpfh_spfh, fpfh_weight, sacia, index_build, uniform_sampling.  Off by default.  The reference's own instrumentation is
+ * fpfh_spfh, fpfh_weight, sacia, prerejective, index_build, uniform_sampling.  Off by default.  The reference's own instrumentation is
  * pcl::ScopeTime("Initial Alignment" / "Final Alignment") (poseestimator.cpp:61,349): the facade keeps those names. */
 int ope_ctx_set_tracing(ope_ctx *ctx, int on);
 /* Bound of every device-side wait of the overlapped update launches (ope_icp_params.update_launch), seconds, 0 .. 40; default 2.
@@ -517,6 +517,63 @@ void ope_sacia_default_params(ope_sacia_params *p);
 int ope_sacia(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const ope_cloud *tgt,
               const ope_index *tgt_index, const float *tgt_feat33, const ope_sacia_params *params,
               const int32_t *forced_samples, float out_T[16], double *best_error, int32_t *best_iteration);
+
+/* ---------------- prerejective coarse alignment ---------------- */
+/* pcl::SampleConsensusPrerejective::align with the parameters of the block the reference keeps commented out
+ * (BuildModel/src/poseestimator.cpp:90-108), the initial guess the identity.  Every iteration is drawn up front, tested by
+ * CorrespondenceRejectorPoly in one launch, and the survivors are fitted and scored together. */
+typedef struct {
+  int32_t max_iterations;      /* 50000 (:97); 1 .. 2^20 */
+  int32_t nr_samples;          /* 3     (:98); 3 .. 8 */
+  int32_t k_correspondences;   /* 5     (:99) setCorrespondenceRandomness; 1 .. 8 */
+  float similarity_threshold;  /* 0.8   (:100); [0, 1) */
+  double max_corr_dist;        /* 0.15  (:101) the inlier distance; > 0 */
+  float inlier_fraction;       /* 0.25  (:102); [0, 1] */
+  uint64_t seed;               /* 1: the LCG stream of ope_sacia */
+} ope_prerejective_params;
+void ope_prerejective_default_params(ope_prerejective_params *p);
+typedef struct {
+  float T[16];             /* column-major; the identity without a winner */
+  double error;            /* the winner's mean squared inlier distance; FLT_MAX without a winner */
+  int32_t best_iteration;  /* -1 without a winner */
+  int32_t inliers;
+  int32_t converged;
+} ope_prerejective_result;
+typedef struct {
+  int64_t iterations;   /* hypotheses drawn (max_iterations) */
+  int64_t survivors;    /* hypotheses the polygon test let through */
+  int64_t launches;     /* kernel launches and copies to the device enqueued (a rocPRIM select counts as one) */
+  int64_t host_syncs;
+  int64_t nr_samples;   /* of that call: what ope_prerejective_last_hypotheses writes per iteration into samples and targets */
+} ope_prerejective_stats;
+/* src_feat33 / tgt_feat33: n * 33 floats in ORIGINAL order.  Per iteration the host draws nr_samples distinct source indices
+ * int(ns * next()) and then nr_samples picks int(k * next()); the target of a sample is the pick-th of the k nearest target
+ * descriptors of its source descriptor.  forced_samples (optional): max_iterations * nr_samples source indices then as many target
+ * indices, taken instead of the draws and the feature search (the features may then be NULL).
+ * An iteration survives iff every edge i -> (i + 1) mod nr_samples has min(ds, dt) / max(ds, dt) >= similarity_threshold^2 (squared
+ * lengths in the source and in the target, float; a NaN ratio fails).  A survivor's transform is Umeyama without scaling over its
+ * pairs (fp64).  Its inliers are the finite source points whose moved image has a nearest target point at a squared distance
+ * (float, widened) < max_corr_dist^2; its error is the fp64 sum of those squared distances over their number (FLT_MAX for
+ * none).  In iteration order a survivor is accepted iff (float)inliers / (float)|source| >= inlier_fraction and its error is below
+ * the lowest so far.  out_inliers (optional, room for every source point): the winner's inliers, ORIGINAL indices ascending,
+ * out->inliers of them.  No winner: OPE_OK, converged = 0.
+ * params may be NULL: the defaults of ope_prerejective_default_params (as ope_sacia takes a NULL params).
+ * OPE_EINVAL, nothing launched: a NULL ctx, src, tgt, tgt_index or out (or features, without forced_samples); a parameter outside
+ * the ranges above; fewer source points than nr_samples; an empty target (a cloud without a finite point, or an index over none);
+ * k_correspondences above the number of target points; a forced index out of range; a context with a communicator.  OPE_EINVAL
+ * after the feature search, nothing more launched: a sampled source descriptor without a single finite distance to a target
+ * descriptor (NaN rows).
+ * Launches and synchronisations depend on neither the iterations, the survivors nor the points (ope_prerejective_last_stats). */
+int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const ope_cloud *tgt, const ope_index *tgt_index,
+                     const float *tgt_feat33, const ope_prerejective_params *params, const int32_t *forced_samples,
+                     ope_prerejective_result *out, int32_t *out_inliers);
+int ope_prerejective_last_stats(const ope_ctx *ctx, ope_prerejective_stats *out);
+/* The iterations of the last ope_prerejective in drawing order: samples and targets (ope_prerejective_stats.nr_samples ORIGINAL
+ * indices each, cap * nr_samples entries of room), survived (1 / 0), T (16 floats, column-major), inliers and error; an iteration
+ * that did not survive has the identity, 0 and FLT_MAX.  Any output may be NULL; at most cap iterations are written, *n_out = how
+ * many there were. */
+int ope_prerejective_last_hypotheses(const ope_ctx *ctx, int32_t *samples, int32_t *targets, uint8_t *survived, float *T,
+                                     int32_t *inliers, double *error, size_t cap, size_t *n_out);
 
 /* ---------------- batched coarse stage ---------------- */
 /* estimateCoarsePose (poseestimator.cpp:16-73) of one model against n candidate clusters in one call: the coarse half of the

@@ -39,6 +39,11 @@
 // clusters of the remainder as --candidates takes them.  Prints `segment planes <k> sizes <c0> <c1> ... rest <m>`,
 // `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
 //
+//   ... --coarse sac-ia|prerejective   (every mode but --depth)
+// The coarse aligner of PoseEstimator::estimateCoarsePose: SAC-IA (the default, the reference's live code) or the
+// pcl::SampleConsensusPrerejective block the reference keeps commented out (BuildModel poseestimator.cpp:90-108; 50 000 iterations on
+// the device).  With prerejective the candidate loop and the tracker run one estimateFinalPose at a time.
+//
 //   ... --recognise <train_dir>   (with --candidates, --candidates-loop, --segment or --frame)
 // Before the pose stage, ope::ObjectDetection::getObjectNames over every cluster in one call against the table under <train_dir>
 // (training_data.list / training_data.f32).  Prints `recognise <i> <name> <distance>` per cluster: the name getObjectName gives
@@ -95,6 +100,14 @@ static const char *branch_name(int b) {
   }
 }
 
+// --coarse's value: false for an unknown name
+static bool parse_coarse(const char *v, ope::PoseEstimator::CoarseMethod &m) {
+  if (!std::strcmp(v, "sac-ia")) { m = ope::PoseEstimator::COARSE_SAC_IA; return true; }
+  if (!std::strcmp(v, "prerejective")) { m = ope::PoseEstimator::COARSE_PREREJECTIVE; return true; }
+  std::fprintf(stderr, "--coarse takes sac-ia or prerejective\n");
+  return false;
+}
+
 // --track / --track-loop
 static int track_main(int argc, char **argv) {
   int mode = 0;   // 1: --track, 2: --track-loop
@@ -102,12 +115,14 @@ static int track_main(int argc, char **argv) {
   std::vector<std::vector<std::string>> frames;
   uint64_t seed = 1;
   bool self_occluded = false, timed = false;
+  ope::PoseEstimator::CoarseMethod coarse = ope::PoseEstimator::COARSE_SAC_IA;
   for (int i = 1; i < argc; ++i) {
     if ((!std::strcmp(argv[i], "--track") || !std::strcmp(argv[i], "--track-loop")) && i + 1 < argc) {
       mode = !std::strcmp(argv[i], "--track") ? 1 : 2;
       model_path = argv[++i];
     } else if (!std::strcmp(argv[i], "--frame")) frames.emplace_back();
     else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
+    else if (!std::strcmp(argv[i], "--coarse") && i + 1 < argc) { if (!parse_coarse(argv[++i], coarse)) return 2; }
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--time")) timed = true;
     else if (!frames.empty()) frames.back().push_back(argv[i]);
@@ -119,6 +134,7 @@ static int track_main(int argc, char **argv) {
   if (pcl::io::loadPCDFile(model_path, model) != 0) return 3;
   ope::ObjectTracker tracker(model);
   tracker.estimator().setSacIaSeed(seed);
+  tracker.estimator().setCoarseMethod(coarse);
   tracker.estimator().setUseSelfOccludedRejector(self_occluded);
   double fitnessScore = 10.0, alignedStrength = 0.0;   // rosinterface.h: kept across frames
   for (size_t k = 0; k < frames.size(); ++k) {
@@ -257,9 +273,11 @@ int main(int argc, char **argv) {
   bool region_grow = false;    // --region-grow (with --frame): from SegmentationRegionGrow::getSegmentRegGrow instead
   bool region_grow_rgb = false;   // --region-grow-rgb (with --frame): from SegmentationRegionGrow::getSegmentRegGrowRgb instead
   std::string recognise;       // --recognise <train_dir>: name every cluster before the pose stage
+  ope::PoseEstimator::CoarseMethod coarse = ope::PoseEstimator::COARSE_SAC_IA;   // --coarse
   float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
+    else if (!std::strcmp(argv[i], "--coarse") && i + 1 < argc) { if (!parse_coarse(argv[++i], coarse)) return 2; }
     else if (!std::strcmp(argv[i], "--recognise") && i + 1 < argc) recognise = argv[++i];
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--candidates")) candidates = 1;
@@ -286,6 +304,7 @@ int main(int argc, char **argv) {
   *cloudSource = *cloudSourceOriginal;
   ope::PoseEstimator poseEstimator;
   poseEstimator.setSacIaSeed(seed);
+  poseEstimator.setCoarseMethod(coarse);
   poseEstimator.setUseSelfOccludedRejector(self_occluded);
   auto print_frame = [&](size_t k, const pcl::Matrix4f &pose, double fitnessScore, double alignedStrength) {
     std::printf("frame %zu fitness %.12g strength %.12g coarse_calls %d icp_iterations %d", k, fitnessScore, alignedStrength,

@@ -14,6 +14,7 @@
 //   NormalEstimation / FPFHEstimation / UniformSampling  poseestimator.cpp:121-125,141-156
 //   removeNaNFromPointCloud / PassThrough / VoxelGrid    poseestimator.cpp:192-194; BuildModel processingpcd.cpp:8-52
 //   SampleConsensusInitialAlignment                      poseestimator.cpp:50-64
+//   SampleConsensusPrerejective                          BuildModel poseestimator.cpp:90-108 (commented out there)
 // Point types are layout-compatible PODs (x@0,y@4,z@8; normal@16 in PointXYZRGBNormal; 16-byte aligned).
 // Errors never throw on the hot path: like PCL, a failed call logs to stderr and leaves
 // hasConverged() == false / the transform at identity (registration_mod.hpp:60-64,73-77).
@@ -1309,6 +1310,67 @@ template <class PointSource, class PointTarget, class FeatureT> class SampleCons
   Matrix4f final_ = Matrix4f::Identity();
   bool converged_ = false;
   double error_ = 0;
+};
+
+// pcl::SampleConsensusPrerejective with the calls of the reference's commented block (BuildModel poseestimator.cpp:92-108), on
+// ope_prerejective.  The class defaults are PCL's (3 samples, correspondence randomness 2, similarity 0.9, inlier fraction 0,
+// Registration's 10 iterations and unbounded distance).  getFitnessScore() is the winner's mean squared inlier distance.
+template <class PointSource, class PointTarget, class FeatureT> class SampleConsensusPrerejective {
+ public:
+  SampleConsensusPrerejective() {
+    ope_prerejective_default_params(&p_);
+    p_.max_iterations = 10; p_.nr_samples = 3; p_.k_correspondences = 2; p_.similarity_threshold = 0.9f; p_.inlier_fraction = 0.f;
+    p_.max_corr_dist = std::sqrt(DBL_MAX);
+  }
+  void setInputSource(const typename PointCloud<PointSource>::ConstPtr &c) { src_ = c; }
+  void setInputTarget(const typename PointCloud<PointTarget>::ConstPtr &c) { tgt_ = c; }
+  void setSourceFeatures(const typename PointCloud<FeatureT>::ConstPtr &f) { sf_ = f; }
+  void setTargetFeatures(const typename PointCloud<FeatureT>::ConstPtr &f) { tf_ = f; }
+  void setMaximumIterations(int n) { p_.max_iterations = n; }
+  void setNumberOfSamples(int n) { p_.nr_samples = n; }
+  void setCorrespondenceRandomness(int k) { p_.k_correspondences = k; }
+  void setSimilarityThreshold(float s) { p_.similarity_threshold = s; }
+  void setMaxCorrespondenceDistance(double d) { p_.max_corr_dist = d; }
+  void setInlierFraction(float f) { p_.inlier_fraction = f; }
+  void setSeed(uint64_t s) { p_.seed = s; }  // PCL draws from unseeded rand(): made explicit here
+  void align(PointCloud<PointSource> &output) {
+    final_ = Matrix4f::Identity();
+    converged_ = false;
+    inliers_.clear();
+    error_ = FLT_MAX;
+    best_ = -1;
+    ope_ctx *ctx = default_context();
+    if (!ctx || !src_ || !tgt_ || !sf_ || !tf_ || sf_->size() != src_->size() || tf_->size() != tgt_->size()) return;
+    if (src_->empty() || tgt_->empty()) return;   // nothing to align (and no first feature row to point at)
+    auto ds = upload(*src_, false), dt = upload(*tgt_, false);
+    IndexHandle ix;
+    if (!ds->h || !dt->h || ope_index_build(ctx, dt->h, nullptr, &ix.h) != OPE_OK) return;
+    ope_prerejective_result r;
+    std::vector<int32_t> idx(src_->size() + 1);
+    if (ope_prerejective(ctx, ds->h, &sf_->points[0].histogram[0], dt->h, ix.h, &tf_->points[0].histogram[0], &p_, nullptr, &r,
+                         idx.data()) != OPE_OK) { log_error("SampleConsensusPrerejective", ctx); return; }
+    std::memcpy(final_.m, r.T, sizeof final_.m);
+    converged_ = r.converged != 0;
+    error_ = r.error;
+    best_ = r.best_iteration;
+    if (converged_) inliers_.assign(idx.begin(), idx.begin() + r.inliers);
+    transformPointCloud(*src_, output, final_);
+  }
+  Matrix4f getFinalTransformation() const { return final_; }
+  bool hasConverged() const { return converged_; }
+  const std::vector<int> &getInliers() const { return inliers_; }
+  double getFitnessScore() const { return error_; }
+  int getBestIteration() const { return best_; }   // not PCL's: the winning iteration, -1 for none
+ private:
+  typename PointCloud<PointSource>::ConstPtr src_;
+  typename PointCloud<PointTarget>::ConstPtr tgt_;
+  typename PointCloud<FeatureT>::ConstPtr sf_, tf_;
+  ope_prerejective_params p_;
+  Matrix4f final_ = Matrix4f::Identity();
+  bool converged_ = false;
+  std::vector<int> inliers_;
+  double error_ = FLT_MAX;
+  int best_ = -1;
 };
 
 }  // namespace compat

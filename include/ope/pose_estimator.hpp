@@ -36,6 +36,10 @@ class PoseEstimator {
 
   PoseEstimator() : alignedSource(new Cloud), cloudModel(new Cloud) {}
 
+  // the coarse aligner: SAC-IA (the reference's live code, the default) or the prerejective block the reference keeps commented out
+  enum CoarseMethod { COARSE_SAC_IA = 0, COARSE_PREREJECTIVE = 1 };
+  void setCoarseMethod(CoarseMethod m) { coarse_method_ = m; }
+  CoarseMethod coarseMethod() const { return coarse_method_; }
   void setSacIaSeed(uint64_t seed) { sacia_seed_ = seed; }
   void setUseSelfOccludedRejector(bool on) { use_self_occluded_ = on; }
   // diagnostics of the last estimateFinalPose call
@@ -86,6 +90,7 @@ class PoseEstimator {
       std::printf("NO target cloud in Initial Alignment\n");
       return Matrix4f::Identity();
     }
+    if (coarse_method_ == COARSE_PREREJECTIVE) return prerejectiveCoarsePose(p_sourceCloud, src, tgt, srcFeat, tgtFeat);
     compat::SampleConsensusInitialAlignment<PointT, PointT, compat::FPFHSignature33> sacia;
     sacia.setInputSource(src);
     sacia.setInputTarget(tgt);
@@ -188,7 +193,7 @@ class PoseEstimator {
     const Cloud original(*p_sourceCloud);
     std::vector<ope_final_batch_result> res(clusters.size());
     int32_t sel = -1;
-    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty();
+    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() && coarse_method_ == COARSE_SAC_IA;   // (the batch's coarse stage is SAC-IA)
     if (batched) {
       ope_ctx *ctx = compat::default_context();
       auto model = compat::upload(original, false);
@@ -299,6 +304,32 @@ class PoseEstimator {
   }
 
  private:
+  // BuildModel/src/poseestimator.cpp:92-107, the block the reference keeps commented out, in SAC-IA's place: the same key points and
+  // features, the k-th coarse call draws with seed + k; without a converged alignment the pose is the identity
+  Matrix4f prerejectiveCoarsePose(const Cloud::Ptr &p_sourceCloud, const Cloud::Ptr &src, const Cloud::Ptr &tgt, const FeatureCloud::Ptr &srcFeat,
+                                  const FeatureCloud::Ptr &tgtFeat) {
+    compat::SampleConsensusPrerejective<PointT, PointT, compat::FPFHSignature33> sacPreRej;
+    sacPreRej.setInputSource(src);
+    sacPreRej.setSourceFeatures(srcFeat);
+    sacPreRej.setInputTarget(tgt);
+    sacPreRej.setTargetFeatures(tgtFeat);
+    sacPreRej.setMaximumIterations(50000);          // :97
+    sacPreRej.setNumberOfSamples(3);                // :98
+    sacPreRej.setCorrespondenceRandomness(5);       // :99
+    sacPreRej.setSimilarityThreshold(0.8f);         // :100
+    sacPreRej.setMaxCorrespondenceDistance(0.15);   // :101
+    sacPreRej.setInlierFraction(0.25f);             // :102
+    sacPreRej.setSeed(sacia_seed_ + (uint64_t)coarse_calls_++);
+    Cloud result;
+    {
+      compat::ScopeTime t("Initial Alignment");
+      sacPreRej.align(result);
+    }
+    const Matrix4f pose = sacPreRej.hasConverged() ? sacPreRej.getFinalTransformation() : Matrix4f::Identity();
+    compat::transformPointCloud(*p_sourceCloud, *alignedSource, pose);
+    return pose;
+  }
+
   // sub-sample at 8 mm, normals (k = 30), xyz + normal packed into PointXYZRGBNormal, NaN normals dropped (:196-216)
   CloudN::Ptr withNormals(const Cloud::Ptr &cloud) {
     Cloud::Ptr sub;
@@ -343,6 +374,7 @@ class PoseEstimator {
   compat::registration::TransformationEstimationSVD<PointT, PointT> svd;
   // knobs and diagnostics
   uint64_t sacia_seed_ = 1;
+  CoarseMethod coarse_method_ = COARSE_SAC_IA;
   int coarse_calls_ = 0;
   bool use_self_occluded_ = false;
   Matrix4f last_coarse_ = Matrix4f::Identity(), last_fine_ = Matrix4f::Identity(), last_rigid_ = Matrix4f::Identity();

@@ -122,6 +122,38 @@ class SaciaParams(C.Structure):
     ]
 
 
+class PrerejectiveParams(C.Structure):
+    _fields_ = [
+        ("max_iterations", C.c_int32),
+        ("nr_samples", C.c_int32),
+        ("k_correspondences", C.c_int32),
+        ("similarity_threshold", C.c_float),
+        ("max_corr_dist", C.c_double),
+        ("inlier_fraction", C.c_float),
+        ("seed", C.c_uint64),
+    ]
+
+
+class PrerejectiveResult(C.Structure):
+    _fields_ = [
+        ("T", C.c_float * 16),
+        ("error", C.c_double),
+        ("best_iteration", C.c_int32),
+        ("inliers", C.c_int32),
+        ("converged", C.c_int32),
+    ]
+
+
+class PrerejectiveStats(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int64),
+        ("survivors", C.c_int64),
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+        ("nr_samples", C.c_int64),
+    ]
+
+
 class CoarseParams(C.Structure):
     _fields_ = [
         ("key_leaf", C.c_float),
@@ -516,6 +548,10 @@ ABI = [
     ("ope_statistical_outlier_removal", C.c_int, [_vp, _vp, C.c_int, C.c_double, _ip, C.POINTER(C.c_size_t), _fp]),
     ("ope_sacia_default_params", None, [C.POINTER(SaciaParams)]),
     ("ope_sacia", C.c_int, [_vp, _vp, _fp, _vp, _vp, _fp, C.POINTER(SaciaParams), _ip, _fp, _dp, _ip]),
+    ("ope_prerejective_default_params", None, [C.POINTER(PrerejectiveParams)]),
+    ("ope_prerejective", C.c_int, [_vp, _vp, _fp, _vp, _vp, _fp, C.POINTER(PrerejectiveParams), _ip, C.POINTER(PrerejectiveResult), _ip]),
+    ("ope_prerejective_last_stats", C.c_int, [_vp, C.POINTER(PrerejectiveStats)]),
+    ("ope_prerejective_last_hypotheses", C.c_int, [_vp, _ip, _ip, C.POINTER(C.c_uint8), _fp, _ip, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("ope_coarse_default_params", None, [C.POINTER(CoarseParams)]),
     ("ope_coarse_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(CoarseParams), C.POINTER(C.c_uint64),
                                          C.POINTER(CoarseBatchResult)]),
@@ -694,6 +730,16 @@ class CoarseOut:
     n_src_keys: int        # model key points
     n_tgt_keys: int        # this cluster's key points
     status: int            # COARSE_OK, COARSE_EMPTY_TARGET or COARSE_FEW_TARGET_FEATURES
+
+
+@dataclass
+class PrerejectiveOut:
+    T: np.ndarray          # (4,4) math layout, float32 — getFinalTransformation(); the identity without a winner
+    error: float           # the winner's mean squared inlier distance (FLT_MAX without a winner)
+    best_iteration: int    # -1 without a winner
+    inliers: int
+    converged: bool
+    inlier_idx: np.ndarray | None   # getInliers(): ORIGINAL source indices, ascending (with_inliers=True)
 
 
 @dataclass
@@ -1748,6 +1794,58 @@ class Context:
         self._chk(lib().ope_sacia(self.h, src.h, _p(sf, _fp), tgt.h, tgt_index.h, _p(tf, _fp), C.byref(p), _p(fs, _ip),
                                   _p(T, _fp), C.byref(err), C.byref(bi)))
         return from_colmajor(T), err.value, bi.value
+
+    def prerejective(self, src: "Cloud", src_feat, tgt: "Cloud", tgt_index: "Index", tgt_feat,
+                     params: PrerejectiveParams | None = None, forced_samples=None, with_inliers: bool = False) -> PrerejectiveOut:
+        """ope_prerejective: pcl::SampleConsensusPrerejective::align of src onto tgt (include/ope.h).  forced_samples:
+        (2, max_iterations, nr_samples) source then target indices, taken instead of the draws (the features may then be None)."""
+        p = params or default_prerejective_params()
+        sf = _f32(src_feat, 33) if src_feat is not None else None
+        tf = _f32(tgt_feat, 33) if tgt_feat is not None else None
+        fs = np.ascontiguousarray(forced_samples, np.int32) if forced_samples is not None else None
+        if fs is not None and fs.size != 2 * max(p.max_iterations, 0) * max(p.nr_samples, 0):
+            raise ValueError("forced_samples holds max_iterations * nr_samples source indices, then as many target indices")
+        res = PrerejectiveResult()
+        idx = np.empty(max(src.n, 1), np.int32) if with_inliers else None
+        self._chk(lib().ope_prerejective(self.h, src.h, _p(sf, _fp), tgt.h, tgt_index.h, _p(tf, _fp), C.byref(p), _p(fs, _ip),
+                                         C.byref(res), _p(idx, _ip)))
+        return PrerejectiveOut(from_colmajor(np.array(res.T, np.float32)), res.error, res.best_iteration, res.inliers,
+                               bool(res.converged), idx[:res.inliers].copy() if with_inliers else None)
+
+    def prerejective_stats(self) -> dict:
+        """ope_prerejective_last_stats: iterations, survivors, launches, host synchronisations, nr_samples of the last prerejective call."""
+        s = PrerejectiveStats()
+        self._chk(lib().ope_prerejective_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in PrerejectiveStats._fields_}
+
+    def prerejective_hypotheses(self) -> dict:
+        """ope_prerejective_last_hypotheses, in drawing order: samples and targets (h, nr_samples) int32, survived (h,) bool,
+        T (h, 4, 4) float32 math layout, inliers (h,) int32, error (h,) float64."""
+        n = C.c_size_t(0)
+        self._chk(lib().ope_prerejective_last_hypotheses(self.h, None, None, None, None, None, None, 0, C.byref(n)))
+        h = n.value
+        sv = np.zeros(max(h, 1), np.uint8)
+        T = np.zeros((max(h, 1), 16), np.float32)
+        inl = np.zeros(max(h, 1), np.int32)
+        err = np.zeros(max(h, 1), np.float64)
+        self._chk(lib().ope_prerejective_last_hypotheses(self.h, None, None, _p(sv, C.POINTER(C.c_uint8)), _p(T, _fp), _p(inl, _ip),
+                                                          _p(err, _dp), h, C.byref(n)))
+        S = int(self.prerejective_stats()["nr_samples"])   # of the call these arrays belong to
+        smp, tg = np.zeros((max(h, 1), S), np.int32), np.zeros((max(h, 1), S), np.int32)
+        self._chk(lib().ope_prerejective_last_hypotheses(self.h, _p(smp, _ip), _p(tg, _ip), None, None, None, None, h, C.byref(n)))
+        return dict(samples=smp[:h].copy(), targets=tg[:h].copy(), survived=sv[:h].astype(bool), T=T[:h].reshape(h, 4, 4).transpose(0, 2, 1).copy(),
+                    inliers=inl[:h].copy(), error=err[:h].copy())
+
+
+def default_prerejective_params(**kw) -> PrerejectiveParams:
+    """ope_prerejective_default_params (50000 / 3 / 5 / 0.8 / 0.15 / 0.25, seed 1: BuildModel poseestimator.cpp:97-102)."""
+    p = PrerejectiveParams()
+    lib().ope_prerejective_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
 
 
 def default_sacia_params(**kw) -> SaciaParams:

@@ -287,6 +287,13 @@ struct ope_ctx {
   std::vector<int32_t> plane_samples, plane_counts;
   std::vector<float> plane_coeffs;
 
+  // the last ope_prerejective (prerejective.hip): what it did, and its iterations in drawing order (ope_prerejective_last_hypotheses)
+  ope_prerejective_stats prerej_stats{};
+  std::vector<int32_t> prerej_samples, prerej_targets, prerej_inliers;
+  std::vector<uint8_t> prerej_survived;
+  std::vector<float> prerej_T;
+  std::vector<double> prerej_error;
+
   ope_depth_stats depth_stats{};   // what the last ope_depth_to_cloud did (depth.hip)
 
   ope_mls_stats mls_stats{};   // what the last ope_mls_smooth* call did (mls.hip)

@@ -1,6 +1,6 @@
 // trace.cpp — optional roctx ranges around the host side of the hot path (the reference's only
 // instrumentation is three pcl::ScopeTime blocks; the GPU side gets named ranges that rocprofv3 --marker-trace shows).
-// Ranges: icp_iter { nn, reduce }, normals, fpfh_spfh, fpfh_weight, sacia, index_build, uniform_sampling.
+// Ranges: icp_iter { nn, reduce }, normals, fpfh_spfh, fpfh_weight, sacia, prerejective, index_build, uniform_sampling.
 // Off by default (ope_ctx_set_tracing); the roctx library is dlopen'ed on first use, so there is no link-time dependency.
 #include <dlfcn.h>
 

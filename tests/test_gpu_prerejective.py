@@ -1,0 +1,373 @@
+"""ope_prerejective (prerejective.hip) against tests/prerejective_ref.py: stage by stage through prerejective_hypotheses(), forced
+samples and the tie rule, real features end to end on the C1 scene, nothing to find, determinism and launch counts, refusals."""
+import importlib
+import multiprocessing as mp
+import os
+import sys
+
+import numpy as np
+import pytest
+from scipy.spatial import cKDTree
+
+import prerejective_ref as ref
+from conftest import ROOT, load_pkg
+
+pytestmark = pytest.mark.gpu
+
+synth = importlib.import_module("object-pose-estimation_amd.synth")
+pcd = importlib.import_module("object-pose-estimation_amd.pcd")
+GOLD = os.path.join(ROOT, "tests", "golden")
+FLT_MAX = float(np.finfo(np.float32).max)
+SEED = 1
+PARAMS = dict(max_iterations=4000, nr_samples=3, k_correspondences=5, similarity_threshold=0.8, max_corr_dist=0.01, inlier_fraction=0.25,
+              seed=SEED)
+
+
+def pose():
+    T = np.eye(4)
+    T[:3, :3] = synth.rot_xyz(25.0, -40.0, 60.0)
+    T[:3, 3] = [0.05, -0.02, 0.11]
+    return T
+
+
+def make_scene(ns, scale=1.0, cut=True, clutter=150):
+    """source: model_surface(ns, 21); target: the moved source, 30 % cut away by a half-space, plus uniform clutter; descriptors
+    uniform in [0, 100)^33, shared by matching points and fresh for the clutter (no ties in the feature search)."""
+    rng = np.random.default_rng(7)
+    src = synth.model_surface(ns, 21)
+    T = pose()
+    mv = (scale * (src.astype(np.float64) @ T[:3, :3].T) + T[:3, 3]).astype(np.float32)
+    keep = np.ones(ns, bool)
+    if cut:
+        d = mv.astype(np.float64) @ np.array([0.6, 0.0, 0.8])
+        keep = d <= np.quantile(d, 0.7)
+    lo, hi = mv.min(0) - 0.02, mv.max(0) + 0.02
+    cl = rng.uniform(lo, hi, (clutter, 3)).astype(np.float32)
+    f_src = rng.uniform(0, 100, (ns, 33)).astype(np.float32)
+    f_cl = rng.uniform(0, 100, (clutter, 33)).astype(np.float32)
+    return dict(src=src, tgt=np.concatenate([mv[keep], cl]), f_src=f_src, f_tgt=np.concatenate([f_src[keep], f_cl]), T=T,
+                keep=np.flatnonzero(keep))
+
+
+@pytest.fixture(scope="module")
+def ope():
+    return load_pkg()
+
+
+@pytest.fixture(scope="module")
+def ctx(ope):
+    c = ope.Context(0)
+    yield c
+    c.close()
+
+
+def upload(ctx, sc):
+    s, t = ctx.upload(sc["src"]), ctx.upload(sc["tgt"])
+    return s, t, ctx.build_index(t)
+
+
+@pytest.fixture(scope="module")
+def scene600():
+    return make_scene(600)
+
+
+@pytest.fixture(scope="module")
+def run600(ope, ctx, scene600):
+    """The device call on the 600-point scene, its hypotheses and stats, and the reference on the same inputs (computed once)."""
+    s, t, ix = upload(ctx, scene600)
+    out = ctx.prerejective(s, scene600["f_src"], t, ix, scene600["f_tgt"], ope.default_prerejective_params(**PARAMS), with_inliers=True)
+    hyp = ctx.prerejective_hypotheses()
+    stats = ctx.prerejective_stats()
+    want = ref.align(scene600["src"], scene600["f_src"], scene600["tgt"], scene600["f_tgt"], **PARAMS)
+    return dict(out=out, hyp=hyp, stats=stats, want=want, handles=(s, t, ix))
+
+
+def valid_call(ope, ctx, handles, sc):
+    """A small valid call on the same context: True when it ran (its stats are the call's own)."""
+    s, t, ix = handles
+    out = ctx.prerejective(s, sc["f_src"], t, ix, sc["f_tgt"], ope.default_prerejective_params(**dict(PARAMS, max_iterations=200)))
+    st = ctx.prerejective_stats()
+    return st["iterations"] == 200 and st["survivors"] == int(ctx.prerejective_hypotheses()["survived"].sum()) and out.best_iteration >= -1
+
+
+# ------------------------------------------------------------------ 1. stage by stage
+def test_stage_by_stage_against_the_reference(scene600, run600):
+    sc, hyp, want, out = scene600, run600["hyp"], run600["want"], run600["out"]
+    H, ns = PARAMS["max_iterations"], len(sc["src"])
+    np.testing.assert_array_equal(hyp["samples"], want["samples"])
+    # the picks are not an output of their own: a target IS its row of nearest descriptors taken at the pick, and with these
+    # descriptors (no two distances equal) a row has K different entries, so equal targets mean equal picks and equal rows
+    np.testing.assert_array_equal(hyp["targets"], want["targets"])
+    rows = ref.feature_knn(sc["f_tgt"], sc["f_src"][np.unique(want["samples"])], PARAMS["k_correspondences"])
+    assert all(len(set(r)) == PARAMS["k_correspondences"] for r in rows.tolist())
+    assert len({int(v) for v in np.unique(want["picks"])}) == PARAMS["k_correspondences"]          # every pick value occurs
+    np.testing.assert_array_equal(hyp["survived"], want["survived"])
+    surv = np.flatnonzero(hyp["survived"])
+    assert 0 < len(surv) < H, len(surv)                                     # both kinds occur
+    assert run600["stats"]["iterations"] == H and run600["stats"]["survivors"] == len(surv)
+    # fits: the reference's fp64 fit, but for nearly collinear source triangles
+    exempt = 0
+    worst = 0.0
+    for it in surv:
+        if ref.singular_ratio(sc["src"][hyp["samples"][it]]) < 1e-2:
+            exempt += 1
+            continue
+        worst = max(worst, float(np.abs(hyp["T"][it].astype(np.float64) - want["T"][it].astype(np.float64)).max()))
+    print(f"survivors {len(surv)} of {H}, exempt {exempt}, worst |T_dev - T_ref| {worst:.3e}")
+    assert exempt <= 0.01 * len(surv), (exempt, len(surv))
+    assert worst <= 2e-6, worst
+    # scores, recomputed by the reference from the DEVICE's transforms
+    bound = 2.0 * (ns - 1) * 2.0 ** -53
+    worst_rel = 0.0
+    for it in surv:
+        _, n, err = ref.score(hyp["T"][it], sc["src"], sc["tgt"], PARAMS["max_corr_dist"])
+        assert hyp["inliers"][it] == n, (it, hyp["inliers"][it], n)
+        if n == 0:
+            assert hyp["error"][it] == FLT_MAX
+        else:
+            worst_rel = max(worst_rel, abs(hyp["error"][it] - err) / err)
+    print(f"worst relative error difference {worst_rel:.3e} (bound {bound:.3e})")
+    assert worst_rel <= bound, (worst_rel, bound)
+    rej = ~hyp["survived"]
+    assert (hyp["inliers"][rej] == 0).all() and (hyp["error"][rej] == FLT_MAX).all()
+    assert (hyp["T"][rej] == np.eye(4, dtype=np.float32)).all()
+    # the winner: the accept replay over the device's own arrays
+    best = ref.accept(hyp["survived"], hyp["inliers"], hyp["error"], ns, PARAMS["inlier_fraction"])
+    accepted = [it for it in surv if np.float32(hyp["inliers"][it]) / np.float32(ns) >= np.float32(PARAMS["inlier_fraction"])]
+    assert len(accepted) >= 1 and best >= 0                                 # seed 1 gives accepted hypotheses
+    assert out.converged and out.best_iteration == best
+    assert out.T.tobytes() == hyp["T"][best].tobytes()
+    assert out.inliers == hyp["inliers"][best] and out.error == hyp["error"][best]
+    mask, _, _ = ref.score(hyp["T"][best], sc["src"], sc["tgt"], PARAMS["max_corr_dist"])
+    np.testing.assert_array_equal(out.inlier_idx, np.flatnonzero(mask))
+    assert np.abs(out.T.astype(np.float64) - sc["T"]).max() < 1e-4
+
+
+# ------------------------------------------------------------------ 2. forced samples
+def test_forced_samples_and_the_tie_rule(ope, ctx, scene600, run600):
+    sc = scene600
+    s, t, ix = run600["handles"]
+    H, S = 40, 3
+    rng = np.random.default_rng(3)
+    fs = np.zeros((2, H, S), np.int32)
+    for it in range(H):
+        fs[0, it] = rng.choice(len(sc["src"]), S, replace=False)
+        fs[1, it] = rng.choice(len(sc["tgt"]), S, replace=False)      # wrong pairings
+    good_t = np.array([5, 200, 390])                                    # target rows that are moved source points ...
+    good_s = sc["keep"][good_t]                                         # ... and the source points they came from
+    assert ref.singular_ratio(sc["src"][good_s]) > 0.1
+    fs[0, 17], fs[1, 17] = good_s, good_t
+    p = ope.default_prerejective_params(**dict(PARAMS, max_iterations=H))
+    one = ctx.prerejective(s, None, t, ix, None, p, forced_samples=fs)
+    h1 = ctx.prerejective_hypotheses()
+    np.testing.assert_array_equal(h1["samples"], fs[0])
+    np.testing.assert_array_equal(h1["targets"], fs[1])
+    assert one.converged and one.best_iteration == 17
+    assert np.abs(one.T.astype(np.float64) - sc["T"]).max() < 1e-4
+    fs[0, 23], fs[1, 23] = good_s, good_t
+    two = ctx.prerejective(s, None, t, ix, None, p, forced_samples=fs)
+    h2 = ctx.prerejective_hypotheses()
+    assert h2["survived"][17] and h2["survived"][23] and h2["error"][17] == h2["error"][23]
+    assert two.best_iteration == 17 and two.T.tobytes() == one.T.tobytes()
+    want = ref.align(sc["src"], None, sc["tgt"], None, **dict(PARAMS, max_iterations=H), forced_samples=fs)
+    assert want["best_iteration"] == 17
+    np.testing.assert_array_equal(h2["survived"], want["survived"])
+
+
+# ------------------------------------------------------------------ 3. real features, end to end
+def test_end_to_end_with_real_features_on_c1(ope, ctx):
+    model, _ = pcd.read_pcd(os.path.join(GOLD, "drill_model_decimated.pcd"))
+    model = np.ascontiguousarray(model, np.float32)
+    g = np.load(os.path.join(GOLD, "drill_scene_c1.npz"))
+    scene = np.ascontiguousarray(g["scene"], np.float32)
+    keys, feats = [], []
+    for cloud in (model, scene):
+        k = cloud[ctx.uniform_sampling(ctx.upload(cloud), 0.01)]
+        c = ctx.upload(k)
+        ctx.normals(c, 30)
+        keys.append(k)
+        feats.append(ctx.fpfh(c, 0.03))
+    s, t = ctx.upload(keys[0]), ctx.upload(keys[1])
+    ix = ctx.build_index(t)
+    p = ope.default_prerejective_params(max_iterations=5000)
+    out = ctx.prerejective(s, feats[0], t, ix, feats[1], p, with_inliers=True)
+    st = ctx.prerejective_stats()
+    assert out.converged
+    q = keys[0].astype(np.float64) @ out.T.astype(np.float64)[:3, :3].T + out.T.astype(np.float64)[:3, 3]
+    d, _ = cKDTree(keys[1].astype(np.float64)).query(q)
+    sure = np.abs(d - p.max_corr_dist) > 1e-6
+    within = int(((d < p.max_corr_dist) & sure).sum())
+    assert within >= np.float32(p.inlier_fraction) * (len(keys[0]) - int((~sure).sum())), (within, len(keys[0]))
+    assert abs(out.inliers - int((d < p.max_corr_dist).sum())) <= int((~sure).sum())
+    print(f"C1: {len(keys[0])} source and {len(keys[1])} target key points, survivors {st['survivors']} of 5000, winner {out.best_iteration}, "
+          f"inliers {out.inliers}, error {out.error:.3e}, |T - gt|_F = {np.linalg.norm(out.T.astype(np.float64) - g['gt']):.4f}")
+
+
+# ------------------------------------------------------------------ 4. nothing to find
+def test_no_survivor_gives_the_identity(ope, ctx):
+    sc = make_scene(600, scale=1.3, cut=False, clutter=0)
+    s, t, ix = upload(ctx, sc)
+    p = ope.default_prerejective_params(**dict(PARAMS, similarity_threshold=0.99, k_correspondences=1))
+    out = ctx.prerejective(s, sc["f_src"], t, ix, sc["f_tgt"], p, with_inliers=True)       # OPE_OK: no exception
+    assert ctx.prerejective_stats()["survivors"] == 0
+    assert not ctx.prerejective_hypotheses()["survived"].any()
+    assert (out.T == np.eye(4, dtype=np.float32)).all() and out.best_iteration == -1 and not out.converged
+    assert out.inliers == 0 and len(out.inlier_idx) == 0
+
+
+def test_survivors_but_none_accepted(ope, ctx, scene600, run600):
+    s, t, ix = run600["handles"]
+    out = ctx.prerejective(s, scene600["f_src"], t, ix, scene600["f_tgt"], ope.default_prerejective_params(**dict(PARAMS, inlier_fraction=1.0)))
+    assert ctx.prerejective_stats()["survivors"] == run600["stats"]["survivors"] > 0
+    assert (out.T == np.eye(4, dtype=np.float32)).all() and out.best_iteration == -1 and not out.converged
+
+
+# ------------------------------------------------------------------ 5. determinism and shape
+def hyp_key(h):
+    return tuple(h[k].tobytes() for k in ("samples", "targets", "survived", "T", "inliers", "error"))
+
+
+def test_two_calls_are_byte_identical(ope, ctx, scene600, run600):
+    s, t, ix = run600["handles"]
+    again = ctx.prerejective(s, scene600["f_src"], t, ix, scene600["f_tgt"], ope.default_prerejective_params(**PARAMS), with_inliers=True)
+    first = run600["out"]
+    assert (again.T.tobytes(), float(again.error).hex(), again.best_iteration, again.inliers, again.inlier_idx.tobytes()) == \
+           (first.T.tobytes(), float(first.error).hex(), first.best_iteration, first.inliers, first.inlier_idx.tobytes())
+    assert hyp_key(ctx.prerejective_hypotheses()) == hyp_key(run600["hyp"])
+
+
+def test_launches_and_syncs_do_not_depend_on_the_sizes(ope, ctx, scene600, run600):
+    s, t, ix = run600["handles"]
+    counts = {}
+    for H in (100, 4000):
+        ctx.prerejective(s, scene600["f_src"], t, ix, scene600["f_tgt"], ope.default_prerejective_params(**dict(PARAMS, max_iterations=H)))
+        st = ctx.prerejective_stats()
+        assert st["iterations"] == H
+        counts[("H", H)] = (st["launches"], st["host_syncs"])
+    sc200 = make_scene(200)
+    s2, t2, ix2 = upload(ctx, sc200)
+    ctx.prerejective(s2, sc200["f_src"], t2, ix2, sc200["f_tgt"], ope.default_prerejective_params(**PARAMS))
+    st = ctx.prerejective_stats()
+    counts[("ns", 200)] = (st["launches"], st["host_syncs"])
+    assert len(set(counts.values())) == 1, counts
+    assert counts[("H", 100)][1] == 3          # the feature rows, the survivor count, the results
+
+
+# ------------------------------------------------------------------ 6. refusals
+BAD = [dict(nr_samples=2), dict(nr_samples=9), dict(k_correspondences=0), dict(k_correspondences=9), dict(similarity_threshold=-0.1),
+       dict(similarity_threshold=1.0), dict(inlier_fraction=-0.1), dict(inlier_fraction=1.5), dict(max_corr_dist=0.0),
+       dict(max_corr_dist=-1.0), dict(max_iterations=0), dict(max_iterations=(1 << 20) + 1)]
+
+
+@pytest.mark.parametrize("bad", BAD, ids=lambda b: "-".join(f"{k}={v}" for k, v in b.items()))
+def test_bad_parameters_are_refused(ope, ctx, scene600, run600, bad):
+    s, t, ix = run600["handles"]
+    before = ctx.prerejective_stats()
+    with pytest.raises(ope.OpeError) as e:
+        ctx.prerejective(s, scene600["f_src"], t, ix, scene600["f_tgt"], ope.default_prerejective_params(**dict(PARAMS, **bad)))
+    assert e.value.code == ope.OPE_EINVAL
+    assert ctx.prerejective_stats() == before                   # nothing launched: the last call's stats stand
+    assert valid_call(ope, ctx, run600["handles"], scene600)
+
+
+def test_bad_arguments_are_refused(ope, ctx, scene600, run600):
+    sc = scene600
+    s, t, ix = run600["handles"]
+    p = ope.default_prerejective_params(**dict(PARAMS, max_iterations=200))
+    L = ope.lib()
+    res = ope.PrerejectiveResult()
+    import ctypes as C
+    fp = C.POINTER(C.c_float)
+    sf, tf = sc["f_src"].ctypes.data_as(fp), sc["f_tgt"].ctypes.data_as(fp)
+    full = [ctx.h, s.h, sf, t.h, ix.h, tf, C.byref(p), None, C.byref(res), None]
+    for hole in (0, 1, 2, 3, 4, 5, 8):                           # ctx, src, features, tgt, index, features, out
+        args = list(full)
+        args[hole] = None
+        assert L.ope_prerejective(*args) == ope.OPE_EINVAL, hole
+        assert valid_call(ope, ctx, run600["handles"], sc)
+
+    def refused(*a, **kw):
+        with pytest.raises(ope.OpeError) as e:
+            ctx.prerejective(*a, **kw)
+        assert e.value.code == ope.OPE_EINVAL
+        assert valid_call(ope, ctx, run600["handles"], sc)
+
+    two = ctx.upload(sc["src"][:2])
+    refused(two, sc["f_src"][:2], t, ix, sc["f_tgt"], p)                                    # ns < nr_samples
+    few = ctx.upload(sc["tgt"][:3])
+    refused(s, sc["f_src"], few, ctx.build_index(few), sc["f_tgt"][:3], p)                  # k_correspondences above |target|
+    # an empty target: a cloud of no points, or of no finite point (an index over such a cloud cannot be built, so the index is another
+    # cloud's: the target cloud decides)
+    one_k = ope.default_prerejective_params(**dict(PARAMS, max_iterations=200, k_correspondences=1))
+    for empty in (np.zeros((0, 3), np.float32), np.full((4, 3), np.nan, np.float32)):
+        before = ctx.prerejective_stats()
+        with pytest.raises(ope.OpeError) as e:
+            ctx.prerejective(s, sc["f_src"], ctx.upload(empty), ix, np.zeros((max(len(empty), 1), 33), np.float32), one_k)
+        assert e.value.code == ope.OPE_EINVAL and "empty target" in str(e.value)
+        assert ctx.prerejective_stats() == before
+        assert valid_call(ope, ctx, run600["handles"], sc)
+    fs = np.zeros((2, 200, 3), np.int32)
+    fs[0, :, 1], fs[0, :, 2] = 1, 2
+    fs[1, 7, 0] = len(sc["tgt"])                                                            # a forced index out of range
+    refused(s, None, t, ix, None, p, forced_samples=fs)
+
+
+def test_null_params_are_the_defaults(ope, ctx):
+    """params == NULL is not a refusal: the call runs with ope_prerejective_default_params, as ope_sacia does with its own."""
+    import ctypes as C
+    sc = make_scene(200)
+    s, t, ix = upload(ctx, sc)
+    fp = C.POINTER(C.c_float)
+    res = ope.PrerejectiveResult()
+    rc = ope.lib().ope_prerejective(ctx.h, s.h, sc["f_src"].ctypes.data_as(fp), t.h, ix.h, sc["f_tgt"].ctypes.data_as(fp), None, None,
+                                    C.byref(res), None)
+    assert rc == ope.OPE_OK
+    st, h = ctx.prerejective_stats(), ctx.prerejective_hypotheses()
+    assert st["iterations"] == 50000 and st["nr_samples"] == 3 and h["samples"].shape == (50000, 3)
+    same = ctx.prerejective(s, sc["f_src"], t, ix, sc["f_tgt"], ope.default_prerejective_params())
+    assert (bytes(res.T), res.error, res.best_iteration, res.inliers) == (ope.colmajor(same.T).tobytes(), same.error, same.best_iteration, same.inliers)
+
+
+def test_hypotheses_report_their_own_sample_count(ope, ctx):
+    """ope_prerejective_stats.nr_samples sizes the sample arrays, also after a call that did not go through Context.prerejective's
+    parameters (5 samples here, then a refused call with 3: the kept arrays stay the 5-sample call's)."""
+    sc = make_scene(200)
+    s, t, ix = upload(ctx, sc)
+    p5 = ope.default_prerejective_params(**dict(PARAMS, max_iterations=300, nr_samples=5, similarity_threshold=0.5))
+    ctx.prerejective(s, sc["f_src"], t, ix, sc["f_tgt"], p5)
+    want = ref.draws(200, 5, 5, 300, SEED)[0]
+    with pytest.raises(ope.OpeError):
+        ctx.prerejective(s, sc["f_src"], t, ix, sc["f_tgt"], ope.default_prerejective_params(**dict(PARAMS, max_corr_dist=0.0)))
+    assert ctx.prerejective_stats()["nr_samples"] == 5
+    np.testing.assert_array_equal(ctx.prerejective_hypotheses()["samples"], want)
+
+
+def _communicator_worker(out_path):
+    sys.path.insert(0, ROOT)
+    import torch  # noqa: F401  (librccl / libamdhip64 of the torch wheel first, as the sharded tests do)
+    ope = importlib.import_module("object-pose-estimation_amd")
+    c = ope.Context(0)
+    c.comm_init(ope.comm_unique_id(), 1, 0)
+    sc = make_scene(200)
+    s, t = c.upload(sc["src"]), c.upload(sc["tgt"])
+    ix = c.build_index(t)
+    p = ope.default_prerejective_params(**dict(PARAMS, max_iterations=200))
+    code = 0
+    try:
+        c.prerejective(s, sc["f_src"], t, ix, sc["f_tgt"], p)
+    except ope.OpeError as e:
+        code = e.code
+    c.comm_destroy()
+    ok = c.prerejective(s, sc["f_src"], t, ix, sc["f_tgt"], p).best_iteration >= -1
+    c.close()
+    np.save(out_path, np.array([code, int(ok)]))
+
+
+@pytest.mark.timeout(300)
+def test_context_with_a_communicator_is_refused(tmp_path):
+    path = str(tmp_path / "comm.npy")
+    pr = mp.get_context("spawn").Process(target=_communicator_worker, args=(path,))
+    pr.start(); pr.join(240)
+    assert pr.exitcode == 0
+    code, ok = np.load(path)
+    assert code == load_pkg().OPE_EINVAL and ok == 1
