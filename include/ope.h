@@ -613,8 +613,8 @@ typedef struct {
  * OPE_COARSE_MAX_KEYS key points.  (Key points are counted on the host before anything is launched.) */
 int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                           const ope_coarse_params *params, const uint64_t *seeds, ope_coarse_batch_result *out);
-/* Key points (ORIGINAL indices into that cloud), normals (n*3) and FPFH rows (n*33) the last ope_coarse_pose_batch computed
- * for `which` (-1 = the model, 0..n-1 = cluster), in key-point order; any output may be NULL.  *n_out = the key points; at
+/* Key points (ORIGINAL indices into that cloud), normals (n*3) and FPFH rows (n*33) the last ope_coarse_pose_batch (or
+ * ope_prerejective_pose_batch, ope_final_pose_batch_prerejective: the front end is the same code) computed for `which` (-1 = the model, 0..n-1 = cluster), in key-point order; any output may be NULL.  *n_out = the key points; at
  * most cap rows are written.  Like ope_icp_correspondences for the single run. */
 int ope_coarse_batch_features(ope_ctx *ctx, int which, int32_t *key_idx, float *normals, float *fpfh33, size_t cap,
                               size_t *n_out);
@@ -678,6 +678,73 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
  * (target); xyz (n*3) and normals (n*3) in key-point order, as they would be handed to ope_cloud_upload; either may be NULL.
  * *n_out = the points; at most cap rows are written. */
 int ope_final_batch_inputs(ope_ctx *ctx, int which, int side, float *xyz, float *normals, size_t cap, size_t *n_out);
+
+/* ---------------- batched prerejective coarse stage ---------------- */
+/* estimateCoarsePose with the prerejective aligner (ope_prerejective) of one model against n candidate clusters in one call:
+ * the front end of ope_coarse_pose_batch (key points, normals, FPFH of every cloud), then every active cluster's draws, polygon
+ * tests, fits and scores together.  The model's key points are the source, a cluster's the target. */
+enum { OPE_PREREJ_OK = 0, OPE_PREREJ_EMPTY_TARGET = 1, OPE_PREREJ_FEW_TARGET_FEATURES = 2, OPE_PREREJ_NAN_FEATURES = 3 };
+typedef struct {
+  float T[16];             /* column-major; identity unless converged */
+  double error;            /* the winner's mean squared inlier distance; FLT_MAX without a winner */
+  int32_t best_iteration;  /* -1 without a winner */
+  int32_t inliers;
+  int32_t converged;
+  int32_t survivors;       /* of this cluster's polygon test */
+  int32_t n_src_keys;      /* model key points after UniformSampling */
+  int32_t n_tgt_keys;      /* this cluster's key points */
+  int32_t status;          /* OPE_PREREJ_* */
+  uint64_t seed;           /* the stream this cluster drew with; 0 unless status == OPE_PREREJ_OK */
+} ope_prerejective_batch_result;
+typedef struct {
+  int64_t clusters;     /* n */
+  int64_t active;       /* clusters that drew (>= 10 key points) */
+  int64_t iterations;   /* per active cluster (max_iterations) */
+  int64_t survivors;    /* of all clusters */
+  int64_t launches;     /* kernel launches and copies to the device enqueued after the front end (a rocPRIM select counts as one) */
+  int64_t host_syncs;   /* of the whole call, the front end's one included */
+  int64_t nr_samples;
+} ope_prerejective_batch_stats;
+/* Synchronous, on the context's stream; n == 0 does nothing.  front gives key_leaf, normals_k, viewpoint and fpfh_radius
+ * (front->sacia is ignored; NULL: ope_coarse_default_params), params everything else (NULL: ope_prerejective_default_params).
+ * Cluster i draws with seeds[i], or with params->seed + i.  Per cluster the result is what ope_prerejective gives for the
+ * model's key points and FPFH rows against the cluster's (ope_coarse_batch_features reports both), n_src = the model's key
+ * points: the same draws, targets, survival flags, transforms and inlier counts; the error sums the same squared distances in
+ * KEY-POINT order (256 key points per partial sum, the partials in order), so it can differ from the single call's, which sums
+ * along its cloud's stored order, in the last bits.
+ * Status: an empty cluster OPE_PREREJ_EMPTY_TARGET; fewer than 10 cluster key points OPE_PREREJ_FEW_TARGET_FEATURES; a cluster in
+ * which a sampled model descriptor has no finite distance to any descriptor (where ope_prerejective answers OPE_EINVAL)
+ * OPE_PREREJ_NAN_FEATURES.  All three keep the identity, report seed 0 and leave the other clusters' results untouched.  No
+ * winner: OPE_PREREJ_OK with converged = 0, the identity and best_iteration = -1.  Each cluster's result is byte-identical
+ * whatever else is in the batch and wherever it sits.  Launches and host synchronisations depend on neither n, the iterations,
+ * the survivors nor the points, as long as the packed draws (2 bytes each) of all active clusters fit the 32 MiB staging block;
+ * beyond it the upload goes in synchronising pieces, which ope_prerejective_batch_last_stats counts.
+ * keep_hypotheses != 0 keeps every iteration of every active cluster for ope_prerejective_batch_hypotheses (3.2 MB per cluster
+ * at the defaults).
+ * OPE_EINVAL, nothing launched: a NULL ctx, model, clusters, a cluster or out; n > 65535; n * max_iterations above 2^31 - 1;
+ * key_leaf or fpfh_radius <= 0; normals_k outside 1..32; a parameter outside ope_prerejective's ranges (max_iterations 1..2^20,
+ * nr_samples 3..8, k_correspondences 1..8, similarity_threshold [0, 1), inlier_fraction [0, 1], max_corr_dist > 0 and finite);
+ * a cloud of more than OPE_COARSE_MAX_POINTS points or more than OPE_COARSE_MAX_KEYS key points; a model with fewer key points
+ * than nr_samples; a context with a communicator. */
+int ope_prerejective_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                                const ope_coarse_params *front, const ope_prerejective_params *params, const uint64_t *seeds,
+                                int keep_hypotheses, ope_prerejective_batch_result *out);
+int ope_prerejective_batch_last_stats(const ope_ctx *ctx, ope_prerejective_batch_stats *out);
+/* The iterations of cluster `which` of the last ope_prerejective_pose_batch with keep_hypotheses, in the shape of
+ * ope_prerejective_last_hypotheses (samples: model key points, targets: the cluster's key points, both in key-point order).
+ * *n_out = the iterations: 0 for a cluster that did not draw.  OPE_EINVAL: no such call yet, or `which` out of range. */
+int ope_prerejective_batch_hypotheses(const ope_ctx *ctx, int which, int32_t *samples, int32_t *targets, uint8_t *survived, float *T,
+                                      int32_t *inliers, double *error, size_t cap, size_t *n_out);
+/* ope_final_pose_batch with ope_prerejective_pose_batch as its coarse stage (params->coarse is its front; prerejective NULL: the
+ * defaults).  out[i].coarse: T, best_error = error, best_iteration, the key counts, status OPE_COARSE_* (OPE_PREREJ_NAN_FEATURES
+ * reads OPE_COARSE_FEW_TARGET_FEATURES); a cluster without a winner stays OPE_COARSE_OK with the identity, which is what
+ * PoseEstimator's prerejective coarse stage leaves (an identity pose and a counted coarse call).  Without seeds cluster i draws
+ * with prerejective->seed + (the clusters before it that drew), the estimator's coarse-call counter; out[i].seed as above.
+ * Everything after the coarse stage, *selected and the refusals are ope_final_pose_batch's; ope_final_batch_inputs reports its
+ * fine inputs. */
+int ope_final_pose_batch_prerejective(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                                      const ope_final_params *params, const ope_prerejective_params *prerejective, const uint64_t *seeds,
+                                      ope_final_batch_result *out, int32_t *selected);
 
 /* ---------------- tracking: the reference's later frames ---------------- */
 /* Every frame after the first (rosinterface.cpp:264-313): the centroid of each cluster and of the source (the model as the

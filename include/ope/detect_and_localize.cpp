@@ -42,7 +42,10 @@
 //   ... --coarse sac-ia|prerejective   (every mode but --depth)
 // The coarse aligner of PoseEstimator::estimateCoarsePose: SAC-IA (the default, the reference's live code) or the
 // pcl::SampleConsensusPrerejective block the reference keeps commented out (BuildModel poseestimator.cpp:90-108; 50 000 iterations on
-// the device).  With prerejective the candidate loop and the tracker run one estimateFinalPose at a time.
+// the device).  With prerejective the candidate loop and the tracker run one estimateFinalPose at a time, unless
+//   ... --coarse-batch   (every mode but --depth, --track and --track-loop)
+// is given: PoseEstimator::setCoarseBatch(true), so --candidates (and --segment, --frame) with --coarse prerejective check all
+// clusters in one ope_final_pose_batch_prerejective call.  Without the flag every mode prints what it printed before.
 //
 //   ... --recognise <train_dir>   (with --candidates, --candidates-loop, --segment or --frame)
 // Before the pose stage, ope::ObjectDetection::getObjectNames over every cluster in one call against the table under <train_dir>
@@ -124,6 +127,7 @@ static int track_main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--coarse") && i + 1 < argc) { if (!parse_coarse(argv[++i], coarse)) return 2; }
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
+    else if (!std::strcmp(argv[i], "--coarse-batch")) { std::fprintf(stderr, "--coarse-batch does not go with --track or --track-loop\n"); return 2; }
     else if (!std::strcmp(argv[i], "--time")) timed = true;
     else if (!frames.empty()) frames.back().push_back(argv[i]);
     else { std::fprintf(stderr, "unexpected argument %s\n", argv[i]); return 2; }
@@ -274,10 +278,12 @@ int main(int argc, char **argv) {
   bool region_grow_rgb = false;   // --region-grow-rgb (with --frame): from SegmentationRegionGrow::getSegmentRegGrowRgb instead
   std::string recognise;       // --recognise <train_dir>: name every cluster before the pose stage
   ope::PoseEstimator::CoarseMethod coarse = ope::PoseEstimator::COARSE_SAC_IA;   // --coarse
+  bool coarse_batch = false;   // --coarse-batch
   float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--coarse") && i + 1 < argc) { if (!parse_coarse(argv[++i], coarse)) return 2; }
+    else if (!std::strcmp(argv[i], "--coarse-batch")) coarse_batch = true;
     else if (!std::strcmp(argv[i], "--recognise") && i + 1 < argc) recognise = argv[++i];
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--candidates")) candidates = 1;
@@ -305,6 +311,7 @@ int main(int argc, char **argv) {
   ope::PoseEstimator poseEstimator;
   poseEstimator.setSacIaSeed(seed);
   poseEstimator.setCoarseMethod(coarse);
+  poseEstimator.setCoarseBatch(coarse_batch);
   poseEstimator.setUseSelfOccludedRejector(self_occluded);
   auto print_frame = [&](size_t k, const pcl::Matrix4f &pose, double fitnessScore, double alignedStrength) {
     std::printf("frame %zu fitness %.12g strength %.12g coarse_calls %d icp_iterations %d", k, fitnessScore, alignedStrength,

@@ -40,6 +40,10 @@ class PoseEstimator {
   enum CoarseMethod { COARSE_SAC_IA = 0, COARSE_PREREJECTIVE = 1 };
   void setCoarseMethod(CoarseMethod m) { coarse_method_ = m; }
   CoarseMethod coarseMethod() const { return coarse_method_; }
+  // estimateFinalPoseCandidates with COARSE_PREREJECTIVE: all clusters in one ope_final_pose_batch_prerejective call instead of one
+  // estimateFinalPose at a time (off by default; SAC-IA always batches)
+  void setCoarseBatch(bool on) { coarse_batch_ = on; }
+  bool coarseBatch() const { return coarse_batch_; }
   void setSacIaSeed(uint64_t seed) { sacia_seed_ = seed; }
   void setUseSelfOccludedRejector(bool on) { use_self_occluded_ = on; }
   // diagnostics of the last estimateFinalPose call
@@ -179,7 +183,8 @@ class PoseEstimator {
   // The reference's first-frame candidate loop (rosinterface.cpp:243-262) in one call:
   //     for each cluster: source = a copy of the original model; if the cluster is not empty, estimateFinalPose(source, cluster);
   //                       stop once fitness < 1e-4 or strength > 0.4
-  // p_sourceCloud is the original model on entry.  Runs ope_final_pose_batch over all clusters, then leaves the estimator and
+  // p_sourceCloud is the original model on entry.  Runs ope_final_pose_batch (with COARSE_PREREJECTIVE and setCoarseBatch(true):
+  // ope_final_pose_batch_prerejective; without the switch that method runs the loop as written above) over all clusters, then leaves the estimator and
   // p_sourceCloud exactly as that loop would: coarse calls counted only for clusters that reached SAC-IA, fitnessScoreFine /
   // alignedStrength from the last cluster (up to the selected one) that ran a fine ICP, alignedSource / cloudModel / firstTimePose
   // / the last* diagnostics as after the last non-empty cluster it processed; p_sourceCloud holds alignedSource, or the original
@@ -193,7 +198,8 @@ class PoseEstimator {
     const Cloud original(*p_sourceCloud);
     std::vector<ope_final_batch_result> res(clusters.size());
     int32_t sel = -1;
-    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() && coarse_method_ == COARSE_SAC_IA;   // (the batch's coarse stage is SAC-IA)
+    // (ope_final_pose_batch's coarse stage is SAC-IA; the prerejective batch is opt-in: setCoarseBatch)
+    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() && (coarse_method_ == COARSE_SAC_IA || coarse_batch_);
     if (batched) {
       ope_ctx *ctx = compat::default_context();
       auto model = compat::upload(original, false);
@@ -204,7 +210,21 @@ class PoseEstimator {
       ope_final_default_params(&p);
       p.coarse.sacia.seed = sacia_seed_ + (uint64_t)coarse_calls_;   // the k-th SAC-IA call draws with seed + k
       if (use_self_occluded_) { p.icp.use_self_occluded_rej = 1; p.icp.self_occluded_thr = 0.6; }   // :291
-      batched = ctx && model->h && ope_final_pose_batch(ctx, model->h, hs.size(), hs.data(), &p, nullptr, res.data(), &sel) == OPE_OK;
+      if (coarse_method_ == COARSE_PREREJECTIVE) {
+        ope_prerejective_params q;
+        ope_prerejective_default_params(&q);
+        q.max_iterations = 50000;          // the literals of prerejectiveCoarsePose (:97-102)
+        q.nr_samples = 3;
+        q.k_correspondences = 5;
+        q.similarity_threshold = 0.8f;
+        q.max_corr_dist = 0.15;
+        q.inlier_fraction = 0.25f;
+        q.seed = sacia_seed_ + (uint64_t)coarse_calls_;   // the k-th coarse call draws with seed + k
+        batched = ctx && model->h &&
+                  ope_final_pose_batch_prerejective(ctx, model->h, hs.size(), hs.data(), &p, &q, nullptr, res.data(), &sel) == OPE_OK;
+      } else {
+        batched = ctx && model->h && ope_final_pose_batch(ctx, model->h, hs.size(), hs.data(), &p, nullptr, res.data(), &sel) == OPE_OK;
+      }
       if (!batched && ctx) compat::log_error("final_pose_batch (running the loop one cluster at a time)", ctx);
     }
     if (!batched) {
@@ -376,6 +396,7 @@ class PoseEstimator {
   uint64_t sacia_seed_ = 1;
   CoarseMethod coarse_method_ = COARSE_SAC_IA;
   int coarse_calls_ = 0;
+  bool coarse_batch_ = false;
   bool use_self_occluded_ = false;
   Matrix4f last_coarse_ = Matrix4f::Identity(), last_fine_ = Matrix4f::Identity(), last_rigid_ = Matrix4f::Identity();
   int last_icp_iterations_ = 0;

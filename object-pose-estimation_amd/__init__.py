@@ -28,6 +28,8 @@ COMM_AUTO, COMM_RCCL, COMM_P2P = 0, 1, 2
 # ope_coarse_batch_result.status; per-cloud limits of ope_coarse_pose_batch
 COARSE_OK, COARSE_EMPTY_TARGET, COARSE_FEW_TARGET_FEATURES = 0, 1, 2
 COARSE_MAX_POINTS, COARSE_MAX_KEYS = 65536, 4096
+# ope_prerejective_batch_result.status
+PREREJ_OK, PREREJ_EMPTY_TARGET, PREREJ_FEW_TARGET_FEATURES, PREREJ_NAN_FEATURES = 0, 1, 2, 3
 # ope_final_batch_result.status
 FINAL_OK, FINAL_EMPTY_TARGET, FINAL_FEW_TARGET_FEATURES, FINAL_FEW_FINE_POINTS = 0, 1, 2, 3
 # ope_track_gate_result.branch; ope_track_result.coarse_status when the coarse stage was skipped
@@ -146,6 +148,33 @@ class PrerejectiveResult(C.Structure):
 
 class PrerejectiveStats(C.Structure):
     _fields_ = [
+        ("iterations", C.c_int64),
+        ("survivors", C.c_int64),
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+        ("nr_samples", C.c_int64),
+    ]
+
+
+class PrerejectiveBatchResult(C.Structure):
+    _fields_ = [
+        ("T", C.c_float * 16),
+        ("error", C.c_double),
+        ("best_iteration", C.c_int32),
+        ("inliers", C.c_int32),
+        ("converged", C.c_int32),
+        ("survivors", C.c_int32),
+        ("n_src_keys", C.c_int32),
+        ("n_tgt_keys", C.c_int32),
+        ("status", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+class PrerejectiveBatchStats(C.Structure):
+    _fields_ = [
+        ("clusters", C.c_int64),
+        ("active", C.c_int64),
         ("iterations", C.c_int64),
         ("survivors", C.c_int64),
         ("launches", C.c_int64),
@@ -560,6 +589,13 @@ ABI = [
     ("ope_final_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(FinalParams), C.POINTER(C.c_uint64),
                                         C.POINTER(FinalBatchResult), _ip]),
     ("ope_final_batch_inputs", C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_prerejective_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(CoarseParams), C.POINTER(PrerejectiveParams),
+                                              C.POINTER(C.c_uint64), C.c_int, C.POINTER(PrerejectiveBatchResult)]),
+    ("ope_prerejective_batch_last_stats", C.c_int, [_vp, C.POINTER(PrerejectiveBatchStats)]),
+    ("ope_prerejective_batch_hypotheses", C.c_int, [_vp, C.c_int, _ip, _ip, C.POINTER(C.c_uint8), _fp, _ip, _dp, C.c_size_t,
+                                                    C.POINTER(C.c_size_t)]),
+    ("ope_final_pose_batch_prerejective", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(FinalParams), C.POINTER(PrerejectiveParams),
+                                                    C.POINTER(C.c_uint64), C.POINTER(FinalBatchResult), C.POINTER(C.c_int32)]),
     ("ope_track_default_params", None, [C.POINTER(TrackParams)]),
     ("ope_track_gate", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(TrackParams), C.POINTER(TrackGateResult),
                                   C.POINTER(TrackCentroid)]),
@@ -740,6 +776,21 @@ class PrerejectiveOut:
     inliers: int
     converged: bool
     inlier_idx: np.ndarray | None   # getInliers(): ORIGINAL source indices, ascending (with_inliers=True)
+
+
+@dataclass
+class PrerejectiveBatchOut:
+    T: np.ndarray          # (4,4) math layout, float32; the identity unless converged
+    error: float           # FLT_MAX without a winner
+    best_iteration: int    # -1 without a winner
+    inliers: int
+    converged: bool
+    survivors: int         # of this cluster's polygon test
+    n_src_keys: int        # model key points
+    n_tgt_keys: int        # this cluster's key points
+    status: int            # PREREJ_OK, PREREJ_EMPTY_TARGET, PREREJ_FEW_TARGET_FEATURES or PREREJ_NAN_FEATURES
+    seed: int              # the stream the cluster drew with (0 unless PREREJ_OK)
+    raw: bytes             # the bytes of its ope_prerejective_batch_result
 
 
 @dataclass
@@ -1073,6 +1124,65 @@ class Context:
         self._chk(lib().ope_final_pose_batch(self.h, model.h, n, hc, C.byref(p), sd, out, C.byref(sel)))
         res = [_final_out(o) for o in out[:n]]
         return res, sel.value
+
+    def _batch_args(self, clusters, seeds):
+        n = len(clusters)
+        hc = (_vp * max(n, 1))(*[c.h for c in clusters])
+        sd = None
+        if seeds is not None:
+            if len(seeds) != n:
+                raise ValueError("one seed per cluster")
+            sd = (C.c_uint64 * max(n, 1))(*[int(x) for x in seeds])
+        return n, hc, sd
+
+    def prerejective_pose_batch(self, model: "Cloud", clusters, front: CoarseParams | None = None, params: PrerejectiveParams | None = None,
+                                seeds=None, keep_hypotheses: bool = False) -> list:
+        """ope_prerejective_pose_batch: estimateCoarsePose with the prerejective aligner of model against every cluster in one
+        call; one PrerejectiveBatchOut each.  front gives key_leaf, normals_k, viewpoint, fpfh_radius; seeds[i] (or params.seed + i
+        without seeds) is cluster i's stream."""
+        n, hc, sd = self._batch_args(clusters, seeds)
+        f = front or default_coarse_params()
+        p = params or default_prerejective_params()
+        out = (PrerejectiveBatchResult * max(n, 1))()
+        self._chk(lib().ope_prerejective_pose_batch(self.h, model.h, n, hc, C.byref(f), C.byref(p), sd, int(bool(keep_hypotheses)), out))
+        return [PrerejectiveBatchOut(from_colmajor(np.frombuffer(o.T, np.float32)), o.error, o.best_iteration, o.inliers, bool(o.converged),
+                                     o.survivors, o.n_src_keys, o.n_tgt_keys, o.status, o.seed, bytes(o)) for o in out[:n]]
+
+    def prerejective_batch_stats(self) -> dict:
+        """ope_prerejective_batch_last_stats: clusters, active, iterations, survivors, launches, host_syncs, nr_samples."""
+        s = PrerejectiveBatchStats()
+        self._chk(lib().ope_prerejective_batch_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in PrerejectiveBatchStats._fields_}
+
+    def prerejective_batch_hypotheses(self, which: int) -> dict:
+        """ope_prerejective_batch_hypotheses of cluster `which` (after keep_hypotheses=True), in the shape of
+        prerejective_hypotheses: samples index the model's key points, targets the cluster's."""
+        n = C.c_size_t(0)
+        L = lib()
+        self._chk(L.ope_prerejective_batch_hypotheses(self.h, which, None, None, None, None, None, None, 0, C.byref(n)))
+        h = n.value
+        S = int(self.prerejective_batch_stats()["nr_samples"])
+        sv = np.zeros(max(h, 1), np.uint8)
+        T = np.zeros((max(h, 1), 16), np.float32)
+        inl = np.zeros(max(h, 1), np.int32)
+        err = np.zeros(max(h, 1), np.float64)
+        smp, tg = np.zeros((max(h, 1), S), np.int32), np.zeros((max(h, 1), S), np.int32)
+        self._chk(L.ope_prerejective_batch_hypotheses(self.h, which, _p(smp, _ip), _p(tg, _ip), _p(sv, C.POINTER(C.c_uint8)), _p(T, _fp),
+                                                      _p(inl, _ip), _p(err, _dp), h, C.byref(n)))
+        return dict(samples=smp[:h].copy(), targets=tg[:h].copy(), survived=sv[:h].astype(bool), T=T[:h].reshape(h, 4, 4).transpose(0, 2, 1).copy(),
+                    inliers=inl[:h].copy(), error=err[:h].copy())
+
+    def final_pose_batch_prerejective(self, model: "Cloud", clusters, params: FinalParams | None = None,
+                                      prerejective: PrerejectiveParams | None = None, seeds=None):
+        """ope_final_pose_batch_prerejective: final_pose_batch with the prerejective aligner as its coarse stage.
+        Returns ([FinalOut per cluster], selected)."""
+        n, hc, sd = self._batch_args(clusters, seeds)
+        p = params or default_final_params()
+        q = prerejective or default_prerejective_params()
+        out = (FinalBatchResult * max(n, 1))()
+        sel = C.c_int32(-1)
+        self._chk(lib().ope_final_pose_batch_prerejective(self.h, model.h, n, hc, C.byref(p), C.byref(q), sd, out, C.byref(sel)))
+        return [_final_out(o) for o in out[:n]], sel.value
 
     def _cluster_args(self, cloud, tolerance, min_size, max_size):
         if not isinstance(cloud, Cloud):

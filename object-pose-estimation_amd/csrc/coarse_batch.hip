@@ -398,8 +398,7 @@ int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const 
 // ope_coarse_pose_batch's refusals (n >= 1, clusters not NULL checked by the caller), before anything is launched: parameters,
 // sizes, and the key points of every cloud that could exceed the cap.  *model_keys = the model's key points.
 int ope::coarse_batch_check(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params &p,
-                            long long *model_keys) {
-  static const char *who = "ope_coarse_pose_batch: ";
+                            long long *model_keys, const char *who) {
   const int S = p.sacia.nr_samples, K = p.sacia.k_correspondences, H = p.sacia.max_iterations;
   if (!(p.key_leaf > 0) || !(p.fpfh_radius > 0)) return set_err(ctx, OPE_EINVAL, std::string(who) + "key_leaf and fpfh_radius must be > 0");
   if (p.normals_k < 1 || p.normals_k > kKnnMaxK) return set_err(ctx, OPE_EINVAL, std::string(who) + "1 <= normals_k <= 32");
@@ -433,25 +432,13 @@ int ope::coarse_batch_check(ope_ctx *ctx, const ope_cloud *model, size_t n, cons
   return OPE_OK;
 }
 
-int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params *params,
-                                const uint64_t *seeds, bool seed_by_rank, ope_coarse_batch_result *out, uint64_t *seeds_used) {
-  static const char *who = "ope_coarse_pose_batch: ";
-  if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_coarse_pose_batch: bad argument");
-  if (n == 0) return OPE_OK;
-  if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
-  if (n > 65535) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 65535 clusters (one grid row each)");
-  ope_coarse_params p;
-  ope_coarse_default_params(&p);
-  if (params) p = *params;
-  const int S = p.sacia.nr_samples, K = p.sacia.k_correspondences, H = p.sacia.max_iterations;
-  long long model_keys = -2;
-  { const int rc = coarse_batch_check(ctx, model, n, clusters, p, &model_keys); if (rc != OPE_OK) return rc; }
+// Steps 1-3 for the model (segment 0) and the n clusters, enqueued: uniform sampling (one synchronisation: the key offsets), then
+// the normals and FPFH launches.  model_keys = coarse_batch_check's count.
+int ope::coarse_front_launch(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                             const ope_coarse_params &p, long long model_keys, CoarseFront &f) {
   const size_t nseg = n + 1;
   const float inv = 1.0f / p.key_leaf;
   auto cloud_of = [&](size_t s) { return s == 0 ? model : clusters[s - 1]; };
-
-  OPE_HIP(ctx, hipSetDevice(ctx->device));
-  TraceRange r_all(ctx, "coarse_batch");
   std::vector<CoarseSeg> segs(nseg);
   std::vector<uint32_t> off(nseg + 1, 0);
   for (size_t s = 0; s < nseg; ++s) {
@@ -472,7 +459,6 @@ int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, 
   }
   const uint32_t total = off[nseg];
 
-  CallTmp tmp{ctx->stream, {}};
   hipError_t e = hipSuccess;
   auto fail = [&](const char *what) { return set_err(ctx, OPE_EHIP, std::string(who) + what + ": " + hipGetErrorString(e)); };
   auto *d_segs = (CoarseSeg *)tmp.get(sizeof(CoarseSeg) * nseg, e);
@@ -482,7 +468,7 @@ int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, 
   if (e != hipSuccess) return fail("buffers");
 
   // ---- 1. uniform sampling of all segments
-  std::vector<uint32_t> key_off;
+  std::vector<uint32_t> &key_off = f.key_off;
   float4 *d_kp = nullptr;
   uint32_t *d_key_off = nullptr;
   {
@@ -531,14 +517,68 @@ int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, 
     e = hipGetLastError();
     if (e != hipSuccess) return fail("features");
   }
+  f.nkeys = nkeys; f.max_keys = max_keys; f.nsk = nsk;
+  f.d_kp = d_kp; f.d_key_off = d_key_off; f.d_nrm = d_nrm; f.d_fpfh = d_fpfh;
+  return OPE_OK;
+}
+
+// the key points (xyz, w = original index), normals and FPFH rows of every segment on their way to the host; the caller synchronises
+hipError_t ope::coarse_front_download(ope_ctx *ctx, CoarseFront &f) {
+  const uint32_t nkeys = f.nkeys;
+  hipError_t e = hipSuccess;
+  f.h_kp.resize(nkeys);
+  if (nkeys) e = hipMemcpyAsync(f.h_kp.data(), f.d_kp, 16 * (size_t)nkeys, hipMemcpyDeviceToHost, ctx->stream);
+  f.h_nrm4.resize((size_t)nkeys * 4);
+  f.h_fpfh.resize((size_t)nkeys * 33);
+  if (e == hipSuccess && nkeys) e = hipMemcpyAsync(f.h_nrm4.data(), f.d_nrm, 16 * (size_t)nkeys, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && nkeys) e = hipMemcpyAsync(f.h_fpfh.data(), f.d_fpfh, sizeof(float) * 33 * (size_t)nkeys, hipMemcpyDeviceToHost, ctx->stream);
+  return e;
+}
+
+// keep what was computed for ope_coarse_batch_features (after the synchronisation that follows coarse_front_download)
+void ope::coarse_front_keep(ope_ctx *ctx, CoarseFront &f) {
+  const uint32_t nkeys = f.nkeys;
+  ctx->coarse_key_off.assign(f.key_off.begin(), f.key_off.end());
+  ctx->coarse_key_idx.resize(nkeys);
+  ctx->coarse_nrm.resize((size_t)nkeys * 3);
+  for (uint32_t j = 0; j < nkeys; ++j) {
+    ctx->coarse_key_idx[j] = orig_index(f.h_kp[j]);
+    for (int d = 0; d < 3; ++d) ctx->coarse_nrm[3 * (size_t)j + d] = f.h_nrm4[4 * (size_t)j + d];
+  }
+  ctx->coarse_fpfh.swap(f.h_fpfh);
+}
+
+int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params *params,
+                                const uint64_t *seeds, bool seed_by_rank, ope_coarse_batch_result *out, uint64_t *seeds_used) {
+  static const char *who = "ope_coarse_pose_batch: ";
+  if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_coarse_pose_batch: bad argument");
+  if (n == 0) return OPE_OK;
+  if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
+  if (n > 65535) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 65535 clusters (one grid row each)");
+  ope_coarse_params p;
+  ope_coarse_default_params(&p);
+  if (params) p = *params;
+  const int S = p.sacia.nr_samples, K = p.sacia.k_correspondences, H = p.sacia.max_iterations;
+  long long model_keys = -2;
+  { const int rc = coarse_batch_check(ctx, model, n, clusters, p, &model_keys); if (rc != OPE_OK) return rc; }
+
+  OPE_HIP(ctx, hipSetDevice(ctx->device));
+  TraceRange r_all(ctx, "coarse_batch");
+  CallTmp tmp{ctx->stream, {}};
+  hipError_t e = hipSuccess;
+  auto fail = [&](const char *what) { return set_err(ctx, OPE_EHIP, std::string(who) + what + ": " + hipGetErrorString(e)); };
+  CoarseFront front;
+  { const int rc = coarse_front_launch(ctx, tmp, who, model, n, clusters, p, model_keys, front); if (rc != OPE_OK) return rc; }
+  const std::vector<uint32_t> &key_off = front.key_off;
+  const uint32_t max_keys = front.max_keys, nsk = front.nsk;
+  float4 *const d_kp = front.d_kp;
+  uint32_t *const d_key_off = front.d_key_off;
+  float *const d_fpfh = front.d_fpfh;
 
   // ---- host: key indices and xyz (the draws need the model's), then the draws while the device computes the features
-  std::vector<float4> h_kp(nkeys);
-  if (nkeys) e = hipMemcpyAsync(h_kp.data(), d_kp, 16 * (size_t)nkeys, hipMemcpyDeviceToHost, ctx->stream);
-  std::vector<float> h_nrm4((size_t)nkeys * 4), h_fpfh((size_t)nkeys * 33);
-  if (e == hipSuccess && nkeys) e = hipMemcpyAsync(h_nrm4.data(), d_nrm, 16 * (size_t)nkeys, hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess && nkeys) e = hipMemcpyAsync(h_fpfh.data(), d_fpfh, sizeof(float) * 33 * (size_t)nkeys, hipMemcpyDeviceToHost, ctx->stream);
+  e = coarse_front_download(ctx, front);
   if (e != hipSuccess) return fail("download");
+  const std::vector<float4> &h_kp = front.h_kp;
 
   static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::vector<int2> active;   // (segment, distinct samples) of every cluster that runs SAC-IA
@@ -564,15 +604,7 @@ int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, 
     if (e != hipSuccess) return fail("download");
     for (uint32_t j = 0; j < nsk; ++j) std::memcpy(&model_xyz[3 * (size_t)j], hx + 3 * (size_t)orig_index(h_kp[j]), 12);
   }
-  // keep what was computed for ope_coarse_batch_features
-  ctx->coarse_key_off.assign(key_off.begin(), key_off.end());
-  ctx->coarse_key_idx.resize(nkeys);
-  ctx->coarse_nrm.resize((size_t)nkeys * 3);
-  for (uint32_t j = 0; j < nkeys; ++j) {
-    ctx->coarse_key_idx[j] = orig_index(h_kp[j]);
-    for (int d = 0; d < 3; ++d) ctx->coarse_nrm[3 * (size_t)j + d] = h_nrm4[4 * (size_t)j + d];
-  }
-  ctx->coarse_fpfh.swap(h_fpfh);
+  coarse_front_keep(ctx, front);
   if (na == 0) return OPE_OK;
 
   // ---- 4. SAC-IA of every active cluster

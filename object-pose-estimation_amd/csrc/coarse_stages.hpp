@@ -73,8 +73,33 @@ int coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, const
                            const uint64_t *seeds, bool seed_by_rank, ope_coarse_batch_result *out, uint64_t *seeds_used);
 
 // coarse_pose_batch_impl's refusals, before anything is launched (n >= 1); *model_keys = the model's key points (optional)
+// who: the entry point its errors name
 int coarse_batch_check(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_coarse_params &p,
-                       long long *model_keys);
+                       long long *model_keys, const char *who = "ope_coarse_pose_batch: ");
+
+// The front end of the batched coarse stages (steps 1-3 of ope_coarse_pose_batch: segmented uniform sampling, normals, SPFH / FPFH)
+// for the model (segment 0) and n clusters (segments 1..n), shared by ope_coarse_pose_batch and ope_prerejective_pose_batch.
+// coarse_front_launch enqueues the launches (one synchronisation: the key offsets, in key_off when it returns); the device arrays
+// are packed by segment from d_key_off.  coarse_front_download enqueues the copies of the key points, normals and FPFH rows to the
+// host; after the caller's next synchronisation coarse_front_keep stores them for ope_coarse_batch_features.
+struct CoarseFront {
+  std::vector<uint32_t> key_off;   // nseg + 1
+  uint32_t nkeys = 0, max_keys = 0, nsk = 0;   // all key points, the most of one segment, the model's
+  float4 *d_kp = nullptr, *d_nrm = nullptr;    // w of a key point = its original index
+  uint32_t *d_key_off = nullptr;
+  float *d_fpfh = nullptr;                     // 33 floats per key point
+  std::vector<float4> h_kp;
+  std::vector<float> h_nrm4, h_fpfh;
+};
+int coarse_front_launch(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                        const ope_coarse_params &p, long long model_keys, CoarseFront &f);
+hipError_t coarse_front_download(ope_ctx *ctx, CoarseFront &f);
+void coarse_front_keep(ope_ctx *ctx, CoarseFront &f);
+
+// prerejective_batch.hip: ope_prerejective_pose_batch.  seed_by_rank as coarse_pose_batch_impl's; who: the entry point its errors name
+int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                                 const ope_coarse_params *front, const ope_prerejective_params *params, const uint64_t *seeds,
+                                 bool seed_by_rank, int keep_hypotheses, ope_prerejective_batch_result *out);
 
 // final_batch.hip: ope_final_pose_batch's refusals before anything is launched, and its fine preparation (steps 1-4: move,
 // sample, normals, NaN-normal drop and upload order, target trees) of n (model, cluster) pairs.  Segment s < n is the model moved
@@ -91,6 +116,10 @@ struct FinePrep {
   float4 *d_fxyz = nullptr, *d_fnrm = nullptr;
 };
 int final_batch_check(ope_ctx *ctx, size_t n, const ope_cloud *const *clusters, const ope_final_params &p);
+// everything of ope_final_pose_batch after its coarse stage (final_fine_prepare, icp_batch_core, the kept inputs, the results):
+// coarse[i] / seed_used[i] are what out[i].coarse / .seed report
+int final_batch_finish(ope_ctx *ctx, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_final_params &p,
+                       const ope_coarse_batch_result *coarse, const uint64_t *seed_used, ope_final_batch_result *out, int32_t *selected);
 int final_fine_prepare(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                        const ope_final_params &p, const ope_coarse_batch_result *coarse, FinePrep &out);
 

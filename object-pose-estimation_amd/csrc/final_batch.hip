@@ -442,13 +442,21 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
     const int rc = coarse_pose_batch_impl(ctx, model, n, clusters, &p.coarse, seeds, seeds == nullptr, coarse.data(), seed_used.data());
     if (rc != OPE_OK) return rc;
   }
+  return final_batch_finish(ctx, who, model, n, clusters, p, coarse.data(), seed_used.data(), out, selected);
+}
+
+}  // extern "C"
+
+int ope::final_batch_finish(ope_ctx *ctx, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                            const ope_final_params &p, const ope_coarse_batch_result *coarse, const uint64_t *seed_used,
+                            ope_final_batch_result *out, int32_t *selected) {
   OPE_HIP(ctx, hipSetDevice(ctx->device));
   TraceRange r_all(ctx, "final_batch");
   const size_t nseg = 2 * n;
   static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   CallTmp tmp{ctx->stream, {}};
   FinePrep fp;
-  { const int rc = final_fine_prepare(ctx, tmp, who, model, n, clusters, p, coarse.data(), fp); if (rc != OPE_OK) return rc; }
+  { const int rc = final_fine_prepare(ctx, tmp, who, model, n, clusters, p, coarse, fp); if (rc != OPE_OK) return rc; }
   const std::vector<uint32_t> &key_off = fp.key_off, &cnt = fp.cnt;
   const std::vector<float> &fbox = fp.fbox;
   const std::vector<int32_t> &status = fp.status;
@@ -538,6 +546,45 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
     }
   }
   return OPE_OK;
+}
+
+extern "C" {
+
+int ope_final_pose_batch_prerejective(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                                      const ope_final_params *params, const ope_prerejective_params *prerejective, const uint64_t *seeds,
+                                      ope_final_batch_result *out, int32_t *selected) {
+  static const char *who = "ope_final_pose_batch_prerejective: ";
+  if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_final_pose_batch_prerejective: bad argument");
+  if (selected) *selected = -1;
+  ctx->final_off.clear();
+  if (n == 0) return OPE_OK;
+  if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
+  if (n > 65535) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 65535 clusters (one grid row each)");
+  ope_final_params p;
+  ope_final_default_params(&p);
+  if (params) p = *params;
+  { const int rc = final_batch_check(ctx, n, clusters, p); if (rc != OPE_OK) return rc; }
+
+  // ---- 0. the coarse stage: the prerejective aligner, seeds counted as the estimator counts its coarse calls
+  std::vector<ope_prerejective_batch_result> pre(n);
+  {
+    const int rc = prerejective_pose_batch_impl(ctx, who, model, n, clusters, &p.coarse, prerejective, seeds, seeds == nullptr, 0, pre.data());
+    if (rc != OPE_OK) return rc;
+  }
+  std::vector<ope_coarse_batch_result> coarse(n);
+  std::vector<uint64_t> seed_used(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    ope_coarse_batch_result &c = coarse[i];
+    std::memcpy(c.T, pre[i].T, sizeof c.T);   // (the identity without a winner: an identity pose and a counted coarse call)
+    c.best_error = pre[i].error;
+    c.best_iteration = pre[i].best_iteration;
+    c.n_src_keys = pre[i].n_src_keys;
+    c.n_tgt_keys = pre[i].n_tgt_keys;
+    c.status = pre[i].status == OPE_PREREJ_OK ? OPE_COARSE_OK
+               : pre[i].status == OPE_PREREJ_EMPTY_TARGET ? OPE_COARSE_EMPTY_TARGET : OPE_COARSE_FEW_TARGET_FEATURES;
+    seed_used[i] = pre[i].seed;
+  }
+  return final_batch_finish(ctx, who, model, n, clusters, p, coarse.data(), seed_used.data(), out, selected);
 }
 
 int ope_final_batch_inputs(ope_ctx *ctx, int which, int side, float *xyz, float *normals, size_t cap, size_t *n_out) {

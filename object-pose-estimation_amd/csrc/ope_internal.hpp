@@ -294,6 +294,16 @@ struct ope_ctx {
   std::vector<float> prerej_T;
   std::vector<double> prerej_error;
 
+  // the last ope_prerejective_pose_batch (prerejective_batch.hip): what it did and, with keep_hypotheses, its iterations: per cluster
+  // the first kept iteration (pb_hyp_off, n + 1; samples / targets / survived are packed from there) and the first survivor
+  // (pb_surv_off, n + 1; iteration, T, inliers, error of the survivors are packed from there)
+  ope_prerejective_batch_stats pb_stats{};
+  std::vector<size_t> pb_hyp_off, pb_surv_off;
+  std::vector<int32_t> pb_samples, pb_targets, pb_surv_it, pb_surv_inl;
+  std::vector<uint8_t> pb_survived;
+  std::vector<float> pb_surv_T;
+  std::vector<double> pb_surv_err;
+
   ope_depth_stats depth_stats{};   // what the last ope_depth_to_cloud did (depth.hip)
 
   ope_mls_stats mls_stats{};   // what the last ope_mls_smooth* call did (mls.hip)

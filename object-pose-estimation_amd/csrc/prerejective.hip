@@ -28,12 +28,10 @@
 #include "coarse_stages.hpp"
 #include "feature_math.hpp"
 #include "icp_update.hpp"
+#include "prerejective_math.hpp"
 
 namespace ope {
 namespace {
-
-constexpr int kPrBlock = 256;
-constexpr int kPrMaxIterations = 1 << 20;
 
 // 1. original order
 __global__ __launch_bounds__(kPrBlock) void prerej_orig_kernel(CloudView c, float4 *__restrict__ pts_o) {
@@ -50,11 +48,6 @@ __global__ __launch_bounds__(256) void prerej_feature_knn_kernel(const float *__
   feature_knn_block(tgt_feat, nt, q_feat + (size_t)blockIdx.x * 33, k, out_idx + (size_t)blockIdx.x * k);
 }
 
-__device__ __forceinline__ float edge_d2(const float4 a, const float4 b) {
-  const float dx = __fsub_rn(a.x, b.x), dy = __fsub_rn(a.y, b.y), dz = __fsub_rn(a.z, b.z);
-  return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
 // 3. CorrespondenceRejectorPoly with cardinality S: edge i -> (i + 1) mod S of the source polygon against the same edge of the
 // target polygon, ratio of the squared lengths (the smaller over the larger) >= thr2.  A NaN ratio (0 / 0, a non-finite point) fails.
 __global__ __launch_bounds__(kPrBlock) void prerej_polygon_kernel(const float4 *__restrict__ src_o, const float4 *__restrict__ tgt_o,
@@ -63,16 +56,7 @@ __global__ __launch_bounds__(kPrBlock) void prerej_polygon_kernel(const float4 *
   const uint32_t it = blockIdx.x * kPrBlock + threadIdx.x;
   if (it >= H) return;
   const int32_t *sa = samp + (size_t)it * S, *co = corr + (size_t)it * S;
-  float4 sp = src_o[sa[0]], tp = tgt_o[co[0]];
-  bool ok = true;
-  for (int i = 0; i < S; ++i) {
-    const int j = i + 1 == S ? 0 : i + 1;   // (the first pair is fetched again for the closing edge: no per-lane array)
-    const float4 sn = src_o[sa[j]], tn = tgt_o[co[j]];
-    const float ds = edge_d2(sp, sn), dt = edge_d2(tp, tn);
-    const float ratio = ds < dt ? __fdiv_rn(ds, dt) : __fdiv_rn(dt, ds);
-    ok = ok && (ratio >= thr2);
-    sp = sn; tp = tn;
-  }
+  const bool ok = polygon_ok(S, thr2, [&](int i, float4 &s, float4 &t) { s = src_o[sa[i]]; t = tgt_o[co[i]]; });
   flags[it] = ok ? 1 : 0;
 }
 
@@ -87,55 +71,7 @@ __global__ __launch_bounds__(64) void prerej_fit_kernel(const float4 *__restrict
   if (k >= *d_nsurv) return;
   const int32_t it = surv[k];
   const int32_t *sa = samp + (size_t)it * S, *co = corr + (size_t)it * S;
-  double sm[3] = {0, 0, 0}, dm[3] = {0, 0, 0};
-  for (int i = 0; i < S; ++i) {
-    const float4 p = src_o[sa[i]], q = tgt_o[co[i]];
-    sm[0] += p.x; sm[1] += p.y; sm[2] += p.z;
-    dm[0] += q.x; dm[1] += q.y; dm[2] += q.z;
-  }
-  const double n = (double)S;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) { sm[d] /= n; dm[d] /= n; }
-  double sigma[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < S; ++i) {
-    const float4 p = src_o[sa[i]], q = tgt_o[co[i]];
-    const double pc[3] = {p.x - sm[0], p.y - sm[1], p.z - sm[2]}, qc[3] = {q.x - dm[0], q.y - dm[1], q.z - dm[2]};
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) sigma[3 * r + c] += qc[r] * pc[c];
-  }
-#pragma unroll
-  for (int j = 0; j < 9; ++j) sigma[j] /= n;
-  double U[9], sv[3], V[9];
-  svd3(sigma, U, sv, V);
-  double Sg[3] = {1, 1, 1};
-  if (det3(sigma) < 0) Sg[2] = -1;
-  int rank = 0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-    if (!(fabs(sv[i]) <= fabs(sv[0]) * 1e-5)) ++rank;
-  if (rank == 2) { Sg[0] = Sg[1] = 1; Sg[2] = (det3(U) * det3(V) > 0) ? 1 : -1; }
-  double R[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      double a = 0;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) a += U[3 * i + c] * Sg[c] * V[3 * j + c];
-      R[3 * i + j] = a;
-    }
-  float *T = T_out + 16 * (size_t)k, *F = rows_out + 12 * (size_t)k;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float t = (float)(dm[i] - (R[3 * i] * sm[0] + R[3 * i + 1] * sm[1] + R[3 * i + 2] * sm[2]));
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { const float v = (float)R[3 * i + c]; T[4 * c + i] = v; F[4 * i + c] = v; }
-    T[12 + i] = t; F[4 * i + 3] = t;
-    T[4 * i + 3] = 0.f;
-  }
-  T[15] = 1.f;
+  umeyama_fit(S, [&](int i, float4 &p, float4 &q) { p = src_o[sa[i]]; q = tgt_o[co[i]]; }, T_out + 16 * (size_t)k, rows_out + 12 * (size_t)k);
 }
 
 // 5a. getFitness of every survivor: item = (survivor, chunk of 256 source points in stored order).  A point is an inlier iff the
@@ -145,8 +81,6 @@ __global__ __launch_bounds__(256) void prerej_score_kernel(CloudView src, BvhVie
                                                             const uint32_t *__restrict__ d_nsurv, uint32_t chunks, double max_d2,
                                                             uint32_t *__restrict__ part_cnt, double *__restrict__ part_sum) {
   __shared__ float s_stk[kMaxDepth + 1][256];
-  __shared__ double s_red[4];
-  __shared__ uint32_t s_cnt[4];
   float *stk = &s_stk[0][threadIdx.x];
   const unsigned long long nitems = (unsigned long long)*d_nsurv * chunks;
   for (unsigned long long item = blockIdx.x; item < nitems; item += gridDim.x) {
@@ -165,15 +99,7 @@ __global__ __launch_bounds__(256) void prerej_score_kernel(CloudView src, BvhVie
       in = v.pos != kNoPos && (double)v.best < max_d2;
       if (in) d = (double)v.best;
     }
-    const unsigned long long b = __ballot(in);
-    const double w = wave_sum(d);
-    if ((threadIdx.x & 63) == 0) { s_red[threadIdx.x >> 6] = w; s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(b); }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      part_sum[item] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-      part_cnt[item] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    }
-    __syncthreads();
+    item_sum(in, d, part_cnt + item, part_sum + item);
   }
 }
 
@@ -183,14 +109,7 @@ __global__ __launch_bounds__(kPrBlock) void prerej_reduce_kernel(const uint32_t 
                                                                  int32_t *__restrict__ inliers, double *__restrict__ error) {
   const uint32_t k = blockIdx.x * kPrBlock + threadIdx.x;
   if (k >= *d_nsurv) return;
-  double sum = 0.0;
-  uint32_t cnt = 0;
-  for (uint32_t c = 0; c < chunks; ++c) {
-    sum += part_sum[(size_t)k * chunks + c];
-    cnt += part_cnt[(size_t)k * chunks + c];
-  }
-  inliers[k] = (int32_t)cnt;
-  error[k] = cnt ? sum / (double)cnt : (double)FLT_MAX;
+  survivor_sum(part_cnt, part_sum, k, chunks, inliers, error);
 }
 
 // 7. the inlier test of one transform, as flags by ORIGINAL index (non-finite points: 0)
@@ -319,21 +238,7 @@ int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33
     std::memcpy(corr.data(), forced_samples + HS, 4 * HS);
   } else {
     std::vector<int32_t> pick(HS);
-    uint64_t rng = p.seed;
-    auto next = [&rng]() {
-      rng = rng * 6364136223846793005ULL + 1442695040888963407ULL;
-      return (double)(rng >> 11) * (1.0 / 9007199254740992.0);
-    };
-    for (int it = 0; it < H; ++it) {
-      int32_t *sm = samp.data() + (size_t)it * S;
-      for (int cnt = 0; cnt < S;) {
-        const int si = (int)(ns * next());
-        bool fresh = true;
-        for (int i = 0; i < cnt; ++i) fresh = fresh && si != sm[i];
-        if (fresh) sm[cnt++] = si;
-      }
-      for (int i = 0; i < S; ++i) pick[(size_t)it * S + i] = (int)(K * next());
-    }
+    prerej_draws(ns, S, K, H, p.seed, samp.data(), pick.data());
     std::vector<int32_t> slot((size_t)ns, -1), uniq;   // the distinct sampled source points, in order of first use
     for (int32_t s : samp)
       if (slot[(size_t)s] < 0) { slot[(size_t)s] = (int32_t)uniq.size(); uniq.push_back(s); }
@@ -427,12 +332,7 @@ int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + "(fitness) " + hipGetErrorString(e));
 
   // ---- 6. the accept loop, replayed in iteration order (survivors are in iteration order)
-  double lowest = (double)FLT_MAX;
-  int64_t best = -1;
-  for (uint32_t k = 0; k < nsurv; ++k) {
-    const float frac = (float)inl[k] / (float)ns;
-    if (frac >= p.inlier_fraction && err[k] < lowest) { lowest = err[k]; best = k; }
-  }
+  const int64_t best = prerej_accept(inl.data(), err.data(), nsurv, ns, p.inlier_fraction);
   ctx->prerej_samples = samp;
   ctx->prerej_targets = corr;
   ctx->prerej_survived = flags;
