@@ -373,6 +373,7 @@ void umeyama_host(const float *src, const float *dst, int n, float T[16]) {
   for (int i = 0; i < 3; ++i)
     if (!(std::fabs(sv[i]) <= std::fabs(sv[0]) * 1e-5)) ++rank;
   if (rank == 2) { Sg[0] = Sg[1] = 1; Sg[2] = (det3h(U) * det3h(V) > 0) ? 1 : -1; }
+  else if (rank < 2) Sg[2] = (det3h(U) * det3h(V) < 0) ? -1 : 1;   // collinear samples: a rotation all the same (icp_update.hpp: umeyama_from_sums)
   double R[9];
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) {

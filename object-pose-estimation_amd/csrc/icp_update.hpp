@@ -201,6 +201,11 @@ __device__ __forceinline__ void umeyama_from_sums(const double *S, const double 
   if (rank == 2) {
     Sg[0] = Sg[1] = 1;
     Sg[2] = (det3(U) * det3(V) > 0) ? 1 : -1;
+  } else if (rank < 2) {
+    // collinear or coincident pairs: the sign of det(sigma) is rounding noise and the completed U, V come out of either
+    // handedness, so U Sg V^T above could be a reflection.  R must be a rotation: the sign follows the bases themselves
+    // (the rule Eigen 3.4's umeyama applies at every rank).  Ranks 2 and 3 are untouched.
+    Sg[2] = (det3(U) * det3(V) < 0) ? -1 : 1;
   }
   double R[9];
 #pragma unroll

@@ -141,6 +141,10 @@ static void umeyama_finish(const double sigma[9], const double src_mean[3], cons
   if (rank == 2) {
     if (det3(U) * det3(V) > 0) { S[0] = S[1] = S[2] = 1; }
     else { S[0] = S[1] = 1; S[2] = -1; }
+  } else if (rank < 2) {
+    /* collinear or coincident pairs: det(sigma) is rounding noise and the completed U, V are of either handedness; R must
+     * still be a rotation, so the sign follows the bases (Eigen 3.4's rule at every rank).  Ranks 2 and 3 are untouched. */
+    S[2] = det3(U) * det3(V) < 0 ? -1 : 1;
   }
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) {
