@@ -575,6 +575,66 @@ int ope_prerejective_last_stats(const ope_ctx *ctx, ope_prerejective_stats *out)
 int ope_prerejective_last_hypotheses(const ope_ctx *ctx, int32_t *samples, int32_t *targets, uint8_t *survived, float *T,
                                      int32_t *inliers, double *error, size_t cap, size_t *n_out);
 
+/* ---------------- feature matches filtered by RANSAC ---------------- */
+/* The third coarse aligner of estimateCoarsePose, which the reference keeps commented out (BuildModel/src/poseestimator.cpp:43-60,
+ * :111-113): pcl::registration::CorrespondenceEstimation over FPFH rows, CorrespondenceRejectorSampleConsensus over the matches,
+ * TransformationEstimationSVD over the matches that remain (tests/corr_sac_ref.py is the specification).
+ *
+ * ope_feature_correspondences: source row i (ORIGINAL order, n * 33 floats) is matched to the target row with the smallest squared
+ * L2 distance (float, component after component), the lowest index on a tie; out_dist (optional) is that squared distance.  A row
+ * without a finite distance (NaN or infinite everywhere) gives no match: *n_out matches are written, in source order (the outputs
+ * have room for n_src), and n_src - *n_out rows were dropped.  No rows on either side: no matches, nothing launched.
+ * OPE_EINVAL, nothing launched: a NULL ctx, output or feature array; more than 2^31 - 1 rows. */
+int ope_feature_correspondences(ope_ctx *ctx, const float *src_feat33, size_t n_src, const float *tgt_feat33, size_t n_tgt,
+                                int32_t *out_src_idx, int32_t *out_tgt_idx, float *out_dist, size_t *n_out);
+typedef struct {
+  double inlier_threshold;   /* 0.05, CorrespondenceRejectorSampleConsensus's default (the reference sets 0.08); > 0 */
+  int32_t max_iterations;    /* 1000; 1 .. 2^20 */
+  double probability;        /* 0.99; inside (0, 1) */
+  uint64_t seed;             /* 12345: std::mt19937 takes its low 32 bits */
+} ope_corr_sac_params;
+void ope_corr_sac_default_params(ope_corr_sac_params *p);
+typedef struct {
+  float T_best[16];     /* getBestTransformation: the winning hypothesis, column-major; the identity without a model */
+  float T_svd[16];      /* TransformationEstimationSVD over the remaining matches (all of them without a model) */
+  int32_t inliers;      /* remaining matches */
+  int32_t best;         /* the winning hypothesis in drawing order; -1 without a model */
+  int32_t iterations;   /* RandomSampleConsensus::iterations_ */
+  int32_t found;
+} ope_corr_sac_result;
+typedef struct {
+  int64_t hypotheses;   /* samples drawn (or forced) and scored */
+  int64_t iterations;
+  int64_t launches;     /* kernel launches, fills and copies to the device enqueued */
+  int64_t host_syncs;
+  double sample_dist_thresh;   /* as the draws used it */
+} ope_corr_sac_stats;
+/* Match i pairs ORIGINAL point src_idx[i] of src with tgt_idx[i] of tgt.  The model is SampleConsensusModelRegistration:
+ * sample_dist_thresh from the eigenvalues of the matched source points' float covariance; a sample is three matches (positions in
+ * 0 .. n - 1) drawn by drawIndexSample with std::mt19937 (seed), redrawn up to 1000 times until every squared edge of its source
+ * triangle is above the threshold; its transform is Umeyama without scaling over the three pairs (fp64, cast to float); a match is
+ * within the distance iff |T s - t|^2 (float, widened) < inlier_threshold^2.  Every sample RandomSampleConsensus::computeModel can
+ * reach (max_iterations + 1) is drawn and scored, and the loop is replayed from the counts.  forced_samples (optional): n_forced
+ * triples of match positions taken instead of the draws (isSampleGood is not asked).
+ * With a model: out_inlier_pos (optional, room for n) receives the positions of the matches within the distance of the winner,
+ * ascending, out->inliers of them.  Without one (fewer than 3 matches, or no good sample in 1000 draws): OPE_OK, found = 0, best = -1,
+ * the identity as T_best, every match remains (positions 0 .. n - 1) and T_svd is fitted over all of them.  n == 0: both the identity,
+ * nothing launched.  refineModel is not built.
+ * params may be NULL: the defaults of ope_corr_sac_default_params.
+ * OPE_EINVAL, nothing launched: a NULL ctx, src, tgt or out (or index arrays with n > 0, or forced_samples with n_forced > 0);
+ * max_iterations outside 1 .. 2^20, inlier_threshold <= 0 or not finite, probability outside (0, 1); more than OPE_COARSE_MAX_KEYS
+ * matches; more than 2^20 + 1 forced samples; a match index out of range; a source index in two matches (PCL's index map would keep
+ * the last); a match on a non-finite point; a forced position out of range; a context with a communicator.
+ * Launches and synchronisations depend on neither the hypotheses, the matches (n >= 1), the iteration the loop stops at nor the
+ * inliers (ope_corr_sac_last_stats). */
+int ope_corr_sac(ope_ctx *ctx, const ope_cloud *src, const ope_cloud *tgt, const int32_t *src_idx, const int32_t *tgt_idx, size_t n,
+                 const ope_corr_sac_params *params, const int32_t *forced_samples, size_t n_forced, ope_corr_sac_result *out,
+                 int32_t *out_inlier_pos);
+int ope_corr_sac_last_stats(const ope_ctx *ctx, ope_corr_sac_stats *out);
+/* The hypotheses of the last ope_corr_sac in drawing order: samples (3 match positions), T (16 floats, column-major) and counts.
+ * Any output may be NULL; at most cap hypotheses are written, *n_out = how many there were. */
+int ope_corr_sac_last_hypotheses(const ope_ctx *ctx, int32_t *samples, float *T, int32_t *counts, size_t cap, size_t *n_out);
+
 /* ---------------- batched coarse stage ---------------- */
 /* estimateCoarsePose (poseestimator.cpp:16-73) of one model against n candidate clusters in one call: the coarse half of the
  * reference's candidate loop (rosinterface.cpp:243-262).  Each cloud is uniformly sampled at key_leaf, gets k-NN normals and

@@ -39,10 +39,12 @@
 // clusters of the remainder as --candidates takes them.  Prints `segment planes <k> sizes <c0> <c1> ... rest <m>`,
 // `segment clusters <n> sizes <s0> <s1> ...`, then the --candidates lines.
 //
-//   ... --coarse sac-ia|prerejective   (every mode but --depth)
-// The coarse aligner of PoseEstimator::estimateCoarsePose: SAC-IA (the default, the reference's live code) or the
+//   ... --coarse sac-ia|prerejective|correspondences   (every mode but --depth)
+// The coarse aligner of PoseEstimator::estimateCoarsePose: SAC-IA (the default, the reference's live code), the
 // pcl::SampleConsensusPrerejective block the reference keeps commented out (BuildModel poseestimator.cpp:90-108; 50 000 iterations on
-// the device).  With prerejective the candidate loop and the tracker run one estimateFinalPose at a time, unless
+// the device), or its other commented block (:43-60, :111-113): FPFH matches, CorrespondenceRejectorSampleConsensus (10 000 iterations
+// at 0.08) and the SVD over the remaining matches.  With correspondences the candidate loop and the tracker always run one
+// estimateFinalPose at a time; with prerejective they do unless
 //   ... --coarse-batch   (every mode but --depth, --track and --track-loop)
 // is given: PoseEstimator::setCoarseBatch(true), so --candidates (and --segment, --frame) with --coarse prerejective check all
 // clusters in one ope_final_pose_batch_prerejective call.  Without the flag every mode prints what it printed before.
@@ -107,7 +109,8 @@ static const char *branch_name(int b) {
 static bool parse_coarse(const char *v, ope::PoseEstimator::CoarseMethod &m) {
   if (!std::strcmp(v, "sac-ia")) { m = ope::PoseEstimator::COARSE_SAC_IA; return true; }
   if (!std::strcmp(v, "prerejective")) { m = ope::PoseEstimator::COARSE_PREREJECTIVE; return true; }
-  std::fprintf(stderr, "--coarse takes sac-ia or prerejective\n");
+  if (!std::strcmp(v, "correspondences")) { m = ope::PoseEstimator::COARSE_CORRESPONDENCES; return true; }
+  std::fprintf(stderr, "--coarse takes sac-ia, prerejective or correspondences\n");
   return false;
 }
 

@@ -15,6 +15,8 @@
 //   removeNaNFromPointCloud / PassThrough / VoxelGrid    poseestimator.cpp:192-194; BuildModel processingpcd.cpp:8-52
 //   SampleConsensusInitialAlignment                      poseestimator.cpp:50-64
 //   SampleConsensusPrerejective                          BuildModel poseestimator.cpp:90-108 (commented out there)
+//   registration::CorrespondenceEstimation<FPFHSignature33, FPFHSignature33>
+//   registration::CorrespondenceRejectorSampleConsensus  BuildModel poseestimator.cpp:43-60 (commented out there)
 // Point types are layout-compatible PODs (x@0,y@4,z@8; normal@16 in PointXYZRGBNormal; 16-byte aligned).
 // Errors never throw on the hot path: like PCL, a failed call logs to stderr and leaves
 // hasConverged() == false / the transform at identity (registration_mod.hpp:60-64,73-77).
@@ -333,6 +335,87 @@ template <class S, class T, class Scalar = float> struct TransformationEstimatio
     }
     if (ope_rigid_transform_svd(ctx, a.data(), b.data(), corrs.size(), out.m) != OPE_OK) log_error("TransformationEstimationSVD", ctx);
   }
+};
+
+// CorrespondenceEstimation over FPFH rows (BuildModel poseestimator.cpp:43-47, commented out there): every source row is matched to
+// the target row with the smallest squared L2 distance, lowest index on a tie (ope_feature_correspondences); `distance` is that
+// squared distance.  Rows without a finite distance give no correspondence.  max_distance keeps distance <= max_distance^2, as the
+// point version does.  Reciprocal matches are not built.
+template <class Scalar> struct CorrespondenceEstimation<FPFHSignature33, FPFHSignature33, Scalar> {
+  typedef std::shared_ptr<CorrespondenceEstimation> Ptr;
+  void setInputSource(const typename PointCloud<FPFHSignature33>::ConstPtr &c) { input_ = c; }
+  void setInputCloud(const typename PointCloud<FPFHSignature33>::ConstPtr &c) { input_ = c; }
+  void setInputTarget(const typename PointCloud<FPFHSignature33>::ConstPtr &c) { target_ = c; }
+  void determineCorrespondences(Correspondences &out, double max_distance = std::sqrt(DBL_MAX)) {
+    out.clear();
+    ope_ctx *ctx = default_context();
+    if (!ctx || !input_ || !target_ || input_->empty() || target_->empty()) return;
+    std::vector<int32_t> q(input_->size()), m(input_->size());
+    std::vector<float> d(input_->size());
+    size_t n = 0;
+    if (ope_feature_correspondences(ctx, &input_->points[0].histogram[0], input_->size(), &target_->points[0].histogram[0], target_->size(),
+                                    q.data(), m.data(), d.data(), &n) != OPE_OK) { log_error("determineCorrespondences", ctx); return; }
+    const double max_d2 = max_distance * max_distance;
+    for (size_t i = 0; i < n; ++i) {
+      if ((double)d[i] > max_d2) continue;
+      Correspondence c;
+      c.index_query = q[i]; c.index_match = m[i]; c.distance = d[i];
+      out.push_back(c);
+    }
+  }
+ private:
+  typename PointCloud<FPFHSignature33>::ConstPtr input_, target_;
+};
+
+// CorrespondenceRejectorSampleConsensus (BuildModel poseestimator.cpp:49-60; DetectAndLocalize :275-281, both commented out there) on
+// ope_corr_sac: RANSAC over SampleConsensusModelRegistration, the class defaults PCL's (threshold 0.05, 1000 iterations).
+// getBestTransformation() is the winning hypothesis, the identity when no model was found (then every correspondence remains).
+// Stand-alone only: inside an ICP loop apply() selects nothing (ICP's fused search has no such stage); refineModel is not built.
+// Two correspondences with one index_query are refused (PCL's index map would silently keep the last): nothing remains.
+template <class PointT> struct CorrespondenceRejectorSampleConsensus : CorrespondenceRejector {
+  typedef std::shared_ptr<CorrespondenceRejectorSampleConsensus> Ptr;
+  CorrespondenceRejectorSampleConsensus() { ope_corr_sac_default_params(&p_); }
+  void setInputSource(const typename PointCloud<PointT>::ConstPtr &c) { src_ = c; }
+  void setInputCloud(const typename PointCloud<PointT>::ConstPtr &c) { src_ = c; }
+  void setInputTarget(const typename PointCloud<PointT>::ConstPtr &c) { tgt_ = c; }
+  void setInlierThreshold(double t) { p_.inlier_threshold = t; }
+  double getInlierThreshold() const { return p_.inlier_threshold; }
+  void setMaximumIterations(int n) { p_.max_iterations = n; }
+  int getMaximumIterations() const { return p_.max_iterations; }
+  void setSeed(uint64_t s) { p_.seed = s; }   // PCL's engine starts from 12345 unless asked for a random seed: made explicit here
+  Matrix4f getBestTransformation() const { return best_; }
+  bool foundModel() const { return found_; }                 // not PCL's: whether RANSAC came back with a model
+  int getNumberOfIterations() const { return iterations_; }  // not PCL's: RandomSampleConsensus::iterations_
+  void apply(ope_icp_params &) const override {}
+  void getRemainingCorrespondences(const Correspondences &original, Correspondences &remaining) override {
+    remaining.clear();
+    best_ = Matrix4f::Identity();
+    found_ = false;
+    iterations_ = 0;
+    ope_ctx *ctx = default_context();
+    if (!ctx || !src_ || !tgt_) { std::fprintf(stderr, "[ope::CorrespondenceRejectorSampleConsensus] input clouds were not set\n"); return; }
+    if (original.empty()) return;
+    auto ds = upload(*src_, false), dt = upload(*tgt_, false);
+    if (!ds->h || !dt->h) return;
+    std::vector<int32_t> q(original.size()), m(original.size()), pos(original.size());
+    for (size_t i = 0; i < original.size(); ++i) { q[i] = original[i].index_query; m[i] = original[i].index_match; }
+    ope_corr_sac_result r;
+    if (ope_corr_sac(ctx, ds->h, dt->h, q.data(), m.data(), q.size(), &p_, nullptr, 0, &r, pos.data()) != OPE_OK) {
+      log_error("CorrespondenceRejectorSampleConsensus", ctx);
+      return;
+    }
+    std::memcpy(best_.m, r.T_best, sizeof best_.m);
+    found_ = r.found != 0;
+    iterations_ = r.iterations;
+    remaining.reserve((size_t)r.inliers);
+    for (int32_t i = 0; i < r.inliers; ++i) remaining.push_back(original[(size_t)pos[(size_t)i]]);
+  }
+ private:
+  typename PointCloud<PointT>::ConstPtr src_, tgt_;
+  ope_corr_sac_params p_;
+  Matrix4f best_ = Matrix4f::Identity();
+  bool found_ = false;
+  int iterations_ = 0;
 };
 
 // Selected by type in setTransformationEstimation: the 6x6 normal equations of the linearised point-to-plane

@@ -36,12 +36,13 @@ class PoseEstimator {
 
   PoseEstimator() : alignedSource(new Cloud), cloudModel(new Cloud) {}
 
-  // the coarse aligner: SAC-IA (the reference's live code, the default) or the prerejective block the reference keeps commented out
-  enum CoarseMethod { COARSE_SAC_IA = 0, COARSE_PREREJECTIVE = 1 };
+  // the coarse aligner: SAC-IA (the reference's live code, the default), the prerejective block the reference keeps commented out, or
+  // its other commented block: feature matches, CorrespondenceRejectorSampleConsensus, the SVD over what remains
+  enum CoarseMethod { COARSE_SAC_IA = 0, COARSE_PREREJECTIVE = 1, COARSE_CORRESPONDENCES = 2 };
   void setCoarseMethod(CoarseMethod m) { coarse_method_ = m; }
   CoarseMethod coarseMethod() const { return coarse_method_; }
   // estimateFinalPoseCandidates with COARSE_PREREJECTIVE: all clusters in one ope_final_pose_batch_prerejective call instead of one
-  // estimateFinalPose at a time (off by default; SAC-IA always batches)
+  // estimateFinalPose at a time (off by default; SAC-IA always batches; COARSE_CORRESPONDENCES has no batched form and runs the loop)
   void setCoarseBatch(bool on) { coarse_batch_ = on; }
   bool coarseBatch() const { return coarse_batch_; }
   void setSacIaSeed(uint64_t seed) { sacia_seed_ = seed; }
@@ -95,6 +96,7 @@ class PoseEstimator {
       return Matrix4f::Identity();
     }
     if (coarse_method_ == COARSE_PREREJECTIVE) return prerejectiveCoarsePose(p_sourceCloud, src, tgt, srcFeat, tgtFeat);
+    if (coarse_method_ == COARSE_CORRESPONDENCES) return correspondencesCoarsePose(p_sourceCloud, src, tgt, srcFeat, tgtFeat);
     compat::SampleConsensusInitialAlignment<PointT, PointT, compat::FPFHSignature33> sacia;
     sacia.setInputSource(src);
     sacia.setInputTarget(tgt);
@@ -199,7 +201,8 @@ class PoseEstimator {
     std::vector<ope_final_batch_result> res(clusters.size());
     int32_t sel = -1;
     // (ope_final_pose_batch's coarse stage is SAC-IA; the prerejective batch is opt-in: setCoarseBatch)
-    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() && (coarse_method_ == COARSE_SAC_IA || coarse_batch_);
+    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() &&
+                   (coarse_method_ == COARSE_SAC_IA || (coarse_method_ == COARSE_PREREJECTIVE && coarse_batch_));
     if (batched) {
       ope_ctx *ctx = compat::default_context();
       auto model = compat::upload(original, false);
@@ -346,6 +349,36 @@ class PoseEstimator {
       sacPreRej.align(result);
     }
     const Matrix4f pose = sacPreRej.hasConverged() ? sacPreRej.getFinalTransformation() : Matrix4f::Identity();
+    compat::transformPointCloud(*p_sourceCloud, *alignedSource, pose);
+    return pose;
+  }
+
+  // BuildModel/src/poseestimator.cpp:43-60 and :111-113, the other block the reference keeps commented out, in SAC-IA's place: the
+  // same key points and features; FPFH matches, the rejector with its 10 000 iterations and 0.08, the SVD over the remaining matches
+  // (over all of them when RANSAC finds no model, as those lines would).  The draws start from PCL's fixed seed: no call counter
+  // enters them, but the call is counted like the other aligners'.
+  Matrix4f correspondencesCoarsePose(const Cloud::Ptr &p_sourceCloud, const Cloud::Ptr &src, const Cloud::Ptr &tgt, const FeatureCloud::Ptr &srcFeat,
+                                     const FeatureCloud::Ptr &tgtFeat) {
+    ++coarse_calls_;
+    Matrix4f pose = Matrix4f::Identity();
+    {
+      compat::ScopeTime t("Initial Alignment");
+      std::shared_ptr<compat::Correspondences> correspondences(new compat::Correspondences);
+      compat::registration::CorrespondenceEstimation<compat::FPFHSignature33, compat::FPFHSignature33> cest;   // :43-47
+      cest.setInputSource(srcFeat);
+      cest.setInputTarget(tgtFeat);
+      cest.determineCorrespondences(*correspondences);
+      compat::registration::CorrespondenceRejectorSampleConsensus<PointT> rejector;                             // :49-60
+      rejector.setInputSource(src);
+      rejector.setInputTarget(tgt);
+      rejector.setInputCorrespondences(correspondences);
+      rejector.setMaximumIterations(10000);   // :55
+      rejector.setInlierThreshold(0.08);      // :56
+      compat::Correspondences remaining;
+      rejector.getCorrespondences(remaining);
+      compat::registration::TransformationEstimationSVD<PointT, PointT> transEst;                               // :111-113
+      transEst.estimateRigidTransformation(*src, *tgt, remaining, pose);
+    }
     compat::transformPointCloud(*p_sourceCloud, *alignedSource, pose);
     return pose;
   }

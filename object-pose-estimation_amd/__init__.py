@@ -156,6 +156,36 @@ class PrerejectiveStats(C.Structure):
     ]
 
 
+class CorrSacParams(C.Structure):
+    _fields_ = [
+        ("inlier_threshold", C.c_double),
+        ("max_iterations", C.c_int32),
+        ("probability", C.c_double),
+        ("seed", C.c_uint64),
+    ]
+
+
+class CorrSacResult(C.Structure):
+    _fields_ = [
+        ("T_best", C.c_float * 16),
+        ("T_svd", C.c_float * 16),
+        ("inliers", C.c_int32),
+        ("best", C.c_int32),
+        ("iterations", C.c_int32),
+        ("found", C.c_int32),
+    ]
+
+
+class CorrSacStats(C.Structure):
+    _fields_ = [
+        ("hypotheses", C.c_int64),
+        ("iterations", C.c_int64),
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
+        ("sample_dist_thresh", C.c_double),
+    ]
+
+
 class PrerejectiveBatchResult(C.Structure):
     _fields_ = [
         ("T", C.c_float * 16),
@@ -589,6 +619,11 @@ ABI = [
     ("ope_final_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(FinalParams), C.POINTER(C.c_uint64),
                                         C.POINTER(FinalBatchResult), _ip]),
     ("ope_final_batch_inputs", C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_feature_correspondences", C.c_int, [_vp, _fp, C.c_size_t, _fp, C.c_size_t, _ip, _ip, _fp, C.POINTER(C.c_size_t)]),
+    ("ope_corr_sac_default_params", None, [C.POINTER(CorrSacParams)]),
+    ("ope_corr_sac", C.c_int, [_vp, _vp, _vp, _ip, _ip, C.c_size_t, C.POINTER(CorrSacParams), _ip, C.c_size_t, C.POINTER(CorrSacResult), _ip]),
+    ("ope_corr_sac_last_stats", C.c_int, [_vp, C.POINTER(CorrSacStats)]),
+    ("ope_corr_sac_last_hypotheses", C.c_int, [_vp, _ip, _fp, _ip, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("ope_prerejective_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(CoarseParams), C.POINTER(PrerejectiveParams),
                                               C.POINTER(C.c_uint64), C.c_int, C.POINTER(PrerejectiveBatchResult)]),
     ("ope_prerejective_batch_last_stats", C.c_int, [_vp, C.POINTER(PrerejectiveBatchStats)]),
@@ -776,6 +811,18 @@ class PrerejectiveOut:
     inliers: int
     converged: bool
     inlier_idx: np.ndarray | None   # getInliers(): ORIGINAL source indices, ascending (with_inliers=True)
+
+
+@dataclass
+class CorrSacOut:
+    T_best: np.ndarray     # (4,4) math layout, float32 — getBestTransformation(); the identity without a model
+    T_svd: np.ndarray      # TransformationEstimationSVD over the remaining matches (all of them without a model)
+    inliers: int           # remaining matches
+    best: int              # the winning hypothesis in drawing order, -1 without a model
+    iterations: int
+    found: bool
+    inlier_pos: np.ndarray           # positions of the remaining matches in the given ones, ascending
+    matches: tuple | None = None     # (src_idx, tgt_idx, dist) when the call made them (coarse_pose_correspondences)
 
 
 @dataclass
@@ -1946,11 +1993,73 @@ class Context:
         return dict(samples=smp[:h].copy(), targets=tg[:h].copy(), survived=sv[:h].astype(bool), T=T[:h].reshape(h, 4, 4).transpose(0, 2, 1).copy(),
                     inliers=inl[:h].copy(), error=err[:h].copy())
 
+    def feature_correspondences(self, src_feat, tgt_feat):
+        """ope_feature_correspondences: the 1-NN match of every source FPFH row among the target's rows.  (src_idx, tgt_idx, dist):
+        int32, int32 and the float32 squared distance; rows without a finite distance are left out (len(src_feat) - len(src_idx))."""
+        sf, tf = _f32(src_feat, 33), _f32(tgt_feat, 33)
+        ns = len(sf)
+        si, ti, d = np.empty(max(ns, 1), np.int32), np.empty(max(ns, 1), np.int32), np.empty(max(ns, 1), np.float32)
+        n = C.c_size_t(0)
+        self._chk(lib().ope_feature_correspondences(self.h, _p(sf, _fp), ns, _p(tf, _fp), len(tf), _p(si, _ip), _p(ti, _ip), _p(d, _fp), C.byref(n)))
+        return si[:n.value].copy(), ti[:n.value].copy(), d[:n.value].copy()
+
+    def corr_sac(self, src: "Cloud", tgt: "Cloud", src_idx, tgt_idx, params: CorrSacParams | None = None, forced_samples=None) -> CorrSacOut:
+        """ope_corr_sac: pcl::registration::CorrespondenceRejectorSampleConsensus over the matches (src_idx[i], tgt_idx[i]) and
+        TransformationEstimationSVD over those that remain (include/ope.h).  params None: the library's defaults.  forced_samples:
+        (h, 3) match positions taken instead of the draws."""
+        si, ti = np.ascontiguousarray(src_idx, np.int32).reshape(-1), np.ascontiguousarray(tgt_idx, np.int32).reshape(-1)
+        if len(si) != len(ti):
+            raise ValueError("src_idx and tgt_idx pair up")
+        fs = np.ascontiguousarray(forced_samples, np.int32).reshape(-1, 3) if forced_samples is not None else None
+        res = CorrSacResult()
+        pos = np.empty(max(len(si), 1), np.int32)
+        self._chk(lib().ope_corr_sac(self.h, src.h, tgt.h, _p(si, _ip), _p(ti, _ip), len(si), C.byref(params) if params is not None else None,
+                                     _p(fs, _ip), len(fs) if fs is not None else 0, C.byref(res), _p(pos, _ip)))
+        return CorrSacOut(from_colmajor(np.array(res.T_best, np.float32)), from_colmajor(np.array(res.T_svd, np.float32)), res.inliers, res.best,
+                          res.iterations, bool(res.found), pos[:res.inliers].copy())
+
+    def corr_sac_stats(self) -> dict:
+        """ope_corr_sac_last_stats: hypotheses, iterations, launches, host_syncs, sample_dist_thresh of the last corr_sac call."""
+        s = CorrSacStats()
+        self._chk(lib().ope_corr_sac_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in CorrSacStats._fields_}
+
+    def corr_sac_hypotheses(self) -> dict:
+        """ope_corr_sac_last_hypotheses, in drawing order: samples (h, 3) int32 match positions, T (h, 4, 4) float32 math layout,
+        counts (h,) int32."""
+        n = C.c_size_t(0)
+        self._chk(lib().ope_corr_sac_last_hypotheses(self.h, None, None, None, 0, C.byref(n)))
+        h = n.value
+        smp = np.zeros((max(h, 1), 3), np.int32)
+        T = np.zeros((max(h, 1), 16), np.float32)
+        cnt = np.zeros(max(h, 1), np.int32)
+        self._chk(lib().ope_corr_sac_last_hypotheses(self.h, _p(smp, _ip), _p(T, _fp), _p(cnt, _ip), h, C.byref(n)))
+        return dict(samples=smp[:h].copy(), T=T[:h].reshape(h, 4, 4).transpose(0, 2, 1).copy(), counts=cnt[:h].copy())
+
+    def coarse_pose_correspondences(self, src: "Cloud", src_feat, tgt: "Cloud", tgt_feat, params: CorrSacParams | None = None) -> CorrSacOut:
+        """The reference's third coarse aligner (BuildModel/src/poseestimator.cpp:43-60, :111-113) over key-point clouds and their
+        FPFH rows: feature_correspondences, corr_sac, and the SVD over the remaining matches (out.T_svd is the coarse pose)."""
+        si, ti, d = self.feature_correspondences(src_feat, tgt_feat)
+        out = self.corr_sac(src, tgt, si, ti, params)
+        out.matches = (si, ti, d)
+        return out
+
 
 def default_prerejective_params(**kw) -> PrerejectiveParams:
     """ope_prerejective_default_params (50000 / 3 / 5 / 0.8 / 0.15 / 0.25, seed 1: BuildModel poseestimator.cpp:97-102)."""
     p = PrerejectiveParams()
     lib().ope_prerejective_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_corr_sac_params(**kw) -> CorrSacParams:
+    """ope_corr_sac_default_params (0.05 / 1000 / 0.99, seed 12345: PCL's own defaults; the reference sets 10000 and 0.08)."""
+    p = CorrSacParams()
+    lib().ope_corr_sac_default_params(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)

@@ -294,6 +294,11 @@ struct ope_ctx {
   std::vector<float> prerej_T;
   std::vector<double> prerej_error;
 
+  // the last ope_corr_sac (corr_sac.hip): what it did, and its hypotheses in drawing order (ope_corr_sac_last_hypotheses)
+  ope_corr_sac_stats corr_sac_stats{};
+  std::vector<int32_t> corr_sac_samples, corr_sac_counts;
+  std::vector<float> corr_sac_T;
+
   // the last ope_prerejective_pose_batch (prerejective_batch.hip): what it did and, with keep_hypotheses, its iterations: per cluster
   // the first kept iteration (pb_hyp_off, n + 1; samples / targets / survived are packed from there) and the first survivor
   // (pb_surv_off, n + 1; iteration, T, inliers, error of the survivors are packed from there)
