@@ -513,7 +513,10 @@ typedef struct {
 void ope_sacia_default_params(ope_sacia_params *p);
 /* pcl::SampleConsensusInitialAlignment::align (poseestimator.cpp:50-64).
  * src_feat/tgt_feat: n*33 floats in ORIGINAL order.  forced_samples (optional):
- * max_iterations*nr_samples source indices then as many target indices. */
+ * max_iterations*nr_samples source indices then as many target indices.
+ * A hypothesis with a drawn sample whose descriptor matches nothing (a NaN row, as ope_fpfh writes
+ * it for a non-finite point) or with a fit that is not finite is void: it scores |source| and its
+ * transform is the identity.  The call goes on and returns OPE_OK. */
 int ope_sacia(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const ope_cloud *tgt,
               const ope_index *tgt_index, const float *tgt_feat33, const ope_sacia_params *params,
               const int32_t *forced_samples, float out_T[16], double *best_error, int32_t *best_iteration);

@@ -673,16 +673,26 @@ int ope_sacia(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const
   }
 
   // ---- one rigid transform per hypothesis from its nr_samples pairs (TransformationEstimationSVD)
+  // A hypothesis is void if a drawn sample has no matching descriptor (its own descriptor is NaN, as ope_fpfh writes it for a
+  // non-finite point, or the target has none that is not) or if its fit is not finite (a non-finite point among its pairs): it
+  // scores |source|, every term 1, and its transform is the identity.  A forced index out of range stays an error.
   std::vector<float> T((size_t)H * 16), rows((size_t)H * 12), ps((size_t)S * 3), pt((size_t)S * 3);
+  std::vector<char> is_void((size_t)H, 0);
   for (int it = 0; it < H; ++it) {
+    float *Th = &T[(size_t)it * 16];
+    bool unmatched = false;
     for (int i = 0; i < S; ++i) {
       const int32_t a = samp[(size_t)it * S + i], b = corr[(size_t)it * S + i];
+      if (!forced_samples && b == -1) { unmatched = true; continue; }
       if (a < 0 || a >= ns || b < 0 || b >= nt) return set_err(ctx, OPE_EINVAL, "ope_sacia: sample index out of range");
       std::memcpy(&ps[3 * i], &src->h_xyz[3 * (size_t)a], 12);
       std::memcpy(&pt[3 * i], &tgt->h_xyz[3 * (size_t)b], 12);
     }
-    umeyama_host(ps.data(), pt.data(), S, &T[(size_t)it * 16]);
-    colmajor_to_rows12(&T[(size_t)it * 16], &rows[(size_t)it * 12]);
+    if (!unmatched) umeyama_host(ps.data(), pt.data(), S, Th);
+    bool finite = !unmatched;
+    for (int k = 0; finite && k < 16; ++k) finite = std::isfinite(Th[k]);
+    if (!finite) { std::memcpy(Th, I4, sizeof I4); is_void[it] = 1; }
+    colmajor_to_rows12(Th, &rows[(size_t)it * 12]);
   }
 
   // ---- error metric of all hypotheses (device), then the reference's "lowest error wins" scan
@@ -713,6 +723,7 @@ int ope_sacia(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const
   for (int it = 0; it < H; ++it) {
     double err = invalid;
     for (int b = 0; b < bx; ++b) err += part[(size_t)it * bx + b];
+    if (is_void[it]) err = (double)src->n;
     if (it == 0 || (float)err < (float)lowest) { lowest = err; best = it; }
   }
   std::memcpy(out_T, &T[(size_t)best * 16], sizeof(float) * 16);

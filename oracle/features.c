@@ -401,13 +401,20 @@ int orc_sacia(const float *src_xyz, const float *src_feat33, int ns, const float
         corr[i] = nn[r] >= 0 ? nn[r] : nn[0];
       }
     }
+    /* a void hypothesis (a sample without a matching descriptor, or a fit that is not finite): the identity, every term 1 */
+    int is_void = 0;
     for (int i = 0; i < nr_samples; ++i) {
+      if (corr[i] < 0) { is_void = 1; continue; }
       memcpy(ps + 3 * i, src_xyz + 3 * samp[i], 3 * sizeof(float));
       memcpy(pt + 3 * i, tgt_xyz + 3 * corr[i], 3 * sizeof(float));
     }
     float T[16];
-    orc_umeyama(ps, pt, nr_samples, 0, T);
-    float err = (float)orc_sacia_error(src_xyz, ns, tree, T, max_corr_dist);
+    if (!is_void) {
+      orc_umeyama(ps, pt, nr_samples, 0, T);
+      for (int k = 0; k < 16; ++k) if (!isfinite(T[k])) is_void = 1;
+    }
+    if (is_void) memcpy(T, I4, sizeof I4);
+    float err = is_void ? (float)ns : (float)orc_sacia_error(src_xyz, ns, tree, T, max_corr_dist);
     if (it == 0 || err < lowest) {
       lowest = err;
       memcpy(out_T, T, sizeof T);
