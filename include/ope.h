@@ -447,7 +447,16 @@ int ope_normals(ope_ctx *ctx, ope_cloud *cloud, int k, const float vp[3], float 
 int ope_normals_from(ope_ctx *ctx, ope_cloud *queries, const ope_index *index, int k, const float vp[3], float *out_normals,
                      float *out_curvature);
 /* pcl::FPFHEstimation::compute with setRadiusSearch(radius) on a cloud that carries
- * normals (poseestimator.cpp:121-125).  out33 n*33 floats. */
+ * normals (poseestimator.cpp:121-125).  out33 n*33 floats, ORIGINAL order.
+ * A point's neighbourhood is every finite point within the radius, squared distance <= radius * radius in float (a point at
+ * exactly the radius is in), itself included.  A non-finite point is in no neighbourhood and gets a NaN row; a finite point
+ * with nothing else in range gets a zero row; every other group of 11 bins sums to 100.
+ * Duplicates: a point at distance 0 that is another point by index is a neighbour: it counts in the bin increment
+ * 100 / (neighbours - 1), its pair is rejected (computePairFeatures: f4 == 0), and the weighted pass leaves out every
+ * neighbour at distance 0, the point itself and its duplicates.
+ * NaN normals (fewer than 3 neighbours, or a collinear neighbourhood: ope_normals) reject nothing and swap nothing, as in PCL,
+ * whose tests are comparisons; a feature that comes out non-finite goes to bin 0 of its own group, feature by feature (PCL's
+ * (int)floor(NaN) followed by its clamp).  The rows stay finite.  tests/fpfh_ref.py states all of it in fp64. */
 int ope_fpfh(ope_ctx *ctx, const ope_cloud *cloud, float radius, float *out33);
 /* pcl::UniformSampling::compute(PointCloud<int>&) with setRadiusSearch(leaf)
  * (poseestimator.cpp:141-145); survivors in ascending voxel-key order. */
@@ -652,7 +661,10 @@ typedef struct {
 void ope_coarse_default_params(ope_coarse_params *p);
 
 /* Limits of one batch: points of one cloud (model or cluster), and key points of one cloud after sampling (each cloud's key
- * points are staged in LDS).  Larger clouds go through the single-cloud calls. */
+ * points are staged in LDS).  Larger clouds go through the single-cloud calls.  The limits are inclusive: a cloud of exactly
+ * OPE_COARSE_MAX_KEYS key points is accepted (its FPFH launch holds 2 x 4096 float4 and the histograms, 148 KB of the 160 KB of
+ * LDS), one more key point is refused.  The batch's FPFH follows ope_fpfh's rules; duplicates never reach it, uniform sampling
+ * keeps one point per voxel. */
 #define OPE_COARSE_MAX_POINTS 65536
 #define OPE_COARSE_MAX_KEYS 4096
 

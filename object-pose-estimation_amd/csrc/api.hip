@@ -477,6 +477,8 @@ void ope_ctx_destroy(ope_ctx *ctx) {
   if (ctx->d_lm_stats) (void)hipFree(ctx->d_lm_stats);
   if (ctx->d_fixed) (void)hipFree(ctx->d_fixed);
   tmp_release_stream(ctx->stream);   // the cached temporaries of this context's stream
+  stage_release_stream(ctx->stream);   // and the threads' small-copy slots that last went to it, or to the context's own
+  if (ctx->own_stream != ctx->stream) stage_release_stream(ctx->own_stream);
   if (ctx->plan_stream) { (void)hipStreamSynchronize(ctx->plan_stream); (void)hipStreamDestroy(ctx->plan_stream); }
   if (ctx->upd_stream) { (void)hipStreamSynchronize(ctx->upd_stream); (void)hipStreamDestroy(ctx->upd_stream); }
   if (ctx->ev_chain_s) (void)hipEventDestroy(ctx->ev_chain_s);
@@ -515,6 +517,7 @@ int ope_ctx_set_stream(ope_ctx *ctx, void *hip_stream) {
     // release them once the context has moved on); frees synchronise, so nothing in flight still uses them
     (void)hipSetDevice(ctx->device);
     tmp_release_stream(ctx->stream);
+    if (ctx->stream != ctx->own_stream) stage_release_stream(ctx->stream);   // a caller's stream may be gone after this call
     if (next != ctx->own_stream) {
       // a caller's stream gets what ope_ctx_create gives the context's own: its queue and the queue's scratch memory, before any
       // launch on it runs beside an update that waits for it under a bound (prime_stream_kernel)

@@ -4,10 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <memory>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <cstdio>
 #include <cstdlib>
@@ -481,8 +483,39 @@ constexpr int kStageRing = 16;
 struct UploadStage {
   unsigned char *big = nullptr; size_t cap = 0;
   unsigned char *ring = nullptr; hipEvent_t ev[kStageRing] = {}; bool used[kStageRing] = {}; int next = 0;
+  hipStream_t on[kStageRing] = {}; uint64_t at[kStageRing] = {};   // the stream of a slot's last copy, and the retirement count then
 };
 inline UploadStage &upload_stage() { static thread_local UploadStage st; return st; }
+// A slot's event may outlive the stream it was last recorded on: the ring belongs to the thread, the stream to a context, and
+// the next context of the same thread comes round to the slot.  The runtime's event keeps a pointer to that stream and
+// hipEventSynchronize looks through it (for a capture in progress), so waiting on such an event reads freed memory: seen as
+// "operation not permitted on an event last recorded in a capturing stream" from the first small copy of a later context.  A
+// stream that goes away is therefore retired here first: it is synchronised, so every copy recorded on it before has landed, and
+// a slot whose last copy went to a stream retired since is reused without touching its event.
+struct RetiredStreams {
+  std::mutex mu;
+  std::unordered_map<hipStream_t, uint64_t> when;   // by handle (a later stream may get the same one): the count at its last retirement
+  std::atomic<uint64_t> count{0};
+};
+inline RetiredStreams &retired_streams() { static RetiredStreams *r = new RetiredStreams(); return *r; }
+// a stream is going away (its context ends, or leaves it for another): before it is destroyed
+inline void stage_release_stream(hipStream_t s) {
+  if (s == nullptr) return;
+  (void)hipStreamSynchronize(s);
+  RetiredStreams &r = retired_streams();
+  std::lock_guard<std::mutex> lock(r.mu);
+  r.when[s] = r.count.fetch_add(1) + 1;
+}
+// wait until the copy that last used slot k has landed.  On the same stream as the coming copy the event is safe (the caller's
+// stream is alive); on another one the retirements are looked up, under the lock that a retirement takes, wait included.
+inline hipError_t stage_wait_slot(UploadStage &st, int k, hipStream_t stream) {
+  if (st.on[k] == stream) return hipEventSynchronize(st.ev[k]);
+  RetiredStreams &r = retired_streams();
+  std::lock_guard<std::mutex> lock(r.mu);
+  const auto it = r.when.find(st.on[k]);
+  if (it != r.when.end() && it->second > st.at[k]) return hipSuccess;
+  return hipEventSynchronize(st.ev[k]);
+}
 // the calling thread's pinned block, at least min(bytes, kStageChunk) large (for callers that fill it themselves: ope_cloud_upload
 // gathers the caller's structs straight into it); *cap_out = its size
 inline hipError_t stage_block(size_t bytes, unsigned char **block, size_t *cap_out) {
@@ -513,8 +546,10 @@ inline hipError_t h2d_copy(hipStream_t stream, void *dst, const void *src, size_
     }
     const int k = st.next;
     st.next = (k + 1) % kRing;
-    if (st.used[k]) { const hipError_t e = hipEventSynchronize(st.ev[k]); if (e != hipSuccess) return e; }
+    if (st.used[k]) { const hipError_t e = stage_wait_slot(st, k, stream); if (e != hipSuccess) return e; }
     std::memcpy(st.ring + (size_t)k * kSmall, src, bytes);
+    st.on[k] = stream;
+    st.at[k] = retired_streams().count.load();
     hipError_t e = hipMemcpyAsync(dst, st.ring + (size_t)k * kSmall, bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipEventRecord(st.ev[k], stream);
     st.used[k] = e == hipSuccess;

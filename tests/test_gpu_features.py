@@ -178,7 +178,9 @@ def test_fpfh_isolated_and_nan_points(ctx):
     ref, _, _ = oracle.fpfh(P[:-1], N[:-1], 0.03)
     assert (out[-2] == 0).all()                               # isolated: only itself in range
     assert np.isnan(out[-1]).all()                            # non-finite point
-    assert np.abs(out[:-2] - ref[:-1]).sum(1).max() < 30.0
+    # every row within 1e-3 (L1, of 300) of the oracle's, the bound of test_fpfh_matches_oracle_on_model_surface; the same cloud
+    # against the fp64 reference, with the zero and the NaN row: test_gpu_fpfh_edges.py, case nan_point_isolated
+    assert np.abs(out[:-2].astype(np.float64) - ref[:-1].astype(np.float64)).sum(1).max() < 1e-3
 
 
 # ------------------------------------------------------------------ uniform sampling
