@@ -689,7 +689,7 @@ typedef struct {
 int ope_coarse_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                           const ope_coarse_params *params, const uint64_t *seeds, ope_coarse_batch_result *out);
 /* Key points (ORIGINAL indices into that cloud), normals (n*3) and FPFH rows (n*33) the last ope_coarse_pose_batch (or
- * ope_prerejective_pose_batch, ope_final_pose_batch_prerejective: the front end is the same code) computed for `which` (-1 = the model, 0..n-1 = cluster), in key-point order; any output may be NULL.  *n_out = the key points; at
+ * ope_prerejective_pose_batch, ope_final_pose_batch_prerejective, ope_corr_sac_pose_batch, ope_final_pose_batch_correspondences: the front end is the same code) computed for `which` (-1 = the model, 0..n-1 = cluster), in key-point order; any output may be NULL.  *n_out = the key points; at
  * most cap rows are written.  Like ope_icp_correspondences for the single run. */
 int ope_coarse_batch_features(ope_ctx *ctx, int which, int32_t *key_idx, float *normals, float *fpfh33, size_t cap,
                               size_t *n_out);
@@ -820,6 +820,69 @@ int ope_prerejective_batch_hypotheses(const ope_ctx *ctx, int which, int32_t *sa
 int ope_final_pose_batch_prerejective(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                                       const ope_final_params *params, const ope_prerejective_params *prerejective, const uint64_t *seeds,
                                       ope_final_batch_result *out, int32_t *selected);
+
+/* ---------------- batched correspondence coarse stage ---------------- */
+/* estimateCoarsePose with the third aligner (ope_feature_correspondences + ope_corr_sac) of one model against n candidate clusters
+ * in one call: the front end of ope_coarse_pose_batch (key points, normals, FPFH of every cloud), then every active cluster's
+ * matches, threshold, fits, counts, inliers and pose together.  The model's key points are the source, a cluster's
+ * the target; every index is in KEY-POINT order (ope_coarse_batch_features reports the key points and rows). */
+enum { OPE_CORRSAC_OK = 0, OPE_CORRSAC_EMPTY_TARGET = 1, OPE_CORRSAC_FEW_TARGET_FEATURES = 2 };
+typedef struct {
+  float T_svd[16];            /* the coarse pose: TransformationEstimationSVD over the remaining matches; identity unless OK and matches > 0 */
+  float T_best[16];           /* the winning hypothesis; identity without a model */
+  double sample_dist_thresh;  /* as this cluster's draws used it */
+  uint64_t seed;              /* the stream it drew with; 0 unless status == OK */
+  int32_t matches;            /* model rows with a finite match in this cluster */
+  int32_t inliers;            /* remaining matches (= matches without a model) */
+  int32_t best, iterations, found;   /* as ope_corr_sac_result */
+  int32_t n_src_keys, n_tgt_keys, status;
+} ope_corr_sac_batch_result;   /* 176 bytes */
+typedef struct {
+  int64_t clusters;     /* n */
+  int64_t active;       /* clusters that reached the matcher (>= 10 key points) */
+  int64_t hypotheses;   /* scored, all clusters */
+  int64_t draw_lists;   /* sample lists drawn and uploaded: clusters with the same seed and the same matched model rows share one */
+  int64_t launches;     /* kernel launches, fills and copies to the device enqueued after the front end */
+  int64_t host_syncs;   /* of the whole call, the front end's one included */
+} ope_corr_sac_batch_stats;
+/* Synchronous, on the context's stream; n == 0 does nothing.  front gives key_leaf, normals_k, viewpoint and fpfh_radius
+ * (front->sacia is ignored; NULL: ope_coarse_default_params), params everything else (NULL: ope_corr_sac_default_params).
+ * Cluster i draws with seeds[i]; without seeds every cluster draws with params->seed (the reference's rejector is a new object per
+ * call and never reseeds).  Per cluster the result is what ope_feature_correspondences + ope_corr_sac give for the model's key
+ * points and FPFH rows against the cluster's: the same matches, distances, threshold, samples, transforms, counts, winner,
+ * iterations, inlier positions and T_svd, bit for bit.
+ * Status: an empty cluster OPE_CORRSAC_EMPTY_TARGET; fewer than 10 cluster key points OPE_CORRSAC_FEW_TARGET_FEATURES; both keep
+ * the identities, report seed 0 and leave the other clusters untouched.  Within OPE_CORRSAC_OK: model rows without a finite
+ * distance are dropped; fewer than 3 matches or no good sample: found = 0, best = -1, T_best the identity, T_svd over all matches;
+ * no match at all: both the identity.  Each cluster's result is byte-identical whatever else is in the batch and wherever it sits.
+ * 12 launches and copies after the front end and 4 synchronisations, whatever n, the hypotheses, the matches, the inliers or the
+ * iteration a loop stops at, as long as the packed samples (6 bytes each) of all draw lists fit the 32 MiB staging block; beyond
+ * it the upload goes in synchronising pieces, which ope_corr_sac_batch_last_stats counts.  When no cluster reaches the matcher
+ * (every one empty or below 10 key points) the call ends after the front end: 0 launches and 2 synchronisations.
+ * keep_hypotheses != 0 keeps every hypothesis of every active cluster for ope_corr_sac_batch_hypotheses (80 bytes each).
+ * OPE_EINVAL, nothing launched: a NULL ctx, model, clusters, a cluster or out; n > 65535; n * (max_iterations + 1) above 2^31 - 1;
+ * a parameter outside ope_corr_sac's ranges; key_leaf or fpfh_radius <= 0; normals_k outside 1..32; a cloud of more than
+ * OPE_COARSE_MAX_POINTS points or more than OPE_COARSE_MAX_KEYS key points; a model with fewer than 3 key points; a context with a
+ * communicator. */
+int ope_corr_sac_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                            const ope_coarse_params *front, const ope_corr_sac_params *params, const uint64_t *seeds,
+                            int keep_hypotheses, ope_corr_sac_batch_result *out);
+int ope_corr_sac_batch_last_stats(const ope_ctx *ctx, ope_corr_sac_batch_stats *out);
+/* Cluster `which` of the last ope_corr_sac_pose_batch.  Its matches in model key order (model key, cluster key, squared descriptor
+ * distance); the remaining matches (ascending positions in the match list and the pair of keys of each); with keep_hypotheses its
+ * hypotheses in drawing order (3 match positions, T column-major, count), otherwise *n_out = 0.  Any output may be NULL; at most cap
+ * entries are written, *n_out = how many there were (0 for a cluster that did not reach the matcher).  OPE_EINVAL: no such call
+ * yet, or `which` out of range. */
+int ope_corr_sac_batch_matches(const ope_ctx *ctx, int which, int32_t *src_key, int32_t *tgt_key, float *dist, size_t cap, size_t *n_out);
+int ope_corr_sac_batch_inliers(const ope_ctx *ctx, int which, int32_t *pos, int32_t *src_key, int32_t *tgt_key, size_t cap, size_t *n_out);
+int ope_corr_sac_batch_hypotheses(const ope_ctx *ctx, int which, int32_t *samples, float *T, int32_t *counts, size_t cap, size_t *n_out);
+/* ope_final_pose_batch with ope_corr_sac_pose_batch as its coarse stage (params->coarse is its front; corr_sac NULL: the defaults;
+ * seeds as above).  out[i].coarse: T = T_svd, best_error = 0 (the pipeline has no error metric), best_iteration = best, the key
+ * counts, status OPE_COARSE_OK for every cluster that reached the matcher, with or without a model (a counted coarse call);
+ * out[i].seed the seed used.  Everything after the coarse stage, *selected and the refusals are ope_final_pose_batch's. */
+int ope_final_pose_batch_correspondences(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                                         const ope_final_params *params, const ope_corr_sac_params *corr_sac, const uint64_t *seeds,
+                                         ope_final_batch_result *out, int32_t *selected);
 
 /* ---------------- tracking: the reference's later frames ---------------- */
 /* Every frame after the first (rosinterface.cpp:264-313): the centroid of each cluster and of the source (the model as the

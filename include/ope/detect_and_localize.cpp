@@ -44,10 +44,14 @@
 // pcl::SampleConsensusPrerejective block the reference keeps commented out (BuildModel poseestimator.cpp:90-108; 50 000 iterations on
 // the device), or its other commented block (:43-60, :111-113): FPFH matches, CorrespondenceRejectorSampleConsensus (10 000 iterations
 // at 0.08) and the SVD over the remaining matches.  With correspondences the candidate loop and the tracker always run one
-// estimateFinalPose at a time; with prerejective they do unless
+// estimateFinalPose at a time unless --correspondences-batch (below) is given; with prerejective they do unless
 //   ... --coarse-batch   (every mode but --depth, --track and --track-loop)
 // is given: PoseEstimator::setCoarseBatch(true), so --candidates (and --segment, --frame) with --coarse prerejective check all
 // clusters in one ope_final_pose_batch_prerejective call.  Without the flag every mode prints what it printed before.
+//   ... --correspondences-batch   (with --coarse correspondences; not with --track or --track-loop)
+// PoseEstimator::setCorrespondencesBatch(true): --candidates (and --segment, --frame) with --coarse correspondences check all clusters
+// in one ope_final_pose_batch_correspondences call.  Exit status 2 without --coarse correspondences.  --coarse-batch does not touch
+// this aligner: with it alone the loop still runs.
 //
 //   ... --recognise <train_dir>   (with --candidates, --candidates-loop, --segment or --frame)
 // Before the pose stage, ope::ObjectDetection::getObjectNames over every cluster in one call against the table under <train_dir>
@@ -131,6 +135,7 @@ static int track_main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--coarse") && i + 1 < argc) { if (!parse_coarse(argv[++i], coarse)) return 2; }
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--coarse-batch")) { std::fprintf(stderr, "--coarse-batch does not go with --track or --track-loop\n"); return 2; }
+    else if (!std::strcmp(argv[i], "--correspondences-batch")) { std::fprintf(stderr, "--correspondences-batch does not go with --track or --track-loop\n"); return 2; }
     else if (!std::strcmp(argv[i], "--time")) timed = true;
     else if (!frames.empty()) frames.back().push_back(argv[i]);
     else { std::fprintf(stderr, "unexpected argument %s\n", argv[i]); return 2; }
@@ -282,11 +287,13 @@ int main(int argc, char **argv) {
   std::string recognise;       // --recognise <train_dir>: name every cluster before the pose stage
   ope::PoseEstimator::CoarseMethod coarse = ope::PoseEstimator::COARSE_SAC_IA;   // --coarse
   bool coarse_batch = false;   // --coarse-batch
+  bool correspondences_batch = false;   // --correspondences-batch
   float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--coarse") && i + 1 < argc) { if (!parse_coarse(argv[++i], coarse)) return 2; }
     else if (!std::strcmp(argv[i], "--coarse-batch")) coarse_batch = true;
+    else if (!std::strcmp(argv[i], "--correspondences-batch")) correspondences_batch = true;
     else if (!std::strcmp(argv[i], "--recognise") && i + 1 < argc) recognise = argv[++i];
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--candidates")) candidates = 1;
@@ -298,6 +305,10 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--region-grow-rgb")) region_grow_rgb = true;
     else if (!std::strcmp(argv[i], "--limits") && i + 6 < argc) { for (int d = 0; d < 6; ++d) limits[d] = std::strtof(argv[++i], nullptr); }
     else files.push_back(argv[i]);
+  }
+  if (correspondences_batch && coarse != ope::PoseEstimator::COARSE_CORRESPONDENCES) {
+    std::fprintf(stderr, "--correspondences-batch goes with --coarse correspondences\n");
+    return 2;
   }
   if (except_plane && !frame) { std::fprintf(stderr, "--except-plane goes with --frame\n"); return 2; }
   if (region_grow && (!frame || except_plane)) { std::fprintf(stderr, "--region-grow goes with --frame and without --except-plane\n"); return 2; }
@@ -315,6 +326,7 @@ int main(int argc, char **argv) {
   poseEstimator.setSacIaSeed(seed);
   poseEstimator.setCoarseMethod(coarse);
   poseEstimator.setCoarseBatch(coarse_batch);
+  poseEstimator.setCorrespondencesBatch(correspondences_batch);
   poseEstimator.setUseSelfOccludedRejector(self_occluded);
   auto print_frame = [&](size_t k, const pcl::Matrix4f &pose, double fitnessScore, double alignedStrength) {
     std::printf("frame %zu fitness %.12g strength %.12g coarse_calls %d icp_iterations %d", k, fitnessScore, alignedStrength,

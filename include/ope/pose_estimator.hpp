@@ -42,9 +42,14 @@ class PoseEstimator {
   void setCoarseMethod(CoarseMethod m) { coarse_method_ = m; }
   CoarseMethod coarseMethod() const { return coarse_method_; }
   // estimateFinalPoseCandidates with COARSE_PREREJECTIVE: all clusters in one ope_final_pose_batch_prerejective call instead of one
-  // estimateFinalPose at a time (off by default; SAC-IA always batches; COARSE_CORRESPONDENCES has no batched form and runs the loop)
+  // estimateFinalPose at a time (off by default; SAC-IA always batches; COARSE_CORRESPONDENCES ignores this switch and has its own,
+  // setCorrespondencesBatch)
   void setCoarseBatch(bool on) { coarse_batch_ = on; }
   bool coarseBatch() const { return coarse_batch_; }
+  // estimateFinalPoseCandidates with COARSE_CORRESPONDENCES: all clusters in one ope_final_pose_batch_correspondences call instead of
+  // one estimateFinalPose at a time (off by default)
+  void setCorrespondencesBatch(bool on) { correspondences_batch_ = on; }
+  bool correspondencesBatch() const { return correspondences_batch_; }
   void setSacIaSeed(uint64_t seed) { sacia_seed_ = seed; }
   void setUseSelfOccludedRejector(bool on) { use_self_occluded_ = on; }
   // diagnostics of the last estimateFinalPose call
@@ -186,7 +191,8 @@ class PoseEstimator {
   //     for each cluster: source = a copy of the original model; if the cluster is not empty, estimateFinalPose(source, cluster);
   //                       stop once fitness < 1e-4 or strength > 0.4
   // p_sourceCloud is the original model on entry.  Runs ope_final_pose_batch (with COARSE_PREREJECTIVE and setCoarseBatch(true):
-  // ope_final_pose_batch_prerejective; without the switch that method runs the loop as written above) over all clusters, then leaves the estimator and
+  // ope_final_pose_batch_prerejective; with COARSE_CORRESPONDENCES and setCorrespondencesBatch(true): ope_final_pose_batch_correspondences;
+  // without their switches those methods run the loop as written above) over all clusters, then leaves the estimator and
   // p_sourceCloud exactly as that loop would: coarse calls counted only for clusters that reached SAC-IA, fitnessScoreFine /
   // alignedStrength from the last cluster (up to the selected one) that ran a fine ICP, alignedSource / cloudModel / firstTimePose
   // / the last* diagnostics as after the last non-empty cluster it processed; p_sourceCloud holds alignedSource, or the original
@@ -202,7 +208,8 @@ class PoseEstimator {
     int32_t sel = -1;
     // (ope_final_pose_batch's coarse stage is SAC-IA; the prerejective batch is opt-in: setCoarseBatch)
     bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() &&
-                   (coarse_method_ == COARSE_SAC_IA || (coarse_method_ == COARSE_PREREJECTIVE && coarse_batch_));
+                   (coarse_method_ == COARSE_SAC_IA || (coarse_method_ == COARSE_PREREJECTIVE && coarse_batch_) ||
+                    (coarse_method_ == COARSE_CORRESPONDENCES && correspondences_batch_));
     if (batched) {
       ope_ctx *ctx = compat::default_context();
       auto model = compat::upload(original, false);
@@ -225,6 +232,13 @@ class PoseEstimator {
         q.seed = sacia_seed_ + (uint64_t)coarse_calls_;   // the k-th coarse call draws with seed + k
         batched = ctx && model->h &&
                   ope_final_pose_batch_prerejective(ctx, model->h, hs.size(), hs.data(), &p, &q, nullptr, res.data(), &sel) == OPE_OK;
+      } else if (coarse_method_ == COARSE_CORRESPONDENCES) {
+        ope_corr_sac_params q;
+        ope_corr_sac_default_params(&q);   // (PCL's fixed seed: every rejector of the loop is a fresh object)
+        q.max_iterations = 10000;          // the literals of correspondencesCoarsePose (:55-56)
+        q.inlier_threshold = 0.08;
+        batched = ctx && model->h &&
+                  ope_final_pose_batch_correspondences(ctx, model->h, hs.size(), hs.data(), &p, &q, nullptr, res.data(), &sel) == OPE_OK;
       } else {
         batched = ctx && model->h && ope_final_pose_batch(ctx, model->h, hs.size(), hs.data(), &p, nullptr, res.data(), &sel) == OPE_OK;
       }
@@ -429,7 +443,7 @@ class PoseEstimator {
   uint64_t sacia_seed_ = 1;
   CoarseMethod coarse_method_ = COARSE_SAC_IA;
   int coarse_calls_ = 0;
-  bool coarse_batch_ = false;
+  bool coarse_batch_ = false, correspondences_batch_ = false;
   bool use_self_occluded_ = false;
   Matrix4f last_coarse_ = Matrix4f::Identity(), last_fine_ = Matrix4f::Identity(), last_rigid_ = Matrix4f::Identity();
   int last_icp_iterations_ = 0;

@@ -30,6 +30,8 @@ COARSE_OK, COARSE_EMPTY_TARGET, COARSE_FEW_TARGET_FEATURES = 0, 1, 2
 COARSE_MAX_POINTS, COARSE_MAX_KEYS = 65536, 4096
 # ope_prerejective_batch_result.status
 PREREJ_OK, PREREJ_EMPTY_TARGET, PREREJ_FEW_TARGET_FEATURES, PREREJ_NAN_FEATURES = 0, 1, 2, 3
+# ope_corr_sac_batch_result.status
+CORRSAC_OK, CORRSAC_EMPTY_TARGET, CORRSAC_FEW_TARGET_FEATURES = 0, 1, 2
 # ope_final_batch_result.status
 FINAL_OK, FINAL_EMPTY_TARGET, FINAL_FEW_TARGET_FEATURES, FINAL_FEW_FINE_POINTS = 0, 1, 2, 3
 # ope_track_gate_result.branch; ope_track_result.coarse_status when the coarse stage was skipped
@@ -183,6 +185,34 @@ class CorrSacStats(C.Structure):
         ("launches", C.c_int64),
         ("host_syncs", C.c_int64),
         ("sample_dist_thresh", C.c_double),
+    ]
+
+
+class CorrSacBatchResult(C.Structure):
+    _fields_ = [
+        ("T_svd", C.c_float * 16),
+        ("T_best", C.c_float * 16),
+        ("sample_dist_thresh", C.c_double),
+        ("seed", C.c_uint64),
+        ("matches", C.c_int32),
+        ("inliers", C.c_int32),
+        ("best", C.c_int32),
+        ("iterations", C.c_int32),
+        ("found", C.c_int32),
+        ("n_src_keys", C.c_int32),
+        ("n_tgt_keys", C.c_int32),
+        ("status", C.c_int32),
+    ]
+
+
+class CorrSacBatchStats(C.Structure):
+    _fields_ = [
+        ("clusters", C.c_int64),
+        ("active", C.c_int64),
+        ("hypotheses", C.c_int64),
+        ("draw_lists", C.c_int64),
+        ("launches", C.c_int64),
+        ("host_syncs", C.c_int64),
     ]
 
 
@@ -631,6 +661,14 @@ ABI = [
                                                     C.POINTER(C.c_size_t)]),
     ("ope_final_pose_batch_prerejective", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(FinalParams), C.POINTER(PrerejectiveParams),
                                                     C.POINTER(C.c_uint64), C.POINTER(FinalBatchResult), C.POINTER(C.c_int32)]),
+    ("ope_corr_sac_pose_batch", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(CoarseParams), C.POINTER(CorrSacParams),
+                                          C.POINTER(C.c_uint64), C.c_int, C.POINTER(CorrSacBatchResult)]),
+    ("ope_corr_sac_batch_last_stats", C.c_int, [_vp, C.POINTER(CorrSacBatchStats)]),
+    ("ope_corr_sac_batch_matches", C.c_int, [_vp, C.c_int, _ip, _ip, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_corr_sac_batch_inliers", C.c_int, [_vp, C.c_int, _ip, _ip, _ip, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_corr_sac_batch_hypotheses", C.c_int, [_vp, C.c_int, _ip, _fp, _ip, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ope_final_pose_batch_correspondences", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(FinalParams), C.POINTER(CorrSacParams),
+                                                       C.POINTER(C.c_uint64), C.POINTER(FinalBatchResult), C.POINTER(C.c_int32)]),
     ("ope_track_default_params", None, [C.POINTER(TrackParams)]),
     ("ope_track_gate", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(TrackParams), C.POINTER(TrackGateResult),
                                   C.POINTER(TrackCentroid)]),
@@ -838,6 +876,23 @@ class PrerejectiveBatchOut:
     status: int            # PREREJ_OK, PREREJ_EMPTY_TARGET, PREREJ_FEW_TARGET_FEATURES or PREREJ_NAN_FEATURES
     seed: int              # the stream the cluster drew with (0 unless PREREJ_OK)
     raw: bytes             # the bytes of its ope_prerejective_batch_result
+
+
+@dataclass
+class CorrSacBatchOut:
+    T_svd: np.ndarray      # (4,4) math layout, float32: the coarse pose; the identity unless CORRSAC_OK and matches > 0
+    T_best: np.ndarray     # the winning hypothesis; the identity without a model
+    sample_dist_thresh: float
+    seed: int              # the stream the cluster drew with (0 unless CORRSAC_OK)
+    matches: int           # model rows with a finite match in this cluster
+    inliers: int           # remaining matches
+    best: int              # the winning hypothesis in drawing order, -1 without a model
+    iterations: int
+    found: bool
+    n_src_keys: int        # model key points
+    n_tgt_keys: int        # this cluster's key points
+    status: int            # CORRSAC_OK, CORRSAC_EMPTY_TARGET or CORRSAC_FEW_TARGET_FEATURES
+    raw: bytes             # the bytes of its ope_corr_sac_batch_result
 
 
 @dataclass
@@ -1229,6 +1284,69 @@ class Context:
         out = (FinalBatchResult * max(n, 1))()
         sel = C.c_int32(-1)
         self._chk(lib().ope_final_pose_batch_prerejective(self.h, model.h, n, hc, C.byref(p), C.byref(q), sd, out, C.byref(sel)))
+        return [_final_out(o) for o in out[:n]], sel.value
+
+    def corr_sac_pose_batch(self, model: "Cloud", clusters, front: CoarseParams | None = None, params: CorrSacParams | None = None,
+                            seeds=None, keep_hypotheses: bool = False) -> list:
+        """ope_corr_sac_pose_batch: estimateCoarsePose with the correspondence aligner (feature matches, RANSAC rejector, SVD over
+        what remains) of model against every cluster in one call; one CorrSacBatchOut each.  front gives key_leaf, normals_k,
+        viewpoint, fpfh_radius; seeds[i] (or params.seed for every cluster without seeds) is cluster i's stream."""
+        n, hc, sd = self._batch_args(clusters, seeds)
+        f = front or default_coarse_params()
+        p = params or default_corr_sac_params()
+        out = (CorrSacBatchResult * max(n, 1))()
+        self._chk(lib().ope_corr_sac_pose_batch(self.h, model.h, n, hc, C.byref(f), C.byref(p), sd, int(bool(keep_hypotheses)), out))
+        return [CorrSacBatchOut(from_colmajor(np.array(o.T_svd, np.float32)), from_colmajor(np.array(o.T_best, np.float32)), o.sample_dist_thresh,
+                                o.seed, o.matches, o.inliers, o.best, o.iterations, bool(o.found), o.n_src_keys, o.n_tgt_keys, o.status, bytes(o))
+                for o in out[:n]]
+
+    def corr_sac_batch_stats(self) -> dict:
+        """ope_corr_sac_batch_last_stats: clusters, active, hypotheses, draw_lists, launches, host_syncs."""
+        s = CorrSacBatchStats()
+        self._chk(lib().ope_corr_sac_batch_last_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in CorrSacBatchStats._fields_}
+
+    def corr_sac_batch_matches(self, which: int):
+        """ope_corr_sac_batch_matches of cluster `which`: (model key, cluster key, squared descriptor distance), in model key order."""
+        n = C.c_size_t(0)
+        self._chk(lib().ope_corr_sac_batch_matches(self.h, which, None, None, None, 0, C.byref(n)))
+        m = n.value
+        si, ti, d = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.float32)
+        self._chk(lib().ope_corr_sac_batch_matches(self.h, which, _p(si, _ip), _p(ti, _ip), _p(d, _fp), m, C.byref(n)))
+        return si[:m].copy(), ti[:m].copy(), d[:m].copy()
+
+    def corr_sac_batch_inliers(self, which: int):
+        """ope_corr_sac_batch_inliers of cluster `which`: (positions in its match list, ascending; model key; cluster key) of the
+        matches that remain."""
+        n = C.c_size_t(0)
+        self._chk(lib().ope_corr_sac_batch_inliers(self.h, which, None, None, None, 0, C.byref(n)))
+        m = n.value
+        pos, si, ti = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32)
+        self._chk(lib().ope_corr_sac_batch_inliers(self.h, which, _p(pos, _ip), _p(si, _ip), _p(ti, _ip), m, C.byref(n)))
+        return pos[:m].copy(), si[:m].copy(), ti[:m].copy()
+
+    def corr_sac_batch_hypotheses(self, which: int) -> dict:
+        """ope_corr_sac_batch_hypotheses of cluster `which` (after keep_hypotheses=True; empty otherwise), in the shape of
+        corr_sac_hypotheses: samples (h, 3) match positions, T (h, 4, 4) math layout, counts (h,)."""
+        n = C.c_size_t(0)
+        self._chk(lib().ope_corr_sac_batch_hypotheses(self.h, which, None, None, None, 0, C.byref(n)))
+        h = n.value
+        smp = np.zeros((max(h, 1), 3), np.int32)
+        T = np.zeros((max(h, 1), 16), np.float32)
+        cnt = np.zeros(max(h, 1), np.int32)
+        self._chk(lib().ope_corr_sac_batch_hypotheses(self.h, which, _p(smp, _ip), _p(T, _fp), _p(cnt, _ip), h, C.byref(n)))
+        return dict(samples=smp[:h].copy(), T=T[:h].reshape(h, 4, 4).transpose(0, 2, 1).copy(), counts=cnt[:h].copy())
+
+    def final_pose_batch_correspondences(self, model: "Cloud", clusters, params: FinalParams | None = None,
+                                         corr_sac: CorrSacParams | None = None, seeds=None):
+        """ope_final_pose_batch_correspondences: final_pose_batch with the correspondence aligner as its coarse stage.
+        Returns ([FinalOut per cluster], selected)."""
+        n, hc, sd = self._batch_args(clusters, seeds)
+        p = params or default_final_params()
+        q = corr_sac or default_corr_sac_params()
+        out = (FinalBatchResult * max(n, 1))()
+        sel = C.c_int32(-1)
+        self._chk(lib().ope_final_pose_batch_correspondences(self.h, model.h, n, hc, C.byref(p), C.byref(q), sd, out, C.byref(sel)))
         return [_final_out(o) for o in out[:n]], sel.value
 
     def _cluster_args(self, cloud, tolerance, min_size, max_size):

@@ -101,6 +101,11 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
                                  const ope_coarse_params *front, const ope_prerejective_params *params, const uint64_t *seeds,
                                  bool seed_by_rank, int keep_hypotheses, ope_prerejective_batch_result *out);
 
+// corr_sac_batch.hip: ope_corr_sac_pose_batch; who: the entry point its errors name
+int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                             const ope_coarse_params *front, const ope_corr_sac_params *params, const uint64_t *seeds, int keep_hypotheses,
+                             ope_corr_sac_batch_result *out);
+
 // final_batch.hip: ope_final_pose_batch's refusals before anything is launched, and its fine preparation (steps 1-4: move,
 // sample, normals, NaN-normal drop and upload order, target trees) of n (model, cluster) pairs.  Segment s < n is the model moved
 // by coarse[s].T when coarse[s].status == OPE_COARSE_OK (as it is otherwise), segment n + i cluster i; per segment its fine

@@ -22,18 +22,13 @@
 //      ope_rigid_transform_svd fit them; positions and pose come back (third synchronisation).
 // No launch count and no synchronisation count depends on the hypotheses, the matches, the iteration RANSAC stops at or the inliers.
 #include <algorithm>
-#include <cfloat>
-#include <climits>
 #include <cmath>
 #include <cstring>
-#include <random>
 #include <string>
 #include <vector>
 
 #include "coarse_stages.hpp"
-#include "feature_math.hpp"
-#include "icp_update.hpp"
-#include "prerejective_math.hpp"
+#include "corr_sac_math.hpp"
 
 namespace ope {
 
@@ -41,13 +36,6 @@ void launch_pairs_svd(hipStream_t, const float *, const float *, uint32_t, doubl
 
 namespace {
 
-constexpr int kCsBlock = 256;            // hypotheses of one count block (one per lane)
-constexpr int kCsTile = 64;              // matched pairs of one LDS tile: 2 x 64 x 16 B = 2 KB
-constexpr int kCsMaxMatches = OPE_COARSE_MAX_KEYS;
-constexpr int kCsPackItems = kCsMaxMatches / 1024;   // matches per lane of the one-block compaction
-constexpr int kCsSumChunk = 2048;        // points the threshold kernel stages at a time (32 KB)
-constexpr int kCsMaxSampleChecks = 1000; // SampleConsensusModel::max_sample_checks_
-static_assert(kCsPackItems * 1024 == kCsMaxMatches, "the compaction block covers every match");
 static_assert(12ull * ((size_t)kPrMaxIterations + 1) <= kStageChunk, "the samples go up in one staged copy");
 
 // the match of one source row per block: the nearest target row (feature_knn_block, k = 1) and its squared distance, the same
@@ -56,16 +44,7 @@ __global__ __launch_bounds__(256) void cs_match_kernel(const float *__restrict__
                                                         int32_t *__restrict__ out_idx, float *__restrict__ out_d) {
   const float *q = src_feat + (size_t)blockIdx.x * 33;
   feature_knn_block(tgt_feat, nt, q, 1, out_idx + blockIdx.x);
-  if (threadIdx.x == 0) {
-    const int32_t t = out_idx[blockIdx.x];
-    float d = INFINITY;
-    if (t >= 0) {
-      const float *f = tgt_feat + (size_t)t * 33;
-      d = 0.f;
-      for (int c = 0; c < 33; ++c) { const float u = q[c] - f[c]; d += u * u; }
-    }
-    out_d[blockIdx.x] = d;
-  }
+  if (threadIdx.x == 0) out_d[blockIdx.x] = cs_row_dist(tgt_feat, q, out_idx[blockIdx.x]);
 }
 
 // 1a. original order
@@ -88,57 +67,9 @@ __global__ __launch_bounds__(kCsBlock) void cs_gather_kernel(const float4 *__res
   pt[i] = make_float4(t.x, t.y, t.z, 0.f);
 }
 
-// 2. computeSampleDistanceThreshold: the nine running sums of computeMeanAndCovarianceMatrix in match order, lane j the j-th (xx xy xz
-// yy yz zz x y z; the last three multiply by 1, which is exact), then pcl::eigen33 (mat, evals): the roots of the matrix over its
-// largest entry, times it; t = ((sqrt l0 + sqrt l1) + sqrt l2) in float, over 3.0 and squared in double.
+// 2. computeSampleDistanceThreshold (cs_thresh_block)
 __global__ __launch_bounds__(kCsBlock) void cs_thresh_kernel(const float4 *__restrict__ ps, uint32_t n, double *__restrict__ out_thr) {
-  __shared__ float4 s_p[kCsSumChunk];
-  __shared__ float s_acc[9];
-  const int j = threadIdx.x;
-  const int ia = j < 3 ? 0 : j < 5 ? 1 : j < 6 ? 2 : j - 6;          // first factor: x x x y y z | x y z
-  const int ib = j < 3 ? j : j < 5 ? j - 2 : j < 6 ? 2 : 3;           // second factor: x y z y z z | 1 1 1
-  float acc = 0.f;
-  for (uint32_t base = 0; base < n; base += kCsSumChunk) {
-    const uint32_t m = min((uint32_t)kCsSumChunk, n - base);
-    __syncthreads();
-    for (uint32_t k = threadIdx.x; k < m; k += kCsBlock) {
-      const float4 p = ps[base + k];
-      s_p[k] = make_float4(p.x, p.y, p.z, 1.f);
-    }
-    __syncthreads();
-    if (j < 9)
-      for (uint32_t k = 0; k < m; ++k) {
-        const float *p = reinterpret_cast<const float *>(&s_p[k]);
-        acc = __fadd_rn(acc, __fmul_rn(p[ia], p[ib]));
-      }
-  }
-  if (j < 9) s_acc[j] = acc;
-  __syncthreads();
-  if (j != 0) return;
-  float accu[9];
-  const float fc = (float)n;
-#pragma unroll
-  for (int a = 0; a < 9; ++a) accu[a] = __fdiv_rn(s_acc[a], fc);
-  float cov[9];
-  cov[0] = __fsub_rn(accu[0], __fmul_rn(accu[6], accu[6]));
-  cov[1] = __fsub_rn(accu[1], __fmul_rn(accu[6], accu[7]));
-  cov[2] = __fsub_rn(accu[2], __fmul_rn(accu[6], accu[8]));
-  cov[4] = __fsub_rn(accu[3], __fmul_rn(accu[7], accu[7]));
-  cov[5] = __fsub_rn(accu[4], __fmul_rn(accu[7], accu[8]));
-  cov[8] = __fsub_rn(accu[5], __fmul_rn(accu[8], accu[8]));
-  cov[3] = cov[1]; cov[6] = cov[2]; cov[7] = cov[5];
-  float scale = 0.f;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) scale = fmaxf(scale, fabsf(cov[i]));
-  if (scale <= 1.17549435e-38f) scale = 1.0f;
-  float sm[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) sm[i] = __fdiv_rn(cov[i], scale);
-  float roots[3];
-  compute_roots(sm, roots);
-  const float r0 = __fsqrt_rn(__fmul_rn(roots[0], scale)), r1 = __fsqrt_rn(__fmul_rn(roots[1], scale)), r2 = __fsqrt_rn(__fmul_rn(roots[2], scale));
-  const double t = (double)__fadd_rn(__fadd_rn(r0, r1), r2) / 3.0;
-  out_thr[0] = t * t;
+  cs_thresh_block(ps, n, out_thr);
 }
 
 // 4. computeModelCoefficients: one lane per hypothesis, Umeyama without scaling over its three pairs
@@ -150,84 +81,28 @@ __global__ __launch_bounds__(64) void cs_fit_kernel(const float4 *__restrict__ p
   umeyama_fit(3, [&](int i, float4 &p, float4 &q) { p = ps[sa[i]]; q = pt[sa[i]]; }, T_out + 16 * (size_t)h, rows_out + 12 * (size_t)h);
 }
 
-// a match is within the distance iff |T s - t|^2 < thr2: the point moved by xform_row, the squared norm (dx dx + dy dy) + dz dz in
-// float, widened
-__device__ __forceinline__ bool cs_within(const float F[12], const float4 s, const float4 t, double thr2) {
-  const float dx = __fsub_rn(xform_row(F + 0, s.x, s.y, s.z), t.x);
-  const float dy = __fsub_rn(xform_row(F + 4, s.x, s.y, s.z), t.y);
-  const float dz = __fsub_rn(xform_row(F + 8, s.x, s.y, s.z), t.z);
-  const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-  return (double)d2 < thr2;
-}
-
 // 5. countWithinDistance of every hypothesis: block (x, y) = hypotheses [256 x, 256 x + 256) against the tiles y, y + gridDim.y, ...
-// of the matches.  A tile is staged once per block (a lane of the first wave loads one pair) and read by every lane at the same
-// address: a broadcast, no bank conflict.  Counts are integers: the atomics' order does not show.
+// of the matches (cs_count_tiles).  Counts are integers: the atomics' order does not show.
 __global__ __launch_bounds__(kCsBlock) void cs_count_kernel(const float4 *__restrict__ ps, const float4 *__restrict__ pt, uint32_t n,
                                                             const float *__restrict__ rows, uint32_t H, double thr2,
                                                             uint32_t *__restrict__ counts) {
-  __shared__ float4 s_s[kCsTile], s_t[kCsTile];
   const uint32_t h = blockIdx.x * kCsBlock + threadIdx.x;
   const bool live = h < H;
   float F[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) F[i] = live ? rows[12 * (size_t)h + i] : 0.f;
-  uint32_t cnt = 0;
-  for (uint32_t base = blockIdx.y * kCsTile; base < n; base += gridDim.y * kCsTile) {
-    const uint32_t m = min((uint32_t)kCsTile, n - base);
-    __syncthreads();
-    if (threadIdx.x < m) { s_s[threadIdx.x] = ps[base + threadIdx.x]; s_t[threadIdx.x] = pt[base + threadIdx.x]; }
-    __syncthreads();
-#pragma unroll 4
-    for (uint32_t k = 0; k < m; ++k) cnt += cs_within(F, s_s[k], s_t[k], thr2) ? 1u : 0u;
-  }
+  const uint32_t cnt = cs_count_tiles(ps, pt, n, F, thr2, blockIdx.y, gridDim.y);
   if (live && cnt) atomicAdd(counts + h, cnt);
 }
 
-// 7. selectWithinDistance of the winner (all != 0: every match), compacted in match order by one block of 1024 lanes: lane l owns
-// the matches [kCsPackItems l, kCsPackItems l + kCsPackItems).  Positions, and the pairs packed as xyz for the pairs-sum kernel.
+// 7. selectWithinDistance of the winner (all != 0: every match), compacted in match order by one block of 1024 lanes (cs_pack_block)
 __global__ __launch_bounds__(1024) void cs_pack_kernel(const float4 *__restrict__ ps, const float4 *__restrict__ pt, uint32_t n,
                                                         const float *__restrict__ F_in, double thr2, int all, int32_t *__restrict__ pos,
                                                         float *__restrict__ sx, float *__restrict__ tx, uint32_t *__restrict__ d_cnt) {
-  __shared__ uint32_t s_wave[16];
   float F[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i) F[i] = F_in[i];
-  bool in[kCsPackItems];
-  uint32_t mine = 0;
-#pragma unroll
-  for (int a = 0; a < kCsPackItems; ++a) {
-    const uint32_t i = threadIdx.x * kCsPackItems + a;
-    in[a] = i < n && (all || cs_within(F, ps[i], pt[i], thr2));
-    mine += in[a] ? 1u : 0u;
-  }
-  // exclusive prefix over the block: within the wave by shuffles, the sixteen waves through LDS
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t inc = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t v = __shfl_up(inc, off, 64);
-    if (lane >= (uint32_t)off) inc += v;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0, total = 0;
-  for (uint32_t w = 0; w < 16; ++w) {
-    if (w < wave) before += s_wave[w];
-    total += s_wave[w];
-  }
-  uint32_t slot = before + inc - mine;
-#pragma unroll
-  for (int a = 0; a < kCsPackItems; ++a) {
-    if (!in[a]) continue;
-    const uint32_t i = threadIdx.x * kCsPackItems + a;
-    const float4 s = ps[i], t = pt[i];
-    pos[slot] = (int32_t)i;
-    sx[3 * slot] = s.x; sx[3 * slot + 1] = s.y; sx[3 * slot + 2] = s.z;
-    tx[3 * slot] = t.x; tx[3 * slot + 1] = t.y; tx[3 * slot + 2] = t.z;
-    ++slot;
-  }
-  if (threadIdx.x == 0) *d_cnt = total;
+  cs_pack_block(ps, pt, n, F, thr2, all, pos, sx, tx, d_cnt);
 }
 
 unsigned grid_of(size_t n, int block = kCsBlock) { return (unsigned)std::max<size_t>((n + block - 1) / block, 1); }
@@ -249,32 +124,6 @@ hipError_t upload_block(hipStream_t st, void *dst, const void *src, size_t bytes
   if (bytes > cap) return hipErrorInvalidValue;
   std::memcpy(blk, src, bytes);
   return hipMemcpyAsync(dst, blk, bytes, hipMemcpyHostToDevice, st);
-}
-
-inline float edge_d2_host(const float4 &a, const float4 &b) {
-  const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-  return (dx * dx + dy * dy) + dz * dz;   // (this file is compiled without contraction)
-}
-
-// getSamples for the H consecutive iterations RANSAC can run: a persistent shuffled_indices_ over all matches, drawIndexSample's three
-// swaps with rnd() = engine() >> 1, up to 1000 redraws while isSampleGood fails (an edge of the source triangle not above the
-// threshold).  The list ends where getSamples would hand back an empty selection.
-void cs_draw(const float4 *ps, int n, double thr, uint32_t seed, size_t H, std::vector<int32_t> &samp) {
-  std::mt19937 eng(seed);
-  std::vector<int32_t> shuf((size_t)n);
-  for (int i = 0; i < n; ++i) shuf[(size_t)i] = i;
-  samp.clear();
-  samp.reserve(3 * H);
-  for (size_t h = 0; h < H; ++h) {
-    bool good = false;
-    for (int check = 0; check < kCsMaxSampleChecks && !good; ++check) {
-      for (int i = 0; i < 3; ++i) std::swap(shuf[(size_t)i], shuf[(size_t)i + (size_t)((eng() >> 1) % (uint32_t)(n - i))]);
-      const float4 &p0 = ps[shuf[0]], &p1 = ps[shuf[1]], &p2 = ps[shuf[2]];
-      good = (double)edge_d2_host(p1, p0) > thr && (double)edge_d2_host(p2, p0) > thr && (double)edge_d2_host(p2, p1) > thr;
-    }
-    if (!good) return;
-    samp.insert(samp.end(), shuf.begin(), shuf.begin() + 3);
-  }
 }
 
 }  // namespace
@@ -484,25 +333,8 @@ int ope_corr_sac(ope_ctx *ctx, const ope_cloud *src, const ope_cloud *tgt, const
   // ---- 6. RandomSampleConsensus::computeModel, replayed: the draws did not depend on the counts, so hypothesis `it` is the one
   // iteration `it` would have drawn
   int best = -1;
-  long long best_cnt = -(long long)INT_MAX;
-  double k = 1.0;
-  int it = 0;
-  const double log_probability = std::log(1.0 - p.probability);
-  while ((double)it < k) {
-    if ((uint32_t)it >= H) break;   // an empty selection
-    const long long c = (long long)cnts[(size_t)it];
-    if (c > best_cnt) {
-      best_cnt = c;
-      best = it;
-      const double w = (double)best_cnt / (double)n;
-      double p_no_outliers = 1.0 - std::pow(w, 3.0);
-      p_no_outliers = std::max(DBL_EPSILON, p_no_outliers);
-      p_no_outliers = std::min(1.0 - DBL_EPSILON, p_no_outliers);
-      k = log_probability / std::log(p_no_outliers);
-    }
-    ++it;
-    if (it > p.max_iterations) break;
-  }
+  long long best_cnt = 0;
+  const int it = cs_replay(cnts.data(), H, n, p.max_iterations, p.probability, &best, &best_cnt);
   St.iterations = it;
   out->iterations = it;
   out->best = best;

@@ -587,6 +587,43 @@ int ope_final_pose_batch_prerejective(ope_ctx *ctx, const ope_cloud *model, size
   return final_batch_finish(ctx, who, model, n, clusters, p, coarse.data(), seed_used.data(), out, selected);
 }
 
+int ope_final_pose_batch_correspondences(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
+                                         const ope_final_params *params, const ope_corr_sac_params *corr_sac, const uint64_t *seeds,
+                                         ope_final_batch_result *out, int32_t *selected) {
+  static const char *who = "ope_final_pose_batch_correspondences: ";
+  if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_final_pose_batch_correspondences: bad argument");
+  if (selected) *selected = -1;
+  ctx->final_off.clear();
+  if (n == 0) return OPE_OK;
+  if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
+  if (n > 65535) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 65535 clusters (one grid row each)");
+  ope_final_params p;
+  ope_final_default_params(&p);
+  if (params) p = *params;
+  { const int rc = final_batch_check(ctx, n, clusters, p); if (rc != OPE_OK) return rc; }
+
+  // ---- 0. the coarse stage: the correspondence aligner; every rejector of the reference's loop draws from the same seed
+  std::vector<ope_corr_sac_batch_result> cs(n);
+  {
+    const int rc = corr_sac_pose_batch_impl(ctx, who, model, n, clusters, &p.coarse, corr_sac, seeds, 0, cs.data());
+    if (rc != OPE_OK) return rc;
+  }
+  std::vector<ope_coarse_batch_result> coarse(n);
+  std::vector<uint64_t> seed_used(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    ope_coarse_batch_result &c = coarse[i];
+    std::memcpy(c.T, cs[i].T_svd, sizeof c.T);   // (the identity without a match: an identity pose and a counted coarse call)
+    c.best_error = 0.0;                          // (the pipeline has no error metric)
+    c.best_iteration = cs[i].best;
+    c.n_src_keys = cs[i].n_src_keys;
+    c.n_tgt_keys = cs[i].n_tgt_keys;
+    c.status = cs[i].status == OPE_CORRSAC_OK ? OPE_COARSE_OK
+               : cs[i].status == OPE_CORRSAC_EMPTY_TARGET ? OPE_COARSE_EMPTY_TARGET : OPE_COARSE_FEW_TARGET_FEATURES;
+    seed_used[i] = cs[i].seed;
+  }
+  return final_batch_finish(ctx, who, model, n, clusters, p, coarse.data(), seed_used.data(), out, selected);
+}
+
 int ope_final_batch_inputs(ope_ctx *ctx, int which, int side, float *xyz, float *normals, size_t cap, size_t *n_out) {
   if (!ctx || !n_out || (side != 0 && side != 1)) return set_err(ctx, OPE_EINVAL, "ope_final_batch_inputs: bad argument");
   *n_out = 0;

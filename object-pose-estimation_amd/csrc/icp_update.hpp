@@ -405,4 +405,54 @@ __device__ __forceinline__ void state_to_lds(IcpState *dst, const IcpState *src)
     reinterpret_cast<uint32_t *>(dst)[i] = reinterpret_cast<const uint32_t *>(src)[i];
 }
 
+// Stand-alone TransformationEstimationSVD on n given pairs (packed xyz): block b of nb (256 lanes) adds the 17 sums about the first
+// source point over the pairs b * 256 + lane, + nb * 256, ...; partials [17][nb].  The single launch (pairs_sums_kernel) and the
+// segmented one of the batched correspondence aligner run these same instructions.
+__device__ __forceinline__ void pairs_sums_block(const float *__restrict__ src, const float *__restrict__ tgt, uint32_t n, uint32_t b,
+                                                 uint32_t nb, double *__restrict__ partials) {
+  __shared__ double s_red[4][kNumSums];
+  const float px = src[0], py = src[1], pz = src[2];
+  double acc[kNumSums];
+#pragma unroll
+  for (int k = 0; k < kNumSums; ++k) acc[k] = 0.0;
+  for (uint32_t i = b * 256 + threadIdx.x; i < n; i += nb * 256) {
+    const double sx = (double)src[3 * i] - px, sy = (double)src[3 * i + 1] - py, sz = (double)src[3 * i + 2] - pz;
+    const double tx = (double)tgt[3 * i] - px, ty = (double)tgt[3 * i + 1] - py, tz = (double)tgt[3 * i + 2] - pz;
+    acc[0] += 1.0;
+    acc[1] += sx; acc[2] += sy; acc[3] += sz;
+    acc[4] += tx; acc[5] += ty; acc[6] += tz;
+    acc[7] += tx * sx; acc[8] += tx * sy; acc[9] += tx * sz;
+    acc[10] += ty * sx; acc[11] += ty * sy; acc[12] += ty * sz;
+    acc[13] += tz * sx; acc[14] += tz * sy; acc[15] += tz * sz;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kNumSums; ++k) {
+    const double v = wave_sum(acc[k]);
+    if (lane == 0) s_red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kNumSums)
+    partials[threadIdx.x * nb + b] = s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x];
+}
+
+// ... and the lane that adds the partials in block order and fits Umeyama (one wave)
+__device__ __forceinline__ void pairs_umeyama_block(const double *__restrict__ partials, int nblocks, const float *__restrict__ src,
+                                                    float *__restrict__ out_T) {
+  __shared__ double s_S[kNumSums];
+  if (threadIdx.x < kNumSums) {
+    double v = 0.0;
+    for (int b = 0; b < nblocks; ++b) v += partials[threadIdx.x * nblocks + b];
+    s_S[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double pivot[3] = {(double)src[0], (double)src[1], (double)src[2]};
+    double T[16];
+    umeyama_from_sums(s_S, pivot, T);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) out_T[i] = (float)T[i];
+  }
+}
+
 }  // namespace ope

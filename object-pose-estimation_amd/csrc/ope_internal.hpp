@@ -301,6 +301,13 @@ struct ope_ctx {
   std::vector<int32_t> corr_sac_samples, corr_sac_counts;
   std::vector<float> corr_sac_T;
 
+  // the last ope_corr_sac_pose_batch (corr_sac_batch.hip): what it did; per cluster (n + 1 offsets each) its matches, its remaining
+  // matches' positions and, with keep_hypotheses, its hypotheses (T, counts) and the draw list they came from (-1: none)
+  ope_corr_sac_batch_stats csb_stats{};
+  std::vector<size_t> csb_match_off, csb_inl_off, csb_hyp_off, csb_list_off;
+  std::vector<int32_t> csb_msrc, csb_mtgt, csb_inl_pos, csb_counts, csb_list_of, csb_list_samp;
+  std::vector<float> csb_mdist, csb_T;
+
   // the last ope_prerejective_pose_batch (prerejective_batch.hip): what it did and, with keep_hypotheses, its iterations: per cluster
   // the first kept iteration (pb_hyp_off, n + 1; samples / targets / survived are packed from there) and the first survivor
   // (pb_surv_off, n + 1; iteration, T, inliers, error of the survivors are packed from there)
