@@ -394,6 +394,57 @@ int ope_icp_last_incremental(ope_ctx *ctx, float out_T[16]);
 enum { OPE_REJ_SURFACE_NORMAL = 0, OPE_REJ_SELF_OCCLUDED = 1 };
 int ope_reject_pairs(ope_ctx *ctx, int kind, const float *a, const float *b, size_t n, double threshold, unsigned char *keep);
 
+/* ---- Global correspondence rejectors (global_rejectors.hip): the three of estimateFinePose's list (poseestimator.cpp:250-292,
+ * blocks 3.1, 3.2, 3.5) that need ALL of an iteration's pairs before they can decide about one, as PCL 1.7.2 applies them without
+ * a data container.  d_i = a pair's `distance` field (squared distance, fp32), m = the pairs that reach the rejector; every
+ * comparison is made in fp64 on the widened value.  tests/global_rejectors_ref.py is the restatement the kernels are pinned to.
+ *   OPE_GREJ_MEDIAN_DISTANCE  (correspondence_rejection_median_distance.cpp) median = the element at position m / 2 of the
+ *       ascending d_i; keep iff d_i <= median * factor.  m = 0 keeps nothing (threshold NaN).
+ *   OPE_GREJ_ONE_TO_ONE       (correspondence_rejection_one_to_one.cpp) among the pairs with one index_match keep the smallest
+ *       d_i, on equal d_i the smallest index_query (PCL's std::sort leaves the tie open).  Stand-alone, pairs with
+ *       index_match < 0 are dropped.  The pairs STAY IN QUERY ORDER: PCL's output is in match order, nothing downstream reads it.
+ *   OPE_GREJ_VAR_TRIMMED      (correspondence_rejection_var_trimmed.cpp, lambda 3) s = the d_i ascending, lo = floor(min_ratio m),
+ *       hi = floor(max_ratio m), L = s[0] + ... + s[lo-1]; for j in [lo, hi): FRMS_j = (1 / r^3)^2 (1 / (j+1)) (s[j] + L) with
+ *       r = (j+1) / m (PCL's expression as written: L is the head only); best = the first j of the smallest FRMS;
+ *       ratio = float(best) / float(m) (fp32); idx = int(double(m) * double(ratio)); keep iff d_i < s[idx] (strict).
+ *       hi <= lo (PCL: undefined): every pair is kept, ratio = 1, threshold NaN.
+ * A list applies its rejectors in order, each over the survivors of the one before.
+ *
+ * Inside the ICP loop the list is context state (like the fixed correspondences): it runs after the search kernel with its fused
+ * pointwise rejectors and before the min_correspondences test (icp_mod.hpp:195-240); the update step reads the 17 sums of the
+ * survivors alone (count, cross-covariance, sum of d^2 -> the MSE of the convergence rule), and n_corr, align_strength and
+ * ope_icp_correspondences report the survivors.  A run with a list launches its update in line, adds the survivor sums in a fixed
+ * order (bit-reproducible whatever deterministic_sums says), synchronises nothing and allocates nothing between iterations, and
+ * its launches per iteration depend on the list alone.  ope_icp_begin answers OPE_EINVAL, nothing launched, while a list is set
+ * and the run asks for reciprocal correspondences, an estimator other than OPE_EST_SVD, fixed correspondences or a context with a
+ * communicator; ope_icp_run_batch, the ope_final_pose_batch* family and ope_track_pose answer OPE_EINVAL while a list is set.
+ * OPE_EINVAL for a parameter out of range: factor not finite or < 0, a ratio outside [0, 1], min_ratio > max_ratio, an unknown
+ * kind, more than OPE_GREJ_MAX rejectors. */
+enum { OPE_GREJ_MEDIAN_DISTANCE = 0, OPE_GREJ_ONE_TO_ONE = 1, OPE_GREJ_VAR_TRIMMED = 2 };
+#define OPE_GREJ_MAX 4
+typedef struct {
+  int kind;
+  double factor;                /* median distance: 1.0 (the reference's block uses 0.8) */
+  double min_ratio, max_ratio;  /* var trimmed: 0.05, 0.95 (the reference's block uses min_ratio 0.3) */
+} ope_global_rejector;
+typedef struct {
+  int64_t n_in, n_out;
+  double threshold;   /* the median or the trimmed distance; NaN for one-to-one */
+  double ratio;       /* var trimmed: the ratio chosen; else NaN */
+  int64_t launches;   /* dispatches this rejector books per application: its own kernels, and one for the rocPRIM sort of var
+                         trimmed whatever that launches inside; a function of the kind alone */
+} ope_global_rejector_stats;
+void ope_global_rejector_defaults(int kind, ope_global_rejector *r);
+/* n <= OPE_GREJ_MAX; n = 0 (or list NULL) clears.  Holds for every later run of the context: ope_icp_begin takes a copy, so a run
+ * in progress keeps the list it began with. */
+int ope_icp_set_global_rejectors(ope_ctx *ctx, const ope_global_rejector *list, size_t n);
+/* Rejector `which` of the list as the last iteration of the last run applied it.  OPE_ESTATE: no such run; OPE_EINVAL: which. */
+int ope_icp_global_rejector_stats(ope_ctx *ctx, size_t which, ope_global_rejector_stats *out);
+/* getRemainingCorrespondences of one rejector on n GIVEN pairs (the same kernels as in the loop): keep[i] = 1 for the survivors,
+ * in the order given.  index_query / index_match are read by one-to-one only and may be NULL for the other kinds. */
+int ope_reject_correspondences(ope_ctx *ctx, const ope_global_rejector *r, const int32_t *index_query, const int32_t *index_match,
+                               const float *distance, size_t n, unsigned char *keep, ope_global_rejector_stats *stats);
+
 /* Registration::getFitnessScore(max_range), registration_mod.hpp:131-165.
  * sum_out/n_out (optional) expose the partial sums for sharded runs. */
 int ope_fitness(ope_ctx *ctx, const ope_cloud *src, const ope_index *tgt, const float T[16], double max_range,

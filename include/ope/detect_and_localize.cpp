@@ -53,6 +53,12 @@
 // in one ope_final_pose_batch_correspondences call.  Exit status 2 without --coarse correspondences.  --coarse-batch does not touch
 // this aligner: with it alone the loop still runs.
 //
+//   ... --fine-rejector median:<factor>|one-to-one|trimmed:<min_ratio>   (every mode but --depth; repeatable)
+// PoseEstimator::addFineRejector: the rejectors estimateFinePose's list keeps commented out (poseestimator.cpp:250-292; the reference's
+// literals are median:0.8 and trimmed:0.3), applied inside the fine ICP in the order given on the command line, behind the
+// surface-normal rejector.  With the flag the candidate loop and the tracker run one estimateFinalPose at a time (the batched and
+// tracked entry points have no such stage).  Exit status 2 for another name or a value that does not parse.
+//
 //   ... --recognise <train_dir>   (with --candidates, --candidates-loop, --segment or --frame)
 // Before the pose stage, ope::ObjectDetection::getObjectNames over every cluster in one call against the table under <train_dir>
 // (training_data.list / training_data.f32).  Prints `recognise <i> <name> <distance>` per cluster: the name getObjectName gives
@@ -109,6 +115,33 @@ static const char *branch_name(int b) {
   }
 }
 
+// --fine-rejector's value: false for an unknown name or a number that does not parse
+static bool parse_fine_rejector(const char *v, ope::PoseEstimator &pe) {
+  namespace reg = pcl::registration;
+  char *end = nullptr;
+  if (!std::strcmp(v, "one-to-one")) { pe.addFineRejector(reg::CorrespondenceRejector::Ptr(new reg::CorrespondenceRejectorOneToOne)); return true; }
+  if (!std::strncmp(v, "median:", 7)) {
+    const double f = std::strtod(v + 7, &end);
+    if (end != v + 7 && *end == 0) {
+      reg::CorrespondenceRejectorMedianDistance::Ptr r(new reg::CorrespondenceRejectorMedianDistance);
+      r->setMedianFactor(f);
+      pe.addFineRejector(r);
+      return true;
+    }
+  }
+  if (!std::strncmp(v, "trimmed:", 8)) {
+    const double f = std::strtod(v + 8, &end);
+    if (end != v + 8 && *end == 0) {
+      reg::CorrespondenceRejectorVarTrimmed::Ptr r(new reg::CorrespondenceRejectorVarTrimmed);
+      r->setMinRatio(f);
+      pe.addFineRejector(r);
+      return true;
+    }
+  }
+  std::fprintf(stderr, "--fine-rejector takes median:<factor>, one-to-one or trimmed:<min_ratio>\n");
+  return false;
+}
+
 // --coarse's value: false for an unknown name
 static bool parse_coarse(const char *v, ope::PoseEstimator::CoarseMethod &m) {
   if (!std::strcmp(v, "sac-ia")) { m = ope::PoseEstimator::COARSE_SAC_IA; return true; }
@@ -126,6 +159,7 @@ static int track_main(int argc, char **argv) {
   uint64_t seed = 1;
   bool self_occluded = false, timed = false;
   ope::PoseEstimator::CoarseMethod coarse = ope::PoseEstimator::COARSE_SAC_IA;
+  std::vector<const char *> fine_rejectors;
   for (int i = 1; i < argc; ++i) {
     if ((!std::strcmp(argv[i], "--track") || !std::strcmp(argv[i], "--track-loop")) && i + 1 < argc) {
       mode = !std::strcmp(argv[i], "--track") ? 1 : 2;
@@ -134,6 +168,7 @@ static int track_main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--coarse") && i + 1 < argc) { if (!parse_coarse(argv[++i], coarse)) return 2; }
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
+    else if (!std::strcmp(argv[i], "--fine-rejector") && i + 1 < argc) fine_rejectors.push_back(argv[++i]);
     else if (!std::strcmp(argv[i], "--coarse-batch")) { std::fprintf(stderr, "--coarse-batch does not go with --track or --track-loop\n"); return 2; }
     else if (!std::strcmp(argv[i], "--correspondences-batch")) { std::fprintf(stderr, "--correspondences-batch does not go with --track or --track-loop\n"); return 2; }
     else if (!std::strcmp(argv[i], "--time")) timed = true;
@@ -148,6 +183,8 @@ static int track_main(int argc, char **argv) {
   tracker.estimator().setSacIaSeed(seed);
   tracker.estimator().setCoarseMethod(coarse);
   tracker.estimator().setUseSelfOccludedRejector(self_occluded);
+  for (const char *v : fine_rejectors)
+    if (!parse_fine_rejector(v, tracker.estimator())) return 2;
   double fitnessScore = 10.0, alignedStrength = 0.0;   // rosinterface.h: kept across frames
   for (size_t k = 0; k < frames.size(); ++k) {
     std::vector<pcl::PointCloud<PointT>::Ptr> clusters;
@@ -288,12 +325,14 @@ int main(int argc, char **argv) {
   ope::PoseEstimator::CoarseMethod coarse = ope::PoseEstimator::COARSE_SAC_IA;   // --coarse
   bool coarse_batch = false;   // --coarse-batch
   bool correspondences_batch = false;   // --correspondences-batch
+  std::vector<const char *> fine_rejectors;   // --fine-rejector, in the order given
   float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--coarse") && i + 1 < argc) { if (!parse_coarse(argv[++i], coarse)) return 2; }
     else if (!std::strcmp(argv[i], "--coarse-batch")) coarse_batch = true;
     else if (!std::strcmp(argv[i], "--correspondences-batch")) correspondences_batch = true;
+    else if (!std::strcmp(argv[i], "--fine-rejector") && i + 1 < argc) fine_rejectors.push_back(argv[++i]);
     else if (!std::strcmp(argv[i], "--recognise") && i + 1 < argc) recognise = argv[++i];
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--candidates")) candidates = 1;
@@ -328,6 +367,8 @@ int main(int argc, char **argv) {
   poseEstimator.setCoarseBatch(coarse_batch);
   poseEstimator.setCorrespondencesBatch(correspondences_batch);
   poseEstimator.setUseSelfOccludedRejector(self_occluded);
+  for (const char *v : fine_rejectors)
+    if (!parse_fine_rejector(v, poseEstimator)) return 2;
   auto print_frame = [&](size_t k, const pcl::Matrix4f &pose, double fitnessScore, double alignedStrength) {
     std::printf("frame %zu fitness %.12g strength %.12g coarse_calls %d icp_iterations %d", k, fitnessScore, alignedStrength,
                 poseEstimator.coarseCalls(), poseEstimator.lastIcpIterations());

@@ -43,8 +43,9 @@ class ObjectTracker {
     if (firstFrame) return first(clusters, fitnessScore, alignedStrength);
     ope_ctx *ctx = compat::default_context();
     const bool skip_coarse = !(poseEstimator.fineFitness() > 0.0001);
-    // (ope_track_pose's coarse stage is SAC-IA: another coarse method takes the loop, one estimateFinalPose at a time)
-    if (!ctx || poseEstimator.coarseMethod() != PoseEstimator::COARSE_SAC_IA || (skip_coarse && !poseEstimator.alignedSourceIs(*cloudSource)))
+    // (ope_track_pose's coarse stage is SAC-IA and its fine stage runs no global rejectors: another coarse method, or an estimator
+    // with fine rejectors, takes the loop, one estimateFinalPose at a time)
+    if (!ctx || poseEstimator.coarseMethod() != PoseEstimator::COARSE_SAC_IA || poseEstimator.hasFineRejectors() || (skip_coarse && !poseEstimator.alignedSourceIs(*cloudSource)))
       return later_loop(clusters, fitnessScore, alignedStrength);
     if (!model_dev_) model_dev_ = compat::upload(*cloudSourceOriginal, false);
     if (!source_dev_) source_dev_ = compat::upload(*cloudSource, false);

@@ -17,6 +17,7 @@
 //   SampleConsensusPrerejective                          BuildModel poseestimator.cpp:90-108 (commented out there)
 //   registration::CorrespondenceEstimation<FPFHSignature33, FPFHSignature33>
 //   registration::CorrespondenceRejectorSampleConsensus  BuildModel poseestimator.cpp:43-60 (commented out there)
+//   registration::CorrespondenceRejectorMedianDistance / OneToOne / VarTrimmed   poseestimator.cpp:250-292 (commented out there)
 // Point types are layout-compatible PODs (x@0,y@4,z@8; normal@16 in PointXYZRGBNormal; 16-byte aligned).
 // Errors never throw on the hot path: like PCL, a failed call logs to stderr and leaves
 // hasConverged() == false / the transform at identity (registration_mod.hpp:60-64,73-77).
@@ -241,6 +242,11 @@ struct CorrespondenceRejector {
   typedef std::shared_ptr<CorrespondenceRejector> Ptr;
   virtual ~CorrespondenceRejector() {}
   virtual void apply(ope_icp_params &p) const = 0;
+  // The global rejectors (median distance, one to one, var trimmed) decide over all of an iteration's pairs: they are not fused
+  // into the search but handed to the context as a list (ope_icp_set_global_rejectors).  global() fills the list entry and says
+  // so; took() receives what the last iteration of an align() did with it.
+  virtual bool global(ope_global_rejector &) const { return false; }
+  virtual void took(const ope_global_rejector_stats &) {}
   virtual void getRemainingCorrespondences(const Correspondences &original, Correspondences &remaining) = 0;
   void setInputCorrespondences(const std::shared_ptr<const Correspondences> &c) { input_correspondences_ = c; }
   void getCorrespondences(Correspondences &out) {
@@ -316,6 +322,71 @@ struct CorrespondenceRejectorSelfOccludedNormal : CorrespondenceRejector {
   }
  private:
   Triples src_n_, src_p_;
+};
+
+// The three rejectors of estimateFinePose's list that need every pair of an iteration (poseestimator.cpp:250-292, blocks 3.1, 3.2
+// and 3.5, commented out there), without a data container as that block uses them: `distance` is what the estimation wrote.
+// Stand-alone they run ope_reject_correspondences; added to an ICP they become the context's list for that align(), in the order
+// added.  The remaining correspondences stay in the order given (PCL's one-to-one returns them in match order).
+struct CorrespondenceRejectorGlobal : CorrespondenceRejector {
+  void apply(ope_icp_params &) const override {}
+  void took(const ope_global_rejector_stats &st) override { stats_ = st; }
+  void getRemainingCorrespondences(const Correspondences &original, Correspondences &remaining) override {
+    remaining.clear();
+    ope_ctx *ctx = default_context();
+    ope_global_rejector r;
+    if (!ctx || !global(r)) return;
+    std::vector<int32_t> q(original.size()), m(original.size());
+    std::vector<float> d(original.size());
+    for (size_t i = 0; i < original.size(); ++i) { q[i] = original[i].index_query; m[i] = original[i].index_match; d[i] = original[i].distance; }
+    std::vector<unsigned char> keep(original.size());
+    if (ope_reject_correspondences(ctx, &r, q.data(), m.data(), d.data(), original.size(), keep.data(), &stats_) != OPE_OK) {
+      log_error("getRemainingCorrespondences", ctx);
+      return;
+    }
+    for (size_t i = 0; i < original.size(); ++i)
+      if (keep[i]) remaining.push_back(original[i]);
+  }
+  const ope_global_rejector_stats &getStats() const { return stats_; }   // not PCL's: pairs in and out, threshold, ratio
+ protected:
+  ope_global_rejector_stats stats_{};
+};
+struct CorrespondenceRejectorMedianDistance : CorrespondenceRejectorGlobal {
+  typedef std::shared_ptr<CorrespondenceRejectorMedianDistance> Ptr;
+  void setMedianFactor(double f) { factor_ = f; }
+  double getMedianFactor() const { return factor_; }
+  double getMedianDistance() const { return stats_.threshold; }
+  bool global(ope_global_rejector &r) const override {
+    ope_global_rejector_defaults(OPE_GREJ_MEDIAN_DISTANCE, &r);
+    r.factor = factor_;
+    return true;
+  }
+ private:
+  double factor_ = 1.0;
+};
+struct CorrespondenceRejectorOneToOne : CorrespondenceRejectorGlobal {
+  typedef std::shared_ptr<CorrespondenceRejectorOneToOne> Ptr;
+  bool global(ope_global_rejector &r) const override {
+    ope_global_rejector_defaults(OPE_GREJ_ONE_TO_ONE, &r);
+    return true;
+  }
+};
+struct CorrespondenceRejectorVarTrimmed : CorrespondenceRejectorGlobal {
+  typedef std::shared_ptr<CorrespondenceRejectorVarTrimmed> Ptr;
+  void setMinRatio(double r) { min_ratio_ = r; }
+  double getMinRatio() const { return min_ratio_; }
+  void setMaxRatio(double r) { max_ratio_ = r; }
+  double getMaxRatio() const { return max_ratio_; }
+  double getTrimmedDistance() const { return stats_.threshold; }
+  double getTrimFactor() const { return stats_.ratio; }
+  bool global(ope_global_rejector &r) const override {
+    ope_global_rejector_defaults(OPE_GREJ_VAR_TRIMMED, &r);
+    r.min_ratio = min_ratio_;
+    r.max_ratio = max_ratio_;
+    return true;
+  }
+ private:
+  double min_ratio_ = 0.05, max_ratio_ = 0.95;
 };
 
 template <class S, class T, class Scalar = float> struct TransformationEstimationSVD {
@@ -508,7 +579,20 @@ template <class PointSource, class PointTarget, class Scalar = float> class Iter
     p.corr_mode = corr_est_ ? corr_est_->mode() : OPE_CORR_NEAREST;
     if (corr_est_) p.k_normal_shooting = corr_est_->k();
     p.use_surface_normal_rej = p.use_self_occluded_rej = 0;
-    for (auto &r : rejectors_) r->apply(p);
+    // the global rejectors become the context's list for this run, in the order added; a pointwise rejector behind one of them
+    // cannot be honoured (the pointwise ones are fused into the search, which runs first)
+    std::vector<ope_global_rejector> glist;
+    std::vector<registration::CorrespondenceRejector *> gown;
+    for (auto &r : rejectors_) {
+      ope_global_rejector g;
+      if (r->global(g)) { glist.push_back(g); gown.push_back(r.get()); continue; }
+      if (!glist.empty()) {
+        std::fprintf(stderr, "[ope::IterativeClosestPoint::align] a pointwise correspondence rejector was added after a global one: "
+                             "pointwise rejectors are fused into the search and cannot run behind it; not aligning\n");
+        return;
+      }
+      r->apply(p);
+    }
     p.mse_threshold_absolute = criteria_->mse_threshold_absolute_;
     p.failure_after_max_iter = criteria_->failure_after_max_iter_ ? 1 : 0;
     const bool nrm = p.corr_mode == OPE_CORR_NORMAL_SHOOTING || p.use_surface_normal_rej || p.use_self_occluded_rej ||
@@ -535,8 +619,20 @@ template <class PointSource, class PointTarget, class Scalar = float> class Iter
         return;
       }
     }
+    if (ope_icp_set_global_rejectors(ctx, glist.data(), glist.size()) != OPE_OK) {
+      log_error("align (global rejectors)", ctx);
+      (void)ope_icp_set_fixed_correspondences(ctx, nullptr, nullptr, nullptr, nullptr, 0);
+      return;
+    }
     ope_icp_result res;
     const int rc_run = ope_icp_run(ctx, src_dev_->h, tgt_index_->h, guess.m, &p, final_.m, &res);
+    if (!glist.empty()) {   // the context is shared between objects: the list is this run's only
+      for (size_t k = 0; rc_run == OPE_OK && k < gown.size(); ++k) {
+        ope_global_rejector_stats st;
+        if (ope_icp_global_rejector_stats(ctx, k, &st) == OPE_OK) gown[k]->took(st);
+      }
+      (void)ope_icp_set_global_rejectors(ctx, nullptr, 0);
+    }
     std::vector<int32_t> fixed_listed, fixed_appended;
     if (corres_fixed_ && !corres_fixed_->empty()) {
       std::vector<float> fd(fq.size());

@@ -52,6 +52,13 @@ class PoseEstimator {
   bool correspondencesBatch() const { return correspondences_batch_; }
   void setSacIaSeed(uint64_t seed) { sacia_seed_ = seed; }
   void setUseSelfOccludedRejector(bool on) { use_self_occluded_ = on; }
+  // The rejectors estimateFinePose's list keeps commented out (:250-292, 3.1 median distance, 3.2 one to one, 3.5 var trimmed), in
+  // the order added, behind the surface-normal rejector.  They run inside the single-cluster estimateFinePose; the candidate batch
+  // and the tracked frame have no such stage (ope.h: the batched and tracked entry points refuse a list), so with rejectors set
+  // estimateFinalPoseCandidates and ope::ObjectTracker run the reference's loop, one estimateFinalPose at a time.
+  void addFineRejector(const compat::registration::CorrespondenceRejector::Ptr &r) { if (r) fine_rejectors_.push_back(r); }
+  void clearFineRejectors() { fine_rejectors_.clear(); }
+  bool hasFineRejectors() const { return !fine_rejectors_.empty(); }
   // diagnostics of the last estimateFinalPose call
   Matrix4f lastCoarsePose() const { return last_coarse_; }
   Matrix4f lastFinePose() const { return last_fine_; }
@@ -156,6 +163,7 @@ class PoseEstimator {
     icp.setCorrespondenceEstimation(corrEstNormShoot);
     icp.addCorrespondenceRejector(corrRejSurNorm);
     if (use_self_occluded_) icp.addCorrespondenceRejector(corrRejSelfNorm);
+    for (const auto &r : fine_rejectors_) icp.addCorrespondenceRejector(r);
     icp.setTransformationEstimation(transfEstSvd);
     CloudN cloudAligned;
     {
@@ -207,7 +215,7 @@ class PoseEstimator {
     std::vector<ope_final_batch_result> res(clusters.size());
     int32_t sel = -1;
     // (ope_final_pose_batch's coarse stage is SAC-IA; the prerejective batch is opt-in: setCoarseBatch)
-    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() &&
+    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() && fine_rejectors_.empty() &&
                    (coarse_method_ == COARSE_SAC_IA || (coarse_method_ == COARSE_PREREJECTIVE && coarse_batch_) ||
                     (coarse_method_ == COARSE_CORRESPONDENCES && correspondences_batch_));
     if (batched) {
@@ -445,6 +453,7 @@ class PoseEstimator {
   int coarse_calls_ = 0;
   bool coarse_batch_ = false, correspondences_batch_ = false;
   bool use_self_occluded_ = false;
+  std::vector<compat::registration::CorrespondenceRejector::Ptr> fine_rejectors_;   // addFineRejector, in the order added
   Matrix4f last_coarse_ = Matrix4f::Identity(), last_fine_ = Matrix4f::Identity(), last_rigid_ = Matrix4f::Identity();
   int last_icp_iterations_ = 0;
 };

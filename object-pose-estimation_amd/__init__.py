@@ -40,6 +40,8 @@ TRACK_BRANCH_NAMES = ["NO_CLUSTERS", "GATED", "REALIGN_ALL", "NOTHING", "REALIGN
 TRACK_COARSE_SKIPPED = -1
 CERT_AUTO, CERT_OFF, CERT_ALWAYS = 0, 1, 2   # ope_icp_params.skip_certificates
 NUM_SUMS, NUM_SUMS_MAX = 17, 44
+GREJ_MEDIAN_DISTANCE, GREJ_ONE_TO_ONE, GREJ_VAR_TRIMMED = 0, 1, 2   # ope_global_rejector.kind
+GREJ_MAX = 4
 COMM_ID_BYTES = 128
 
 
@@ -85,6 +87,14 @@ class IcpParams(C.Structure):
         ("update_launch", C.c_int),
         ("skip_certificates", C.c_int),
     ]
+
+
+class GlobalRejector(C.Structure):
+    _fields_ = [("kind", C.c_int), ("factor", C.c_double), ("min_ratio", C.c_double), ("max_ratio", C.c_double)]
+
+
+class GlobalRejectorStats(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_out", C.c_int64), ("threshold", C.c_double), ("ratio", C.c_double), ("launches", C.c_int64)]
 
 
 class IcpResult(C.Structure):
@@ -614,6 +624,10 @@ ABI = [
     ("ope_icp_correspondences", C.c_int, [_vp, _ip, _ip, _fp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("ope_icp_last_incremental", C.c_int, [_vp, _fp]),
     ("ope_reject_pairs", C.c_int, [_vp, C.c_int, _fp, _fp, C.c_size_t, C.c_double, C.POINTER(C.c_ubyte)]),
+    ("ope_global_rejector_defaults", None, [C.c_int, C.POINTER(GlobalRejector)]),
+    ("ope_icp_set_global_rejectors", C.c_int, [_vp, C.POINTER(GlobalRejector), C.c_size_t]),
+    ("ope_icp_global_rejector_stats", C.c_int, [_vp, C.c_size_t, C.POINTER(GlobalRejectorStats)]),
+    ("ope_reject_correspondences", C.c_int, [_vp, C.POINTER(GlobalRejector), _ip, _ip, _fp, C.c_size_t, C.POINTER(C.c_ubyte), C.POINTER(GlobalRejectorStats)]),
     ("ope_fitness", C.c_int, [_vp, _vp, _vp, _fp, C.c_double, _dp, _dp, C.POINTER(C.c_int64)]),
     ("ope_rigid_transform_svd", C.c_int, [_vp, _fp, _fp, C.c_size_t, _fp]),
     ("ope_transform_cloud", C.c_int, [_vp, _vp, _fp, _fp]),
@@ -802,6 +816,17 @@ def default_mls_upsample_params(**kw) -> MlsUpsampleParams:
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def global_rejector(kind: int, **kw) -> GlobalRejector:
+    """ope_global_rejector_defaults (factor 1.0, min_ratio 0.05, max_ratio 0.95) with the given fields set."""
+    r = GlobalRejector()
+    lib().ope_global_rejector_defaults(kind, C.byref(r))
+    for k, v in kw.items():
+        if not hasattr(r, k):
+            raise AttributeError(k)
+        setattr(r, k, v)
+    return r
 
 
 def default_icp_params(**kw) -> IcpParams:
@@ -1851,6 +1876,30 @@ class Context:
         keep = np.zeros(len(a), np.uint8)
         self._chk(lib().ope_reject_pairs(self.h, kind, _p(a, _fp), _p(b, _fp), len(a), threshold, keep.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return keep.astype(bool)
+
+    def icp_set_global_rejectors(self, rejectors=None):
+        """The global correspondence rejectors of every later ope_icp_run / step-wise run of this context, applied in order after
+        the search (ope.h): GlobalRejector structures (global_rejector(...)); None or an empty list clears."""
+        rejectors = list(rejectors or [])
+        arr = (GlobalRejector * max(len(rejectors), 1))(*rejectors)
+        self._chk(lib().ope_icp_set_global_rejectors(self.h, arr, len(rejectors)))
+
+    def icp_global_rejector_stats(self, i: int) -> GlobalRejectorStats:
+        """Rejector i of the list as the last iteration of the last run applied it."""
+        st = GlobalRejectorStats()
+        self._chk(lib().ope_icp_global_rejector_stats(self.h, i, C.byref(st)))
+        return st
+
+    def reject_correspondences(self, rej: GlobalRejector, index_query, index_match, distance):
+        """getRemainingCorrespondences of one global rejector on given pairs: (bool mask in the order given, GlobalRejectorStats)."""
+        d = np.ascontiguousarray(distance, np.float32)
+        q = np.ascontiguousarray(index_query, np.int32) if index_query is not None else None
+        m = np.ascontiguousarray(index_match, np.int32) if index_match is not None else None
+        keep = np.zeros(len(d), np.uint8)
+        st = GlobalRejectorStats()
+        self._chk(lib().ope_reject_correspondences(self.h, C.byref(rej), _p(q, _ip) if q is not None else None, _p(m, _ip) if m is not None else None,
+                                                   _p(d, _fp), len(d), keep.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(st)))
+        return keep.astype(bool), st
 
     def fitness(self, src: "Cloud", tgt: "Index", T, max_range: float = float(np.finfo(np.float64).max)):
         t = colmajor(T)

@@ -130,7 +130,9 @@ static int chain_join(ope_ctx *ctx) {
 // (fp64 atomics; the update kernel leaves them at zero again), which saves the reduction kernel and one kernel boundary
 // per iteration (C3: 181 -> 174 us per step) — the addition order, and with it the last bit of the sums, varies from
 // run to run.  OPE_DETERMINISTIC_SUMS=1 keeps one row per block and reduces the rows in a fixed tree instead.
-static bool atomic_sums(const ope_ctx *ctx) { return ctx->run_params.deterministic_sums == 0; }
+// A run under global rejectors (global_rejectors.hip) never reads the search launch's sums: its launches keep their rows, and the
+// stage behind them writes the survivors' rows.
+static bool atomic_sums(const ope_ctx *ctx) { return ctx->run_params.deterministic_sums == 0 && ctx->n_grej_run == 0; }
 
 // ---- which 1-NN kernel a run uses (ope_index_params.grid == 1: automatic)
 // The grid kernel is the better one while (nearly) every query has a model point within one grid cell; queries beyond that
@@ -476,6 +478,8 @@ void ope_ctx_destroy(ope_ctx *ctx) {
   if (ctx->d_deal) (void)hipFree(ctx->d_deal);
   if (ctx->d_lm_stats) (void)hipFree(ctx->d_lm_stats);
   if (ctx->d_fixed) (void)hipFree(ctx->d_fixed);
+  grej_free(ctx->grej);
+  grej_free(ctx->grej_alone);
   tmp_release_stream(ctx->stream);   // the cached temporaries of this context's stream
   stage_release_stream(ctx->stream);   // and the threads' small-copy slots that last went to it, or to the context's own
   if (ctx->own_stream != ctx->stream) stage_release_stream(ctx->own_stream);
@@ -1133,6 +1137,13 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
     if ((p.use_surface_normal_rej && !ctx->fixed_has_nrm) || ((p.use_self_occluded_rej || p.corr_mode == OPE_CORR_NORMAL_SHOOTING) && !ctx->fixed_has_src_nrm))
       return set_err(ctx, OPE_EINVAL, "ope_icp_begin: the clouds the fixed correspondences were gathered from had no normals");
   }
+  if (ctx->n_grej > 0) {
+    // global correspondence rejectors (global_rejectors.hip): the stage rewrites the 17 sums of the SVD estimator on one GPU
+    if (p.use_reciprocal) return set_err(ctx, OPE_EINVAL, "ope_icp_begin: global rejectors and reciprocal correspondences do not combine (ope_icp_set_global_rejectors with n = 0 clears the list)");
+    if (p.estimator != OPE_EST_SVD) return set_err(ctx, OPE_EINVAL, "ope_icp_begin: global rejectors are supported with the SVD estimator only");
+    if (ctx->n_fixed > 0) return set_err(ctx, OPE_EINVAL, "ope_icp_begin: global rejectors and fixed correspondences do not combine");
+    if (ctx->nccl_comm != nullptr || ctx->p2p_ok) return set_err(ctx, OPE_EINVAL, "ope_icp_begin: global rejectors are not supported on a context with a communicator (they need every rank's pairs)");
+  }
   if ((p.estimator == OPE_EST_POINT_TO_PLANE_LLS || p.estimator == OPE_EST_POINT_TO_PLANE_LM) && !tgt->d_nrm)
     return set_err(ctx, OPE_EINVAL, "ope_icp_begin: the point-to-plane estimator needs target normals (build the index from a cloud with normals)");
   if (p.use_surface_normal_rej && !tgt->d_nrm)
@@ -1171,6 +1182,14 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
     OPE_HIP(ctx, hipMalloc((void **)&ctx->d_cert_pos, sizeof(uint32_t) * kCertCand * std::max<size_t>(src->n, 1)));
     OPE_HIP(ctx, hipMalloc((void **)&ctx->d_cert_l, sizeof(float) * std::max<size_t>(src->n, 1)));
     ctx->corr_cap = std::max<size_t>(src->n, 1);
+  }
+  ctx->n_grej_run = 0;
+  if (ctx->n_grej > 0) {
+    // the second stage's buffers, sized here from the source's and the target's size: nothing is allocated between iterations
+    OPE_HIP(ctx, grej_ensure(&ctx->grej, ctx->stream, src->n_valid, tgt->n_total, ctx->grej_list, ctx->n_grej));
+    OPE_HIP(ctx, grej_prepare_run(ctx->grej, ctx->stream, tgt->view(), tgt->n_total));
+    for (size_t k = 0; k < ctx->n_grej; ++k) ctx->grej_run_list[k] = ctx->grej_list[k];
+    ctx->n_grej_run = ctx->n_grej;
   }
   ctx->use_grid = false;
   ctx->force_plan_at = -1;
@@ -1337,7 +1356,7 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
   // update's wave finds room beside it whenever it arrives.
   ctx->chained = p.update_launch == OPE_UPDATE_OVERLAPPED && !ctx->chain_broken && p.corr_mode == OPE_CORR_NEAREST && !p.use_reciprocal &&
                  p.deterministic_sums == 0 && p.estimator != OPE_EST_POINT_TO_PLANE_LM && ctx->nccl_comm == nullptr && !ctx->p2p_ok &&
-                 ctx->n_fixed == 0;
+                 ctx->n_fixed == 0 && ctx->n_grej_run == 0;   // (a run under global rejectors updates in line, like LM)
   ctx->n_fixed_run = ctx->n_fixed;
   ctx->chain_on = false;
   ctx->chain_seq = 0;
@@ -1423,6 +1442,18 @@ int ope_icp_set_fixed_correspondences(ope_ctx *ctx, const ope_cloud *src, const 
 
 // the given pairs' share of the sums, after an accumulate launch (sharded runs: the caller sets them on exactly one rank, with
 // indices into that rank's shard, so that they are added once)
+// The second stage of an iteration under global rejectors: the list over the pairs the search launch left, then the survivors'
+// sums in one row per block, reduced by the fixed tree of icp_reduce_update_kernel (with the update step, or without for the
+// step-wise entry points).  In line on the launch stream; no host synchronisation, no allocation.
+static int enqueue_global_rejectors(ope_ctx *ctx, bool do_update) {
+  const CloudView sv = ctx->run_src->view();
+  OPE_HIP(ctx, grej_apply(ctx->stream, ctx->grej, ctx->grej_run_list, ctx->n_grej_run, ctx->d_state, sv.n_valid, ctx->d_corr_match, ctx->d_corr_d2,
+                          nullptr, sv.xyzw, true));
+  const int nb = grej_sums(ctx->stream, ctx->grej, sv, ctx->run_tgt->view(), ctx->d_state, ctx->d_corr_match, ctx->d_corr_d2);
+  launch_icp_reduce_update(ctx->stream, ctx->d_state, grej_partials(ctx->grej), sums_ptr(ctx), nb, do_update, ctx->d_work_counter);
+  return OPE_OK;
+}
+
 static void enqueue_fixed_pairs(ope_ctx *ctx) {
   if (ctx->n_fixed_run == 0) return;
   launch_icp_fixed_pairs(ctx->stream, ctx->d_state, ctx->d_fixed, (uint32_t)ctx->n_fixed_run, sums_ptr(ctx),
@@ -1462,7 +1493,10 @@ int ope_icp_accumulate(ope_ctx *ctx) {
   ctx->chain_on = false;
   rc = enqueue_accumulate(ctx, atomic);
   if (rc != OPE_OK) return rc;
-  if (!atomic)
+  if (ctx->n_grej_run > 0) {
+    rc = enqueue_global_rejectors(ctx, /*do_update=*/false);
+    if (rc != OPE_OK) return rc;
+  } else if (!atomic)
     launch_icp_reduce_update(ctx->stream, ctx->d_state, ctx->d_partials, sums_ptr(ctx), ctx->acc_blocks, /*do_update=*/false, ctx->d_work_counter);
   enqueue_fixed_pairs(ctx);
   OPE_HIP(ctx, hipGetLastError());
@@ -1529,6 +1563,11 @@ int ope_icp_iterate(ope_ctx *ctx, int n_iterations) {
       ctx->chain_tickets += (uint32_t)ctx->launch_blocks;
       launch_icp_update_chained(ctx->upd_stream, ctx->d_state, run_nsums(ctx), chain_ptr(ctx), ctx->chain_seq, ctx->chain_tickets, ctx->wait_ticks);
       ++ctx->chain_seq;
+      continue;
+    }
+    if (ctx->n_grej_run > 0) {   // (one rank, SVD estimator, no fixed pairs: ope_icp_begin)
+      rc = enqueue_global_rejectors(ctx, /*do_update=*/true);
+      if (rc != OPE_OK) return rc;
       continue;
     }
     if (ctx->run_params.estimator == OPE_EST_POINT_TO_PLANE_LM) {

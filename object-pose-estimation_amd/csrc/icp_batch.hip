@@ -315,6 +315,8 @@ extern "C" int ope_icp_run_batch(ope_ctx *ctx, size_t n, const ope_cloud *const 
 int ope::icp_batch_check_params(ope_ctx *ctx, const ope_icp_params &p) {
   if (ctx->nccl_comm != nullptr || ctx->p2p_ok || ctx->p2p_broken)
     return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: not on a context with a communicator (batched problems are not sharded)");
+  if (ctx->n_grej > 0)
+    return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: global correspondence rejectors are set (ope_icp_set_global_rejectors): the batched and tracked loops do not run them");
   if (p.use_reciprocal) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: reciprocal correspondences are not supported");
   if (p.estimator == OPE_EST_POINT_TO_PLANE_LM) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: the LM estimator is not supported");
   if (p.estimator != OPE_EST_SVD && p.estimator != OPE_EST_POINT_TO_PLANE_LLS) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: unknown estimator");

@@ -138,6 +138,8 @@ constexpr uint32_t kDealStripes = 64;
 constexpr uint32_t kDealLineWords = 32;
 constexpr size_t kDealBytes = sizeof(uint32_t) * 2 * kDealStripes * kDealLineWords;
 
+struct GrejWork;   // device buffers of the global correspondence rejectors (global_rejectors.hip)
+
 }  // namespace ope
 
 // std::vector without the zero fill on resize (the host copies of multi-million-point clouds are written in full
@@ -253,6 +255,11 @@ struct ope_ctx {
   const ope_cloud *fixed_src = nullptr;  // the source cloud they index (checked by ope_icp_begin)
   size_t fixed_tgt_n = 0;                // size of the target cloud they index
   bool fixed_has_nrm = false, fixed_has_src_nrm = false;
+  // global correspondence rejectors (ope_icp_set_global_rejectors; global_rejectors.hip): the list as set / as taken by the last
+  // ope_icp_begin, the run's work area and the stand-alone entry point's (ope_reject_correspondences)
+  ope_global_rejector grej_list[OPE_GREJ_MAX] = {}, grej_run_list[OPE_GREJ_MAX] = {};
+  size_t n_grej = 0, n_grej_run = 0;
+  ope::GrejWork *grej = nullptr, *grej_alone = nullptr;
 
   // optional per-launch timing of the accumulate kernel (HIP events on the launch stream)
   bool prof_enabled = false;
@@ -650,6 +657,18 @@ void icp_state_init(IcpState *h, const ope_cloud *src, const ope_index *tgt, con
 inline int index_build_tmp(ope_ctx *ctx, const ope_cloud *target, const ope_index_params *params, ope_index **out) {
   return index_build_impl(ctx, target, params, true, out);
 }
+// global_rejectors.hip: the second stage of an ICP iteration under a list of global rejectors (ope.h).  grej_ensure sizes the work
+// area (ope_icp_begin, never between iterations), grej_prepare_run adds what the survivor sums need, grej_apply enqueues the list
+// over the run's pairs and grej_sums the survivors' 17 sums, one row per block (the number of blocks is returned) into grej_partials.
+int grej_check(const ope_global_rejector *r);
+hipError_t grej_ensure(GrejWork **w, hipStream_t stream, size_t n_pairs, size_t n_tgt, const ope_global_rejector *list, size_t n_list);
+hipError_t grej_prepare_run(GrejWork *w, hipStream_t stream, const BvhView &tgt, size_t n_total);
+hipError_t grej_apply(hipStream_t stream, GrejWork *w, const ope_global_rejector *list, size_t n_list, const IcpState *st, uint32_t n,
+                      const int32_t *match, const float *d2, const int32_t *qidx, const float4 *src_xyzw, bool keep_from_match,
+                      ope_ctx *timed = nullptr);   // timed: bracket the launches for ope_profile_kernels (stand-alone only)
+int grej_sums(hipStream_t stream, GrejWork *w, const CloudView &src, const BvhView &tgt, const IcpState *st, int32_t *match, const float *d2);
+const double *grej_partials(const GrejWork *w);
+void grej_free(GrejWork *w);
 // features.hip: the SAC-IA host side that ope_sacia and ope_coarse_pose_batch share (same draws, same fits)
 void sacia_draws(const float *xyz, int ns, int S, int K, int H, float min_sample_dist, uint64_t seed, int32_t *samp, int32_t *pick);
 void umeyama_host(const float *src, const float *dst, int n, float T[16]);
