@@ -13,51 +13,6 @@
 
 namespace ope {
 
-// launchers defined in icp_kernels.hip
-void launch_icp_accumulate(hipStream_t, int, int, bool, bool, const CloudView &, const BvhView &, const BvhView &,
-                           const IcpState *, double *, int32_t *, float *, uint32_t *, uint32_t *, const uint32_t *,
-                           uint32_t *, const uint32_t *, bool, int, double *, const uint32_t *, float *, const uint32_t *, hipEvent_t, hipEvent_t, bool,
-                           uint32_t *, uint32_t, float4 *, uint32_t *, uint32_t *, uint32_t, uint32_t, float *, uint32_t *, uint32_t);
-void plan_heavy(hipStream_t, const uint32_t *, uint32_t, float, float, uint32_t, uint32_t, float, uint32_t *);
-void plan_slots(hipStream_t, const uint32_t *, uint32_t, const uint32_t *, uint32_t, float, uint32_t *);
-int icp_accumulate_blocks_per_cu(bool, bool, bool);
-int icp_accumulate_cert_blocks_per_cu(bool, bool, bool);
-int chunk_plan(hipStream_t, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *, uint32_t, void *, size_t &);
-void fill_iota(hipStream_t, uint32_t *, uint32_t);
-hipError_t concat_device(hipStream_t, const CloudView &, const float *, const CloudView &, float *, float[3], float[3], const uint32_t *,
-                         const uint32_t *, uint32_t *);
-hipError_t build_bvh_device(hipStream_t, const float4 *, const float4 *, size_t, int, const float[3], const float[3], int *, float4 **,
-                            float4 **, float4 **, float4 **, bool);
-void launch_icp_accumulate_grid(hipStream_t, int, bool, const CloudView &, const BvhView &, const GridView &, const IcpState *, double *, int32_t *,
-                                float *, uint32_t *, uint32_t *, const uint32_t *, unsigned char *, const uint32_t *, uint32_t *, const uint32_t *,
-                                double *, hipEvent_t, hipEvent_t, bool, uint32_t *, uint32_t, uint32_t *, uint32_t, uint32_t, float4 *, uint32_t *, uint32_t *, float *);
-int grid_plan(hipStream_t, bool, const unsigned char *, uint32_t, uint32_t *, uint32_t *, const uint32_t *, uint32_t *, uint32_t *, const uint32_t *,
-              uint32_t *, uint32_t, uint32_t, float, float, void *, size_t);
-size_t grid_plan_tmp_bytes(uint32_t, uint32_t);
-void grid_count_far(hipStream_t, const float *, uint32_t, float, uint32_t *);
-void grid_count_outside(hipStream_t, const CloudView &, const float[12], const float[3], const float[3], float, uint32_t *);
-void grid_hints_to_leaves(hipStream_t, const uint32_t *, const uint32_t *, uint32_t, uint32_t, int, uint32_t *, uint32_t *);
-hipError_t build_grid_device(hipStream_t, const float4 *, const float4 *, size_t, const float[3], const float[3], double, uint32_t, GridView *,
-                             float4 **, float4 **, uint32_t **, uint32_t **);
-void launch_icp_reduce_update(hipStream_t, IcpState *, const double *, double *, int, bool, uint32_t *);
-void launch_icp_update(hipStream_t, IcpState *, double *, int, const float *);
-void launch_icp_update_chained(hipStream_t, IcpState *, int, uint32_t *, uint32_t, uint32_t, uint32_t);
-void launch_gather_fixed_pairs(hipStream_t, const CloudView &, const CloudView &, const uint32_t *, uint32_t, float4 *);
-void launch_icp_fixed_pairs(hipStream_t, const IcpState *, const float4 *, uint32_t, double *, float2 *);
-void launch_lm_stats(hipStream_t, int, const CloudView &, const BvhView &, const IcpState *, const int32_t *, double *);
-void launch_icp_lm_update(hipStream_t, IcpState *, double *, double *);
-void launch_lm_pos_to_orig(hipStream_t, const BvhView &, int32_t *, uint32_t);
-void launch_nn_search(hipStream_t, const CloudView &, const BvhView &, const float *, int32_t *, float *);
-void launch_knn_search(hipStream_t, const CloudView &, const BvhView &, const float *, int, int32_t *, float *);
-void launch_fitness(hipStream_t, int, const CloudView &, const BvhView &, const float *, double, double *, const uint32_t *);
-void launch_seed_hints(hipStream_t, const CloudView &, const BvhView &, const IcpState *, uint32_t *);
-void launch_pairs_svd(hipStream_t, const float *, const float *, uint32_t, double *, int, float *);
-// comm.cpp
-int comm_allreduce_sums(ope_ctx *ctx, double *d_sums, int count);
-bool comm_uses_p2p(const ope_ctx *ctx);
-int comm_p2p_exchange_update(ope_ctx *ctx, IcpState *d_state, double *d_sums, int nsums);
-int comm_p2p_exchange(ope_ctx *ctx, double *d_sums, int nsums);
-
 static thread_local std::string g_global_err;
 
 constexpr double kGridMaxTreeShare = 0.03, kGridMinTreeShare = 0.015;
@@ -79,12 +34,6 @@ int set_err(ope_ctx *ctx, int code, const std::string &msg) {
 }
 
 static inline bool finite3(const float *p) { return std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]); }
-
-// column-major 4x4 -> 12 floats, rows of [R|t]
-static void colmajor_to_rows(const float *T, float rows[12]) {
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 4; ++c) rows[4 * r + c] = T[4 * c + r];
-}
 
 static int ensure_scratch(ope_ctx *ctx, size_t bytes) {
   if (ctx->scratch_bytes >= bytes) return OPE_OK;
@@ -219,6 +168,37 @@ static bool plan_step_after(const ope_ctx *ctx, int launch) {
   return ((launch & (launch - 1)) == 0 && launch <= kPlanPeriod) || launch % kPlanPeriod == 0 || launch == ctx->force_plan_at;
 }
 
+// What the grid and the tree launch share (AccLaunch), filled right before the launch itself: here the launch takes its number and,
+// under ope_icp_profile, its pair of events.  certify: the launch takes the certifying instantiation; cost_w: see enqueue_accumulate.
+static void fill_acc_launch(ope_ctx *ctx, AccLaunch &a, bool certify, uint32_t *cost_w, bool atomic_sums) {
+  const bool timed = ctx->prof_enabled && ctx->prof_used < ctx->prof_events.size() / 2;
+  ctx->launch_blocks = certify ? std::min(ctx->acc_blocks, ctx->acc_blocks_cert) : ctx->acc_blocks;   // (the certifying instantiation holds fewer blocks per CU)
+  a.stream = ctx->stream;
+  a.nblocks = ctx->launch_blocks;
+  a.src = ctx->run_src->view();
+  a.tgt = ctx->run_tgt->view();
+  a.st = ctx->d_state;
+  a.partials = ctx->d_partials;
+  a.corr_match = ctx->d_corr_match;
+  a.corr_d2 = ctx->d_corr_d2;
+  a.hint = ctx->d_hint;
+  a.chunk_cost = cost_w;
+  a.plan_info = ctx->d_work_counter + 8;
+  a.S_atomic = atomic_sums ? sums_ptr(ctx) : nullptr;
+  a.e0 = timed ? ctx->prof_events[2 * ctx->prof_used] : nullptr;
+  a.e1 = timed ? ctx->prof_events[2 * ctx->prof_used + 1] : nullptr;
+  a.measuring = ctx->measuring_flag;
+  a.chain = ctx->chain_on ? chain_ptr(ctx) : nullptr;
+  a.chain_seq = ctx->chain_seq;
+  a.pace = ctx->d_pace;
+  a.launch_no = ++ctx->launch_no;
+  a.wait_ticks = ctx->wait_ticks;
+  a.cert_q = certify ? ctx->d_cert_q : nullptr;
+  a.cert_pos = ctx->d_cert_pos;
+  a.cert_l = ctx->d_cert_l;
+  if (timed) ++ctx->prof_used;
+}
+
 static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
   pace_wait(ctx);
   if (ctx->cert_run && !ctx->cert_seen && ctx->h_pace != nullptr && *(volatile uint32_t *)(ctx->h_pace + 1) != 0u) ctx->cert_seen = true;
@@ -273,18 +253,18 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
         if (rcp != OPE_OK) return rcp;
       }
     }
-    const bool timed = ctx->prof_enabled && ctx->prof_used < ctx->prof_events.size() / 2;
     const bool certify = ctx->cert_run && ctx->cert_seen;
-    ctx->launch_blocks = certify ? std::min(ctx->acc_blocks, ctx->acc_blocks_cert) : ctx->acc_blocks;   // (the certifying instantiation holds fewer blocks per CU)
     ++ctx->kernel_launches[OPE_KERNEL_GRID];
-    launch_icp_accumulate_grid(ctx->stream, ctx->launch_blocks, nrm, ctx->run_src->view(), ctx->run_tgt->view(), ctx->run_tgt->grid, ctx->d_state,
-                               ctx->d_partials, ctx->d_corr_match, ctx->d_corr_d2, ctx->d_hint, ctx->d_ghint, ctx->d_qorder, ctx->d_qclass,
-                               ctx->plan_valid ? ctx->d_chunk_order : nullptr, cost_w, ctx->d_work_counter + 8,
-                               atomic_sums ? sums_ptr(ctx) : nullptr, timed ? ctx->prof_events[2 * ctx->prof_used] : nullptr,
-                               timed ? ctx->prof_events[2 * ctx->prof_used + 1] : nullptr, ctx->measuring_flag,
-                               ctx->chain_on ? chain_ptr(ctx) : nullptr, ctx->chain_seq, ctx->d_pace, ++ctx->launch_no, ctx->wait_ticks,
-                               certify ? ctx->d_cert_q : nullptr, ctx->d_cert_pos, ctx->d_work_counter + 40, ctx->d_cert_l);
-    if (timed) ++ctx->prof_used;
+    AccGridLaunch a;
+    fill_acc_launch(ctx, a, certify, cost_w, atomic_sums);
+    a.nrm = nrm;
+    a.chunk_order = ctx->plan_valid ? ctx->d_chunk_order : nullptr;
+    a.grid = ctx->run_tgt->grid;
+    a.ghint = ctx->d_ghint;
+    a.qorder = ctx->d_qorder;
+    a.qclass = ctx->d_qclass;
+    a.cert_stats = ctx->d_work_counter + 40;
+    launch_icp_accumulate_grid(a);
     return OPE_OK;
   }
   if (ctx->grid_auto && grid_probe_poll(ctx, it_done) > 0) {
@@ -350,7 +330,6 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
   const ope_icp_params &p = ctx->run_params;
   const bool nrm = p.corr_mode == OPE_CORR_NORMAL_SHOOTING || p.use_surface_normal_rej || p.use_self_occluded_rej ||
                    p.estimator == OPE_EST_POINT_TO_PLANE_LLS;   // (LM reads the target normals in its own kernel)
-  const bool timed = ctx->prof_enabled && ctx->prof_used < ctx->prof_events.size() / 2;
   const bool recip = p.use_reciprocal != 0;
   // packet walks for coherent chunks pay off when the launch fills the GPU (C3: 195 -> 184 us); on an underfilled
   // one (a 1/8 shard, C2) the longer dependent chain of a packet costs more than its gathers save (77 -> 88 us)
@@ -359,18 +338,23 @@ static int enqueue_accumulate(ope_ctx *ctx, bool atomic_sums = false) {
                       : p.tree_walk == OPE_WALK_LANE ? false : nch > packet_min;
   ++ctx->kernel_launches[p.corr_mode != OPE_CORR_NEAREST ? OPE_KERNEL_KNN : (packet && !recip) ? OPE_KERNEL_TREE_PACKET : OPE_KERNEL_TREE_LANE];
   const bool certify = ctx->cert_run && ctx->cert_seen && p.corr_mode == OPE_CORR_NEAREST && !recip;
-  const int blocks = certify ? std::min(ctx->acc_blocks, ctx->acc_blocks_cert) : ctx->acc_blocks;   // (the certifying instantiation holds fewer blocks per CU)
-  ctx->launch_blocks = blocks;
-  launch_icp_accumulate(ctx->stream, blocks, p.corr_mode, nrm, recip, ctx->run_src->view(), ctx->run_tgt->view(),
-                        recip ? ctx->run_src_index->view() : ctx->run_tgt->view(), ctx->d_state, ctx->d_partials, ctx->d_corr_match, ctx->d_corr_d2, ctx->d_work_counter, ctx->d_hint,
-                        ctx->plan_valid ? ctx->d_plan_order[ctx->plan_cur] : nullptr, cost_w, ctx->d_work_counter + 8, packet, p.k_normal_shooting, atomic_sums ? sums_ptr(ctx) : nullptr,
-                        (ctx->plan_valid && ctx->plan_cur_slots) ? ctx->d_plan_slots[ctx->plan_cur] : nullptr,
-                        p.corr_mode == OPE_CORR_NORMAL_SHOOTING ? ctx->d_knn_rk : nullptr, ctx->d_plan_out + 8 * ctx->plan_cur,
-                        timed ? ctx->prof_events[2 * ctx->prof_used] : nullptr, timed ? ctx->prof_events[2 * ctx->prof_used + 1] : nullptr,
-                        ctx->measuring_flag, ctx->chain_on ? chain_ptr(ctx) : nullptr, ctx->chain_seq, certify ? ctx->d_cert_q : nullptr, ctx->d_cert_pos, ctx->d_pace, ++ctx->launch_no, ctx->wait_ticks, ctx->d_cert_l,
-                        ctx->d_deal, ctx->deal_parity);
+  AccTreeLaunch a;
+  fill_acc_launch(ctx, a, certify, cost_w, atomic_sums);
+  a.nrm = nrm;
+  a.chunk_order = ctx->plan_valid ? ctx->d_plan_order[ctx->plan_cur] : nullptr;
+  a.mode = p.corr_mode;
+  a.recip = recip;
+  a.srcix = recip ? ctx->run_src_index->view() : ctx->run_tgt->view();
+  a.work_counter = ctx->d_work_counter;
+  a.packet = packet;
+  a.k_normal_shooting = p.k_normal_shooting;
+  a.slot_list = (ctx->plan_valid && ctx->plan_cur_slots) ? ctx->d_plan_slots[ctx->plan_cur] : nullptr;
+  a.knn_rk = p.corr_mode == OPE_CORR_NORMAL_SHOOTING ? ctx->d_knn_rk : nullptr;
+  a.plan_out = ctx->d_plan_out + 8 * ctx->plan_cur;
+  a.deal = ctx->d_deal;
+  a.deal_parity = ctx->deal_parity;
+  launch_icp_accumulate(a);
   ctx->deal_parity ^= 1u;   // this launch has cleared the other set of queue counters for the next one
-  if (timed) ++ctx->prof_used;
   return OPE_OK;
 }
 
@@ -744,7 +728,7 @@ int ope_cloud_concat(ope_ctx *ctx, const ope_cloud *a, const float T_a[16], cons
   if (e == hipSuccess && n) e = hipMalloc((void **)&d_raw, 12 * n);
   if (e == hipSuccess && n) e = hipMalloc((void **)&d_perm, 4 * n);
   if (e == hipSuccess && T_a) {
-    colmajor_to_rows(T_a, rows);
+    colmajor_to_rows12(T_a, rows);
     e = hipMalloc((void **)&d_rows, sizeof rows);
     if (e == hipSuccess) e = h2d_copy(ctx->stream, d_rows, rows, sizeof rows);
   }
@@ -869,7 +853,7 @@ static int upload_T(ope_ctx *ctx, const float *T, float **d_T) {
   *d_T = nullptr;
   if (!T) return OPE_OK;
   float rows[12];
-  colmajor_to_rows(T, rows);
+  colmajor_to_rows12(T, rows);
   int rc = ensure_scratch(ctx, 1 << 16);
   if (rc != OPE_OK) return rc;
   OPE_HIP(ctx, h2d_copy(ctx->stream, ctx->d_scratch, rows, sizeof rows));
@@ -1044,7 +1028,7 @@ void ope::icp_state_init(IcpState *h, const ope_cloud *src, const ope_index *tgt
   static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   const float *g = guess ? guess : I4;
   for (int i = 0; i < 16; ++i) { h->F[i] = g[i]; h->Tk[i] = I4[i]; }
-  colmajor_to_rows(g, h->Ff);
+  colmajor_to_rows12(g, h->Ff);
   for (int d = 0; d < 3; ++d) h->pivot[d] = tgt->pivot[d];
   h->prev_mse = h->cur_mse = std::numeric_limits<double>::max();
   // thresholds wired as at icp_mod.hpp:164-168 (quirk Q1: rotation threshold = 1 - transformation_epsilon)
@@ -1208,7 +1192,7 @@ static int icp_begin_impl(ope_ctx *ctx, const ope_cloud *src, const ope_index *t
     // outside the target's bounding box (grid_build.hip); above the threshold the run starts on the tree kernel
     static const float I4g[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     float rows[12];
-    colmajor_to_rows(guess ? guess : I4g, rows);
+    colmajor_to_rows12(guess ? guess : I4g, rows);
     uint32_t n_out = 0;
     grid_count_outside(ctx->stream, src->view(), rows, tgt->bb_lo, tgt->bb_hi, 8.0f / tgt->grid.inv, ctx->d_work_counter + 20);
     OPE_HIP(ctx, hipMemcpyAsync(&n_out, ctx->d_work_counter + 20, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1827,7 +1811,7 @@ int ope_fitness(ope_ctx *ctx, const ope_cloud *src, const ope_index *tgt, const 
   int rc = ensure_scratch(ctx, 1 << 16);
   if (rc != OPE_OK) return rc;
   float rows[12];
-  colmajor_to_rows(T, rows);
+  colmajor_to_rows12(T, rows);
   float *d_T = static_cast<float *>(ctx->d_scratch);
   double *d_part = reinterpret_cast<double *>(static_cast<unsigned char *>(ctx->d_scratch) + 256);
   OPE_HIP(ctx, h2d_copy(ctx->stream, d_T, rows, sizeof rows));

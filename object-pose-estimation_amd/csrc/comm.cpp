@@ -48,8 +48,6 @@ Rccl &rccl() {
 }
 }  // namespace
 
-void launch_icp_p2p_update(hipStream_t, IcpState *, double *, int, const P2pView &, uint32_t, unsigned long long, bool, double *);
-
 P2pView p2p_view(const ope_ctx *ctx) {
   P2pView v{};
   v.nranks = ctx->comm_nranks;

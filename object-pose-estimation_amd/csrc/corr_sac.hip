@@ -32,8 +32,6 @@
 
 namespace ope {
 
-void launch_pairs_svd(hipStream_t, const float *, const float *, uint32_t, double *, int, float *);
-
 namespace {
 
 static_assert(12ull * ((size_t)kPrMaxIterations + 1) <= kStageChunk, "the samples go up in one staged copy");

@@ -26,8 +26,6 @@
 
 namespace ope {
 
-hipError_t self_leaves(hipStream_t, const BvhView &, size_t, uint32_t *);   // features.hip
-
 __global__ __launch_bounds__(256) void box_flags_kernel(CloudView c, float lox, float loy, float loz, float hix, float hiy,
                                                          float hiz, unsigned char *__restrict__ flags_orig) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;

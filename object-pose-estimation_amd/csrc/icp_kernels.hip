@@ -1357,28 +1357,24 @@ __global__ __launch_bounds__(256) void fitness_kernel(CloudView q, BvhView tgt, 
 
 // ------------------------------------------------------------------------------------------
 // host launchers (called from api.hip)
-void launch_icp_accumulate(hipStream_t stream, int nblocks, int mode, bool nrm, bool recip, const CloudView &src,
-                           const BvhView &tgt, const BvhView &srcix, const IcpState *st, double *partials,
-                           int32_t *corr_match, float *corr_d2, uint32_t *work_counter, uint32_t *hint,
-                           const uint32_t *chunk_order, uint32_t *chunk_cost, const uint32_t *plan_info, bool packet,
-                           int k_normal_shooting, double *S_atomic, const uint32_t *slot_list, float *knn_rk, const uint32_t *plan_out,
-                           hipEvent_t e0, hipEvent_t e1, bool measuring, uint32_t *chain, uint32_t chain_seq, float4 *cert_q, uint32_t *cert_pos,
-                           uint32_t *pace, uint32_t launch_no, uint32_t wait_ticks, float *cert_l, uint32_t *deal, uint32_t deal_parity) {
-  const uint32_t mflag = measuring ? 1u : 0u;
+void launch_icp_accumulate(const AccTreeLaunch &a) {
+  const uint32_t mflag = a.measuring ? 1u : 0u;
   // e0 / e1 (ope_icp_profile): the launch's own start and stop time stamps, taken by the dispatch itself (hipExtLaunchKernelGGL).
   // Round 3 measured what a hipEventRecord before and after every launch costs the loop it times: 7-11 us per iteration (two
   // more packets with barriers between dependent dispatches), 5 % of the number the bench reports.
 #define OPE_KLAUNCH(KERNEL, BLK, LDS)                                                                                         \
   do {                                                                                                                        \
-    if (e0 != nullptr)                                                                                                        \
-      hipExtLaunchKernelGGL(KERNEL, dim3(nblocks), dim3(BLK), LDS, stream, e0, e1, 0, src, tgt, srcix, st, partials, corr_match, \
-                            corr_d2, work_counter, hint, chunk_order, chunk_cost, plan_info, S_atomic, slot_list, knn_rk, plan_out, mflag, chain, chain_seq, cert_q, cert_pos, pace, launch_no, wait_ticks, cert_l, deal, deal_parity); \
+    if (a.e0 != nullptr)                                                                                                      \
+      hipExtLaunchKernelGGL(KERNEL, dim3(a.nblocks), dim3(BLK), LDS, a.stream, a.e0, a.e1, 0, a.src, a.tgt, a.srcix, a.st, a.partials, a.corr_match, \
+                            a.corr_d2, a.work_counter, a.hint, a.chunk_order, a.chunk_cost, a.plan_info, a.S_atomic, a.slot_list, a.knn_rk, a.plan_out, mflag, a.chain, a.chain_seq, a.cert_q, a.cert_pos, a.pace, a.launch_no, a.wait_ticks, a.cert_l, a.deal, a.deal_parity); \
     else                                                                                                                      \
-      hipLaunchKernelGGL(KERNEL, dim3(nblocks), dim3(BLK), LDS, stream, src, tgt, srcix, st, partials, corr_match, corr_d2,   \
-                         work_counter, hint, chunk_order, chunk_cost, plan_info, S_atomic, slot_list, knn_rk, plan_out, mflag, chain, chain_seq, cert_q, cert_pos, pace, launch_no, wait_ticks, cert_l, deal, deal_parity); \
+      hipLaunchKernelGGL(KERNEL, dim3(a.nblocks), dim3(BLK), LDS, a.stream, a.src, a.tgt, a.srcix, a.st, a.partials, a.corr_match, a.corr_d2, \
+                         a.work_counter, a.hint, a.chunk_order, a.chunk_cost, a.plan_info, a.S_atomic, a.slot_list, a.knn_rk, a.plan_out, mflag, a.chain, a.chain_seq, a.cert_q, a.cert_pos, a.pace, a.launch_no, a.wait_ticks, a.cert_l, a.deal, a.deal_parity); \
   } while (0)
 #define OPE_LAUNCH_ACC(M, N, R, BLK, LDS) OPE_KLAUNCH((icp_accumulate_kernel<M, N, R>), BLK, LDS)
-  const bool certify = cert_q != nullptr && mode == 0 && !recip;   // the certifying instantiation (api.hip decides when)
+  const int mode = a.mode;   // what the ladder below picks the instantiation by
+  const bool nrm = a.nrm, recip = a.recip, packet = a.packet;
+  const bool certify = a.cert_q != nullptr && mode == 0 && !recip;   // the certifying instantiation (api.hip decides when)
   if (mode == 0 && !recip && packet) {
     if (certify) { if (nrm) OPE_KLAUNCH((icp_accumulate_kernel<0, true, false, true, 20, true>), kAccBlock, 0); else OPE_KLAUNCH((icp_accumulate_kernel<0, false, false, true, 20, true>), kAccBlock, 0); }
     else if (nrm) OPE_KLAUNCH((icp_accumulate_kernel<0, true, false, true>), kAccBlock, 0);
@@ -1394,7 +1390,7 @@ void launch_icp_accumulate(hipStream_t stream, int nblocks, int mode, bool nrm, 
     // multiple of four, and at the class default 10): the LDS list of round 1 took 2.4 ms per C3 iteration where the
     // register list takes ~0.5 ms, and held the kernel at two waves per SIMD
 #define OPE_LAUNCH_NS(KR) OPE_KLAUNCH((icp_accumulate_kernel<2, true, false, false, KR>), kKnnBlock, 0)
-    const int k = k_normal_shooting;
+    const int k = a.k_normal_shooting;
     if (k == 10) OPE_LAUNCH_NS(10);
     else if (k <= 4) OPE_LAUNCH_NS(4);
     else if (k <= 8) OPE_LAUNCH_NS(8);
@@ -1440,23 +1436,19 @@ int icp_accumulate_cert_blocks_per_cu(bool nrm, bool packet, bool grid) {
   return (ec == hipSuccess && nc > 0) ? nc : 0;
 }
 
-void launch_icp_accumulate_grid(hipStream_t stream, int nblocks, bool nrm, const CloudView &src, const BvhView &tgt, const GridView &grid,
-                                const IcpState *st, double *partials, int32_t *corr_match, float *corr_d2, uint32_t *hint, uint32_t *ghint,
-                                const uint32_t *qorder, unsigned char *qclass, const uint32_t *chunk_order, uint32_t *chunk_cost,
-                                const uint32_t *plan_info, double *S_atomic, hipEvent_t e0, hipEvent_t e1, bool measuring, uint32_t *chain,
-                                uint32_t chain_seq, uint32_t *pace, uint32_t launch_no, uint32_t wait_ticks, float4 *cert_q, uint32_t *cert_pos,
-                                uint32_t *cert_stats, float *cert_l) {
-  const uint32_t mflag = measuring ? 1u : 0u;
+void launch_icp_accumulate_grid(const AccGridLaunch &a) {
+  const uint32_t mflag = a.measuring ? 1u : 0u;
 #define OPE_KLAUNCH(KERNEL)                                                                                                   \
   do {                                                                                                                        \
-    if (e0 != nullptr)                                                                                                        \
-      hipExtLaunchKernelGGL(KERNEL, dim3(nblocks), dim3(kAccBlock), 0, stream, e0, e1, 0, src, tgt, grid, st, partials, corr_match, \
-                            corr_d2, hint, ghint, qorder, qclass, chunk_order, chunk_cost, plan_info, S_atomic, mflag, chain, chain_seq, pace, launch_no, wait_ticks, cert_q, cert_pos, cert_stats, cert_l); \
+    if (a.e0 != nullptr)                                                                                                      \
+      hipExtLaunchKernelGGL(KERNEL, dim3(a.nblocks), dim3(kAccBlock), 0, a.stream, a.e0, a.e1, 0, a.src, a.tgt, a.grid, a.st, a.partials, a.corr_match, \
+                            a.corr_d2, a.hint, a.ghint, a.qorder, a.qclass, a.chunk_order, a.chunk_cost, a.plan_info, a.S_atomic, mflag, a.chain, a.chain_seq, a.pace, a.launch_no, a.wait_ticks, a.cert_q, a.cert_pos, a.cert_stats, a.cert_l); \
     else                                                                                                                      \
-      hipLaunchKernelGGL(KERNEL, dim3(nblocks), dim3(kAccBlock), 0, stream, src, tgt, grid, st, partials, corr_match, corr_d2, \
-                         hint, ghint, qorder, qclass, chunk_order, chunk_cost, plan_info, S_atomic, mflag, chain, chain_seq, pace, launch_no, wait_ticks, cert_q, cert_pos, cert_stats, cert_l); \
+      hipLaunchKernelGGL(KERNEL, dim3(a.nblocks), dim3(kAccBlock), 0, a.stream, a.src, a.tgt, a.grid, a.st, a.partials, a.corr_match, a.corr_d2, \
+                         a.hint, a.ghint, a.qorder, a.qclass, a.chunk_order, a.chunk_cost, a.plan_info, a.S_atomic, mflag, a.chain, a.chain_seq, a.pace, a.launch_no, a.wait_ticks, a.cert_q, a.cert_pos, a.cert_stats, a.cert_l); \
   } while (0)
-  if (cert_q != nullptr) { if (nrm) OPE_KLAUNCH((icp_accumulate_grid_kernel<true, true>)); else OPE_KLAUNCH((icp_accumulate_grid_kernel<false, true>)); }
+  const bool nrm = a.nrm;
+  if (a.cert_q != nullptr) { if (nrm) OPE_KLAUNCH((icp_accumulate_grid_kernel<true, true>)); else OPE_KLAUNCH((icp_accumulate_grid_kernel<false, true>)); }
   else if (nrm) OPE_KLAUNCH((icp_accumulate_grid_kernel<true>));
   else OPE_KLAUNCH((icp_accumulate_grid_kernel<false>));
 #undef OPE_KLAUNCH

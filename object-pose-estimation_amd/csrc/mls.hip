@@ -30,8 +30,6 @@
 
 namespace ope {
 
-hipError_t self_leaves(hipStream_t, const BvhView &, size_t, uint32_t *);   // features.hip
-
 constexpr int kMlsBlock = 256;
 
 struct MlsPlaneVisitor {

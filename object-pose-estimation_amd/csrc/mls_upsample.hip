@@ -27,8 +27,6 @@
 
 namespace ope {
 
-hipError_t self_leaves(hipStream_t, const BvhView &, size_t, uint32_t *);   // features.hip
-
 constexpr int kUpBlock = 256;
 constexpr unsigned long long kNoKey = ~0ull;              // a dropped dilation neighbour: sorts behind every key
 constexpr unsigned long long kMaxDataSize = 1ull << 21;   // keys stay below 2^63

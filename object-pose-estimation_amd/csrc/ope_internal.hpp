@@ -672,6 +672,100 @@ void grej_free(GrejWork *w);
 // features.hip: the SAC-IA host side that ope_sacia and ope_coarse_pose_batch share (same draws, same fits)
 void sacia_draws(const float *xyz, int ns, int S, int K, int H, float min_sample_dist, uint64_t seed, int32_t *samp, int32_t *pick);
 void umeyama_host(const float *src, const float *dst, int n, float T[16]);
-void colmajor_to_rows12(const float *T, float rows[12]);
+void colmajor_to_rows12(const float *T, float rows[12]);   // column-major 4x4 -> 12 floats, rows of [R|t]
+hipError_t self_leaves(hipStream_t stream, const BvhView &t, size_t n_total, uint32_t *leaf_of_orig);
+
+// icp_kernels.hip: the arguments of one accumulate launch (api.hip: enqueue_accumulate fills them name by name).  AccLaunch is what
+// the tree and the grid kernel share; a kernel still receives its arguments one by one, in its own order.
+struct AccLaunch {
+  hipStream_t stream = nullptr;
+  int nblocks = 0;
+  bool nrm = false, measuring = false;
+  CloudView src{};
+  BvhView tgt{};
+  const IcpState *st = nullptr;
+  double *partials = nullptr, *S_atomic = nullptr;
+  int32_t *corr_match = nullptr;
+  float *corr_d2 = nullptr;
+  uint32_t *hint = nullptr, *chunk_cost = nullptr;
+  const uint32_t *chunk_order = nullptr, *plan_info = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  uint32_t *chain = nullptr, *pace = nullptr;
+  uint32_t chain_seq = 0, launch_no = 0, wait_ticks = 0;
+  float4 *cert_q = nullptr;
+  uint32_t *cert_pos = nullptr;
+  float *cert_l = nullptr;
+};
+struct AccTreeLaunch : AccLaunch {
+  int mode = 0, k_normal_shooting = 0;
+  bool recip = false, packet = false;
+  BvhView srcix{};
+  uint32_t *work_counter = nullptr, *deal = nullptr;
+  uint32_t deal_parity = 0;
+  const uint32_t *slot_list = nullptr, *plan_out = nullptr;
+  float *knn_rk = nullptr;
+};
+struct AccGridLaunch : AccLaunch {
+  GridView grid{};
+  uint32_t *ghint = nullptr, *cert_stats = nullptr;
+  const uint32_t *qorder = nullptr;
+  unsigned char *qclass = nullptr;
+};
+void launch_icp_accumulate(const AccTreeLaunch &a);
+void launch_icp_accumulate_grid(const AccGridLaunch &a);
+// icp_kernels.hip: the other launchers of the ICP loop, the plain searches and the fitness pass
+int icp_accumulate_blocks_per_cu(bool nrm, bool packet, bool grid);
+int icp_accumulate_cert_blocks_per_cu(bool nrm, bool packet, bool grid);
+void launch_icp_reduce_update(hipStream_t stream, IcpState *st, const double *partials, double *S, int nblocks, bool do_update,
+                              uint32_t *work_counter);
+void launch_icp_p2p_update(hipStream_t stream, IcpState *st, double *S, int nsums, const P2pView &pv, uint32_t seq,
+                           unsigned long long timeout_ticks, bool do_update, double *out_sums);
+void launch_icp_lm_update(hipStream_t stream, IcpState *st, double *S, double *stats);
+void launch_icp_update_chained(hipStream_t stream, IcpState *st, int nsums, uint32_t *chain, uint32_t seq, uint32_t tickets, uint32_t wait_ticks);
+void launch_icp_update(hipStream_t stream, IcpState *st, double *S, int nsums, const float *Tk_ext);
+void launch_gather_fixed_pairs(hipStream_t stream, const CloudView &src, const CloudView &tgt, const uint32_t *pos, uint32_t n, float4 *fix);
+void launch_icp_fixed_pairs(hipStream_t stream, const IcpState *st, const float4 *fix, uint32_t n, double *S, float2 *seen);
+void launch_pairs_svd(hipStream_t stream, const float *d_src, const float *d_tgt, uint32_t n, double *d_partials, int nblocks, float *d_out_T);
+void launch_nn_search(hipStream_t stream, const CloudView &q, const BvhView &tgt, const float *d_T, int32_t *out_idx, float *out_d2);
+void launch_knn_search(hipStream_t stream, const CloudView &q, const BvhView &tgt, const float *d_T, int k, int32_t *out_idx, float *out_d2);
+void launch_seed_hints(hipStream_t stream, const CloudView &src, const BvhView &tgt, const IcpState *st, uint32_t *hint);
+void launch_fitness(hipStream_t stream, int nblocks, const CloudView &q, const BvhView &tgt, const float *d_T, double max_range,
+                    double *partials, const uint32_t *hint);
+// lm.hip
+void launch_lm_pos_to_orig(hipStream_t stream, const BvhView &tgt, int32_t *d_corr, uint32_t n);
+void launch_lm_stats(hipStream_t stream, int n_cu, const CloudView &src, const BvhView &tgt, const IcpState *st, const int32_t *d_corr_pos,
+                     double *d_stats);
+// sampling.hip: the plan steps of the accumulate launches, and ope_cloud_concat's device side
+int chunk_plan(hipStream_t stream, const uint32_t *cost, uint32_t *cost_sorted, const uint32_t *ids, uint32_t *order, uint32_t n, void *tmp,
+               size_t &tmp_bytes);
+void plan_slots(hipStream_t stream, const uint32_t *cost_sorted_desc, uint32_t n, const uint32_t *plan_info, uint32_t slots, float share,
+                uint32_t *slot_list);
+void plan_heavy(hipStream_t stream, const uint32_t *cost_sorted_desc, uint32_t n, float factor, float load_factor, uint32_t n_waves,
+                uint32_t slots, float share, uint32_t *plan_info);
+void grid_count_far(hipStream_t stream, const float *corr_d2, uint32_t n_valid, float thr2, uint32_t *plan_info);
+int grid_plan(hipStream_t stream, bool repartition, const unsigned char *qclass, uint32_t n_valid, uint32_t *qorder, uint32_t *plan_info,
+              const uint32_t *cost, uint32_t *keys, uint32_t *cost_sorted, const uint32_t *ids, uint32_t *order, uint32_t nch, uint32_t n_waves,
+              float factor_override, float load_factor, void *tmp, size_t tmp_bytes);
+size_t grid_plan_tmp_bytes(uint32_t n_valid, uint32_t nch);
+void fill_iota(hipStream_t stream, uint32_t *v, uint32_t n);
+hipError_t concat_device(hipStream_t stream, const CloudView &a, const float *d_T_rows, const CloudView &b, float *d_raw, float lo[3],
+                         float hi[3], const uint32_t *rgb_a, const uint32_t *rgb_b, uint32_t *d_rgb_raw);
+// bvh_build_device.hip
+hipError_t build_bvh_device(hipStream_t stream, const float4 *d_src, const float4 *d_src_nrm, size_t n, int leaf_size, const float bb_lo[3],
+                            const float bb_hi[3], int *out_depth, float4 **d_nodes, float4 **d_pts, float4 **d_nrm, float4 **d_axis2,
+                            bool tmp_alloc);
+// grid_build.hip
+hipError_t build_grid_device(hipStream_t stream, const float4 *d_pts, const float4 *d_nrm, size_t n_, const float bb_lo[3],
+                             const float bb_hi[3], double fill_target, uint32_t max_cells, GridView *out, float4 **out_gpts, float4 **out_gnrm,
+                             uint32_t **out_cell_start, uint32_t **out_gpos);
+void grid_hints_to_leaves(hipStream_t stream, const uint32_t *ghint, const uint32_t *gpos_of_bvhpos, uint32_t nq, uint32_t n_t, int depth,
+                          uint32_t *hint, uint32_t *d_inv);
+void grid_count_outside(hipStream_t stream, const CloudView &src, const float rows[12], const float lo[3], const float hi[3], float margin,
+                        uint32_t *d_count);
+// comm.cpp
+int comm_allreduce_sums(ope_ctx *ctx, double *d_sums, int count);
+bool comm_uses_p2p(const ope_ctx *ctx);
+int comm_p2p_exchange_update(ope_ctx *ctx, IcpState *d_state, double *d_sums, int nsums);
+int comm_p2p_exchange(ope_ctx *ctx, double *d_sums, int nsums);
 
 }  // namespace ope

@@ -38,8 +38,6 @@
 
 namespace ope {
 
-hipError_t self_leaves(hipStream_t, const BvhView &, size_t, uint32_t *);   // features.hip
-
 namespace {
 
 // normals passed in (ORIGINAL order, w = curvature) -> the cloud's sorted order

@@ -36,8 +36,6 @@
 
 namespace ope {
 
-hipError_t self_leaves(hipStream_t, const BvhView &, size_t, uint32_t *);   // features.hip
-
 namespace {
 
 constexpr int kRgbMaxK = 128;

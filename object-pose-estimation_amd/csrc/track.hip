@@ -23,8 +23,6 @@
 
 namespace ope {
 
-void launch_pairs_svd(hipStream_t, const float *, const float *, uint32_t, double *, int, float *);
-
 namespace {
 
 constexpr int kGateBlock = 256;
