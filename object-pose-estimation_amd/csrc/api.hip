@@ -10,6 +10,7 @@
 #include <thread>
 
 #include "ope_internal.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 
@@ -1025,9 +1026,8 @@ int ope_icp_begin(ope_ctx *ctx, const ope_cloud *src, const ope_index *tgt, cons
 void ope::icp_state_init(IcpState *h, const ope_cloud *src, const ope_index *tgt, const float *guess, const ope_icp_params &p, bool cert_run,
                          bool cluttered) {
   std::memset(h, 0, sizeof *h);
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  const float *g = guess ? guess : I4;
-  for (int i = 0; i < 16; ++i) { h->F[i] = g[i]; h->Tk[i] = I4[i]; }
+  const float *g = guess ? guess : kIdentity4;
+  for (int i = 0; i < 16; ++i) { h->F[i] = g[i]; h->Tk[i] = kIdentity4[i]; }
   colmajor_to_rows12(g, h->Ff);
   for (int d = 0; d < 3; ++d) h->pivot[d] = tgt->pivot[d];
   h->prev_mse = h->cur_mse = std::numeric_limits<double>::max();
@@ -1735,8 +1735,7 @@ int ope_icp_last_incremental(ope_ctx *ctx, float out_T[16]) {
 
 int ope_icp_run(ope_ctx *ctx, const ope_cloud *src, const ope_index *tgt, const float *guess,
                 const ope_icp_params *params, float out_T[16], ope_icp_result *result) {
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  if (out_T) std::memcpy(out_T, I4, sizeof I4);
+  if (out_T) std::memcpy(out_T, kIdentity4, sizeof kIdentity4);
   if (result) std::memset(result, 0, sizeof *result);
   int rc = ope_icp_begin(ctx, src, tgt, guess, params);
   if (rc != OPE_OK) return rc;

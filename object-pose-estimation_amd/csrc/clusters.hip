@@ -29,6 +29,7 @@
 
 #include "coarse_stages.hpp"
 #include "morton.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 namespace {
@@ -392,8 +393,6 @@ int bits_for(unsigned long long v) {   // bits that hold every value <= v
   return b;
 }
 
-unsigned grid_of(size_t n) { return (unsigned)std::max<size_t>((n + kCcBlock - 1) / kCcBlock, 1); }
-
 struct Result {
   uint32_t K = 0;                  // kept components
   std::vector<uint32_t> off;       // offsets of the written clusters (kw + 1)
@@ -432,26 +431,12 @@ int make_grid(ope_ctx *ctx, const char *who, const ope_cloud *cloud, double tol_
   return OPE_OK;
 }
 
-#define CC_LAUNCH(name, bytes, ...)                  \
-  do {                                               \
-    KernelTimer kt_(ctx, #name, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++ctx->cluster_stats.launches;                   \
-  } while (0)
-#define CC_PRIM(label, call)                          \
-  do {                                                \
-    if (e == hipSuccess) {                            \
-      KernelTimer kt_(ctx, label, 0.0);               \
-      e = (call);                                     \
-      ++ctx->cluster_stats.launches;                  \
-    }                                                 \
-  } while (0)
-
 // Steps 1-4.  On success, the device buffers the _cloud form needs stay in tmp: *d_idx (the written clusters' points, packed),
 // *d_roff (offsets), *d_pts_by_o, *d_pos_by_o.  want_idx / want_label: what comes back to the host.
 int cluster_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *cloud, const ope_cluster_params &p, size_t max_clusters,
                  bool want_idx, int32_t *out_idx, int32_t *out_offsets, int32_t *out_label, Result &res, const int32_t **d_idx_out,
                  const uint32_t **d_roff_out, const float4 **d_pts_out, const uint32_t **d_pos_out) {
+  ope_cluster_stats &St = ctx->cluster_stats;
   const uint32_t n = (uint32_t)cloud->n, n_valid = (uint32_t)cloud->n_valid;
   const float tol_f = (float)p.tolerance;
   const float r2 = (float)((double)tol_f * (double)tol_f);
@@ -504,34 +489,36 @@ int cluster_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *c
   if (e == hipSuccess) e = hipMemsetAsync(rank_of, 0xff, 4ull * n, st);
   if (e == hipSuccess) e = hipMemsetAsync(rsize + n, 0, 4, st);
   if (e == hipSuccess) e = hipMemsetAsync(cstart, 0, 4, st);
-  ctx->cluster_stats.launches += 6;
+  St.launches += 6;
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  CC_LAUNCH(cc_key_kernel, 40.0 * n, dim3(grid_of(n)), dim3(kCcBlock), 0, st, cv, g, n_cells, keys, vals, pts_by_o, pos_by_o);
-  CC_PRIM("cc_sort_cells", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), keys, skey, vals, sval, n, 0, cell_bits, st));
+  STAGE_LAUNCH(ctx, St.launches, cc_key_kernel, 40.0 * n, dim3(grid_of(n, kCcBlock)), dim3(kCcBlock), 0, st, cv, g, n_cells, keys, vals, pts_by_o, pos_by_o);
+  STAGE_PRIM(ctx, St.launches, e, "cc_sort_cells", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), keys, skey, vals, sval, n, 0, cell_bits, st));
   // 2. cells
   if (e == hipSuccess && n_valid > 0) {
-    CC_LAUNCH(cc_head_kernel, 20.0 * n_valid, dim3(grid_of(n_valid)), dim3(kCcBlock), 0, st, skey, n_valid, head);
-    CC_PRIM("cc_scan_cells", rocprim::inclusive_scan(d_tmp, (t1 = tb), head, cid1, n_valid, rocprim::plus<uint32_t>(), st));
+    STAGE_LAUNCH(ctx, St.launches, cc_head_kernel, 20.0 * n_valid, dim3(grid_of(n_valid, kCcBlock)), dim3(kCcBlock), 0, st, skey, n_valid, head);
+    STAGE_PRIM(ctx, St.launches, e, "cc_scan_cells", rocprim::inclusive_scan(d_tmp, (t1 = tb), head, cid1, n_valid, rocprim::plus<uint32_t>(), st));
   }
-  CC_LAUNCH(cc_cells_kernel, 60.0 * n, dim3(grid_of(n)), dim3(kCcBlock), 0, st, skey, sval, cid1, pts_by_o, n, n_valid, cstart, ckey, parent,
-            cellof, cpts, d_m);
+  STAGE_LAUNCH(ctx, St.launches, cc_cells_kernel, 60.0 * n, dim3(grid_of(n, kCcBlock)), dim3(kCcBlock), 0, st, skey, sval, cid1, pts_by_o, n, n_valid, cstart,
+               ckey, parent, cellof, cpts, d_m);
   // 3. unions: face neighbours, the other forward neighbours, flatten
   const unsigned link_blocks = (unsigned)std::min<size_t>(std::max<size_t>(((size_t)n_valid + kCcWaves - 1) / kCcWaves, 1), (size_t)ctx->n_cu * 32);
-  CC_LAUNCH(cc_link_kernel, 0.0, dim3(link_blocks), dim3(kCcBlock), 0, st, ckey, cstart, cpts, d_m, g, r2, 0, kFaceOffsets, parent, pairs);
-  CC_LAUNCH(cc_link_kernel, 0.0, dim3(link_blocks), dim3(kCcBlock), 0, st, ckey, cstart, cpts, d_m, g, r2, kFaceOffsets, kForwardOffsets, parent, pairs);
-  const unsigned flat_blocks = (unsigned)std::min<size_t>(grid_of(n_valid), (size_t)ctx->n_cu * 16);
-  CC_LAUNCH(cc_flatten_kernel, 8.0 * n_valid, dim3(flat_blocks), dim3(kCcBlock), 0, st, d_m, parent);
+  STAGE_LAUNCH(ctx, St.launches, cc_link_kernel, 0.0, dim3(link_blocks), dim3(kCcBlock), 0, st, ckey, cstart, cpts, d_m, g, r2, 0, kFaceOffsets, parent, pairs);
+  STAGE_LAUNCH(ctx, St.launches, cc_link_kernel, 0.0, dim3(link_blocks), dim3(kCcBlock), 0, st, ckey, cstart, cpts, d_m, g, r2, kFaceOffsets, kForwardOffsets,
+               parent, pairs);
+  const unsigned flat_blocks = (unsigned)std::min<size_t>(grid_of(n_valid, kCcBlock), (size_t)ctx->n_cu * 16);
+  STAGE_LAUNCH(ctx, St.launches, cc_flatten_kernel, 8.0 * n_valid, dim3(flat_blocks), dim3(kCcBlock), 0, st, d_m, parent);
   // 4. components, ranks, offsets, labels, indices by rank
-  CC_LAUNCH(cc_comp_kernel, 32.0 * n_valid, dim3(grid_of(n_valid)), dim3(kCcBlock), 0, st, d_m, parent, cstart, cpts, csize, cmin);
-  CC_LAUNCH(cc_rank_key_kernel, 28.0 * n, dim3(grid_of(n)), dim3(kCcBlock), 0, st, d_m, parent, csize, cmin, cpts, n, n_valid, bn,
-            (uint32_t)p.min_size, (uint32_t)p.max_size, drop, keys, vals);
-  CC_PRIM("cc_sort_ranks", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), keys, skey, vals, sval, n, 0, 2 * bn, st));
-  CC_LAUNCH(cc_rank_kernel, 24.0 * n, dim3(grid_of(n)), dim3(kCcBlock), 0, st, skey, sval, n, bn, drop, rank_of, rsize, d_K);
-  CC_PRIM("cc_scan_offsets", rocprim::exclusive_scan(d_tmp, (t1 = tb), rsize, roff, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+  STAGE_LAUNCH(ctx, St.launches, cc_comp_kernel, 32.0 * n_valid, dim3(grid_of(n_valid, kCcBlock)), dim3(kCcBlock), 0, st, d_m, parent, cstart, cpts, csize,
+               cmin);
+  STAGE_LAUNCH(ctx, St.launches, cc_rank_key_kernel, 28.0 * n, dim3(grid_of(n, kCcBlock)), dim3(kCcBlock), 0, st, d_m, parent, csize, cmin, cpts, n, n_valid,
+               bn, (uint32_t)p.min_size, (uint32_t)p.max_size, drop, keys, vals);
+  STAGE_PRIM(ctx, St.launches, e, "cc_sort_ranks", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), keys, skey, vals, sval, n, 0, 2 * bn, st));
+  STAGE_LAUNCH(ctx, St.launches, cc_rank_kernel, 24.0 * n, dim3(grid_of(n, kCcBlock)), dim3(kCcBlock), 0, st, skey, sval, n, bn, drop, rank_of, rsize, d_K);
+  STAGE_PRIM(ctx, St.launches, e, "cc_scan_offsets", rocprim::exclusive_scan(d_tmp, (t1 = tb), rsize, roff, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
   auto *lkey = (uint32_t *)head, *lval = cid1, *lkey2 = (uint32_t *)csize, *idx = (uint32_t *)cmin;   // (free again by now)
-  CC_LAUNCH(cc_label_kernel, 36.0 * n, dim3(grid_of(n)), dim3(kCcBlock), 0, st, cpts, cellof, parent, rank_of, n, n_valid, (uint32_t)kcap, label, lkey,
-            lval);
-  CC_PRIM("cc_sort_labels", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), lkey, lkey2, lval, idx, n, 0, lbits, st));
+  STAGE_LAUNCH(ctx, St.launches, cc_label_kernel, 36.0 * n, dim3(grid_of(n, kCcBlock)), dim3(kCcBlock), 0, st, cpts, cellof, parent, rank_of, n, n_valid,
+               (uint32_t)kcap, label, lkey, lval);
+  STAGE_PRIM(ctx, St.launches, e, "cc_sort_labels", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), lkey, lkey2, lval, idx, n, 0, lbits, st));
   // the one read-back: m, K, pair tests, offsets, indices, labels
   unsigned long long hw[2] = {0, 0};
   std::vector<uint32_t> off(kcap + 1, 0);
@@ -540,10 +527,10 @@ int cluster_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *c
   if (e == hipSuccess && want_idx && n) e = hipMemcpyAsync(out_idx, idx, 4ull * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && out_label && n) e = hipMemcpyAsync(out_label, label, 4ull * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  ++ctx->cluster_stats.host_syncs;
+  ++St.host_syncs;
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  ctx->cluster_stats.cells = (int64_t)(uint32_t)hw[0];
-  ctx->cluster_stats.pairs_tested = (int64_t)hw[1];
+  St.cells = (int64_t)(uint32_t)hw[0];
+  St.pairs_tested = (int64_t)hw[1];
   res.K = (uint32_t)(hw[0] >> 32);
   res.kw = std::min<size_t>(res.K, kcap);
   off.resize(res.kw + 1);
@@ -562,20 +549,6 @@ int cluster_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *c
 // The tail of the _cloud forms (ope_euclidean_clusters_cloud, ope_region_grow_cloud): the kw written clusters (host offsets `off`,
 // device offsets d_roff, packed ORIGINAL indices d_idx) as new device clouds, gathered, boxed, Morton-sorted and scattered in
 // batched launches.  d_pts_by_o / d_pos_by_o: the input cloud's points and sorted positions by original index.
-#define CB_LAUNCH(name, bytes, ...)                  \
-  do {                                               \
-    KernelTimer kt_(ctx, #name, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++*launches;                                     \
-  } while (0)
-#define CB_PRIM(label, call)                          \
-  do {                                                \
-    if (e == hipSuccess) {                            \
-      KernelTimer kt_(ctx, label, 0.0);               \
-      e = (call);                                     \
-      ++*launches;                                    \
-    }                                                 \
-  } while (0)
 int clusters_build_clouds(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *cloud, size_t kw, const std::vector<uint32_t> &off,
                           const int32_t *d_idx, const uint32_t *d_roff, const float4 *d_pts, const uint32_t *d_pos, ope_cloud **out_clouds,
                           int64_t *launches, int64_t *host_syncs) {
@@ -608,13 +581,13 @@ int clusters_build_clouds(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope
   if (e == hipSuccess) { e = h2d_copy(ctx->stream, d_outs, outs.data(), sizeof(ClusterOut) * kw); ++*launches; }
   const hipStream_t st = ctx->stream;
   if (e == hipSuccess) {
-    CB_LAUNCH(cc_gather_box_kernel, 24.0 * total, dim3((unsigned)kw), dim3(kCcBlock), 0, st, d_idx, d_roff, d_pts, raw, clof, bb);
-    CB_LAUNCH(cc_morton_key_kernel, 32.0 * total, dim3(grid_of(total)), dim3(kCcBlock), 0, st, raw, clof, bb, total, mkey, mval);
-    CB_PRIM("cc_sort_morton", rocprim::radix_sort_pairs(d_tmp, tb, mkey, mkey2, mval, mval2, total, 0, mbits, st));
+    STAGE_LAUNCH(ctx, *launches, cc_gather_box_kernel, 24.0 * total, dim3((unsigned)kw), dim3(kCcBlock), 0, st, d_idx, d_roff, d_pts, raw, clof, bb);
+    STAGE_LAUNCH(ctx, *launches, cc_morton_key_kernel, 32.0 * total, dim3(grid_of(total, kCcBlock)), dim3(kCcBlock), 0, st, raw, clof, bb, total, mkey, mval);
+    STAGE_PRIM(ctx, *launches, e, "cc_sort_morton", rocprim::radix_sort_pairs(d_tmp, tb, mkey, mkey2, mval, mval2, total, 0, mbits, st));
   }
   if (e == hipSuccess)
-    CB_LAUNCH(cc_cloud_scatter_kernel, 48.0 * total, dim3(grid_of(total)), dim3(kCcBlock), 0, st, mkey2, mval2, d_roff, raw, d_idx, d_pos,
-              cloud->d_nrm, (const uint32_t *)cloud->d_rgb, d_outs, total);
+    STAGE_LAUNCH(ctx, *launches, cc_cloud_scatter_kernel, 48.0 * total, dim3(grid_of(total, kCcBlock)), dim3(kCcBlock), 0, st, mkey2, mval2, d_roff, raw, d_idx,
+                 d_pos, cloud->d_nrm, (const uint32_t *)cloud->d_rgb, d_outs, total);
   std::vector<uint32_t> h_bb(8 * kw);
   if (e == hipSuccess) e = hipMemcpyAsync(h_bb.data(), bb, 32ull * kw, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -635,8 +608,6 @@ int clusters_build_clouds(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope
   }
   return OPE_OK;
 }
-#undef CB_LAUNCH
-#undef CB_PRIM
 
 }  // namespace ope
 

@@ -26,6 +26,7 @@
 
 #include "coarse_stages.hpp"
 #include "feature_math.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 
@@ -340,20 +341,14 @@ hipError_t coarse_sample_segments(ope_ctx *ctx, CallTmp &tmp, const CoarseSeg *d
   if (total) e = rocprim::segmented_radix_sort_pairs(d_tmp, tb, d_keys, d_keys2, d_vals, d_vals2, total, (unsigned)nseg, d_off, d_off + 1, 0,
                                                      kKeyBits, ctx->stream);
   if (e != hipSuccess) return e;
-  {
-    KernelTimer kt(ctx, "coarse_voxel_pick_kernel", 40.0 * total);
-    hipLaunchKernelGGL(coarse_voxel_pick_kernel, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off, (uint32_t)nseg, total, d_keys2,
-                       d_vals2, d_win, d_flags);
-  }
+  STAGE_LAUNCH_TIMED(ctx, coarse_voxel_pick_kernel, "coarse_voxel_pick_kernel", 40.0 * total, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off,
+                     (uint32_t)nseg, total, d_keys2, d_vals2, d_win, d_flags);
   what = "scan";
   tb = std::max(tb_sort, tb_scan);
   e = rocprim::exclusive_scan(d_tmp, tb, d_flags, d_slot, 0u, (size_t)nt1, rocprim::plus<uint32_t>(), ctx->stream);
   if (e != hipSuccess) return e;
-  {
-    KernelTimer kt(ctx, "coarse_key_pack_kernel", 28.0 * total);
-    hipLaunchKernelGGL(coarse_key_pack_kernel, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off, (uint32_t)nseg, total, d_win,
-                       d_flags, d_slot, d_kp, d_key_off);
-  }
+  STAGE_LAUNCH_TIMED(ctx, coarse_key_pack_kernel, "coarse_key_pack_kernel", 28.0 * total, dim3(nb), dim3(kCoarseBlock), 0, ctx->stream, d_segs, d_off,
+                     (uint32_t)nseg, total, d_win, d_flags, d_slot, d_kp, d_key_off);
   what = "uniform sampling";
   e = hipMemcpyAsync(key_off.data(), d_key_off, 4 * (nseg + 1), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess && extra_bytes) e = hipMemcpyAsync(h_extra, d_extra, extra_bytes, hipMemcpyDeviceToHost, ctx->stream);
@@ -580,12 +575,11 @@ int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, 
   if (e != hipSuccess) return fail("download");
   const std::vector<float4> &h_kp = front.h_kp;
 
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::vector<int2> active;   // (segment, distinct samples) of every cluster that runs SAC-IA
   std::vector<size_t> active_cluster;
   for (size_t i = 0; i < n; ++i) {
     ope_coarse_batch_result &o = out[i];
-    std::memcpy(o.T, I4, sizeof I4);
+    std::memcpy(o.T, kIdentity4, sizeof kIdentity4);
     o.best_error = 0;
     o.best_iteration = -1;
     o.n_src_keys = (int32_t)nsk;
@@ -632,11 +626,8 @@ int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, 
   if (e == hipSuccess) e = h2d_copy(ctx->stream, d_uniq, uniq.data(), 4 * uniq.size());
   if (e != hipSuccess) return fail("buffers");
   std::vector<int32_t> nn(uniq.size() * K);
-  {
-    KernelTimer kt(ctx, "coarse_feature_knn_kernel", 132.0 * (double)uniq.size() * (double)max_keys);
-    hipLaunchKernelGGL(coarse_feature_knn_kernel, dim3((unsigned)max_uniq, (unsigned)na), dim3(256), 0, ctx->stream, d_fpfh, d_key_off,
-                       d_active, d_uniq, max_uniq, K, d_nn);
-  }
+  STAGE_LAUNCH_TIMED(ctx, coarse_feature_knn_kernel, "coarse_feature_knn_kernel", 132.0 * (double)uniq.size() * (double)max_keys,
+                     dim3((unsigned)max_uniq, (unsigned)na), dim3(256), 0, ctx->stream, d_fpfh, d_key_off, d_active, d_uniq, max_uniq, K, d_nn);
   e = hipMemcpyAsync(nn.data(), d_nn, 4 * nn.size(), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) return fail("feature knn");
@@ -665,11 +656,8 @@ int ope::coarse_pose_batch_impl(ope_ctx *ctx, const ope_cloud *model, size_t n, 
   if (e == hipSuccess) e = hipFuncSetAttribute((const void *)coarse_sacia_error_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16 * max_keys));
   if (e != hipSuccess) return fail("buffers");
   std::vector<double> err(na * (size_t)H);
-  {
-    KernelTimer kt(ctx, "coarse_sacia_error_kernel", 16.0 * (double)nsk * (double)H * (double)na);
-    hipLaunchKernelGGL(coarse_sacia_error_kernel, dim3((unsigned)H, (unsigned)na), dim3(256), 16 * (size_t)max_keys, ctx->stream, d_kp, d_key_off,
-                       d_active, d_rows, (float)p.sacia.max_corr_dist, d_err);
-  }
+  STAGE_LAUNCH_TIMED(ctx, coarse_sacia_error_kernel, "coarse_sacia_error_kernel", 16.0 * (double)nsk * (double)H * (double)na, dim3((unsigned)H, (unsigned)na),
+                     dim3(256), 16 * (size_t)max_keys, ctx->stream, d_kp, d_key_off, d_active, d_rows, (float)p.sacia.max_corr_dist, d_err);
   e = hipMemcpyAsync(err.data(), d_err, sizeof(double) * err.size(), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) return fail("error metric");

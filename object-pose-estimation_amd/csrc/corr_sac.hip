@@ -29,6 +29,7 @@
 
 #include "coarse_stages.hpp"
 #include "corr_sac_math.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 
@@ -103,27 +104,6 @@ __global__ __launch_bounds__(1024) void cs_pack_kernel(const float4 *__restrict_
   cs_pack_block(ps, pt, n, F, thr2, all, pos, sx, tx, d_cnt);
 }
 
-unsigned grid_of(size_t n, int block = kCsBlock) { return (unsigned)std::max<size_t>((n + block - 1) / block, 1); }
-
-#define CS_LAUNCH(name, bytes, ...)                  \
-  do {                                               \
-    KernelTimer kt_(ctx, #name, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++St.launches;                                   \
-  } while (0)
-
-// A host array to the device in stream order, through the pinned staging block: one copy that does not synchronise (the caller
-// synchronises before it stages again).  Both uploads of a call fit the block (at most 32 KB of indices, 12 MB of samples).
-hipError_t upload_block(hipStream_t st, void *dst, const void *src, size_t bytes) {
-  unsigned char *blk = nullptr;
-  size_t cap = 0;
-  hipError_t e = stage_block(bytes, &blk, &cap);
-  if (e != hipSuccess) return e;
-  if (bytes > cap) return hipErrorInvalidValue;
-  std::memcpy(blk, src, bytes);
-  return hipMemcpyAsync(dst, blk, bytes, hipMemcpyHostToDevice, st);
-}
-
 }  // namespace
 }  // namespace ope
 
@@ -152,11 +132,8 @@ int ope_feature_correspondences(ope_ctx *ctx, const float *src_feat33, size_t n_
   if (e == hipSuccess) e = h2d_copy(st, d_sf, src_feat33, sb);
   if (e == hipSuccess) e = h2d_copy(st, d_tf, tgt_feat33, tb);
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  {
-    KernelTimer kt(ctx, "cs_match_kernel", 132.0 * ((double)n_src * (double)n_tgt + (double)n_src));
-    hipLaunchKernelGGL(cs_match_kernel, dim3((unsigned)n_src), dim3(256), 0, st, (const float *)d_tf, (int)n_tgt, (const float *)d_sf, (int32_t *)d_back,
-                       (float *)(d_back + 4 * n_src));
-  }
+  STAGE_LAUNCH_TIMED(ctx, cs_match_kernel, "cs_match_kernel", 132.0 * ((double)n_src * (double)n_tgt + (double)n_src), dim3((unsigned)n_src), dim3(256), 0, st,
+                     (const float *)d_tf, (int)n_tgt, (const float *)d_sf, (int32_t *)d_back, (float *)(d_back + 4 * n_src));
   std::vector<unsigned char> back(8 * n_src);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(back.data(), d_back, back.size(), hipMemcpyDeviceToHost, st);
@@ -188,11 +165,10 @@ int ope_corr_sac(ope_ctx *ctx, const ope_cloud *src, const ope_cloud *tgt, const
                  const ope_corr_sac_params *params, const int32_t *forced_samples, size_t n_forced, ope_corr_sac_result *out,
                  int32_t *out_inlier_pos) {
   static const char *who = "ope_corr_sac: ";
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   if (!ctx) return OPE_EINVAL;
   if (out) {
-    std::memcpy(out->T_best, I4, sizeof I4);
-    std::memcpy(out->T_svd, I4, sizeof I4);
+    std::memcpy(out->T_best, kIdentity4, sizeof kIdentity4);
+    std::memcpy(out->T_svd, kIdentity4, sizeof kIdentity4);
     out->inliers = 0;
     out->best = -1;
     out->iterations = 0;
@@ -203,15 +179,11 @@ int ope_corr_sac(ope_ctx *ctx, const ope_cloud *src, const ope_cloud *tgt, const
   ope_corr_sac_params p;
   ope_corr_sac_default_params(&p);
   if (params) p = *params;
-  if (p.max_iterations < 1 || p.max_iterations > kPrMaxIterations) return set_err(ctx, OPE_EINVAL, std::string(who) + "max_iterations must be 1 .. 2^20");
-  if (!(p.inlier_threshold > 0.0) || !std::isfinite(p.inlier_threshold))
-    return set_err(ctx, OPE_EINVAL, std::string(who) + "inlier_threshold must be > 0 and finite");
-  if (!(p.probability > 0.0 && p.probability < 1.0)) return set_err(ctx, OPE_EINVAL, std::string(who) + "probability must be inside (0, 1)");
+  if (const int rc = corr_sac_check_params(ctx, who, p)) return rc;
   if (n > (size_t)kCsMaxMatches) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than OPE_COARSE_MAX_KEYS matches");
   if (n_forced > (size_t)kPrMaxIterations + 1) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 2^20 + 1 forced samples");
   if (src->n > (size_t)0x7fffffff || tgt->n > (size_t)0x7fffffff) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 2^31 - 1 points");
-  if (ctx->nccl_comm != nullptr || ctx->p2p_ok || ctx->p2p_broken)
-    return set_err(ctx, OPE_EINVAL, std::string(who) + "the context carries a communicator (one device runs a whole alignment)");
+  if (const int rc = refuse_communicator(ctx, who)) return rc;
   for (size_t i = 0; i < n; ++i)
     if (src_idx[i] < 0 || (size_t)src_idx[i] >= src->n || tgt_idx[i] < 0 || (size_t)tgt_idx[i] >= tgt->n)
       return set_err(ctx, OPE_EINVAL, std::string(who) + "match index out of range");
@@ -269,15 +241,14 @@ int ope_corr_sac(ope_ctx *ctx, const ope_cloud *src, const ope_cloud *tgt, const
     std::vector<int32_t> both(2 * n);
     std::memcpy(both.data(), src_idx, 4 * n);
     std::memcpy(both.data() + n, tgt_idx, 4 * n);
-    e = upload_block(st, d_idx, both.data(), 8 * n);
-    ++St.launches;
+    e = upload_staged(st, d_idx, both.data(), 8 * n, &St.launches, &St.host_syncs);   // (at most 32 KB: one copy, no synchronisation)
   }
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  CS_LAUNCH(cs_orig_kernel, 32.0 * src->n, dim3(grid_of(src->n)), dim3(kCsBlock), 0, st, src->view(), src_o);
-  CS_LAUNCH(cs_orig_kernel, 32.0 * tgt->n, dim3(grid_of(tgt->n)), dim3(kCsBlock), 0, st, tgt->view(), tgt_o);
-  CS_LAUNCH(cs_gather_kernel, 72.0 * n, dim3(grid_of(n)), dim3(kCsBlock), 0, st, (const float4 *)src_o, (const float4 *)tgt_o, (const int32_t *)d_idx,
-            (const int32_t *)(d_idx + n), nn, d_ps, d_pt);
-  CS_LAUNCH(cs_thresh_kernel, 16.0 * n, dim3(1), dim3(kCsBlock), 0, st, (const float4 *)d_ps, nn, d_thr);
+  STAGE_LAUNCH(ctx, St.launches, cs_orig_kernel, 32.0 * src->n, dim3(grid_of(src->n, kCsBlock)), dim3(kCsBlock), 0, st, src->view(), src_o);
+  STAGE_LAUNCH(ctx, St.launches, cs_orig_kernel, 32.0 * tgt->n, dim3(grid_of(tgt->n, kCsBlock)), dim3(kCsBlock), 0, st, tgt->view(), tgt_o);
+  STAGE_LAUNCH(ctx, St.launches, cs_gather_kernel, 72.0 * n, dim3(grid_of(n, kCsBlock)), dim3(kCsBlock), 0, st, (const float4 *)src_o, (const float4 *)tgt_o,
+               (const int32_t *)d_idx, (const int32_t *)(d_idx + n), nn, d_ps, d_pt);
+  STAGE_LAUNCH(ctx, St.launches, cs_thresh_kernel, 16.0 * n, dim3(1), dim3(kCsBlock), 0, st, (const float4 *)d_ps, nn, d_thr);
   std::vector<unsigned char> down(16 * n + 16);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(down.data(), d_down, down.size(), hipMemcpyDeviceToHost, st);
@@ -299,8 +270,7 @@ int ope_corr_sac(ope_ctx *ctx, const ope_cloud *src, const ope_cloud *tgt, const
   {
     std::vector<int32_t> up(samp);
     up.resize(std::max<size_t>(up.size(), 3), 0);   // (one copy whether or not anything was drawn)
-    e = upload_block(st, d_samp, up.data(), 4 * up.size());
-    ++St.launches;
+    e = upload_staged(st, d_samp, up.data(), 4 * up.size(), &St.launches, &St.host_syncs);   // (at most 12 MB: one copy, no synchronisation)
   }
   if (e == hipSuccess) e = hipMemsetAsync(d_back + 64 * Hmax, 0, 4 * Hmax, st);
   ++St.launches;
@@ -310,12 +280,12 @@ int ope_corr_sac(ope_ctx *ctx, const ope_cloud *src, const ope_cloud *tgt, const
   const double thr2 = p.inlier_threshold * p.inlier_threshold;
   auto *d_T = (float *)d_back;
   auto *d_cnt = (uint32_t *)(d_back + 64 * Hmax);
-  CS_LAUNCH(cs_fit_kernel, 208.0 * H, dim3(grid_of(H, 64)), dim3(64), 0, st, (const float4 *)d_ps, (const float4 *)d_pt, (const int32_t *)d_samp, H, d_T,
-            d_rows);
-  const unsigned hb = grid_of(H), tiles = grid_of(n, kCsTile);
+  STAGE_LAUNCH(ctx, St.launches, cs_fit_kernel, 208.0 * H, dim3(grid_of(H, 64)), dim3(64), 0, st, (const float4 *)d_ps, (const float4 *)d_pt,
+               (const int32_t *)d_samp, H, d_T, d_rows);
+  const unsigned hb = grid_of(H, kCsBlock), tiles = grid_of(n, kCsTile);
   const unsigned split = std::min(tiles, std::max(1u, (2u * (unsigned)ctx->n_cu + hb - 1) / hb));
-  CS_LAUNCH(cs_count_kernel, 32.0 * n * hb + 52.0 * H, dim3(hb, split), dim3(kCsBlock), 0, st, (const float4 *)d_ps, (const float4 *)d_pt, nn,
-            (const float *)d_rows, H, thr2, d_cnt);
+  STAGE_LAUNCH(ctx, St.launches, cs_count_kernel, 32.0 * n * hb + 52.0 * H, dim3(hb, split), dim3(kCsBlock), 0, st, (const float4 *)d_ps, (const float4 *)d_pt,
+               nn, (const float *)d_rows, H, thr2, d_cnt);
   std::vector<float> Ts(16 * std::max<size_t>(H, 1));
   std::vector<uint32_t> cnts(std::max<size_t>(H, 1));
   e = hipGetLastError();
@@ -348,8 +318,8 @@ int ope_corr_sac(ope_ctx *ctx, const ope_cloud *src, const ope_cloud *tgt, const
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
   auto *d_pcnt = (uint32_t *)((unsigned char *)d_pos + 4 * n);
   auto *d_Tsvd = (float *)((unsigned char *)d_pos + 4 * n + 64);
-  CS_LAUNCH(cs_pack_kernel, 92.0 * n, dim3(1), dim3(1024), 0, st, (const float4 *)d_ps, (const float4 *)d_pt, nn, (const float *)d_wrows, thr2,
-            best >= 0 ? 0 : 1, d_pos, d_sx, d_tx, d_pcnt);
+  STAGE_LAUNCH(ctx, St.launches, cs_pack_kernel, 92.0 * n, dim3(1), dim3(1024), 0, st, (const float4 *)d_ps, (const float4 *)d_pt, nn, (const float *)d_wrows,
+               thr2, best >= 0 ? 0 : 1, d_pos, d_sx, d_tx, d_pcnt);
   {
     // (the two launches of ope_rigid_transform_svd, with its grid: the same bits for the same pairs)
     KernelTimer kt(ctx, "cs_pairs_svd", 24.0 * n_rem);

@@ -30,6 +30,7 @@
 
 #include "coarse_stages.hpp"
 #include "corr_sac_math.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 namespace {
@@ -171,38 +172,11 @@ __global__ __launch_bounds__(64) void csb_pairs_umeyama_kernel(const double *__r
   pairs_umeyama_block(partials + (size_t)a * kNumSums * max_blocks, (int)csb_svd_blocks(n), sx + 3 * (size_t)a * nsk, T_svd + 16 * (size_t)a);
 }
 
-unsigned grid_of(size_t n, int block) { return (unsigned)std::max<size_t>((n + block - 1) / block, 1); }
-
-#define CB_LAUNCH(name, bytes, ...)                  \
-  do {                                               \
-    KernelTimer kt_(ctx, #name, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++St.launches;                                   \
-  } while (0)
-
-// A host array to the device in stream order through the pinned staging block: one copy that does not synchronise (the caller
-// synchronises before it stages again).  Beyond the block's size: h2d_copy's synchronising pieces, counted in *syncs as h2d_copy
-// cuts them today (one piece and one synchronisation per staging block of `cap` bytes; stage_block has just sized the block, so
-// cap is the size h2d_copy uses).  If h2d_copy's chunking changes, this count has to follow it.
-hipError_t upload_staged(hipStream_t st, void *dst, const void *src, size_t bytes, int64_t *syncs) {
-  unsigned char *blk = nullptr;
-  size_t cap = 0;
-  hipError_t e = stage_block(bytes, &blk, &cap);
-  if (e != hipSuccess) return e;
-  if (bytes > cap) {
-    *syncs += (int64_t)((bytes + cap - 1) / cap);
-    return h2d_copy(st, dst, src, bytes);
-  }
-  std::memcpy(blk, src, bytes);
-  return hipMemcpyAsync(dst, blk, bytes, hipMemcpyHostToDevice, st);
-}
-
 }  // namespace
 
 int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                              const ope_coarse_params *front, const ope_corr_sac_params *params, const uint64_t *seeds, int keep_hypotheses,
                              ope_corr_sac_batch_result *out) {
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   if (!ctx) return OPE_EINVAL;
   if (n == 0) return OPE_OK;
   if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
@@ -213,15 +187,11 @@ int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *mod
   ope_corr_sac_params p;
   ope_corr_sac_default_params(&p);
   if (params) p = *params;
-  if (p.max_iterations < 1 || p.max_iterations > kPrMaxIterations) return set_err(ctx, OPE_EINVAL, std::string(who) + "max_iterations must be 1 .. 2^20");
-  if (!(p.inlier_threshold > 0.0) || !std::isfinite(p.inlier_threshold))
-    return set_err(ctx, OPE_EINVAL, std::string(who) + "inlier_threshold must be > 0 and finite");
-  if (!(p.probability > 0.0 && p.probability < 1.0)) return set_err(ctx, OPE_EINVAL, std::string(who) + "probability must be inside (0, 1)");
+  if (const int rc = corr_sac_check_params(ctx, who, p)) return rc;
   const size_t Hmax = (size_t)p.max_iterations + 1;
   if ((unsigned long long)n * (unsigned long long)Hmax > 0x7fffffffull)
     return set_err(ctx, OPE_EINVAL, std::string(who) + "clusters x (max_iterations + 1) above 2^31 - 1");
-  if (ctx->nccl_comm != nullptr || ctx->p2p_ok || ctx->p2p_broken)
-    return set_err(ctx, OPE_EINVAL, std::string(who) + "the context carries a communicator (one device runs a whole alignment)");
+  if (const int rc = refuse_communicator(ctx, who)) return rc;
   // the front end's refusals (sizes, key points; the model needs three key points)
   fp.sacia.nr_samples = 3; fp.sacia.k_correspondences = 1; fp.sacia.max_iterations = p.max_iterations;
   long long model_keys = -2;
@@ -251,8 +221,8 @@ int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *mod
   for (size_t i = 0; i < n; ++i) {
     ope_corr_sac_batch_result &o = out[i];
     std::memset(&o, 0, sizeof o);
-    std::memcpy(o.T_svd, I4, sizeof I4);
-    std::memcpy(o.T_best, I4, sizeof I4);
+    std::memcpy(o.T_svd, kIdentity4, sizeof kIdentity4);
+    std::memcpy(o.T_best, kIdentity4, sizeof kIdentity4);
     o.best = -1;
     o.n_src_keys = (int32_t)nsk;
     o.n_tgt_keys = (int32_t)(key_off[i + 2] - key_off[i + 1]);
@@ -282,8 +252,7 @@ int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *mod
   auto *d_down = (unsigned char *)tmp.get(down_bytes, e);
   auto *d_ps = (float4 *)tmp.get(16 * slots, e);
   auto *d_pt = (float4 *)tmp.get(16 * slots, e);
-  if (e == hipSuccess) e = upload_staged(st, d_active, active.data(), sizeof(int2) * na, &St.host_syncs);
-  ++St.launches;
+  if (e == hipSuccess) e = upload_staged(st, d_active, active.data(), sizeof(int2) * na, &St.launches, &St.host_syncs);
   if (e != hipSuccess) return fail("buffers");
   CbView v{};
   v.kp = fr.d_kp; v.fpfh = fr.d_fpfh; v.key_off = fr.d_key_off; v.active = d_active;
@@ -295,9 +264,9 @@ int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *mod
   v.mdist = (float *)(v.mtgt + slots);
   v.ps = d_ps; v.pt = d_pt;
   v.nsk = nsk; v.Hmax = (uint32_t)Hmax;
-  CB_LAUNCH(csb_match_kernel, 132.0 * (double)na * (double)nsk * (double)fr.max_keys, dim3(nsk, (unsigned)na), dim3(256), 0, st, v);
-  CB_LAUNCH(csb_compact_kernel, 52.0 * (double)slots, dim3((unsigned)na), dim3(1024), 0, st, v);
-  CB_LAUNCH(csb_thresh_kernel, 16.0 * (double)slots, dim3((unsigned)na), dim3(kCsBlock), 0, st, v);
+  STAGE_LAUNCH(ctx, St.launches, csb_match_kernel, 132.0 * (double)na * (double)nsk * (double)fr.max_keys, dim3(nsk, (unsigned)na), dim3(256), 0, st, v);
+  STAGE_LAUNCH(ctx, St.launches, csb_compact_kernel, 52.0 * (double)slots, dim3((unsigned)na), dim3(1024), 0, st, v);
+  STAGE_LAUNCH(ctx, St.launches, csb_thresh_kernel, 16.0 * (double)slots, dim3((unsigned)na), dim3(kCsBlock), 0, st, v);
   std::vector<unsigned char> down(down_bytes);
   e = hipGetLastError();
   if (e == hipSuccess) e = coarse_front_download(ctx, fr);
@@ -383,8 +352,7 @@ int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *mod
   const uint32_t max_blocks = std::min<uint32_t>(std::max<uint32_t>((nsk + 255) / 256, 1), 512);
   auto *d_part = (double *)tmp.get(sizeof(double) * kNumSums * (size_t)max_blocks * na, e);
   if (e != hipSuccess) return fail("buffers");
-  e = upload_staged(st, d_up, up.data(), up_bytes, &St.host_syncs);
-  ++St.launches;
+  e = upload_staged(st, d_up, up.data(), up_bytes, &St.launches, &St.host_syncs);
   if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, 4 * hyps, st);
   ++St.launches;
   if (e != hipSuccess) return fail("upload");
@@ -393,7 +361,8 @@ int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *mod
 
   // ---- e, f. fits and counts
   const double thr2 = p.inlier_threshold * p.inlier_threshold;
-  CB_LAUNCH(csb_fit_kernel, 208.0 * (double)St.hypotheses, dim3(grid_of(hyps, 64)), dim3(64), 0, st, v, d_rec, d_samp, (uint32_t)hyps, d_T, d_rows);
+  STAGE_LAUNCH(ctx, St.launches, csb_fit_kernel, 208.0 * (double)St.hypotheses, dim3(grid_of(hyps, 64)), dim3(64), 0, st, v, d_rec, d_samp, (uint32_t)hyps, d_T,
+               d_rows);
   uint32_t nm_max = 0;
   unsigned long long hyp_blocks = 0;
   for (size_t a = 0; a < na; ++a) {
@@ -402,8 +371,9 @@ int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *mod
   }
   const unsigned hb = grid_of(Hmax, kCsBlock), tiles = grid_of(nm_max, kCsTile);
   const unsigned split = (unsigned)std::min<unsigned long long>(tiles, std::max<unsigned long long>(1, (2ull * (unsigned)ctx->n_cu + hyp_blocks - 1) / std::max<unsigned long long>(hyp_blocks, 1)));
-  CB_LAUNCH(csb_count_kernel, 32.0 * (double)nm_max * (double)hyp_blocks + 52.0 * (double)St.hypotheses, dim3(hb, (unsigned)na, split), dim3(kCsBlock), 0,
-            st, (const float4 *)d_ps, (const float4 *)d_pt, (const uint32_t *)v.nm, d_rec, (const float *)d_rows, nsk, (uint32_t)Hmax, thr2, d_cnt);
+  STAGE_LAUNCH(ctx, St.launches, csb_count_kernel, 32.0 * (double)nm_max * (double)hyp_blocks + 52.0 * (double)St.hypotheses, dim3(hb, (unsigned)na, split),
+               dim3(kCsBlock), 0, st, (const float4 *)d_ps, (const float4 *)d_pt, (const uint32_t *)v.nm, d_rec, (const float *)d_rows, nsk, (uint32_t)Hmax,
+               thr2, d_cnt);
   std::vector<uint32_t> cnts(hyps);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(cnts.data(), d_cnt, 4 * hyps, hipMemcpyDeviceToHost, st);
@@ -429,8 +399,7 @@ int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *mod
     winner[a] = best;
     if (best >= 0) n_rem[a] = (uint32_t)best_cnt;
   }
-  e = upload_staged(st, d_winner, winner.data(), 4 * na, &St.host_syncs);
-  ++St.launches;
+  e = upload_staged(st, d_winner, winner.data(), 4 * na, &St.launches, &St.host_syncs);
   if (e != hipSuccess) return fail("upload");
 
   // ---- h. the remaining matches and their pose
@@ -438,12 +407,12 @@ int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *mod
   auto *d_Tbest = (float *)(d_fin + 4 * na);
   auto *d_Tsvd = (float *)(d_fin + 68 * na);
   auto *d_pos = (int32_t *)(d_fin + 132 * na);
-  CB_LAUNCH(csb_pack_kernel, 92.0 * (double)slots, dim3((unsigned)na), dim3(1024), 0, st, v, (const int32_t *)d_winner, (const float *)d_T,
-            (const float *)d_rows, thr2, d_pos, d_sx, d_tx, d_pcnt, d_Tbest);
-  CB_LAUNCH(csb_pairs_sums_kernel, 24.0 * (double)slots, dim3(max_blocks, (unsigned)na), dim3(256), 0, st, (const float *)d_sx, (const float *)d_tx,
-            (const uint32_t *)d_pcnt, nsk, max_blocks, d_part);
-  CB_LAUNCH(csb_pairs_umeyama_kernel, 136.0 * (double)max_blocks * (double)na, dim3((unsigned)na), dim3(64), 0, st, (const double *)d_part,
-            (const float *)d_sx, (const uint32_t *)d_pcnt, nsk, max_blocks, d_Tsvd);
+  STAGE_LAUNCH(ctx, St.launches, csb_pack_kernel, 92.0 * (double)slots, dim3((unsigned)na), dim3(1024), 0, st, v, (const int32_t *)d_winner, (const float *)d_T,
+               (const float *)d_rows, thr2, d_pos, d_sx, d_tx, d_pcnt, d_Tbest);
+  STAGE_LAUNCH(ctx, St.launches, csb_pairs_sums_kernel, 24.0 * (double)slots, dim3(max_blocks, (unsigned)na), dim3(256), 0, st, (const float *)d_sx,
+               (const float *)d_tx, (const uint32_t *)d_pcnt, nsk, max_blocks, d_part);
+  STAGE_LAUNCH(ctx, St.launches, csb_pairs_umeyama_kernel, 136.0 * (double)max_blocks * (double)na, dim3((unsigned)na), dim3(64), 0, st, (const double *)d_part,
+               (const float *)d_sx, (const uint32_t *)d_pcnt, nsk, max_blocks, d_Tsvd);
   std::vector<unsigned char> fin(fin_bytes);
   std::vector<float> Ts;
   e = hipGetLastError();

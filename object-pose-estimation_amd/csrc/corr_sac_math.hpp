@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "feature_math.hpp"
@@ -25,6 +26,15 @@ constexpr int kCsPackItems = kCsMaxMatches / 1024;   // matches per lane of the 
 constexpr int kCsSumChunk = 2048;        // points the threshold kernel stages at a time (32 KB)
 constexpr int kCsMaxSampleChecks = 1000; // SampleConsensusModel::max_sample_checks_
 static_assert(kCsPackItems * 1024 == kCsMaxMatches, "the compaction block covers every match");
+
+// the refusals of the parameters, the same for one call and for a batch; who: the entry point its errors name
+inline int corr_sac_check_params(ope_ctx *ctx, const char *who, const ope_corr_sac_params &p) {
+  const auto refuse = [&](const char *why) { return set_err(ctx, OPE_EINVAL, std::string(who) + why); };
+  if (p.max_iterations < 1 || p.max_iterations > kPrMaxIterations) return refuse("max_iterations must be 1 .. 2^20");
+  if (!(p.inlier_threshold > 0.0) || !std::isfinite(p.inlier_threshold)) return refuse("inlier_threshold must be > 0 and finite");
+  if (!(p.probability > 0.0 && p.probability < 1.0)) return refuse("probability must be inside (0, 1)");
+  return OPE_OK;
+}
 
 // the squared distance of query row q to target row t (t < 0: no match, infinity): feature_knn_block's sequential float sum
 __device__ __forceinline__ float cs_row_dist(const float *__restrict__ tgt_feat, const float *__restrict__ q, int32_t t) {

@@ -16,6 +16,7 @@
 
 #include "bvh_traverse.hpp"
 #include "feature_math.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 
@@ -613,8 +614,7 @@ void ope_sacia_default_params(ope_sacia_params *p) {
 int ope_sacia(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const ope_cloud *tgt, const ope_index *tgt_index,
               const float *tgt_feat33, const ope_sacia_params *params, const int32_t *forced_samples, float out_T[16],
               double *best_error, int32_t *best_iteration) {
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  if (out_T) std::memcpy(out_T, I4, sizeof I4);
+  if (out_T) std::memcpy(out_T, kIdentity4, sizeof kIdentity4);
   if (best_error) *best_error = 0;
   if (best_iteration) *best_iteration = -1;
   if (!ctx || !src || !tgt || !tgt_index || !out_T || (!forced_samples && (!src_feat33 || !tgt_feat33)))
@@ -653,11 +653,9 @@ int ope_sacia(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const
     if (e == hipSuccess) e = h2d_copy(ctx->stream, d_qf, qf.data(), sizeof(float) * qf.size());
     if (e == hipSuccess) e = tmp_malloc(ctx->stream, (void **)&d_nn, sizeof(int32_t) * nn.size());
     if (e == hipSuccess) {
-      {
-        // every query descriptor is compared with every target descriptor: 132 B of each, the target set once per query
-        KernelTimer kt(ctx, "feature_knn_kernel", 132.0 * ((double)uniq.size() * (double)nt + (double)uniq.size()));
-        hipLaunchKernelGGL(feature_knn_kernel, dim3((unsigned)uniq.size()), dim3(256), 0, ctx->stream, d_tf, nt, d_qf, K, d_nn);
-      }
+      // every query descriptor is compared with every target descriptor: 132 B of each, the target set once per query
+      STAGE_LAUNCH_TIMED(ctx, feature_knn_kernel, "feature_knn_kernel", 132.0 * ((double)uniq.size() * (double)nt + (double)uniq.size()),
+                         dim3((unsigned)uniq.size()), dim3(256), 0, ctx->stream, d_tf, nt, d_qf, K, d_nn);
       e = hipMemcpyAsync(nn.data(), d_nn, sizeof(int32_t) * nn.size(), hipMemcpyDeviceToHost, ctx->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
@@ -691,7 +689,7 @@ int ope_sacia(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const
     if (!unmatched) umeyama_host(ps.data(), pt.data(), S, Th);
     bool finite = !unmatched;
     for (int k = 0; finite && k < 16; ++k) finite = std::isfinite(Th[k]);
-    if (!finite) { std::memcpy(Th, I4, sizeof I4); is_void[it] = 1; }
+    if (!finite) { std::memcpy(Th, kIdentity4, sizeof kIdentity4); is_void[it] = 1; }
     colmajor_to_rows12(Th, &rows[(size_t)it * 12]);
   }
 
@@ -704,12 +702,9 @@ int ope_sacia(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33, const
   if (e == hipSuccess) e = h2d_copy(ctx->stream, d_rows, rows.data(), sizeof(float) * rows.size());
   if (e == hipSuccess) e = tmp_malloc(ctx->stream, (void **)&d_part, sizeof(double) * part.size());
   if (e == hipSuccess) {
-    {
-      // 24 N_s per hypothesis (read the source point, gather its nearest target point)
-      KernelTimer kt(ctx, "sacia_error_kernel", 24.0 * (double)src->n_valid * (double)H);
-      hipLaunchKernelGGL(sacia_error_kernel, dim3(bx, H), dim3(256), 0, ctx->stream, src->view(), tgt_index->view(), d_rows,
-                         (float)p.max_corr_dist, d_part);
-    }
+    // 24 N_s per hypothesis (read the source point, gather its nearest target point)
+    STAGE_LAUNCH_TIMED(ctx, sacia_error_kernel, "sacia_error_kernel", 24.0 * (double)src->n_valid * (double)H, dim3(bx, H), dim3(256), 0, ctx->stream,
+                       src->view(), tgt_index->view(), d_rows, (float)p.max_corr_dist, d_part);
     e = hipMemcpyAsync(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   }

@@ -27,6 +27,7 @@
 #include "bvh_traverse.hpp"
 #include "coarse_stages.hpp"
 #include "morton.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 
@@ -230,13 +231,12 @@ int final_fine_prepare(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cl
   std::vector<FineIn> fin(nseg);
   std::vector<CoarseSeg> segs(nseg);
   std::vector<uint32_t> off(nseg + 1, 0);
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   for (size_t s = 0; s < nseg; ++s) {
     const bool src = s < n;
     const ope_cloud *c = src ? model : clusters[s - n];
     fin[s].c = c->view();
     fin[s].moved = src && coarse[s].status == OPE_COARSE_OK;
-    std::memcpy(fin[s].T, fin[s].moved ? coarse[s].T : I4, sizeof I4);
+    std::memcpy(fin[s].T, fin[s].moved ? coarse[s].T : kIdentity4, sizeof kIdentity4);
     off[s + 1] = off[s] + (uint32_t)c->n;
   }
   const uint32_t total = off[nseg];
@@ -277,10 +277,8 @@ int final_fine_prepare(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cl
         hipLaunchKernelGGL(fine_transform_kernel, dim3((total + kCoarseBlock - 1) / kCoarseBlock), dim3(kCoarseBlock), 0, ctx->stream, d_fin, d_off,
                            (uint32_t)nseg, total, d_raw, d_box, d_bad);
     }
-    {
-      KernelTimer kt(ctx, "fine_geom_kernel", 0.0);
-      hipLaunchKernelGGL(fine_geom_kernel, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, ctx->stream, d_segs, d_box, (uint32_t)nseg, inv, d_bad);
-    }
+    STAGE_LAUNCH_TIMED(ctx, fine_geom_kernel, "fine_geom_kernel", 0.0, dim3((unsigned)((nseg + 63) / 64)), dim3(64), 0, ctx->stream, d_segs, d_box,
+                       (uint32_t)nseg, inv, d_bad);
     e = hipGetLastError();
     if (e != hipSuccess) return fail("transform");
   }
@@ -324,11 +322,8 @@ int final_fine_prepare(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cl
   }
 
   // ---- 3. NaN-normal drop and the upload order; one synchronisation: the fine clouds' sizes and boxes
-  {
-    KernelTimer kt(ctx, "fine_order_kernel", 64.0 * nkeys);
-    hipLaunchKernelGGL(fine_order_kernel, dim3((unsigned)nseg), dim3(kCoarseBlock), 0, ctx->stream, d_kp, d_nrm, d_key_off, d_fxyz, d_fnrm, d_cnt,
-                       d_fbox);
-  }
+  STAGE_LAUNCH_TIMED(ctx, fine_order_kernel, "fine_order_kernel", 64.0 * nkeys, dim3((unsigned)nseg), dim3(kCoarseBlock), 0, ctx->stream, d_kp, d_nrm,
+                     d_key_off, d_fxyz, d_fnrm, d_cnt, d_fbox);
   cnt.assign(nseg, 0u);
   fbox.assign(6 * nseg, 0.f);
   e = hipGetLastError();
@@ -453,7 +448,6 @@ int ope::final_batch_finish(ope_ctx *ctx, const char *who, const ope_cloud *mode
   OPE_HIP(ctx, hipSetDevice(ctx->device));
   TraceRange r_all(ctx, "final_batch");
   const size_t nseg = 2 * n;
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   CallTmp tmp{ctx->stream, {}};
   FinePrep fp;
   { const int rc = final_fine_prepare(ctx, tmp, who, model, n, clusters, p, coarse, fp); if (rc != OPE_OK) return rc; }
@@ -534,7 +528,7 @@ int ope::final_batch_finish(ope_ctx *ctx, const char *who, const ope_cloud *mode
     std::memset(&o, 0, sizeof o);
     o.coarse = coarse[i];
     o.seed = seed_used[i];
-    std::memcpy(o.fine.T, I4, sizeof I4);
+    std::memcpy(o.fine.T, kIdentity4, sizeof kIdentity4);
     o.fine.fitness = std::numeric_limits<double>::max();
     o.n_fine_src = (int32_t)cnt[i];
     o.n_fine_tgt = (int32_t)cnt[n + i];

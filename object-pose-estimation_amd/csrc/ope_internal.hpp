@@ -546,7 +546,8 @@ inline hipError_t stage_block(size_t bytes, unsigned char **block, size_t *cap_o
   *cap_out = st.cap;
   return hipSuccess;
 }
-inline hipError_t h2d_copy(hipStream_t stream, void *dst, const void *src, size_t bytes) {
+// *pieces (optional) grows by the synchronising pieces the copy was cut into (none for a small copy)
+inline hipError_t h2d_copy(hipStream_t stream, void *dst, const void *src, size_t bytes, int64_t *pieces = nullptr) {
   constexpr size_t kSmall = kStageSmall;
   constexpr int kRing = kStageRing;
   UploadStage &st = upload_stage();
@@ -580,6 +581,7 @@ inline hipError_t h2d_copy(hipStream_t stream, void *dst, const void *src, size_
     hipError_t e = hipMemcpyAsync(static_cast<unsigned char *>(dst) + off, st.big, c, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) return e;
+    if (pieces) ++*pieces;
   }
   return hipSuccess;
 }

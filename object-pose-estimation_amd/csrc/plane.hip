@@ -31,6 +31,7 @@
 
 #include "coarse_stages.hpp"
 #include "feature_math.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 namespace {
@@ -353,15 +354,6 @@ __global__ __launch_bounds__(kPlBlock) void pl_compose_kernel(const int32_t *__r
   if (j < n) out[j] = outer[inner[j]];
 }
 
-unsigned grid_of(size_t n) { return (unsigned)std::max<size_t>((n + kPlBlock - 1) / kPlBlock, 1); }
-
-#define PL_LAUNCH(name, bytes, ...)                  \
-  do {                                               \
-    KernelTimer kt_(ctx, #name, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++ctx->plane_stats.launches;                     \
-  } while (0)
-
 int check_plane_params(ope_ctx *ctx, const char *who, const ope_plane_params *params, ope_plane_params &p) {
   ope_plane_default_params(&p);
   if (params) p = *params;
@@ -473,12 +465,12 @@ int fit_run(ope_ctx *ctx, const char *who, const FitBufs &B, const ope_cloud *cl
   if (e == hipSuccess) e = hipMemsetAsync(d_back, 0, back_bytes, st);
   ++S.launches;
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  if (cloud) PL_LAUNCH(pl_orig_kernel, 36.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, cloud->view(), pts_o, shuf);
-  PL_LAUNCH(pl_draw_kernel, 0.0, dim3(1), dim3(64), 0, st, pts_o, n, shuf, (uint32_t)(p.seed & 0xffffffffull), H, d_inj, (uint32_t)n_samples, hyp, samp,
-            meta);
-  const unsigned score_blocks = (unsigned)std::min<size_t>(grid_of(n), (size_t)ctx->n_cu * 8);
-  PL_LAUNCH(pl_score_kernel, 16.0 * n, dim3(score_blocks), dim3(kPlBlock), 0, st, cloud ? (const float4 *)cloud->d_xyzw : (const float4 *)pts_o, n, hyp, meta,
-            p.distance_threshold, cnt);
+  if (cloud) STAGE_LAUNCH(ctx, S.launches, pl_orig_kernel, 36.0 * n, dim3(grid_of(n, kPlBlock)), dim3(kPlBlock), 0, st, cloud->view(), pts_o, shuf);
+  STAGE_LAUNCH(ctx, S.launches, pl_draw_kernel, 0.0, dim3(1), dim3(64), 0, st, pts_o, n, shuf, (uint32_t)(p.seed & 0xffffffffull), H, d_inj,
+               (uint32_t)n_samples, hyp, samp, meta);
+  const unsigned score_blocks = (unsigned)std::min<size_t>(grid_of(n, kPlBlock), (size_t)ctx->n_cu * 8);
+  STAGE_LAUNCH(ctx, S.launches, pl_score_kernel, 16.0 * n, dim3(score_blocks), dim3(kPlBlock), 0, st,
+               cloud ? (const float4 *)cloud->d_xyzw : (const float4 *)pts_o, n, hyp, meta, p.distance_threshold, cnt);
   // ---- the first synchronisation: hypotheses and counts
   std::vector<unsigned char> back(back_bytes);
   e = hipGetLastError();
@@ -527,11 +519,12 @@ int fit_run(ope_ctx *ctx, const char *who, const FitBufs &B, const ope_cloud *cl
   const float4 *c_best = hyp + best;
   const float4 *c_final = c_best;
   if (p.optimize_coefficients) {
-    PL_LAUNCH(pl_flag_kernel, 20.0 * n, dim3(grid_of((size_t)n + 1)), dim3(kPlBlock), 0, st, pts_o, n, c_best, p.distance_threshold, flags);
+    STAGE_LAUNCH(ctx, S.launches, pl_flag_kernel, 20.0 * n, dim3(grid_of((size_t)n + 1, kPlBlock)), dim3(kPlBlock), 0, st, pts_o, n, c_best,
+                 p.distance_threshold, flags);
     e = scan_flags(ctx, d_tmp, tb, flags, rank, n);
     if (e == hipSuccess) {
-      PL_LAUNCH(pl_pack_kernel, 40.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, pts_o, n, flags, rank, packed);
-      PL_LAUNCH(pl_refine_kernel, 16.0 * n, dim3(1), dim3(kPlBlock), 0, st, packed, rank + n, c_best, d_coeff);
+      STAGE_LAUNCH(ctx, S.launches, pl_pack_kernel, 40.0 * n, dim3(grid_of(n, kPlBlock)), dim3(kPlBlock), 0, st, pts_o, n, flags, rank, packed);
+      STAGE_LAUNCH(ctx, S.launches, pl_refine_kernel, 16.0 * n, dim3(1), dim3(kPlBlock), 0, st, packed, rank + n, c_best, d_coeff);
     }
     c_final = d_coeff;
   } else if (e == hipSuccess) {
@@ -539,13 +532,15 @@ int fit_run(ope_ctx *ctx, const char *who, const FitBufs &B, const ope_cloud *cl
     ++S.launches;
   }
   if (e == hipSuccess) {
-    PL_LAUNCH(pl_flag_kernel, 20.0 * n, dim3(grid_of((size_t)n + 1)), dim3(kPlBlock), 0, st, pts_o, n, c_final, p.distance_threshold, flags);
+    STAGE_LAUNCH(ctx, S.launches, pl_flag_kernel, 20.0 * n, dim3(grid_of((size_t)n + 1, kPlBlock)), dim3(kPlBlock), 0, st, pts_o, n, c_final,
+                 p.distance_threshold, flags);
     e = scan_flags(ctx, d_tmp, tb, flags, rank, n);
   }
-  if (e == hipSuccess && !peel) PL_LAUNCH(pl_index_kernel, 16.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, n, flags, rank, idx, rest);
+  if (e == hipSuccess && !peel)
+    STAGE_LAUNCH(ctx, S.launches, pl_index_kernel, 16.0 * n, dim3(grid_of(n, kPlBlock)), dim3(kPlBlock), 0, st, n, flags, rank, idx, rest);
   if (e == hipSuccess && peel)
-    PL_LAUNCH(pl_peel_kernel, 52.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, pts_o, peel->orig, n, flags, rank, peel->round, peel->pts_next,
-              peel->orig_next, peel->label, shuf, peel->d_m);
+    STAGE_LAUNCH(ctx, S.launches, pl_peel_kernel, 52.0 * n, dim3(grid_of(n, kPlBlock)), dim3(kPlBlock), 0, st, pts_o, peel->orig, n, flags, rank, peel->round,
+                 peel->pts_next, peel->orig_next, peel->label, shuf, peel->d_m);
   // ---- the second synchronisation: coefficients, count (and the indices, whose number the host does not know yet)
   uint32_t n_in = 0;
   if (e == hipSuccess) e = hipGetLastError();
@@ -591,10 +586,13 @@ int prism_run(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *clou
   void *d_tmp = tmp.get(std::max<size_t>(tb, 16), e);
   if (e == hipSuccess) { e = h2d_copy(st, d_hull, hull, 12 * m); ++ctx->plane_stats.launches; }
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  PL_LAUNCH(pl_hull_kernel, 0.0, dim3(1), dim3(64), 0, st, d_hull, (uint32_t)m, hp);
-  PL_LAUNCH(pl_prism_kernel, 20.0 * n, dim3(grid_of((size_t)n + 1)), dim3(kPlBlock), 0, st, pts_o, n, hp, d_hull, (uint32_t)m, hmin, hmax, flags);
+  STAGE_LAUNCH(ctx, ctx->plane_stats.launches, pl_hull_kernel, 0.0, dim3(1), dim3(64), 0, st, d_hull, (uint32_t)m, hp);
+  STAGE_LAUNCH(ctx, ctx->plane_stats.launches, pl_prism_kernel, 20.0 * n, dim3(grid_of((size_t)n + 1, kPlBlock)), dim3(kPlBlock), 0, st, pts_o, n, hp, d_hull,
+               (uint32_t)m, hmin, hmax, flags);
   e = scan_flags(ctx, d_tmp, tb, flags, rank, n);
-  if (e == hipSuccess) PL_LAUNCH(pl_index_kernel, 12.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, st, n, flags, rank, idx, (int32_t *)nullptr);
+  if (e == hipSuccess)
+    STAGE_LAUNCH(ctx, ctx->plane_stats.launches, pl_index_kernel, 12.0 * n, dim3(grid_of(n, kPlBlock)), dim3(kPlBlock), 0, st, n, flags, rank, idx,
+                 (int32_t *)nullptr);
   float hc[4] = {0, 0, 0, 0};
   if (e == hipSuccess) e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(count, rank + n, 4, hipMemcpyDeviceToHost, st);
@@ -710,7 +708,8 @@ int ope_plane_peel(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_params 
   int32_t *d_label = label ? (int32_t *)tmp.get(4 * n1, e) : nullptr;
   uint32_t *d_m = (uint32_t *)tmp.get(16, e);
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  if (n0) PL_LAUNCH(pl_peel_init_kernel, 8.0 * n0, dim3(grid_of(n0)), dim3(kPlBlock), 0, st, n0, orig_cur, d_label);
+  if (n0)
+    STAGE_LAUNCH(ctx, ctx->plane_stats.launches, pl_peel_init_kernel, 8.0 * n0, dim3(grid_of(n0, kPlBlock)), dim3(kPlBlock), 0, st, n0, orig_cur, d_label);
   uint32_t m = n0;
   int32_t n_planes = 0, stop = OPE_PEEL_FRACTION;
   // objectsegmentationplane.cpp:300-319.  The host knows m from the round's second synchronisation; no cloud is built per round.
@@ -787,7 +786,8 @@ int ope_prism_extract(ope_ctx *ctx, const ope_cloud *cloud, const float *hull, s
   hipError_t e = hipSuccess;
   auto *pts_o = (float4 *)tmp.get(16 * std::max<size_t>(n, 1), e);
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  PL_LAUNCH(pl_orig_kernel, 32.0 * n, dim3(grid_of(n)), dim3(kPlBlock), 0, ctx->stream, cloud->view(), pts_o, (int32_t *)nullptr);
+  STAGE_LAUNCH(ctx, ctx->plane_stats.launches, pl_orig_kernel, 32.0 * n, dim3(grid_of(n, kPlBlock)), dim3(kPlBlock), 0, ctx->stream, cloud->view(), pts_o,
+               (int32_t *)nullptr);
   int32_t *d_idx = nullptr;
   uint32_t count = 0;
   int rc = prism_run(ctx, tmp, who, cloud, pts_o, hull, m, height_min, height_max, &d_idx, &count, out_idx, hull_coeff);
@@ -833,7 +833,8 @@ int ope_tabletop_segment(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_p
   uint32_t mm[4] = {0xffffffffu, 0xffffffffu, 0u, 0u};
   if (e == hipSuccess) { e = h2d_copy(st, d_mm, mm, 16); ++ctx->plane_stats.launches; }
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  PL_LAUNCH(pl_project_minmax_kernel, 20.0 * f1.n_in, dim3(grid_of(f1.n_in)), dim3(kPlBlock), 0, st, f1.d_pts_o, f1.d_idx, f1.n_in, f1.d_coeff, d_mm);
+  STAGE_LAUNCH(ctx, ctx->plane_stats.launches, pl_project_minmax_kernel, 20.0 * f1.n_in, dim3(grid_of(f1.n_in, kPlBlock)), dim3(kPlBlock), 0, st, f1.d_pts_o,
+               f1.d_idx, f1.n_in, f1.d_coeff, d_mm);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(mm, d_mm, 16, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -878,12 +879,14 @@ int ope_tabletop_segment(ope_ctx *ctx, const ope_cloud *cloud, const ope_plane_p
   if (rc == OPE_OK && (plane_idx || not_plane_idx)) {
     auto *d_map = (int32_t *)tmp.get(4 * std::max<size_t>(n_prism, 1), e);
     if (e == hipSuccess && plane_idx) {
-      PL_LAUNCH(pl_compose_kernel, 12.0 * f2.n_in, dim3(grid_of(f2.n_in)), dim3(kPlBlock), 0, st, d_pidx, f2.d_idx, f2.n_in, d_map);
+      STAGE_LAUNCH(ctx, ctx->plane_stats.launches, pl_compose_kernel, 12.0 * f2.n_in, dim3(grid_of(f2.n_in, kPlBlock)), dim3(kPlBlock), 0, st, d_pidx, f2.d_idx,
+                   f2.n_in, d_map);
       if (f2.n_in) e = hipMemcpyAsync(plane_idx, d_map, 4ull * f2.n_in, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess && not_plane_idx) {
       const uint32_t nr = n_prism - f2.n_in;
-      PL_LAUNCH(pl_compose_kernel, 12.0 * nr, dim3(grid_of(nr)), dim3(kPlBlock), 0, st, d_pidx, f2.d_rest, nr, d_map);
+      STAGE_LAUNCH(ctx, ctx->plane_stats.launches, pl_compose_kernel, 12.0 * nr, dim3(grid_of(nr, kPlBlock)), dim3(kPlBlock), 0, st, d_pidx, f2.d_rest, nr,
+                   d_map);
       if (nr) e = hipMemcpyAsync(not_plane_idx, d_map, 4ull * nr, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);

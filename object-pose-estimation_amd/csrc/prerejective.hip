@@ -29,6 +29,7 @@
 #include "feature_math.hpp"
 #include "icp_update.hpp"
 #include "prerejective_math.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 namespace {
@@ -134,35 +135,6 @@ __global__ __launch_bounds__(256) void prerej_inlier_kernel(CloudView src, BvhVi
   flags_o[o] = in ? 1 : 0;
 }
 
-unsigned grid_of(size_t n, int block = kPrBlock) { return (unsigned)std::max<size_t>((n + block - 1) / block, 1); }
-
-#define PR_LAUNCH(name, bytes, ...)                  \
-  do {                                               \
-    KernelTimer kt_(ctx, #name, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++ctx->prerej_stats.launches;                    \
-  } while (0)
-
-// Two host arrays into one device block [a | b] in stream order.  Up to the size of the pinned staging block this is one copy
-// that does not synchronise (the caller synchronises before it stages again); beyond it, h2d_copy's synchronising chunks.
-hipError_t upload_pair(ope_ctx *ctx, unsigned char *dst, const void *a, size_t na, const void *b, size_t nb) {
-  unsigned char *blk = nullptr;
-  size_t cap = 0;
-  hipError_t e = stage_block(na + nb, &blk, &cap);
-  if (e != hipSuccess) return e;
-  ++ctx->prerej_stats.launches;
-  if (na + nb <= cap) {
-    std::memcpy(blk, a, na);
-    std::memcpy(blk + na, b, nb);
-    return hipMemcpyAsync(dst, blk, na + nb, hipMemcpyHostToDevice, ctx->stream);
-  }
-  ++ctx->prerej_stats.launches;
-  ctx->prerej_stats.host_syncs += (int64_t)((na + cap - 1) / cap + (nb + cap - 1) / cap);
-  e = h2d_copy(ctx->stream, dst, a, na);
-  if (e == hipSuccess) e = h2d_copy(ctx->stream, dst + na, b, nb);
-  return e;
-}
-
 }  // namespace
 }  // namespace ope
 
@@ -185,10 +157,9 @@ int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33
                      const float *tgt_feat33, const ope_prerejective_params *params, const int32_t *forced_samples,
                      ope_prerejective_result *out, int32_t *out_inliers) {
   static const char *who = "ope_prerejective: ";
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   if (!ctx) return OPE_EINVAL;
   if (out) {
-    std::memcpy(out->T, I4, sizeof I4);
+    std::memcpy(out->T, kIdentity4, sizeof kIdentity4);
     out->error = (double)FLT_MAX;
     out->best_iteration = -1;
     out->inliers = 0;
@@ -200,20 +171,13 @@ int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33
   ope_prerejective_default_params(&p);
   if (params) p = *params;
   const int S = p.nr_samples, K = p.k_correspondences, H = p.max_iterations;
-  if (H < 1 || H > kPrMaxIterations) return set_err(ctx, OPE_EINVAL, std::string(who) + "max_iterations must be 1 .. 2^20");
-  if (S < 3 || S > 8) return set_err(ctx, OPE_EINVAL, std::string(who) + "nr_samples must be 3 .. 8");
-  if (K < 1 || K > kFeatK) return set_err(ctx, OPE_EINVAL, std::string(who) + "k_correspondences must be 1 .. 8");
-  if (!(p.similarity_threshold >= 0.f && p.similarity_threshold < 1.f))
-    return set_err(ctx, OPE_EINVAL, std::string(who) + "similarity_threshold must be inside [0, 1)");
-  if (!(p.inlier_fraction >= 0.f && p.inlier_fraction <= 1.f)) return set_err(ctx, OPE_EINVAL, std::string(who) + "inlier_fraction must be inside [0, 1]");
-  if (!(p.max_corr_dist > 0.0) || !std::isfinite(p.max_corr_dist)) return set_err(ctx, OPE_EINVAL, std::string(who) + "max_corr_dist must be > 0 and finite");
+  if (const int rc = prerej_check_params(ctx, who, p)) return rc;
   if (tgt->n_valid == 0 || tgt_index->n == 0) return set_err(ctx, OPE_EINVAL, std::string(who) + "empty target (no finite point in the cloud or in the index)");
   if (src->n > (size_t)0x7fffffff || tgt->n > (size_t)0x7fffffff) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 2^31 - 1 points");
   const int ns = (int)src->n, nt = (int)tgt->n;
   if (ns < S) return set_err(ctx, OPE_EINVAL, std::string(who) + "fewer source points than nr_samples");
   if (K > nt) return set_err(ctx, OPE_EINVAL, std::string(who) + "k_correspondences above the number of target points");
-  if (ctx->nccl_comm != nullptr || ctx->p2p_ok || ctx->p2p_broken)
-    return set_err(ctx, OPE_EINVAL, std::string(who) + "the context carries a communicator (one device runs a whole alignment)");
+  if (const int rc = refuse_communicator(ctx, who)) return rc;
   const size_t HS = (size_t)H * S;
   if (forced_samples)
     for (size_t j = 0; j < HS; ++j)
@@ -248,10 +212,11 @@ int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33
     const size_t tf_bytes = sizeof(float) * 33 * (size_t)nt, qf_bytes = sizeof(float) * qf.size();
     auto *d_feat = (unsigned char *)tmp.get(tf_bytes + qf_bytes, e);
     auto *d_nn = (int32_t *)tmp.get(sizeof(int32_t) * nn.size(), e);
-    if (e == hipSuccess) e = upload_pair(ctx, d_feat, tgt_feat33, tf_bytes, qf.data(), qf_bytes);
+    const HostRange feats[2] = {{tgt_feat33, tf_bytes}, {qf.data(), qf_bytes}};
+    if (e == hipSuccess) e = upload_staged(st, d_feat, feats, 2, &St.launches, &St.host_syncs);
     if (e == hipSuccess) {
-      PR_LAUNCH(prerej_feature_knn_kernel, 132.0 * ((double)uniq.size() * (double)nt + (double)uniq.size()), dim3((unsigned)uniq.size()), dim3(256), 0,
-                st, (const float *)d_feat, nt, (const float *)(d_feat + tf_bytes), K, d_nn);
+      STAGE_LAUNCH(ctx, St.launches, prerej_feature_knn_kernel, 132.0 * ((double)uniq.size() * (double)nt + (double)uniq.size()), dim3((unsigned)uniq.size()),
+                   dim3(256), 0, st, (const float *)d_feat, nt, (const float *)(d_feat + tf_bytes), K, d_nn);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(nn.data(), d_nn, sizeof(int32_t) * nn.size(), hipMemcpyDeviceToHost, st);
@@ -275,22 +240,18 @@ int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33
   auto *d_surv = (int32_t *)tmp.get(4 * (size_t)H, e);
   auto *d_nsurv = (uint32_t *)tmp.get(16, e);
   size_t tb = 0;
-  if (e == hipSuccess)
-    e = rocprim::select(nullptr, tb, rocprim::counting_iterator<int32_t>(0), d_flags, d_surv, d_nsurv, (size_t)H, st);
+  if (e == hipSuccess) e = select_flagged_bytes(st, d_flags, d_surv, d_nsurv, (size_t)H, &tb);
   void *d_sel = tmp.get(std::max<size_t>(tb, 16), e);
-  if (e == hipSuccess) e = upload_pair(ctx, d_pairs, samp.data(), 4 * HS, corr.data(), 4 * HS);
+  const HostRange pairs[2] = {{samp.data(), 4 * HS}, {corr.data(), 4 * HS}};
+  if (e == hipSuccess) e = upload_staged(st, d_pairs, pairs, 2, &St.launches, &St.host_syncs);
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
   const auto *d_samp = (const int32_t *)d_pairs, *d_corr = (const int32_t *)(d_pairs + 4 * HS);
-  PR_LAUNCH(prerej_orig_kernel, 32.0 * ns, dim3(grid_of(ns)), dim3(kPrBlock), 0, st, src->view(), src_o);
-  PR_LAUNCH(prerej_orig_kernel, 32.0 * nt, dim3(grid_of(nt)), dim3(kPrBlock), 0, st, tgt->view(), tgt_o);
+  STAGE_LAUNCH(ctx, St.launches, prerej_orig_kernel, 32.0 * ns, dim3(grid_of(ns, kPrBlock)), dim3(kPrBlock), 0, st, src->view(), src_o);
+  STAGE_LAUNCH(ctx, St.launches, prerej_orig_kernel, 32.0 * nt, dim3(grid_of(nt, kPrBlock)), dim3(kPrBlock), 0, st, tgt->view(), tgt_o);
   const float thr2 = p.similarity_threshold * p.similarity_threshold;
-  PR_LAUNCH(prerej_polygon_kernel, (double)H * (40.0 * S + 1.0), dim3(grid_of(H)), dim3(kPrBlock), 0, st, src_o, tgt_o, d_samp, d_corr, (uint32_t)H, S,
-            thr2, d_flags);
-  {
-    KernelTimer kt(ctx, "prerej_select", 5.0 * H);
-    ++St.launches;
-    e = rocprim::select(d_sel, tb, rocprim::counting_iterator<int32_t>(0), d_flags, d_surv, d_nsurv, (size_t)H, st);
-  }
+  STAGE_LAUNCH(ctx, St.launches, prerej_polygon_kernel, (double)H * (40.0 * S + 1.0), dim3(grid_of(H, kPrBlock)), dim3(kPrBlock), 0, st, src_o, tgt_o, d_samp,
+               d_corr, (uint32_t)H, S, thr2, d_flags);
+  e = select_flagged(ctx, "prerej_select", 5.0 * H, &St.launches, d_sel, tb, d_flags, d_surv, d_nsurv, (size_t)H);
   uint32_t nsurv = 0;
   if (e == hipSuccess) e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(&nsurv, d_nsurv, 4, hipMemcpyDeviceToHost, st);
@@ -310,13 +271,13 @@ int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33
   auto *d_err = (double *)tmp.get(8 * ns1, e);
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
   const double max_d2 = p.max_corr_dist * p.max_corr_dist;
-  PR_LAUNCH(prerej_fit_kernel, (double)nsurv * (40.0 * S + 112.0), dim3(grid_of(nsurv, 64)), dim3(64), 0, st, src_o, tgt_o, d_samp, d_corr, S, d_surv,
-            d_nsurv, d_T, d_rows);
+  STAGE_LAUNCH(ctx, St.launches, prerej_fit_kernel, (double)nsurv * (40.0 * S + 112.0), dim3(grid_of(nsurv, 64)), dim3(64), 0, st, src_o, tgt_o, d_samp, d_corr,
+               S, d_surv, d_nsurv, d_T, d_rows);
   const unsigned score_blocks = (unsigned)std::min<size_t>(nitems, (size_t)ctx->n_cu * 16);
-  PR_LAUNCH(prerej_score_kernel, 24.0 * (double)src->n_valid * (double)nsurv, dim3(score_blocks), dim3(256), 0, st, src->view(), tgt_index->view(), d_rows,
-            d_nsurv, (uint32_t)chunks, max_d2, d_pcnt, d_psum);
-  PR_LAUNCH(prerej_reduce_kernel, 12.0 * (double)nitems, dim3(grid_of(nsurv)), dim3(kPrBlock), 0, st, d_pcnt, d_psum, d_nsurv, (uint32_t)chunks, d_inl,
-            d_err);
+  STAGE_LAUNCH(ctx, St.launches, prerej_score_kernel, 24.0 * (double)src->n_valid * (double)nsurv, dim3(score_blocks), dim3(256), 0, st, src->view(),
+               tgt_index->view(), d_rows, d_nsurv, (uint32_t)chunks, max_d2, d_pcnt, d_psum);
+  STAGE_LAUNCH(ctx, St.launches, prerej_reduce_kernel, 12.0 * (double)nitems, dim3(grid_of(nsurv, kPrBlock)), dim3(kPrBlock), 0, st, d_pcnt, d_psum, d_nsurv,
+               (uint32_t)chunks, d_inl, d_err);
   std::vector<uint8_t> flags((size_t)H);
   std::vector<int32_t> surv(ns1), inl(ns1);
   std::vector<float> Ts(16 * ns1);
@@ -339,7 +300,7 @@ int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33
   ctx->prerej_T.resize(16 * (size_t)H);
   ctx->prerej_inliers.assign((size_t)H, 0);
   ctx->prerej_error.assign((size_t)H, (double)FLT_MAX);
-  for (int it = 0; it < H; ++it) std::memcpy(&ctx->prerej_T[16 * (size_t)it], I4, sizeof I4);
+  for (int it = 0; it < H; ++it) std::memcpy(&ctx->prerej_T[16 * (size_t)it], kIdentity4, sizeof kIdentity4);
   for (uint32_t k = 0; k < nsurv; ++k) {
     const size_t it = (size_t)surv[k];
     if (it >= (size_t)H) return set_err(ctx, OPE_EHIP, std::string(who) + "a survivor's iteration is out of range");
@@ -364,17 +325,13 @@ int ope_prerejective(ope_ctx *ctx, const ope_cloud *src, const float *src_feat33
     auto *d_idx = (int32_t *)tmp.get(4 * (size_t)ns, e);
     auto *d_cnt = (uint32_t *)tmp.get(16, e);
     size_t tb2 = 0;
-    if (e == hipSuccess) e = rocprim::select(nullptr, tb2, rocprim::counting_iterator<int32_t>(0), d_fo, d_idx, d_cnt, (size_t)ns, st);
+    if (e == hipSuccess) e = select_flagged_bytes(st, d_fo, d_idx, d_cnt, (size_t)ns, &tb2);
     void *d_sel2 = tmp.get(std::max<size_t>(tb2, 16), e);
     if (e == hipSuccess) { e = h2d_copy(st, d_wrows, rows, 48); ++St.launches; }
     if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-    PR_LAUNCH(prerej_inlier_kernel, 24.0 * (double)src->n_valid, dim3(grid_of(ns, 256)), dim3(256), 0, st, src->view(), tgt_index->view(), d_wrows, max_d2,
-              d_fo);
-    {
-      KernelTimer kt(ctx, "prerej_select", 5.0 * ns);
-      ++St.launches;
-      e = rocprim::select(d_sel2, tb2, rocprim::counting_iterator<int32_t>(0), d_fo, d_idx, d_cnt, (size_t)ns, st);
-    }
+    STAGE_LAUNCH(ctx, St.launches, prerej_inlier_kernel, 24.0 * (double)src->n_valid, dim3(grid_of(ns, 256)), dim3(256), 0, st, src->view(), tgt_index->view(),
+                 d_wrows, max_d2, d_fo);
+    e = select_flagged(ctx, "prerej_select", 5.0 * ns, &St.launches, d_sel2, tb2, d_fo, d_idx, d_cnt, (size_t)ns);
     uint32_t cnt = 0;
     std::vector<int32_t> idx((size_t)ns);
     if (e == hipSuccess) e = hipGetLastError();

@@ -30,6 +30,7 @@
 #include "coarse_stages.hpp"
 #include "feature_math.hpp"
 #include "prerejective_math.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 namespace {
@@ -143,21 +144,11 @@ __global__ __launch_bounds__(kPrBlock) void prerej_batch_reduce_kernel(const uin
   survivor_sum(part_cnt, part_sum, k, chunks, inliers, error);
 }
 
-unsigned grid_of(size_t n, int block = kPrBlock) { return (unsigned)std::max<size_t>((n + block - 1) / block, 1); }
-
-#define PB_LAUNCH(name, bytes, ...)                  \
-  do {                                               \
-    KernelTimer kt_(ctx, #name, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++St.launches;                                   \
-  } while (0)
-
 }  // namespace
 
 int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                                  const ope_coarse_params *front, const ope_prerejective_params *params, const uint64_t *seeds,
                                  bool seed_by_rank, int keep_hypotheses, ope_prerejective_batch_result *out) {
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   if (!ctx) return OPE_EINVAL;
   if (n == 0) return OPE_OK;
   if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
@@ -169,17 +160,10 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
   ope_prerejective_default_params(&p);
   if (params) p = *params;
   const int S = p.nr_samples, K = p.k_correspondences, H = p.max_iterations;
-  if (H < 1 || H > kPrMaxIterations) return set_err(ctx, OPE_EINVAL, std::string(who) + "max_iterations must be 1 .. 2^20");
-  if (S < 3 || S > 8) return set_err(ctx, OPE_EINVAL, std::string(who) + "nr_samples must be 3 .. 8");
-  if (K < 1 || K > kFeatK) return set_err(ctx, OPE_EINVAL, std::string(who) + "k_correspondences must be 1 .. 8");
-  if (!(p.similarity_threshold >= 0.f && p.similarity_threshold < 1.f))
-    return set_err(ctx, OPE_EINVAL, std::string(who) + "similarity_threshold must be inside [0, 1)");
-  if (!(p.inlier_fraction >= 0.f && p.inlier_fraction <= 1.f)) return set_err(ctx, OPE_EINVAL, std::string(who) + "inlier_fraction must be inside [0, 1]");
-  if (!(p.max_corr_dist > 0.0) || !std::isfinite(p.max_corr_dist)) return set_err(ctx, OPE_EINVAL, std::string(who) + "max_corr_dist must be > 0 and finite");
+  if (const int rc = prerej_check_params(ctx, who, p)) return rc;
   if ((unsigned long long)n * (unsigned long long)H > 0x7fffffffull)
     return set_err(ctx, OPE_EINVAL, std::string(who) + "clusters x max_iterations above 2^31 - 1");
-  if (ctx->nccl_comm != nullptr || ctx->p2p_ok || ctx->p2p_broken)
-    return set_err(ctx, OPE_EINVAL, std::string(who) + "the context carries a communicator (one device runs a whole alignment)");
+  if (const int rc = refuse_communicator(ctx, who)) return rc;
   // the front end's refusals (sizes, key points; the model needs nr_samples key points)
   fp.sacia.nr_samples = S; fp.sacia.k_correspondences = K; fp.sacia.max_iterations = H;
   long long model_keys = -2;
@@ -211,7 +195,7 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
   for (size_t i = 0; i < n; ++i) {
     ope_prerejective_batch_result &o = out[i];
     std::memset(&o, 0, sizeof o);
-    std::memcpy(o.T, I4, sizeof I4);
+    std::memcpy(o.T, kIdentity4, sizeof kIdentity4);
     o.error = (double)FLT_MAX;
     o.best_iteration = -1;
     o.n_src_keys = (int32_t)nsk;
@@ -254,46 +238,26 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
   auto *d_surv = (uint32_t *)tmp.get(4 * total, e);
   auto *d_words = (uint32_t *)tmp.get(4 * (2 * na + 2), e);   // [nsurv | off (na + 1) | NaN words (na)]
   size_t tb = 0;
-  if (e == hipSuccess)
-    e = rocprim::select(nullptr, tb, rocprim::counting_iterator<uint32_t>(0), d_flags, d_surv, d_words, total, st);
+  if (e == hipSuccess) e = select_flagged_bytes(st, d_flags, d_surv, d_words, total, &tb);
   void *d_sel = tmp.get(std::max<size_t>(tb, 16), e);
   if (e == hipSuccess) e = h2d_copy(st, d_active, active.data(), sizeof(int2) * na);
   if (e != hipSuccess) return fail("buffers");
   uint32_t *d_nsurv = d_words, *d_off = d_words + 1, *d_nan = d_words + 2 + na;
-  {
-    // one copy through the pinned staging block (nothing stages again before the next synchronisation); beyond its size,
-    // h2d_copy's synchronising chunks
-    unsigned char *blk = nullptr;
-    size_t cap = 0;
-    e = stage_block(draw_bytes, &blk, &cap);
-    if (e != hipSuccess) return fail("staging");
-    ++St.launches;
-    if (draw_bytes <= cap) {
-      std::memcpy(blk, draws.data(), draw_bytes);
-      e = hipMemcpyAsync(d_draws, blk, draw_bytes, hipMemcpyHostToDevice, st);
-    } else {
-      St.host_syncs += (int64_t)((draw_bytes + cap - 1) / cap);
-      e = h2d_copy(st, d_draws, draws.data(), draw_bytes);
-    }
-    if (e == hipSuccess) { e = hipMemsetAsync(d_nan, 0, 4 * na, st); ++St.launches; }
-    if (e != hipSuccess) return fail("upload");
-  }
+  e = upload_staged(st, d_draws, draws.data(), draw_bytes, &St.launches, &St.host_syncs);   // (nothing stages again before the next synchronisation)
+  if (e == hipSuccess) { e = hipMemsetAsync(d_nan, 0, 4 * na, st); ++St.launches; }
+  if (e != hipSuccess) return fail("upload");
 
   // ---- c, d, e. feature rows, polygon test, survivors in (cluster, iteration) order and every cluster's first
   const PbView v{fr.d_kp, fr.d_key_off, d_active, d_draws, d_nn, (uint32_t)H, nsk, S, K};
-  PB_LAUNCH(prerej_batch_knn_kernel, 132.0 * (double)na * (double)nsk * (double)fr.max_keys, dim3(nsk, (unsigned)na), dim3(256), 0, st,
-            (const float *)fr.d_fpfh, (const uint32_t *)fr.d_key_off, (const int2 *)d_active, K, d_nn);
+  STAGE_LAUNCH(ctx, St.launches, prerej_batch_knn_kernel, 132.0 * (double)na * (double)nsk * (double)fr.max_keys, dim3(nsk, (unsigned)na), dim3(256), 0, st,
+               (const float *)fr.d_fpfh, (const uint32_t *)fr.d_key_off, (const int2 *)d_active, K, d_nn);
   const float thr2 = p.similarity_threshold * p.similarity_threshold;
-  PB_LAUNCH(prerej_batch_polygon_kernel, (double)total * (38.0 * S + 1.0), dim3(grid_of(total)), dim3(kPrBlock), 0, st, v, (uint32_t)total, thr2,
-            d_flags, d_nan);
-  {
-    KernelTimer kt(ctx, "prerej_batch_select", 5.0 * (double)total);
-    ++St.launches;
-    e = rocprim::select(d_sel, tb, rocprim::counting_iterator<uint32_t>(0), d_flags, d_surv, d_nsurv, total, st);
-  }
+  STAGE_LAUNCH(ctx, St.launches, prerej_batch_polygon_kernel, (double)total * (38.0 * S + 1.0), dim3(grid_of(total, kPrBlock)), dim3(kPrBlock), 0, st, v,
+               (uint32_t)total, thr2, d_flags, d_nan);
+  e = select_flagged(ctx, "prerej_batch_select", 5.0 * (double)total, &St.launches, d_sel, tb, d_flags, d_surv, d_nsurv, total);
   if (e != hipSuccess) return fail("select");
-  PB_LAUNCH(prerej_batch_offsets_kernel, 8.0 * (double)na, dim3(grid_of(na + 1)), dim3(kPrBlock), 0, st, (const uint32_t *)d_surv,
-            (const uint32_t *)d_nsurv, (uint32_t)na, (uint32_t)H, d_off);
+  STAGE_LAUNCH(ctx, St.launches, prerej_batch_offsets_kernel, 8.0 * (double)na, dim3(grid_of(na + 1, kPrBlock)), dim3(kPrBlock), 0, st,
+               (const uint32_t *)d_surv, (const uint32_t *)d_nsurv, (uint32_t)na, (uint32_t)H, d_off);
   std::vector<uint32_t> words(2 * na + 2);
   e = hipGetLastError();
   if (e == hipSuccess) e = coarse_front_download(ctx, fr);
@@ -320,13 +284,13 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
   if (e == hipSuccess) e = hipFuncSetAttribute((const void *)prerej_batch_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return fail("buffers");
   const double max_d2 = p.max_corr_dist * p.max_corr_dist;
-  PB_LAUNCH(prerej_batch_fit_kernel, (double)nsurv * (38.0 * S + 112.0), dim3(grid_of(nsurv, 64)), dim3(64), 0, st, v, (const uint32_t *)d_surv, nsurv,
-            d_T, d_rows);
+  STAGE_LAUNCH(ctx, St.launches, prerej_batch_fit_kernel, (double)nsurv * (38.0 * S + 112.0), dim3(grid_of(nsurv, 64)), dim3(64), 0, st, v,
+               (const uint32_t *)d_surv, nsurv, d_T, d_rows);
   const unsigned score_blocks = (unsigned)std::min<size_t>(std::max<size_t>(nitems, 1), (size_t)1 << 30);
-  PB_LAUNCH(prerej_batch_score_kernel, 16.0 * (double)nsk * (double)nsurv, dim3(score_blocks), dim3(256), lds, st, v, (const uint32_t *)d_surv,
-            (const float *)d_rows, (unsigned long long)nitems, (uint32_t)chunks, max_d2, d_pcnt, d_psum);
-  PB_LAUNCH(prerej_batch_reduce_kernel, 12.0 * (double)nitems, dim3(grid_of(nsurv)), dim3(kPrBlock), 0, st, (const uint32_t *)d_pcnt,
-            (const double *)d_psum, nsurv, (uint32_t)chunks, d_inl, d_err);
+  STAGE_LAUNCH(ctx, St.launches, prerej_batch_score_kernel, 16.0 * (double)nsk * (double)nsurv, dim3(score_blocks), dim3(256), lds, st, v,
+               (const uint32_t *)d_surv, (const float *)d_rows, (unsigned long long)nitems, (uint32_t)chunks, max_d2, d_pcnt, d_psum);
+  STAGE_LAUNCH(ctx, St.launches, prerej_batch_reduce_kernel, 12.0 * (double)nitems, dim3(grid_of(nsurv, kPrBlock)), dim3(kPrBlock), 0, st,
+               (const uint32_t *)d_pcnt, (const double *)d_psum, nsurv, (uint32_t)chunks, d_inl, d_err);
   std::vector<uint32_t> surv(ns1);
   std::vector<int32_t> inl(ns1);
   std::vector<float> Ts(16 * ns1);
@@ -410,7 +374,6 @@ int ope_prerejective_batch_last_stats(const ope_ctx *ctx, ope_prerejective_batch
 
 int ope_prerejective_batch_hypotheses(const ope_ctx *ctx, int which, int32_t *samples, int32_t *targets, uint8_t *survived, float *T,
                                       int32_t *inliers, double *error, size_t cap, size_t *n_out) {
-  static const float I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   if (!ctx || !n_out) return OPE_EINVAL;
   *n_out = 0;
   if (ctx->pb_hyp_off.empty() || which < 0 || (size_t)which + 1 >= ctx->pb_hyp_off.size()) return OPE_EINVAL;
@@ -420,7 +383,7 @@ int ope_prerejective_batch_hypotheses(const ope_ctx *ctx, int which, int32_t *sa
   if (targets && w) std::memcpy(targets, ctx->pb_targets.data() + S * h0, 4 * S * w);
   if (survived && w) std::memcpy(survived, ctx->pb_survived.data() + h0, w);
   for (size_t it = 0; it < w; ++it) {
-    if (T) std::memcpy(T + 16 * it, I4, sizeof I4);
+    if (T) std::memcpy(T + 16 * it, kIdentity4, sizeof kIdentity4);
     if (inliers) inliers[it] = 0;
     if (error) error[it] = (double)FLT_MAX;
   }

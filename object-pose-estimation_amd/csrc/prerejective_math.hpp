@@ -5,15 +5,30 @@
 #pragma once
 
 #include <cfloat>
+#include <cmath>
 #include <cstdint>
+#include <string>
 
 #include "bvh_traverse.hpp"
+#include "feature_math.hpp"
 #include "icp_update.hpp"
 
 namespace ope {
 
 constexpr int kPrBlock = 256;
 constexpr int kPrMaxIterations = 1 << 20;
+
+// the refusals of the parameters, the same for one alignment and for a batch; who: the entry point its errors name
+inline int prerej_check_params(ope_ctx *ctx, const char *who, const ope_prerejective_params &p) {
+  const auto refuse = [&](const char *why) { return set_err(ctx, OPE_EINVAL, std::string(who) + why); };
+  if (p.max_iterations < 1 || p.max_iterations > kPrMaxIterations) return refuse("max_iterations must be 1 .. 2^20");
+  if (p.nr_samples < 3 || p.nr_samples > 8) return refuse("nr_samples must be 3 .. 8");
+  if (p.k_correspondences < 1 || p.k_correspondences > kFeatK) return refuse("k_correspondences must be 1 .. 8");
+  if (!(p.similarity_threshold >= 0.f && p.similarity_threshold < 1.f)) return refuse("similarity_threshold must be inside [0, 1)");
+  if (!(p.inlier_fraction >= 0.f && p.inlier_fraction <= 1.f)) return refuse("inlier_fraction must be inside [0, 1]");
+  if (!(p.max_corr_dist > 0.0) || !std::isfinite(p.max_corr_dist)) return refuse("max_corr_dist must be > 0 and finite");
+  return OPE_OK;
+}
 
 // The draws of every iteration (host; they depend on nothing the device computes): nr_samples distinct source indices
 // int(ns * next()), then nr_samples picks int(K * next()), from the LCG stream of sacia_draws.  samp / pick: H * S entries.

@@ -104,7 +104,5 @@ int bits_for(unsigned long long v) {
   while (b < 64 && (v >> b) != 0ull) ++b;
   return b;
 }
-unsigned grid_of(size_t n) { return (unsigned)std::max<size_t>((n + kRgBlock - 1) / kRgBlock, 1); }
-
 }  // namespace
 }  // namespace ope

@@ -35,6 +35,7 @@
 #include "bvh_traverse.hpp"
 #include "coarse_stages.hpp"
 #include "region_common.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 
@@ -228,25 +229,11 @@ int check_params(ope_ctx *ctx, const char *who, const ope_cloud *cloud, const op
   return OPE_OK;
 }
 
-#define RG_LAUNCH(name, label, bytes, ...)           \
-  do {                                               \
-    KernelTimer kt_(ctx, label, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++ctx->region_stats.launches;                    \
-  } while (0)
-#define RG_PRIM(label, call)                          \
-  do {                                                \
-    if (e == hipSuccess) {                            \
-      KernelTimer kt_(ctx, label, 0.0);               \
-      e = (call);                                     \
-      ++ctx->region_stats.launches;                   \
-    }                                                 \
-  } while (0)
-
 // Steps 0-5.  On success the device buffers the _cloud form needs stay in tmp.
 int region_core(ope_ctx *ctx, CallTmp &tmp, const char *who, ope_cloud *cloud, const ope_region_params &p, const float *normals, const float *curvature,
                 size_t max_clusters, bool want_idx, int32_t *out_idx, int32_t *out_offsets, int32_t *out_label, Result &res,
                 const int32_t **d_idx_out, const uint32_t **d_roff_out, const float4 **d_pts_out, const uint32_t **d_pos_out) {
+  ope_region_stats &St = ctx->region_stats;
   const uint32_t n = (uint32_t)cloud->n, n_valid = (uint32_t)cloud->n_valid;
   const int k = p.number_of_neighbours;
   const float c = (float)std::cos((double)(float)p.smoothness_threshold);
@@ -292,10 +279,10 @@ int region_core(ope_ctx *ctx, CallTmp &tmp, const char *who, ope_cloud *cloud, c
   if (e == hipSuccess) e = hipMemsetAsync(words, 0, 64, st);
   if (e == hipSuccess) e = hipMemsetAsync(rsz, 0, 4ull * n, st);
   if (e == hipSuccess) e = hipMemsetAsync(osize, 0, 4ull * (n + 1), st);
-  ctx->region_stats.launches += 3;
+  St.launches += 3;
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
   // 0. positions; the caller's normals into the sorted order
-  RG_LAUNCH(rg_pos_kernel, "rg_pos_kernel", 36.0 * n, dim3(grid_of(n)), dim3(kRgBlock), 0, st, cv, pts_by_o, pos_by_o);
+  STAGE_LAUNCH(ctx, St.launches, rg_pos_kernel, 36.0 * n, dim3(grid_of(n, kRgBlock)), dim3(kRgBlock), 0, st, cv, pts_by_o, pos_by_o);
   const float4 *nrm = cloud->d_nrm;
   if (normals) {
     std::vector<float> packed(4ull * n);
@@ -303,29 +290,29 @@ int region_core(ope_ctx *ctx, CallTmp &tmp, const char *who, ope_cloud *cloud, c
       packed[4 * i] = normals[3 * i]; packed[4 * i + 1] = normals[3 * i + 1]; packed[4 * i + 2] = normals[3 * i + 2];
       packed[4 * i + 3] = curvature[i];
     }
-    e = h2d_copy(st, nrm_by_o, packed.data(), 16ull * n);
-    if (16ull * n > kStageSmall) ctx->region_stats.host_syncs += (int64_t)((16ull * n + kStageChunk - 1) / kStageChunk);   // (a staged upload waits per chunk)
+    e = h2d_copy(st, nrm_by_o, packed.data(), 16ull * n, &St.host_syncs);   // (a staged upload waits per chunk)
     if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-    RG_LAUNCH(rg_gather_normals_kernel, "rg_gather_normals_kernel", 36.0 * n, dim3(grid_of(n)), dim3(kRgBlock), 0, st, cv, nrm_by_o, nrm_own);
+    STAGE_LAUNCH(ctx, St.launches, rg_gather_normals_kernel, 36.0 * n, dim3(grid_of(n, kRgBlock)), dim3(kRgBlock), 0, st, cv, nrm_by_o, nrm_own);
     nrm = nrm_own;
   }
   if (!nrm) return set_err(ctx, OPE_ESTATE, std::string(who) + "the cloud carries no normals");
   // 1. the refusal count, then the ranks
-  RG_LAUNCH(rg_key_kernel, "rg_key_kernel", 32.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, cv, nrm, curv_thr, keys, vals, words);
+  STAGE_LAUNCH(ctx, St.launches, rg_key_kernel, 32.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, cv, nrm, curv_thr, keys, vals, words);
   uint32_t refused = 0;
   e = hipMemcpyAsync(&refused, words, 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  ++ctx->region_stats.host_syncs;
+  ++St.host_syncs;
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  ctx->region_stats.refused_curvature = (int64_t)refused;
+  St.refused_curvature = (int64_t)refused;
   if (refused)
     return set_err(ctx, OPE_EINVAL, std::string(who) + std::to_string(refused) + " point(s) have a curvature above curvature_threshold: PCL's rule "
                    "for such points (labelled, not expanded unless a seed) is not built");
   uint64_t one_way = 0;
   int sweeps = 0;
   if (n_valid > 0) {
-    RG_PRIM("rg_sort_ranks", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), keys, skey, vals, sval, n_valid, 0, 64, st));
-    RG_LAUNCH(rg_rank_kernel, "rg_rank_kernel", 16.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, sval, n_valid, rank_of_pos, parent, L);
+    STAGE_PRIM(ctx, St.launches, e, "rg_sort_ranks", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), keys, skey, vals, sval, n_valid, 0, 64, st));
+    STAGE_LAUNCH(ctx, St.launches, rg_rank_kernel, 16.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, sval, n_valid, rank_of_pos, parent,
+                 L);
     if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
     // 2. the cloud's own tree, start leaves, the graph
     ope_index *ix = nullptr;
@@ -336,31 +323,31 @@ int region_core(ope_ctx *ctx, CallTmp &tmp, const char *who, ope_cloud *cloud, c
     if (rc != OPE_OK) return rc;
     struct FreeIx { ope_index *p; ~FreeIx() { ope_index_free(p); } } free_ix{ix};
     e = self_leaves(st, ix->view(), n, self_leaf);
-    ctx->region_stats.launches += 2;
+    St.launches += 2;
     if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
     const unsigned gblocks = (unsigned)std::min<size_t>(((size_t)n_valid + kKnnBlock - 1) / kKnnBlock, 4096);
     if (k == 15)
-      RG_LAUNCH(rg_graph_kernel<15>, "rg_graph_kernel", (double)n_valid * (16.0 + 36.0 * k), dim3(gblocks), dim3(kKnnBlock), 0, st, cv, ix->view(), nrm,
-                pos_by_o, self_leaf, k, c, adj);
+      STAGE_LAUNCH_AS(ctx, St.launches, rg_graph_kernel<15>, "rg_graph_kernel", (double)n_valid * (16.0 + 36.0 * k), dim3(gblocks), dim3(kKnnBlock), 0, st, cv,
+                      ix->view(), nrm, pos_by_o, self_leaf, k, c, adj);
     else
-      RG_LAUNCH(rg_graph_kernel<0>, "rg_graph_kernel", (double)n_valid * (16.0 + 36.0 * k), dim3(gblocks), dim3(kKnnBlock), kKnnLdsBytes, st, cv,
-                ix->view(), nrm, pos_by_o, self_leaf, k, c, adj);
+      STAGE_LAUNCH_AS(ctx, St.launches, rg_graph_kernel<0>, "rg_graph_kernel", (double)n_valid * (16.0 + 36.0 * k), dim3(gblocks), dim3(kKnnBlock),
+                      kKnnLdsBytes, st, cv, ix->view(), nrm, pos_by_o, self_leaf, k, c, adj);
     // 3. mutual edges -> components
-    RG_LAUNCH(rg_mutual_kernel, "rg_mutual_kernel", (double)n_valid * 8.0 * k, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, adj, rank_of_pos, n_valid, k, parent,
-              ow, (unsigned long long *)(words + 4));
-    RG_LAUNCH(rg_flatten_kernel, "rg_flatten_kernel", 8.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, n_valid, parent);
+    STAGE_LAUNCH(ctx, St.launches, rg_mutual_kernel, (double)n_valid * 8.0 * k, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, adj, rank_of_pos,
+                 n_valid, k, parent, ow, (unsigned long long *)(words + 4));
+    STAGE_LAUNCH(ctx, St.launches, rg_flatten_kernel, 8.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, n_valid, parent);
     // 4. sweeps, four at a time, until one changes nothing
     for (bool done = false; !done;) {
       e = hipMemsetAsync(words + 8, 0, 4 * kSweepBatch, st);
-      ++ctx->region_stats.launches;
+      ++St.launches;
       if (e != hipSuccess) break;
       for (int s = 0; s < kSweepBatch; ++s)
-        RG_LAUNCH(rg_sweep_kernel, "rg_sweep_kernel", (double)n_valid * (12.0 + 4.0 * k), dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, ow, rank_of_pos,
-                  parent, n_valid, k, L, words + 8 + s);
+        STAGE_LAUNCH(ctx, St.launches, rg_sweep_kernel, (double)n_valid * (12.0 + 4.0 * k), dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, ow,
+                     rank_of_pos, parent, n_valid, k, L, words + 8 + s);
       uint32_t hw[8 + kSweepBatch];
       e = hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
-      ++ctx->region_stats.host_syncs;
+      ++St.host_syncs;
       if (e != hipSuccess) break;
       one_way = (uint64_t)hw[4] | ((uint64_t)hw[5] << 32);
       for (int s = 0; s < kSweepBatch && !done; ++s) {
@@ -370,18 +357,19 @@ int region_core(ope_ctx *ctx, CallTmp &tmp, const char *who, ope_cloud *cloud, c
     }
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e)); }
     // 5. sizes, the filter, the order
-    RG_LAUNCH(rg_size_kernel, "rg_size_kernel", 16.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, parent, L, n_valid, lab, rsz);
-    RG_LAUNCH(rg_flag_kernel, "rg_flag_kernel", 8.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, rsz, n_valid, (uint32_t)p.min_size,
-              (uint32_t)p.max_size, flag, words + 1);
-    RG_PRIM("rg_scan_regions", rocprim::exclusive_scan(d_tmp, (t1 = tb), flag, rrank, 0u, (size_t)n_valid, rocprim::plus<uint32_t>(), st));
-    RG_LAUNCH(rg_order_kernel, "rg_order_kernel", 16.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, flag, rrank, rsz, n_valid, osize,
-              words + 2);
+    STAGE_LAUNCH(ctx, St.launches, rg_size_kernel, 16.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, parent, L, n_valid, lab, rsz);
+    STAGE_LAUNCH(ctx, St.launches, rg_flag_kernel, 8.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, rsz, n_valid, (uint32_t)p.min_size,
+                 (uint32_t)p.max_size, flag, words + 1);
+    STAGE_PRIM(ctx, St.launches, e, "rg_scan_regions",
+               rocprim::exclusive_scan(d_tmp, (t1 = tb), flag, rrank, 0u, (size_t)n_valid, rocprim::plus<uint32_t>(), st));
+    STAGE_LAUNCH(ctx, St.launches, rg_order_kernel, 16.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, flag, rrank, rsz, n_valid, osize,
+                 words + 2);
     // (the index goes back here; the stream's later work runs behind the walk that read it)
   }
-  RG_PRIM("rg_scan_offsets", rocprim::exclusive_scan(d_tmp, (t1 = tb), osize, roff, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-  RG_LAUNCH(rg_label_kernel, "rg_label_kernel", 32.0 * n, dim3(grid_of(n)), dim3(kRgBlock), 0, st, pos_by_o, rank_of_pos, lab, flag, rrank, n, n_valid,
-            (uint32_t)kcap, label, lkey, lval);
-  RG_PRIM("rg_sort_labels", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), lkey, lkey2, lval, idx, n, 0, lbits, st));
+  STAGE_PRIM(ctx, St.launches, e, "rg_scan_offsets", rocprim::exclusive_scan(d_tmp, (t1 = tb), osize, roff, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
+  STAGE_LAUNCH(ctx, St.launches, rg_label_kernel, 32.0 * n, dim3(grid_of(n, kRgBlock)), dim3(kRgBlock), 0, st, pos_by_o, rank_of_pos, lab, flag, rrank, n,
+               n_valid, (uint32_t)kcap, label, lkey, lval);
+  STAGE_PRIM(ctx, St.launches, e, "rg_sort_labels", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), lkey, lkey2, lval, idx, n, 0, lbits, st));
   // the read-back: regions, K, offsets, indices, labels
   uint32_t hw[4] = {0, 0, 0, 0};
   std::vector<uint32_t> off(kcap + 1, 0);
@@ -390,11 +378,11 @@ int region_core(ope_ctx *ctx, CallTmp &tmp, const char *who, ope_cloud *cloud, c
   if (e == hipSuccess && want_idx && n) e = hipMemcpyAsync(out_idx, idx, 4ull * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && out_label && n) e = hipMemcpyAsync(out_label, label, 4ull * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  ++ctx->region_stats.host_syncs;
+  ++St.host_syncs;
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  ctx->region_stats.sweeps = sweeps;
-  ctx->region_stats.one_way_edges = (int64_t)one_way;
-  ctx->region_stats.regions_before_size_filter = (int64_t)hw[1];
+  St.sweeps = sweeps;
+  St.one_way_edges = (int64_t)one_way;
+  St.regions_before_size_filter = (int64_t)hw[1];
   res.K = hw[2];
   res.kw = std::min<size_t>(res.K, kcap);
   off.resize(res.kw + 1);

@@ -33,6 +33,7 @@
 #include "bvh_traverse.hpp"
 #include "coarse_stages.hpp"
 #include "region_common.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 
@@ -378,20 +379,6 @@ int check_params(ope_ctx *ctx, const char *who, const ope_cloud *cloud, const op
   return OPE_OK;
 }
 
-#define RGB_LAUNCH(name, label, bytes, ...)          \
-  do {                                               \
-    KernelTimer kt_(ctx, label, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++stats.launches;                                \
-  } while (0)
-#define RGB_PRIM(label, call)                         \
-  do {                                                \
-    if (e == hipSuccess) {                            \
-      KernelTimer kt_(ctx, label, 0.0);               \
-      e = (call);                                     \
-      ++stats.launches;                               \
-    }                                                 \
-  } while (0)
 #define RGB_CHECK()                                                                              \
   do {                                                                                           \
     if (e == hipSuccess) e = hipGetLastError();                                                  \
@@ -465,7 +452,7 @@ int region_rgb_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud
   if (e == hipSuccess) e = hipMemsetAsync(kept_n, 0, 4ull * nv1, st);
   stats.launches += 4;
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
-  RGB_LAUNCH(rg_pos_kernel, "rg_pos_kernel", 36.0 * n, dim3(grid_of(n)), dim3(kRgBlock), 0, st, cv, pts_by_o, pos_by_o);
+  STAGE_LAUNCH(ctx, stats.launches, rg_pos_kernel, 36.0 * n, dim3(grid_of(n, kRgBlock)), dim3(kRgBlock), 0, st, cv, pts_by_o, pos_by_o);
   std::vector<int32_t> cluster_of_seg;
   std::vector<uint32_t> cluster_size;
   uint64_t one_way = 0;
@@ -473,9 +460,10 @@ int region_rgb_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud
   uint32_t S = 0;
   if (n_valid > 0) {
     // 1. ranks
-    RGB_LAUNCH(rgb_finite_kernel, "rgb_finite_kernel", 8.0 * n, dim3(grid_of(n)), dim3(kRgBlock), 0, st, pos_by_o, n, n_valid, fin);
-    RGB_PRIM("rgb_scan_ranks", rocprim::exclusive_scan(d_tmp, (t1 = tb), fin, frank, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-    RGB_LAUNCH(rgb_rank_kernel, "rgb_rank_kernel", 32.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, cv, frank, rank_of_pos, parent, L);
+    STAGE_LAUNCH(ctx, stats.launches, rgb_finite_kernel, 8.0 * n, dim3(grid_of(n, kRgBlock)), dim3(kRgBlock), 0, st, pos_by_o, n, n_valid, fin);
+    STAGE_PRIM(ctx, stats.launches, e, "rgb_scan_ranks", rocprim::exclusive_scan(d_tmp, (t1 = tb), fin, frank, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+    STAGE_LAUNCH(ctx, stats.launches, rgb_rank_kernel, 32.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, cv, frank, rank_of_pos, parent,
+                 L);
     RGB_CHECK();
     // 2. the cloud's own tree, start leaves, the search
     ope_index *ix = nullptr;
@@ -489,12 +477,12 @@ int region_rgb_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud
     stats.launches += 2;
     RGB_CHECK();
     const unsigned sblocks = (unsigned)std::min<size_t>(((size_t)n_valid + kRgbLanes - 1) / kRgbLanes, 16384);
-    RGB_LAUNCH(rgb_search_kernel, "rgb_search_kernel", (double)n_valid * (20.0 + 24.0 * k), dim3(sblocks), dim3(kRgbLanes), lds, st, cv, ix->view(), pos_by_o,
-               self_leaf, k, nbr, nd2, rowmax);
+    STAGE_LAUNCH(ctx, stats.launches, rgb_search_kernel, (double)n_valid * (20.0 + 24.0 * k), dim3(sblocks), dim3(kRgbLanes), lds, st, cv, ix->view(), pos_by_o,
+                 self_leaf, k, nbr, nd2, rowmax);
     // 3. edges -> components
-    RGB_LAUNCH(rgb_edges_kernel, "rgb_edges_kernel", (double)n_valid * 16.0 * k, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, nbr, nd2, rowmax, cloud->d_rgb,
-               rank_of_pos, n_valid, k, p2_thr, parent, ow, (unsigned long long *)(words + 4));
-    RGB_LAUNCH(rg_flatten_kernel, "rg_flatten_kernel", 8.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, n_valid, parent);
+    STAGE_LAUNCH(ctx, stats.launches, rgb_edges_kernel, (double)n_valid * 16.0 * k, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, nbr, nd2, rowmax,
+                 cloud->d_rgb, rank_of_pos, n_valid, k, p2_thr, parent, ow, (unsigned long long *)(words + 4));
+    STAGE_LAUNCH(ctx, stats.launches, rg_flatten_kernel, 8.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, n_valid, parent);
     RGB_CHECK();
     // 4. sweeps, four at a time, until one changes nothing
     for (bool done = false; !done;) {
@@ -502,8 +490,8 @@ int region_rgb_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud
       ++stats.launches;
       if (e != hipSuccess) break;
       for (int s = 0; s < kSweepBatch; ++s)
-        RGB_LAUNCH(rg_sweep_kernel, "rg_sweep_kernel", (double)n_valid * (12.0 + 4.0 * k), dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, ow, rank_of_pos,
-                   parent, n_valid, k, L, words + 8 + s);
+        STAGE_LAUNCH(ctx, stats.launches, rg_sweep_kernel, (double)n_valid * (12.0 + 4.0 * k), dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, ow,
+                     rank_of_pos, parent, n_valid, k, L, words + 8 + s);
       uint32_t hw[8 + kSweepBatch];
       e = hipMemcpyAsync(hw, words, sizeof hw, hipMemcpyDeviceToHost, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -517,19 +505,21 @@ int region_rgb_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud
     }
     RGB_CHECK();
     // 5. segments: label per rank, sizes by seed rank, dense numbers, colour sums
-    RGB_LAUNCH(rg_size_kernel, "rg_size_kernel", 16.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, parent, L, n_valid, lab, rsz);
-    RGB_LAUNCH(rgb_seed_kernel, "rgb_seed_kernel", 8.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, rsz, n_valid, flag);
-    RGB_PRIM("rgb_scan_segments", rocprim::exclusive_scan(d_tmp, (t1 = tb), flag, segno, 0u, (size_t)n_valid, rocprim::plus<uint32_t>(), st));
-    RGB_LAUNCH(rgb_stats_kernel, "rgb_stats_kernel", 24.0 * n_valid, dim3(grid_of(n_valid)), dim3(kRgBlock), 0, st, rank_of_pos, lab, segno, flag, cloud->d_rgb,
-               n_valid, seg_of_pos, stat, words);
+    STAGE_LAUNCH(ctx, stats.launches, rg_size_kernel, 16.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, parent, L, n_valid, lab, rsz);
+    STAGE_LAUNCH(ctx, stats.launches, rgb_seed_kernel, 8.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, rsz, n_valid, flag);
+    STAGE_PRIM(ctx, stats.launches, e, "rgb_scan_segments",
+               rocprim::exclusive_scan(d_tmp, (t1 = tb), flag, segno, 0u, (size_t)n_valid, rocprim::plus<uint32_t>(), st));
+    STAGE_LAUNCH(ctx, stats.launches, rgb_stats_kernel, 24.0 * n_valid, dim3(grid_of(n_valid, kRgBlock)), dim3(kRgBlock), 0, st, rank_of_pos, lab, segno, flag,
+                 cloud->d_rgb, n_valid, seg_of_pos, stat, words);
     // 6. segment pairs: (seg u, seg v) -> min d2
     const size_t total = (size_t)n_valid * (size_t)k;
-    RGB_LAUNCH(rgb_pair_keys_kernel, "rgb_pair_keys_kernel", 20.0 * total, dim3(grid_of(total)), dim3(kRgBlock), 0, st, nbr, nd2, seg_of_pos, total, k, pkey,
-               pval);
-    RGB_PRIM("rgb_sort_pairs", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), pkey, pkey2, pval, pval2, total, 0, 64, st));
-    RGB_PRIM("rgb_reduce_pairs", rocprim::reduce_by_key(d_tmp, (t1 = tb), pkey2, pval2, total, pkey, pval, words + 2, rocprim::minimum<uint32_t>(),
-                                                        rocprim::equal_to<unsigned long long>(), st));
-    RGB_LAUNCH(rgb_pair_count_kernel, "rgb_pair_count_kernel", 16.0, dim3(1), dim3(1), 0, st, pkey, words + 2, words);
+    STAGE_LAUNCH(ctx, stats.launches, rgb_pair_keys_kernel, 20.0 * total, dim3(grid_of(total, kRgBlock)), dim3(kRgBlock), 0, st, nbr, nd2, seg_of_pos, total, k,
+                 pkey, pval);
+    STAGE_PRIM(ctx, stats.launches, e, "rgb_sort_pairs", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), pkey, pkey2, pval, pval2, total, 0, 64, st));
+    STAGE_PRIM(ctx, stats.launches, e, "rgb_reduce_pairs",
+               rocprim::reduce_by_key(d_tmp, (t1 = tb), pkey2, pval2, total, pkey, pval, words + 2, rocprim::minimum<uint32_t>(),
+                                      rocprim::equal_to<unsigned long long>(), st));
+    STAGE_LAUNCH(ctx, stats.launches, rgb_pair_count_kernel, 16.0, dim3(1), dim3(1), 0, st, pkey, words + 2, words);
     uint32_t hw[2] = {0, 0};
     if (e == hipSuccess) e = hipMemcpyAsync(hw, words, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -543,11 +533,11 @@ int region_rgb_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud
     auto *kept_d = (uint32_t *)tmp.get(4ull * sk, e), *kept_t = (uint32_t *)tmp.get(4ull * sk, e);
     if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string(who) + hipGetErrorString(e));
     const uint32_t np1 = std::max<uint32_t>(np, 1);
-    RGB_LAUNCH(rgb_pair_rekey_kernel, "rgb_pair_rekey_kernel", 24.0 * np, dim3(grid_of(np1)), dim3(kRgBlock), 0, st, pkey, pval, np, pkey2, pval2);
-    RGB_PRIM("rgb_sort_kept", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), pkey2, pkey, pval2, pval, (size_t)np, 0, 32 + sbits, st));
-    RGB_LAUNCH(rgb_pair_start_kernel, "rgb_pair_start_kernel", 12.0 * np, dim3(grid_of(np1)), dim3(kRgBlock), 0, st, pkey, np, pstart);
-    RGB_LAUNCH(rgb_pair_keep_kernel, "rgb_pair_keep_kernel", 24.0 * np, dim3(grid_of(np1)), dim3(kRgBlock), 0, st, pkey, pval, np, pstart, k, kept_d, kept_t,
-               kept_n);
+    STAGE_LAUNCH(ctx, stats.launches, rgb_pair_rekey_kernel, 24.0 * np, dim3(grid_of(np1, kRgBlock)), dim3(kRgBlock), 0, st, pkey, pval, np, pkey2, pval2);
+    STAGE_PRIM(ctx, stats.launches, e, "rgb_sort_kept", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), pkey2, pkey, pval2, pval, (size_t)np, 0, 32 + sbits, st));
+    STAGE_LAUNCH(ctx, stats.launches, rgb_pair_start_kernel, 12.0 * np, dim3(grid_of(np1, kRgBlock)), dim3(kRgBlock), 0, st, pkey, np, pstart);
+    STAGE_LAUNCH(ctx, stats.launches, rgb_pair_keep_kernel, 24.0 * np, dim3(grid_of(np1, kRgBlock)), dim3(kRgBlock), 0, st, pkey, pval, np, pstart, k, kept_d,
+                 kept_t, kept_n);
     // 7. the one download of the tables, and the merges on the host
     Segments g;
     g.S = S;
@@ -584,9 +574,9 @@ int region_rgb_core(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   ++stats.host_syncs;
   RGB_CHECK();
-  RGB_LAUNCH(rgb_label_kernel, "rgb_label_kernel", 32.0 * n, dim3(grid_of(n)), dim3(kRgBlock), 0, st, pos_by_o, seg_of_pos, (const int32_t *)d_up, n, n_valid,
-             (uint32_t)kcap, label, lkey, lval);
-  RGB_PRIM("rgb_sort_labels", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), lkey, lkey2, lval, idx, n, 0, lbits, st));
+  STAGE_LAUNCH(ctx, stats.launches, rgb_label_kernel, 32.0 * n, dim3(grid_of(n, kRgBlock)), dim3(kRgBlock), 0, st, pos_by_o, seg_of_pos, (const int32_t *)d_up,
+               n, n_valid, (uint32_t)kcap, label, lkey, lval);
+  STAGE_PRIM(ctx, stats.launches, e, "rgb_sort_labels", rocprim::radix_sort_pairs(d_tmp, (t1 = tb), lkey, lkey2, lval, idx, n, 0, lbits, st));
   if (e == hipSuccess && want_idx && n) e = hipMemcpyAsync(out_idx, idx, 4ull * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && out_label && n) e = hipMemcpyAsync(out_label, label, 4ull * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);

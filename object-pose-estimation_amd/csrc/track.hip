@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "coarse_stages.hpp"
+#include "stage_host.hpp"
 
 namespace ope {
 
@@ -151,14 +152,10 @@ int gate_run(ope_ctx *ctx, CallTmp &tmp, const ope_cloud *source, size_t n, cons
         hipLaunchKernelGGL(track_scatter_kernel, dim3((total + kGateBlock - 1) / kGateBlock), dim3(kGateBlock), 0, ctx->stream, d_segs, d_off,
                            (uint32_t)nseg, total, d_pts);
     }
-    {
-      KernelTimer kt(ctx, "track_centroid_kernel", 12.0 * (off[ncent]));
-      hipLaunchKernelGGL(track_centroid_kernel, dim3((unsigned)ncent), dim3(kGateBlock), 0, ctx->stream, d_segs, d_off, d_pts, d_cent);
-    }
-    {
-      KernelTimer kt(ctx, "track_decide_kernel", 0.0);
-      hipLaunchKernelGGL(track_decide_kernel, dim3(1), dim3(kGateBlock), 0, ctx->stream, d_cent, (uint32_t)n, gate, d_dist, d_dec);
-    }
+    STAGE_LAUNCH_TIMED(ctx, track_centroid_kernel, "track_centroid_kernel", 12.0 * (off[ncent]), dim3((unsigned)ncent), dim3(kGateBlock), 0, ctx->stream,
+                       d_segs, d_off, d_pts, d_cent);
+    STAGE_LAUNCH_TIMED(ctx, track_decide_kernel, "track_decide_kernel", 0.0, dim3(1), dim3(kGateBlock), 0, ctx->stream, d_cent, (uint32_t)n, gate, d_dist,
+                       d_dec);
   }
   std::vector<unsigned char> back(back_bytes);
   e = hipGetLastError();
@@ -201,8 +198,6 @@ void matmul4(const float *a, const float *b, float *out) {
     }
   std::memcpy(out, r, sizeof r);
 }
-
-const float kI4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
 }  // namespace
 
@@ -255,7 +250,7 @@ int ope_track_pose(ope_ctx *ctx, const ope_cloud *model, const ope_cloud *source
   out->coarse_status = OPE_TRACK_COARSE_SKIPPED;
   out->status = OPE_FINAL_EMPTY_TARGET;
   out->fitness = std::numeric_limits<double>::max();
-  for (float *m : {out->coarse, out->fine, out->rigid, out->final_pose}) std::memcpy(m, kI4, sizeof kI4);
+  for (float *m : {out->coarse, out->fine, out->rigid, out->final_pose}) std::memcpy(m, kIdentity4, sizeof kIdentity4);
   if (n == 0) return OPE_OK;
   // refusals before anything is launched: what ope_final_pose_batch refuses for (model, clusters) and, when the coarse stage is
   // to run, what the coarse stage refuses for (source, clusters)
@@ -294,7 +289,7 @@ int ope_track_pose(ope_ctx *ctx, const ope_cloud *model, const ope_cloud *source
   const ope_cloud *cl = clusters[g];
   ope_coarse_batch_result cres;
   std::memset(&cres, 0, sizeof cres);
-  std::memcpy(cres.T, kI4, sizeof kI4);
+  std::memcpy(cres.T, kIdentity4, sizeof kIdentity4);
   cres.status = OPE_TRACK_COARSE_SKIPPED;
   cres.best_iteration = -1;
   if (coarse_runs) {

@@ -25,6 +25,7 @@
 
 #include "coarse_stages.hpp"
 #include "feature_math.hpp"
+#include "stage_host.hpp"
 
 struct ope_vfh_db {
   ope_ctx *ctx = nullptr;
@@ -247,13 +248,6 @@ __global__ __launch_bounds__(kVfhBlock) void vfh_chi2_kernel(const float *__rest
   }
 }
 
-#define VFH_LAUNCH(name, label, bytes, ...)          \
-  do {                                               \
-    KernelTimer kt_(ctx, label, (double)(bytes));    \
-    hipLaunchKernelGGL(name, __VA_ARGS__);           \
-    ++ctx->vfh_stats.launches;                       \
-  } while (0)
-
 bool finite3(const float *v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 // the refusals of the VFH stages, before anything is launched
@@ -296,8 +290,8 @@ int match_enqueue(ope_ctx *ctx, CallTmp &tmp, const ope_vfh_db *db, const float 
   *d_idx = (int32_t *)tmp.get(4ull * q * (size_t)k, e);
   *d_dist = (float *)tmp.get(4ull * q * (size_t)k, e);
   if (e != hipSuccess) return set_err(ctx, OPE_EHIP, std::string("ope_vfh_match: buffers: ") + hipGetErrorString(e));
-  VFH_LAUNCH(vfh_chi2_kernel, "vfh_chi2_kernel", (double)q * (4.0 * kVfhBins * (double)db->m + 4.0 * kVfhBins), dim3((unsigned)q), dim3(kVfhBlock), 0,
-             ctx->stream, db->d_cols, (uint32_t)db->m, d_queries, k, dist, *d_idx, *d_dist);
+  STAGE_LAUNCH(ctx, ctx->vfh_stats.launches, vfh_chi2_kernel, (double)q * (4.0 * kVfhBins * (double)db->m + 4.0 * kVfhBins), dim3((unsigned)q), dim3(kVfhBlock),
+               0, ctx->stream, db->d_cols, (uint32_t)db->m, d_queries, k, dist, *d_idx, *d_dist);
   return OPE_OK;
 }
 
@@ -335,8 +329,7 @@ int vfh_enqueue(ope_ctx *ctx, CallTmp &tmp, const std::string &who, size_t n, op
   *d_sig = (float *)tmp.get(4ull * kVfhBins * n, e);
   *d_bins = want_bins ? (uchar4 *)tmp.get(4ull * std::max<uint32_t>(total, 1), e) : nullptr;
   *d_words = (uint32_t *)tmp.get(16, e);
-  if (e == hipSuccess) e = h2d_copy(st, d_head, head.data(), head.size());
-  if (head.size() > kStageSmall) ++ctx->vfh_stats.host_syncs;   // (a staged upload waits: beyond ~100 clusters)
+  if (e == hipSuccess) e = h2d_copy(st, d_head, head.data(), head.size(), &ctx->vfh_stats.host_syncs);   // (a staged upload waits: beyond ~100 clusters)
   if (e == hipSuccess) e = hipMemsetAsync(*d_counts, 0, 4ull * kVfhBins * n, st);
   if (e == hipSuccess) e = hipMemsetAsync(*d_words, 0, 16, st);
   ctx->vfh_stats.launches += 2;
@@ -352,13 +345,13 @@ int vfh_enqueue(ope_ctx *ctx, CallTmp &tmp, const std::string &who, size_t n, op
   const unsigned pblocks = (total + kVfhBlock - 1) / kVfhBlock;
   TraceRange r(ctx, "vfh");
   if (total)
-    VFH_LAUNCH(vfh_scatter_kernel, "vfh_scatter_kernel", 64.0 * total, dim3(pblocks), dim3(kVfhBlock), 0, st, d_segs, d_off, (uint32_t)n, total, pts, nrm,
-               *d_words);
-  VFH_LAUNCH(vfh_centroid_kernel, "vfh_centroid_kernel", 32.0 * total, dim3((unsigned)n), dim3(kVfhBlock), 0, st, d_off, pts, nrm, g, geo);
+    STAGE_LAUNCH(ctx, ctx->vfh_stats.launches, vfh_scatter_kernel, 64.0 * total, dim3(pblocks), dim3(kVfhBlock), 0, st, d_segs, d_off, (uint32_t)n, total, pts,
+                 nrm, *d_words);
+  STAGE_LAUNCH(ctx, ctx->vfh_stats.launches, vfh_centroid_kernel, 32.0 * total, dim3((unsigned)n), dim3(kVfhBlock), 0, st, d_off, pts, nrm, g, geo);
   if (total)
-    VFH_LAUNCH(vfh_bins_kernel, "vfh_bins_kernel", 36.0 * total, dim3(pblocks), dim3(kVfhBlock), 0, st, d_off, (uint32_t)n, total, pts, nrm, geo, *d_counts,
-               *d_bins, *d_words);
-  VFH_LAUNCH(vfh_signature_kernel, "vfh_signature_kernel", 8.0 * kVfhBins * n, dim3((unsigned)n), dim3(kVfhSigBlock), 0, st, d_off, *d_counts, *d_sig);
+    STAGE_LAUNCH(ctx, ctx->vfh_stats.launches, vfh_bins_kernel, 36.0 * total, dim3(pblocks), dim3(kVfhBlock), 0, st, d_off, (uint32_t)n, total, pts, nrm, geo,
+                 *d_counts, *d_bins, *d_words);
+  STAGE_LAUNCH(ctx, ctx->vfh_stats.launches, vfh_signature_kernel, 8.0 * kVfhBins * n, dim3((unsigned)n), dim3(kVfhSigBlock), 0, st, d_off, *d_counts, *d_sig);
   return OPE_OK;
 }
 

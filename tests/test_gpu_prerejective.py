@@ -253,6 +253,38 @@ def test_launches_and_syncs_do_not_depend_on_the_sizes(ope, ctx, scene600, run60
     assert counts[("H", 100)][1] == 3          # the feature rows, the survivor count, the results
 
 
+def test_pairs_above_the_staging_block_arrive_whole(ope, ctx):
+    """2^20 iterations of 8 samples: each half of the pairs (samples, targets) is 4 * 8 * 2^20 B = 32 MiB, exactly one staging
+    block, so the two together take the chunked upload, one synchronising piece per half.  Every iteration samples source points
+    0..7; iterations 0, 2^19 and 2^20 - 1 pair them with the congruent targets 0..7 (every edge ratio 1), all others with targets
+    8..15, the source scaled by 2 (every edge ratio 0.25 < 0.8^2)."""
+    H, S = 1 << 20, 8
+    src = np.array([[0.00, 0.00, 0.00], [0.10, 0.00, 0.00], [0.00, 0.07, 0.00], [0.00, 0.00, 0.05],
+                    [0.09, 0.06, 0.01], [0.02, 0.08, 0.04], [0.07, 0.01, 0.06], [0.04, 0.05, 0.09]], np.float32)
+    src += np.float32(0.03)                                       # no point at the centre of the scaling
+    assert np.linalg.matrix_rank((src[1:] - src[0]).astype(np.float64)) == 3
+    tgt = np.concatenate([src, np.float32(2.0) * src])
+    good = np.array([0, H // 2, H - 1])
+    fs = np.empty((2, H, S), np.int32)
+    fs[0] = np.arange(S, dtype=np.int32)
+    fs[1] = np.arange(S, 2 * S, dtype=np.int32)
+    fs[1, good] = np.arange(S, dtype=np.int32)
+    s, t = ctx.upload(src), ctx.upload(tgt)
+    ix = ctx.build_index(t)
+    p = ope.default_prerejective_params(max_iterations=H, nr_samples=S, similarity_threshold=0.8, inlier_fraction=0.25)
+    out = ctx.prerejective(s, None, t, ix, None, p, forced_samples=fs)
+    st = ctx.prerejective_stats()
+    survived = ctx.prerejective_hypotheses()["survived"]
+    print(f"survivors {st['survivors']}, launches {st['launches']}, host_syncs {st['host_syncs']}, best {out.best_iteration}, "
+          f"inliers {out.inliers}, |T - I| {np.abs(out.T.astype(np.float64) - np.eye(4)).max():.3e}")
+    np.testing.assert_array_equal(np.flatnonzero(survived), good)
+    assert st["survivors"] == 3 and out.converged and out.inliers == 8 and out.best_iteration in good
+    assert np.abs(out.T.astype(np.float64) - np.eye(4)).max() <= 1e-6
+    # launches: two for the chunked upload, two original-order launches, polygon, select, fit, score, reduce;
+    # synchronisations: one per upload piece, the survivor count, the results
+    assert (st["launches"], st["host_syncs"]) == (9, 4)
+
+
 # ------------------------------------------------------------------ 6. refusals
 BAD = [dict(nr_samples=2), dict(nr_samples=9), dict(k_correspondences=0), dict(k_correspondences=9), dict(similarity_threshold=-0.1),
        dict(similarity_threshold=1.0), dict(inlier_fraction=-0.1), dict(inlier_fraction=1.5), dict(max_corr_dist=0.0),
