@@ -785,58 +785,58 @@ def from_colmajor(t16) -> np.ndarray:
     return np.asarray(t16, np.float32).reshape(4, 4).T.copy()
 
 
+def _T_stack(T16) -> np.ndarray:
+    """(h, 16) column-major transforms -> (h, 4, 4) math layout."""
+    return T16.reshape(len(T16), 4, 4).transpose(0, 2, 1).copy()
+
+
+def _set_fields(p, kw):
+    """The keyword arguments of a parameter constructor onto its struct: AttributeError for a name that is no field (setattr would
+    quietly make a Python attribute of it); an array field takes any sequence of its length."""
+    types = dict(p._fields_)
+    for k, v in kw.items():
+        if k not in types:
+            raise AttributeError(k)
+        if issubclass(types[k], C.Array):
+            getattr(p, k)[:] = list(v)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _params(Struct, entry: str, kw):
+    """Struct filled by the library's `entry`(Struct *), then the keyword arguments."""
+    p = Struct()
+    getattr(lib(), entry)(C.byref(p))
+    return _set_fields(p, kw)
+
+
 def default_depth_params(sensor="kinect", **kw) -> DepthParams:
     """ope_depth_sensor_params: one of the reference's three presets ("kinect", "astra", "euclid" or an OPE_SENSOR_* value)."""
     p = DepthParams()
     code = SENSORS[sensor] if isinstance(sensor, str) else int(sensor)
     if lib().ope_depth_sensor_params(code, C.byref(p)) != OPE_OK:
         raise ValueError(f"unknown sensor {sensor!r}")
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _set_fields(p, kw)
 
 
 def default_mls_params(**kw) -> MlsParams:
-    p = MlsParams()
-    lib().ope_mls_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(MlsParams, "ope_mls_default_params", kw)
 
 
 def default_mls_upsample_params(**kw) -> MlsUpsampleParams:
-    p = MlsUpsampleParams()
-    lib().ope_mls_upsample_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(MlsUpsampleParams, "ope_mls_upsample_default_params", kw)
 
 
 def global_rejector(kind: int, **kw) -> GlobalRejector:
     """ope_global_rejector_defaults (factor 1.0, min_ratio 0.05, max_ratio 0.95) with the given fields set."""
     r = GlobalRejector()
     lib().ope_global_rejector_defaults(kind, C.byref(r))
-    for k, v in kw.items():
-        if not hasattr(r, k):
-            raise AttributeError(k)
-        setattr(r, k, v)
-    return r
+    return _set_fields(r, kw)
 
 
 def default_icp_params(**kw) -> IcpParams:
-    p = IcpParams()
-    lib().ope_icp_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(IcpParams, "ope_icp_default_params", kw)
 
 
 @dataclass
@@ -1047,6 +1047,33 @@ class Context:
         if rc != OPE_OK:
             raise OpeError(rc, (lib().ope_last_error(self.h) or b"").decode())
 
+    def _stats(self, entry: str, Struct) -> dict:
+        """`entry`(ctx, Struct *) as {field: value}."""
+        s = Struct()
+        self._chk(getattr(lib(), entry)(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in Struct._fields_}
+
+    def _read(self, entry: str, lead, outs) -> list:
+        """A "size, then fill" entry point, `entry`(ctx, *lead, one pointer per output array, cap, size_t *n): ask n with no arrays,
+        fetch, and return the arrays cut to n.  outs: one (dtype, trailing shape) per array."""
+        fn = getattr(lib(), entry)
+        n = C.c_size_t(0)
+        self._chk(fn(self.h, *lead, *[None] * len(outs), 0, C.byref(n)))
+        h = n.value
+        arrs = [np.zeros((max(h, 1), *shape), dt) for dt, shape in outs]
+        ptrs = [a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype))) for a in arrs]
+        self._chk(fn(self.h, *lead, *ptrs, h, C.byref(n)))
+        return [a[:h].copy() for a in arrs]
+
+    def _segments(self, idx, off, k: int, cap: int, handles=None):
+        """The segment lists idx / off of a call that reported k segments and had room for cap: the index arrays or, with the
+        call's cloud handles, (Clouds, index arrays).  last_cluster_count is k, not the number written."""
+        self.last_cluster_count = k
+        indices = [idx[off[i]:off[i + 1]].copy() for i in range(min(k, cap))]
+        if handles is None:
+            return indices
+        return [Cloud(self, _vp(handles[i]), len(c)) for i, c in enumerate(indices)], indices
+
     def set_stream(self, stream_ptr: int | None):
         self._chk(lib().ope_ctx_set_stream(self.h, _vp(stream_ptr) if stream_ptr else None))
 
@@ -1211,14 +1238,8 @@ class Context:
     def coarse_pose_batch(self, model: "Cloud", clusters, params: CoarseParams | None = None, seeds=None) -> list:
         """ope_coarse_pose_batch: estimateCoarsePose(model, clusters[i]) for every cluster in one call; one CoarseOut each.
         seeds[i] (or params.sacia.seed + i without seeds) is cluster i's SAC-IA stream."""
-        n = len(clusters)
+        n, hc, sd = self._batch_args(clusters, seeds)
         p = params or default_coarse_params()
-        hc = (_vp * max(n, 1))(*[c.h for c in clusters])
-        sd = None
-        if seeds is not None:
-            if len(seeds) != n:
-                raise ValueError("one seed per cluster")
-            sd = (C.c_uint64 * max(n, 1))(*[int(x) for x in seeds])
         out = (CoarseBatchResult * max(n, 1))()
         self._chk(lib().ope_coarse_pose_batch(self.h, model.h, n, hc, C.byref(p), sd, out))
         return [CoarseOut(from_colmajor(np.frombuffer(o.T, np.float32)), o.best_error, o.best_iteration, o.n_src_keys, o.n_tgt_keys,
@@ -1227,30 +1248,21 @@ class Context:
     def coarse_batch_features(self, which: int):
         """What the last coarse_pose_batch computed for `which` (-1 = the model, i = cluster i): (key indices into that
         cloud, normals (m,3), FPFH (m,33)), in key-point order."""
-        m = C.c_size_t(0)
-        self._chk(lib().ope_coarse_batch_features(self.h, which, None, None, None, 0, C.byref(m)))
-        idx = np.empty(max(m.value, 1), np.int32)
-        nrm = np.empty((max(m.value, 1), 3), np.float32)
-        f = np.empty((max(m.value, 1), 33), np.float32)
-        self._chk(lib().ope_coarse_batch_features(self.h, which, _p(idx, _ip), _p(nrm, _fp), _p(f, _fp), m.value, C.byref(m)))
-        return idx[: m.value].copy(), nrm[: m.value].copy(), f[: m.value].copy()
+        return tuple(self._read("ope_coarse_batch_features", (which,), [(np.int32, ()), (np.float32, (3,)), (np.float32, (33,))]))
+
+    def _final_pose_batch(self, entry: str, model, clusters, params, extra, seeds):
+        """One of the three ope_final_pose_batch* entries; extra: the coarse stage's own parameter struct, if it has one."""
+        n, hc, sd = self._batch_args(clusters, seeds)
+        p = params or default_final_params()
+        out = (FinalBatchResult * max(n, 1))()
+        sel = C.c_int32(-1)
+        self._chk(getattr(lib(), entry)(self.h, model.h, n, hc, C.byref(p), *[C.byref(q) for q in extra], sd, out, C.byref(sel)))
+        return [_final_out(o) for o in out[:n]], sel.value
 
     def final_pose_batch(self, model: "Cloud", clusters, params: FinalParams | None = None, seeds=None):
         """ope_final_pose_batch: estimateFinalPose(model, clusters[i]) of a fresh estimator for every cluster in one call.
         Returns ([FinalOut per cluster], selected): selected = the first accepted cluster, or -1."""
-        n = len(clusters)
-        p = params or default_final_params()
-        hc = (_vp * max(n, 1))(*[c.h for c in clusters])
-        sd = None
-        if seeds is not None:
-            if len(seeds) != n:
-                raise ValueError("one seed per cluster")
-            sd = (C.c_uint64 * max(n, 1))(*[int(x) for x in seeds])
-        out = (FinalBatchResult * max(n, 1))()
-        sel = C.c_int32(-1)
-        self._chk(lib().ope_final_pose_batch(self.h, model.h, n, hc, C.byref(p), sd, out, C.byref(sel)))
-        res = [_final_out(o) for o in out[:n]]
-        return res, sel.value
+        return self._final_pose_batch("ope_final_pose_batch", model, clusters, params, (), seeds)
 
     def _batch_args(self, clusters, seeds):
         n = len(clusters)
@@ -1277,39 +1289,22 @@ class Context:
 
     def prerejective_batch_stats(self) -> dict:
         """ope_prerejective_batch_last_stats: clusters, active, iterations, survivors, launches, host_syncs, nr_samples."""
-        s = PrerejectiveBatchStats()
-        self._chk(lib().ope_prerejective_batch_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in PrerejectiveBatchStats._fields_}
+        return self._stats("ope_prerejective_batch_last_stats", PrerejectiveBatchStats)
 
     def prerejective_batch_hypotheses(self, which: int) -> dict:
         """ope_prerejective_batch_hypotheses of cluster `which` (after keep_hypotheses=True), in the shape of
         prerejective_hypotheses: samples index the model's key points, targets the cluster's."""
-        n = C.c_size_t(0)
-        L = lib()
-        self._chk(L.ope_prerejective_batch_hypotheses(self.h, which, None, None, None, None, None, None, 0, C.byref(n)))
-        h = n.value
         S = int(self.prerejective_batch_stats()["nr_samples"])
-        sv = np.zeros(max(h, 1), np.uint8)
-        T = np.zeros((max(h, 1), 16), np.float32)
-        inl = np.zeros(max(h, 1), np.int32)
-        err = np.zeros(max(h, 1), np.float64)
-        smp, tg = np.zeros((max(h, 1), S), np.int32), np.zeros((max(h, 1), S), np.int32)
-        self._chk(L.ope_prerejective_batch_hypotheses(self.h, which, _p(smp, _ip), _p(tg, _ip), _p(sv, C.POINTER(C.c_uint8)), _p(T, _fp),
-                                                      _p(inl, _ip), _p(err, _dp), h, C.byref(n)))
-        return dict(samples=smp[:h].copy(), targets=tg[:h].copy(), survived=sv[:h].astype(bool), T=T[:h].reshape(h, 4, 4).transpose(0, 2, 1).copy(),
-                    inliers=inl[:h].copy(), error=err[:h].copy())
+        smp, tg, sv, T, inl, err = self._read("ope_prerejective_batch_hypotheses", (which,), [
+            (np.int32, (S,)), (np.int32, (S,)), (np.uint8, ()), (np.float32, (16,)), (np.int32, ()), (np.float64, ())])
+        return dict(samples=smp, targets=tg, survived=sv.astype(bool), T=_T_stack(T), inliers=inl, error=err)
 
     def final_pose_batch_prerejective(self, model: "Cloud", clusters, params: FinalParams | None = None,
                                       prerejective: PrerejectiveParams | None = None, seeds=None):
         """ope_final_pose_batch_prerejective: final_pose_batch with the prerejective aligner as its coarse stage.
         Returns ([FinalOut per cluster], selected)."""
-        n, hc, sd = self._batch_args(clusters, seeds)
-        p = params or default_final_params()
-        q = prerejective or default_prerejective_params()
-        out = (FinalBatchResult * max(n, 1))()
-        sel = C.c_int32(-1)
-        self._chk(lib().ope_final_pose_batch_prerejective(self.h, model.h, n, hc, C.byref(p), C.byref(q), sd, out, C.byref(sel)))
-        return [_final_out(o) for o in out[:n]], sel.value
+        return self._final_pose_batch("ope_final_pose_batch_prerejective", model, clusters, params,
+                                      (prerejective or default_prerejective_params(),), seeds)
 
     def corr_sac_pose_batch(self, model: "Cloud", clusters, front: CoarseParams | None = None, params: CorrSacParams | None = None,
                             seeds=None, keep_hypotheses: bool = False) -> list:
@@ -1327,52 +1322,29 @@ class Context:
 
     def corr_sac_batch_stats(self) -> dict:
         """ope_corr_sac_batch_last_stats: clusters, active, hypotheses, draw_lists, launches, host_syncs."""
-        s = CorrSacBatchStats()
-        self._chk(lib().ope_corr_sac_batch_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in CorrSacBatchStats._fields_}
+        return self._stats("ope_corr_sac_batch_last_stats", CorrSacBatchStats)
 
     def corr_sac_batch_matches(self, which: int):
         """ope_corr_sac_batch_matches of cluster `which`: (model key, cluster key, squared descriptor distance), in model key order."""
-        n = C.c_size_t(0)
-        self._chk(lib().ope_corr_sac_batch_matches(self.h, which, None, None, None, 0, C.byref(n)))
-        m = n.value
-        si, ti, d = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.float32)
-        self._chk(lib().ope_corr_sac_batch_matches(self.h, which, _p(si, _ip), _p(ti, _ip), _p(d, _fp), m, C.byref(n)))
-        return si[:m].copy(), ti[:m].copy(), d[:m].copy()
+        return tuple(self._read("ope_corr_sac_batch_matches", (which,), [(np.int32, ()), (np.int32, ()), (np.float32, ())]))
 
     def corr_sac_batch_inliers(self, which: int):
         """ope_corr_sac_batch_inliers of cluster `which`: (positions in its match list, ascending; model key; cluster key) of the
         matches that remain."""
-        n = C.c_size_t(0)
-        self._chk(lib().ope_corr_sac_batch_inliers(self.h, which, None, None, None, 0, C.byref(n)))
-        m = n.value
-        pos, si, ti = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32)
-        self._chk(lib().ope_corr_sac_batch_inliers(self.h, which, _p(pos, _ip), _p(si, _ip), _p(ti, _ip), m, C.byref(n)))
-        return pos[:m].copy(), si[:m].copy(), ti[:m].copy()
+        return tuple(self._read("ope_corr_sac_batch_inliers", (which,), [(np.int32, ()), (np.int32, ()), (np.int32, ())]))
 
     def corr_sac_batch_hypotheses(self, which: int) -> dict:
         """ope_corr_sac_batch_hypotheses of cluster `which` (after keep_hypotheses=True; empty otherwise), in the shape of
         corr_sac_hypotheses: samples (h, 3) match positions, T (h, 4, 4) math layout, counts (h,)."""
-        n = C.c_size_t(0)
-        self._chk(lib().ope_corr_sac_batch_hypotheses(self.h, which, None, None, None, 0, C.byref(n)))
-        h = n.value
-        smp = np.zeros((max(h, 1), 3), np.int32)
-        T = np.zeros((max(h, 1), 16), np.float32)
-        cnt = np.zeros(max(h, 1), np.int32)
-        self._chk(lib().ope_corr_sac_batch_hypotheses(self.h, which, _p(smp, _ip), _p(T, _fp), _p(cnt, _ip), h, C.byref(n)))
-        return dict(samples=smp[:h].copy(), T=T[:h].reshape(h, 4, 4).transpose(0, 2, 1).copy(), counts=cnt[:h].copy())
+        smp, T, cnt = self._read("ope_corr_sac_batch_hypotheses", (which,), [(np.int32, (3,)), (np.float32, (16,)), (np.int32, ())])
+        return dict(samples=smp, T=_T_stack(T), counts=cnt)
 
     def final_pose_batch_correspondences(self, model: "Cloud", clusters, params: FinalParams | None = None,
                                          corr_sac: CorrSacParams | None = None, seeds=None):
         """ope_final_pose_batch_correspondences: final_pose_batch with the correspondence aligner as its coarse stage.
         Returns ([FinalOut per cluster], selected)."""
-        n, hc, sd = self._batch_args(clusters, seeds)
-        p = params or default_final_params()
-        q = corr_sac or default_corr_sac_params()
-        out = (FinalBatchResult * max(n, 1))()
-        sel = C.c_int32(-1)
-        self._chk(lib().ope_final_pose_batch_correspondences(self.h, model.h, n, hc, C.byref(p), C.byref(q), sd, out, C.byref(sel)))
-        return [_final_out(o) for o in out[:n]], sel.value
+        return self._final_pose_batch("ope_final_pose_batch_correspondences", model, clusters, params,
+                                      (corr_sac or default_corr_sac_params(),), seeds)
 
     def _cluster_args(self, cloud, tolerance, min_size, max_size):
         if not isinstance(cloud, Cloud):
@@ -1394,9 +1366,7 @@ class Context:
         k = C.c_size_t(0)
         self._chk(lib().ope_euclidean_clusters(self.h, cloud.h, C.byref(p), cap, C.byref(k), _p(idx, _ip), _p(off, _ip),
                                                _p(lab, _ip) if lab is not None else None))
-        kw = min(k.value, cap)
-        out = [idx[off[i]:off[i + 1]].copy() for i in range(kw)]
-        self.last_cluster_count = k.value
+        out = self._segments(idx, off, k.value, cap)
         return (out, lab[:n].copy()) if want_labels else out
 
     def euclidean_clusters_cloud(self, cloud, tolerance: float = 0.05, min_size: int = 300, max_size: int = 100000,
@@ -1411,17 +1381,11 @@ class Context:
         hs = (_vp * max(cap, 1))()
         k = C.c_size_t(0)
         self._chk(lib().ope_euclidean_clusters_cloud(self.h, cloud.h, C.byref(p), cap, C.byref(k), hs, _p(idx, _ip), _p(off, _ip)))
-        kw = min(k.value, cap)
-        self.last_cluster_count = k.value
-        indices = [idx[off[i]:off[i + 1]].copy() for i in range(kw)]
-        clouds = [Cloud(self, _vp(hs[i]), len(indices[i])) for i in range(kw)]
-        return clouds, indices
+        return self._segments(idx, off, k.value, cap, hs)
 
     def cluster_stats(self) -> dict:
         """ope_cluster_last_stats: launches, host synchronisations, occupied cells and compared cell pairs of the last call."""
-        s = ClusterStats()
-        self._chk(lib().ope_cluster_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in ClusterStats._fields_}
+        return self._stats("ope_cluster_last_stats", ClusterStats)
 
     def region_grow(self, cloud, params: "RegionParams | None" = None, normals=None, curvature=None, max_clusters: int | None = None,
                     clouds: bool = False):
@@ -1452,22 +1416,15 @@ class Context:
         if clouds:
             hs = (_vp * max(cap, 1))()
             self._chk(lib().ope_region_grow_cloud(self.h, cloud.h, C.byref(p), pn, pc, cap, C.byref(k), hs, _p(idx, _ip), _p(off, _ip)))
-        else:
-            lab = np.empty(max(n, 1), np.int32)
-            self._chk(lib().ope_region_grow(self.h, cloud.h, C.byref(p), pn, pc, cap, C.byref(k), _p(idx, _ip), _p(off, _ip), _p(lab, _ip)))
-        kw = min(k.value, cap)
-        self.last_cluster_count = k.value
-        indices = [idx[off[i]:off[i + 1]].copy() for i in range(kw)]
-        if clouds:
-            return [Cloud(self, _vp(hs[i]), len(indices[i])) for i in range(kw)], indices, self.region_stats()
-        return indices, lab[:n].copy(), self.region_stats()
+            return (*self._segments(idx, off, k.value, cap, hs), self.region_stats())
+        lab = np.empty(max(n, 1), np.int32)
+        self._chk(lib().ope_region_grow(self.h, cloud.h, C.byref(p), pn, pc, cap, C.byref(k), _p(idx, _ip), _p(off, _ip), _p(lab, _ip)))
+        return self._segments(idx, off, k.value, cap), lab[:n].copy(), self.region_stats()
 
     def region_stats(self) -> dict:
         """ope_region_last_stats: launches, host synchronisations, sweeps, one-way edges, regions before the size filter and the
         points refused for their curvature, of the last region_grow."""
-        s = RegionStats()
-        self._chk(lib().ope_region_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in RegionStats._fields_}
+        return self._stats("ope_region_last_stats", RegionStats)
 
     def region_grow_rgb(self, cloud: "Cloud", params: "RegionRgbParams | None" = None, max_clusters: int | None = None, clouds: bool = False):
         """ope_region_grow_rgb: pcl::RegionGrowingRGB (segmentationregiongrow.cpp:85-151) of a Cloud with colours (set_rgb).
@@ -1483,23 +1440,16 @@ class Context:
         if clouds:
             hs = (_vp * max(cap, 1))()
             self._chk(lib().ope_region_grow_rgb_cloud(self.h, cloud.h, C.byref(p), cap, C.byref(k), hs, _p(idx, _ip), _p(off, _ip)))
-        else:
-            lab = np.empty(max(n, 1), np.int32)
-            self._chk(lib().ope_region_grow_rgb(self.h, cloud.h, C.byref(p), cap, C.byref(k), _p(idx, _ip), _p(off, _ip), _p(lab, _ip)))
-        kw = min(k.value, cap)
-        self.last_cluster_count = k.value
-        indices = [idx[off[i]:off[i + 1]].copy() for i in range(kw)]
-        if clouds:
-            return [Cloud(self, _vp(hs[i]), len(indices[i])) for i in range(kw)], indices, self.region_rgb_stats()
-        return indices, lab[:n].copy(), self.region_rgb_stats()
+            return (*self._segments(idx, off, k.value, cap, hs), self.region_rgb_stats())
+        lab = np.empty(max(n, 1), np.int32)
+        self._chk(lib().ope_region_grow_rgb(self.h, cloud.h, C.byref(p), cap, C.byref(k), _p(idx, _ip), _p(off, _ip), _p(lab, _ip)))
+        return self._segments(idx, off, k.value, cap), lab[:n].copy(), self.region_rgb_stats()
 
     def region_rgb_stats(self) -> dict:
         """ope_region_rgb_last_stats: launches, host synchronisations, sweeps, one-way edges, segments, directed segment pairs,
         homogeneous regions, regions absorbed by the small-region merge and regions before the size filter, of the last
         region_grow_rgb."""
-        s = RegionRgbStats()
-        self._chk(lib().ope_region_rgb_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in RegionRgbStats._fields_}
+        return self._stats("ope_region_rgb_last_stats", RegionRgbStats)
 
     # ---- recognition (vfh.hip)
     def _vfh_clusters(self, clusters):
@@ -1558,9 +1508,7 @@ class Context:
     def vfh_stats(self) -> dict:
         """ope_vfh_last_stats: points, rejected pairs, clouds whose normals were estimated, empty clouds, launches and host
         synchronisations of the last vfh / vfh_match / vfh_recognise."""
-        s = VfhStats()
-        self._chk(lib().ope_vfh_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in VfhStats._fields_}
+        return self._stats("ope_vfh_last_stats", VfhStats)
 
     def plane_segment(self, cloud, params: "PlaneParams | None" = None, samples=None, want_clouds: bool = False) -> "PlaneOut":
         """ope_plane_segment: pcl::SACSegmentation (SACMODEL_PLANE, SAC_RANSAC; objectsegmentationplane.cpp:36-55) of a Cloud (or
@@ -1585,18 +1533,11 @@ class Context:
 
     def plane_stats(self) -> dict:
         """ope_plane_last_stats: iterations, hypotheses scored, launches, host synchronisations, winner, found."""
-        s = PlaneStats()
-        self._chk(lib().ope_plane_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in PlaneStats._fields_}
+        return self._stats("ope_plane_last_stats", PlaneStats)
 
     def plane_hypotheses(self):
         """ope_plane_last_hypotheses: (samples (h, 3) int32, coefficients (h, 4) float32, counts (h,) int32) in drawing order."""
-        n = C.c_size_t(0)
-        self._chk(lib().ope_plane_last_hypotheses(self.h, None, None, None, 0, C.byref(n)))
-        h = n.value
-        s, c, k = np.empty((max(h, 1), 3), np.int32), np.empty((max(h, 1), 4), np.float32), np.empty(max(h, 1), np.int32)
-        self._chk(lib().ope_plane_last_hypotheses(self.h, _p(s, _ip), _p(c, _fp), _p(k, _ip), h, C.byref(n)))
-        return s[:h].copy(), c[:h].copy(), k[:h].copy()
+        return tuple(self._read("ope_plane_last_hypotheses", (), [(np.int32, (3,)), (np.float32, (4,)), (np.int32, ())]))
 
     def prism_extract(self, cloud, hull, height_min: float = 0.0, height_max: float = float(np.finfo(np.float32).max),
                       want_cloud: bool = False):
@@ -1714,9 +1655,7 @@ class Context:
 
     def depth_stats(self) -> dict:
         """ope_depth_last_stats: launches, host synchronisations, pixels, valid pixels, points kept."""
-        s = DepthStats()
-        self._chk(lib().ope_depth_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in DepthStats._fields_}
+        return self._stats("ope_depth_last_stats", DepthStats)
 
     def track_gate(self, source: "Cloud", clusters, params: TrackParams | None = None) -> GateOut:
         """ope_track_gate: the centroid gate of the reference's later frames (rosinterface.cpp:264-304)."""
@@ -1755,12 +1694,7 @@ class Context:
     def final_batch_inputs(self, which: int, side: int):
         """The fine inputs the last final_pose_batch prepared for cluster `which`: side 0 the moved model, 1 the cluster.
         (xyz (m,3), normals (m,3)) in key-point order, as they would be uploaded."""
-        m = C.c_size_t(0)
-        self._chk(lib().ope_final_batch_inputs(self.h, which, side, None, None, 0, C.byref(m)))
-        xyz = np.empty((max(m.value, 1), 3), np.float32)
-        nrm = np.empty((max(m.value, 1), 3), np.float32)
-        self._chk(lib().ope_final_batch_inputs(self.h, which, side, _p(xyz, _fp), _p(nrm, _fp), m.value, C.byref(m)))
-        return xyz[: m.value].copy(), nrm[: m.value].copy()
+        return tuple(self._read("ope_final_batch_inputs", (which, side), [(np.float32, (3,)), (np.float32, (3,))]))
 
     def icp_begin(self, src: "Cloud", tgt: "Index", params: IcpParams | None = None, guess=None):
         p = params or default_icp_params()
@@ -2098,15 +2032,11 @@ class Context:
 
     def mls_upsample_stats(self) -> dict:
         """ope_mls_upsample_last_stats: what the last mls_upsample did (include/ope.h)."""
-        s = MlsUpsampleStats()
-        self._chk(lib().ope_mls_upsample_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in MlsUpsampleStats._fields_}
+        return self._stats("ope_mls_upsample_last_stats", MlsUpsampleStats)
 
     def mls_stats(self) -> dict:
         """ope_mls_last_stats: n_in, n_out, n_plane_only, n_dropped, neighbours_total of the last mls_smooth."""
-        s = MlsStats()
-        self._chk(lib().ope_mls_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in MlsStats._fields_}
+        return self._stats("ope_mls_last_stats", MlsStats)
 
     def sacia(self, src: "Cloud", src_feat, tgt: "Cloud", tgt_index: "Index", tgt_feat, params: SaciaParams | None = None,
               forced_samples=None):
@@ -2138,27 +2068,15 @@ class Context:
 
     def prerejective_stats(self) -> dict:
         """ope_prerejective_last_stats: iterations, survivors, launches, host synchronisations, nr_samples of the last prerejective call."""
-        s = PrerejectiveStats()
-        self._chk(lib().ope_prerejective_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in PrerejectiveStats._fields_}
+        return self._stats("ope_prerejective_last_stats", PrerejectiveStats)
 
     def prerejective_hypotheses(self) -> dict:
         """ope_prerejective_last_hypotheses, in drawing order: samples and targets (h, nr_samples) int32, survived (h,) bool,
         T (h, 4, 4) float32 math layout, inliers (h,) int32, error (h,) float64."""
-        n = C.c_size_t(0)
-        self._chk(lib().ope_prerejective_last_hypotheses(self.h, None, None, None, None, None, None, 0, C.byref(n)))
-        h = n.value
-        sv = np.zeros(max(h, 1), np.uint8)
-        T = np.zeros((max(h, 1), 16), np.float32)
-        inl = np.zeros(max(h, 1), np.int32)
-        err = np.zeros(max(h, 1), np.float64)
-        self._chk(lib().ope_prerejective_last_hypotheses(self.h, None, None, _p(sv, C.POINTER(C.c_uint8)), _p(T, _fp), _p(inl, _ip),
-                                                          _p(err, _dp), h, C.byref(n)))
         S = int(self.prerejective_stats()["nr_samples"])   # of the call these arrays belong to
-        smp, tg = np.zeros((max(h, 1), S), np.int32), np.zeros((max(h, 1), S), np.int32)
-        self._chk(lib().ope_prerejective_last_hypotheses(self.h, _p(smp, _ip), _p(tg, _ip), None, None, None, None, h, C.byref(n)))
-        return dict(samples=smp[:h].copy(), targets=tg[:h].copy(), survived=sv[:h].astype(bool), T=T[:h].reshape(h, 4, 4).transpose(0, 2, 1).copy(),
-                    inliers=inl[:h].copy(), error=err[:h].copy())
+        smp, tg, sv, T, inl, err = self._read("ope_prerejective_last_hypotheses", (), [
+            (np.int32, (S,)), (np.int32, (S,)), (np.uint8, ()), (np.float32, (16,)), (np.int32, ()), (np.float64, ())])
+        return dict(samples=smp, targets=tg, survived=sv.astype(bool), T=_T_stack(T), inliers=inl, error=err)
 
     def feature_correspondences(self, src_feat, tgt_feat):
         """ope_feature_correspondences: the 1-NN match of every source FPFH row among the target's rows.  (src_idx, tgt_idx, dist):
@@ -2187,21 +2105,13 @@ class Context:
 
     def corr_sac_stats(self) -> dict:
         """ope_corr_sac_last_stats: hypotheses, iterations, launches, host_syncs, sample_dist_thresh of the last corr_sac call."""
-        s = CorrSacStats()
-        self._chk(lib().ope_corr_sac_last_stats(self.h, C.byref(s)))
-        return {k: getattr(s, k) for k, _ in CorrSacStats._fields_}
+        return self._stats("ope_corr_sac_last_stats", CorrSacStats)
 
     def corr_sac_hypotheses(self) -> dict:
         """ope_corr_sac_last_hypotheses, in drawing order: samples (h, 3) int32 match positions, T (h, 4, 4) float32 math layout,
         counts (h,) int32."""
-        n = C.c_size_t(0)
-        self._chk(lib().ope_corr_sac_last_hypotheses(self.h, None, None, None, 0, C.byref(n)))
-        h = n.value
-        smp = np.zeros((max(h, 1), 3), np.int32)
-        T = np.zeros((max(h, 1), 16), np.float32)
-        cnt = np.zeros(max(h, 1), np.int32)
-        self._chk(lib().ope_corr_sac_last_hypotheses(self.h, _p(smp, _ip), _p(T, _fp), _p(cnt, _ip), h, C.byref(n)))
-        return dict(samples=smp[:h].copy(), T=T[:h].reshape(h, 4, 4).transpose(0, 2, 1).copy(), counts=cnt[:h].copy())
+        smp, T, cnt = self._read("ope_corr_sac_last_hypotheses", (), [(np.int32, (3,)), (np.float32, (16,)), (np.int32, ())])
+        return dict(samples=smp, T=_T_stack(T), counts=cnt)
 
     def coarse_pose_correspondences(self, src: "Cloud", src_feat, tgt: "Cloud", tgt_feat, params: CorrSacParams | None = None) -> CorrSacOut:
         """The reference's third coarse aligner (BuildModel/src/poseestimator.cpp:43-60, :111-113) over key-point clouds and their
@@ -2214,113 +2124,59 @@ class Context:
 
 def default_prerejective_params(**kw) -> PrerejectiveParams:
     """ope_prerejective_default_params (50000 / 3 / 5 / 0.8 / 0.15 / 0.25, seed 1: BuildModel poseestimator.cpp:97-102)."""
-    p = PrerejectiveParams()
-    lib().ope_prerejective_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(PrerejectiveParams, "ope_prerejective_default_params", kw)
 
 
 def default_corr_sac_params(**kw) -> CorrSacParams:
     """ope_corr_sac_default_params (0.05 / 1000 / 0.99, seed 12345: PCL's own defaults; the reference sets 10000 and 0.08)."""
-    p = CorrSacParams()
-    lib().ope_corr_sac_default_params(C.byref(p))
-    for k, v in kw.items():
-        if not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, v)
-    return p
+    return _params(CorrSacParams, "ope_corr_sac_default_params", kw)
 
 
 def default_sacia_params(**kw) -> SaciaParams:
-    p = SaciaParams()
-    lib().ope_sacia_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(SaciaParams, "ope_sacia_default_params", kw)
 
 
 def default_coarse_params(**kw) -> CoarseParams:
     """ope_coarse_default_params (the reference's values); keyword arguments set fields, `sacia` takes a SaciaParams."""
-    p = CoarseParams()
-    lib().ope_coarse_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k == "viewpoint":
-            p.viewpoint[:] = [float(x) for x in v]
-        else:
-            setattr(p, k, v)
-    return p
+    return _params(CoarseParams, "ope_coarse_default_params", kw)
 
 
 def default_cluster_params(**kw) -> ClusterParams:
     """ope_cluster_default_params (tolerance 0.05, min 300, max 100000: objectsegmentationplane.cpp:85-87)."""
-    p = ClusterParams()
-    lib().ope_cluster_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(ClusterParams, "ope_cluster_default_params", kw)
 
 
 def default_region_params(**kw) -> RegionParams:
     """ope_region_default_params (15 neighbours, normals k 30, smoothness 10 degrees, curvature 1.0, sizes 500 .. 1000000:
     segmentationregiongrow.cpp:25-36)."""
-    p = RegionParams()
-    lib().ope_region_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(RegionParams, "ope_region_default_params", kw)
 
 
 def default_region_rgb_params(**kw) -> RegionRgbParams:
     """pcl::RegionGrowingRGB as SegmentationRegionGrow::getSegmentRegGrowRgb sets it (segmentationregiongrow.cpp:97-106)"""
-    p = RegionRgbParams()
-    lib().ope_region_rgb_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(RegionRgbParams, "ope_region_rgb_default_params", kw)
 
 
 def default_vfh_params(**kw) -> VfhParams:
     """ope_vfh_default_params (normals_k 30, viewpoint 0 0 0, no given centroid or normal); viewpoint / centroid / normal take
     3-sequences."""
-    p = VfhParams()
-    lib().ope_vfh_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k in ("viewpoint", "centroid", "normal"):
-            setattr(p, k, (C.c_float * 3)(*[float(x) for x in v]))
-        else:
-            setattr(p, k, v)
-    return p
+    return _params(VfhParams, "ope_vfh_default_params", kw)
 
 
 def default_plane_params(**kw) -> PlaneParams:
     """ope_plane_default_params (threshold 0.01, 50 iterations, probability 0.99, optimised coefficients, seed 12345)."""
-    p = PlaneParams()
-    lib().ope_plane_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(PlaneParams, "ope_plane_default_params", kw)
 
 
 def default_track_params(**kw) -> TrackParams:
     """ope_track_default_params (gate 0.05, coarse stage above 1e-4, the final stages' defaults); keyword arguments set fields."""
-    p = TrackParams()
-    lib().ope_track_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(TrackParams, "ope_track_default_params", kw)
 
 
 def default_final_params(**kw) -> FinalParams:
     """ope_final_default_params (the reference's values); keyword arguments set fields (`coarse` a CoarseParams, `icp` an
     IcpParams)."""
-    p = FinalParams()
-    lib().ope_final_default_params(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+    return _params(FinalParams, "ope_final_default_params", kw)
 
 
 def comm_unique_id() -> bytes:

@@ -5,8 +5,10 @@ import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -44,6 +46,65 @@ def test_library_exports_every_declared_symbol(ope):
 def test_python_binding_table_covers_the_header(ope):
     bound = {name for name, _, _ in ope.ABI}
     assert set(declared_symbols()) <= bound
+
+
+def header_source():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def test_every_struct_lays_out_as_the_header_says(ope):
+    declared = set(re.findall(r"typedef\s+struct\s*\{[^{}]*\}\s*(ope_\w+)\s*;", header_source()))
+    mirrors = {"ope_" + re.sub(r"(?<!^)(?=[A-Z])", "_", name).lower(): S for name, S in vars(ope).items()
+               if isinstance(S, type) and issubclass(S, ctypes.Structure) and S is not ctypes.Structure}
+    assert sorted(mirrors) == sorted(declared)   # both directions: no struct on one side only
+    assert len(declared) == 45
+    structs = {S: ctype for ctype, S in mirrors.items()}
+    assert ctypes_layout(structs) == c_layout(structs)
+
+
+def test_every_signature_has_the_header_s_arity(ope):
+    decls = re.findall(r"([\w \t*]+?)\b(ope_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header_source())
+    assert sorted(name for _, name, _ in decls) == declared_symbols() and len(decls) == 152   # each declared once, none missed
+    names = [name for name, _, _ in ope.ABI]
+    assert len(names) == len(set(names))
+    assert set(names) == {name for _, name, _ in decls}   # (the other direction of test_python_binding_table_covers_the_header)
+    table = {name: (res, args) for name, res, args in ope.ABI}
+    for ret, name, params in decls:
+        res, args = table[name]
+        assert len(args) == (0 if params.strip() == "void" else len(params.split(","))), name
+        assert (res is None) == (ret.strip() == "void"), name
+
+
+CONSTRUCTORS = [   # (constructor, leading arguments, a real field, a value for it)
+    ("default_icp_params", (), "max_iterations", 7),
+    ("default_mls_params", (), "order", 1),
+    ("default_mls_upsample_params", (), "dilation_iterations", 2),
+    ("default_depth_params", (), "z_max", 3.5),
+    ("default_prerejective_params", (), "seed", 7),
+    ("default_corr_sac_params", (), "max_iterations", 10),
+    ("global_rejector", (0,), "factor", 2.0),
+    ("default_sacia_params", (), "nr_samples", 4),
+    ("default_coarse_params", (), "normals_k", 12),
+    ("default_cluster_params", (), "min_size", 1),
+    ("default_region_params", (), "min_size", 1),
+    ("default_region_rgb_params", (), "min_size", 1),
+    ("default_vfh_params", (), "use_given_centroid", 1),
+    ("default_plane_params", (), "seed", 7),
+    ("default_track_params", (), "gate_distance", 0.25),
+    ("default_final_params", (), "min_fine_points", 5),
+]
+
+
+@pytest.mark.parametrize("name,lead,field,value", CONSTRUCTORS, ids=[c[0] for c in CONSTRUCTORS])
+def test_every_constructor_refuses_an_unknown_field(ope, name, lead, field, value):
+    make = getattr(ope, name)
+    assert getattr(make(*lead), field) != value
+    assert getattr(make(*lead, **{field: value}), field) == value
+    array = {"default_coarse_params": "viewpoint", "default_vfh_params": "centroid"}.get(name)
+    if array:
+        assert list(getattr(make(**{array: (1, 2.5, np.float32(3))}), array)) == [1.0, 2.5, 3.0]
+    with pytest.raises(AttributeError):
+        make(*lead, no_such_field=1)
 
 
 def test_library_contains_gfx950_code_object(ope):

@@ -5,11 +5,11 @@ with a literal port of PCL's seed-queue search, order included."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 from cluster_ref import pcl_bfs, reference_clusters
 
@@ -32,36 +32,11 @@ def test_cluster_entry_is_declared_exported_and_bound(ope, name):
     assert name in {n for n, _, _ in ope.ABI}
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_s %zu\n", sizeof(ope_cluster_params), sizeof(ope_cluster_stats));
-  O(ope_cluster_params, "p", tolerance); O(ope_cluster_params, "p", min_size); O(ope_cluster_params, "p", max_size);
-  O(ope_cluster_stats, "s", launches); O(ope_cluster_stats, "s", host_syncs); O(ope_cluster_stats, "s", cells);
-  O(ope_cluster_stats, "s", pairs_tested);
-  printf("abi %d\n", OPE_ABI_VERSION);
-  return 0;
-}
-"""
-
-
-def test_cluster_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    want = dict(line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    want = {k: int(v) for k, v in want.items()}
-    structs = {"p": ope.ClusterParams, "s": ope.ClusterStats}
-    got = {"sizeof_" + t: ctypes.sizeof(S) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = getattr(S, name).offset
+def test_cluster_layouts_match_the_c_compiler(ope):
+    structs = {ope.ClusterParams: "ope_cluster_params", ope.ClusterStats: "ope_cluster_stats"}
+    got = ctypes_layout(structs)
     got["abi"] = 5   # the change only adds to the ABI
-    assert got == want
+    assert got == c_layout(structs, extra={"abi": "OPE_ABI_VERSION"})
 
 
 def test_cluster_defaults_are_the_reference_literals(ope):

@@ -4,10 +4,10 @@ defaults are the reference's values."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -29,43 +29,14 @@ def test_coarse_entry_is_declared_exported_and_bound(ope, name):
     assert name in {n for n, _, _ in ope.ABI}
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define P(m) printf("p.%s %zu\n", #m, offsetof(ope_coarse_params, m))
-#define S(m) printf("p.sacia.%s %zu\n", #m, offsetof(ope_coarse_params, sacia) + offsetof(ope_sacia_params, m))
-#define R(m) printf("r.%s %zu\n", #m, offsetof(ope_coarse_batch_result, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_r %zu\n", sizeof(ope_coarse_params), sizeof(ope_coarse_batch_result));
-  P(key_leaf); P(normals_k); P(viewpoint); P(fpfh_radius); P(sacia);
-  S(max_iterations); S(nr_samples); S(k_correspondences); S(max_corr_dist); S(min_sample_dist); S(seed);
-  R(T); R(best_error); R(best_iteration); R(n_src_keys); R(n_tgt_keys); R(status);
-  printf("limits.points %d\nlimits.keys %d\n", OPE_COARSE_MAX_POINTS, OPE_COARSE_MAX_KEYS);
-  printf("status.ok %d\nstatus.empty %d\nstatus.few %d\n", OPE_COARSE_OK, OPE_COARSE_EMPTY_TARGET, OPE_COARSE_FEW_TARGET_FEATURES);
-  return 0;
-}
-"""
-
-
-def test_coarse_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    want = dict(line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    want = {k: int(v) for k, v in want.items()}
-    P, S, R = ope.CoarseParams, ope.SaciaParams, ope.CoarseBatchResult
-    got = {"sizeof_p": ctypes.sizeof(P), "sizeof_r": ctypes.sizeof(R)}
-    for name, _ in P._fields_:
-        got["p." + name] = getattr(P, name).offset
-    for name, _ in S._fields_:
-        got["p.sacia." + name] = P.sacia.offset + getattr(S, name).offset
-    for name, _ in R._fields_:
-        got["r." + name] = getattr(R, name).offset
+def test_coarse_layouts_match_the_c_compiler(ope):
+    structs = {ope.CoarseParams: "ope_coarse_params", ope.SaciaParams: "ope_sacia_params", ope.CoarseBatchResult: "ope_coarse_batch_result"}
+    got = ctypes_layout(structs)
     got["limits.points"], got["limits.keys"] = ope.COARSE_MAX_POINTS, ope.COARSE_MAX_KEYS
     got["status.ok"], got["status.empty"], got["status.few"] = ope.COARSE_OK, ope.COARSE_EMPTY_TARGET, ope.COARSE_FEW_TARGET_FEATURES
-    assert got == want
+    assert got == c_layout(structs, extra={"limits.points": "OPE_COARSE_MAX_POINTS", "limits.keys": "OPE_COARSE_MAX_KEYS",
+                                           "status.ok": "OPE_COARSE_OK", "status.empty": "OPE_COARSE_EMPTY_TARGET",
+                                           "status.few": "OPE_COARSE_FEW_TARGET_FEATURES"})
 
 
 def test_coarse_defaults_are_the_reference_values(ope):

@@ -3,10 +3,10 @@ compiler lays out ope_corr_sac_params / _result / _stats; the defaults are PCL's
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -32,43 +32,16 @@ def test_corr_sac_entry_is_declared_exported_and_bound(ope, name):
     assert callable(ope.default_corr_sac_params)
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_r %zu\nsizeof_s %zu\n", sizeof(ope_corr_sac_params), sizeof(ope_corr_sac_result), sizeof(ope_corr_sac_stats));
-  O(ope_corr_sac_params, "p", inlier_threshold); O(ope_corr_sac_params, "p", max_iterations); O(ope_corr_sac_params, "p", probability);
-  O(ope_corr_sac_params, "p", seed);
-  O(ope_corr_sac_result, "r", T_best); O(ope_corr_sac_result, "r", T_svd); O(ope_corr_sac_result, "r", inliers);
-  O(ope_corr_sac_result, "r", best); O(ope_corr_sac_result, "r", iterations); O(ope_corr_sac_result, "r", found);
-  O(ope_corr_sac_stats, "s", hypotheses); O(ope_corr_sac_stats, "s", iterations); O(ope_corr_sac_stats, "s", launches);
-  O(ope_corr_sac_stats, "s", host_syncs); O(ope_corr_sac_stats, "s", sample_dist_thresh);
-  printf("abi %d\n", OPE_ABI_VERSION);
-  return 0;
-}
-"""
-
-
-def test_corr_sac_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    want = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1] for ln in lines}
-    structs = {"p": ope.CorrSacParams, "r": ope.CorrSacResult, "s": ope.CorrSacStats}
-    got = {"sizeof_" + t: str(ctypes.sizeof(S)) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = str(getattr(S, name).offset)
+def test_corr_sac_layouts_match_the_c_compiler(ope):
+    P, R, S = "ope_corr_sac_params", "ope_corr_sac_result", "ope_corr_sac_stats"
+    structs = {ope.CorrSacParams: P, ope.CorrSacResult: R, ope.CorrSacStats: S}
+    got = {k: str(v) for k, v in ctypes_layout(structs).items()}
     got["abi"] = "5"   # the change only adds to the ABI
-    assert got == want
+    assert got == {k: str(v) for k, v in c_layout(structs, extra={"abi": "OPE_ABI_VERSION"}).items()}
     # the layout itself, pinned
-    assert (got["sizeof_p"], got["sizeof_r"], got["sizeof_s"]) == ("32", "144", "40")
-    assert [got["p." + n] for n, _ in ope.CorrSacParams._fields_] == ["0", "8", "16", "24"]
-    assert [got["r." + n] for n, _ in ope.CorrSacResult._fields_] == ["0", "64", "128", "132", "136", "140"]
+    assert (got[P, "sizeof"], got[R, "sizeof"], got[S, "sizeof"]) == ("32", "144", "40")
+    assert [got[P, n] for n, _ in ope.CorrSacParams._fields_] == ["0", "8", "16", "24"]
+    assert [got[R, n] for n, _ in ope.CorrSacResult._fields_] == ["0", "64", "128", "132", "136", "140"]
     assert [n for n, _ in ope.CorrSacStats._fields_] == ["hypotheses", "iterations", "launches", "host_syncs", "sample_dist_thresh"]
 
 

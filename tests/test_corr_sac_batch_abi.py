@@ -3,10 +3,10 @@ as the C compiler lays out ope_corr_sac_batch_result / _stats; the status consta
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -33,44 +33,19 @@ def test_corr_sac_batch_entry_is_declared_exported_and_bound(ope, name):
         assert callable(getattr(ope.Context, method))
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_r %zu\nsizeof_s %zu\n", sizeof(ope_corr_sac_batch_result), sizeof(ope_corr_sac_batch_stats));
-  O(ope_corr_sac_batch_result, "r", T_svd); O(ope_corr_sac_batch_result, "r", T_best); O(ope_corr_sac_batch_result, "r", sample_dist_thresh);
-  O(ope_corr_sac_batch_result, "r", seed); O(ope_corr_sac_batch_result, "r", matches); O(ope_corr_sac_batch_result, "r", inliers);
-  O(ope_corr_sac_batch_result, "r", best); O(ope_corr_sac_batch_result, "r", iterations); O(ope_corr_sac_batch_result, "r", found);
-  O(ope_corr_sac_batch_result, "r", n_src_keys); O(ope_corr_sac_batch_result, "r", n_tgt_keys); O(ope_corr_sac_batch_result, "r", status);
-  O(ope_corr_sac_batch_stats, "s", clusters); O(ope_corr_sac_batch_stats, "s", active); O(ope_corr_sac_batch_stats, "s", hypotheses);
-  O(ope_corr_sac_batch_stats, "s", draw_lists); O(ope_corr_sac_batch_stats, "s", launches); O(ope_corr_sac_batch_stats, "s", host_syncs);
-  printf("status %d %d %d\n", OPE_CORRSAC_OK, OPE_CORRSAC_EMPTY_TARGET, OPE_CORRSAC_FEW_TARGET_FEATURES);
-  printf("abi %d\n", OPE_ABI_VERSION);
-  return 0;
-}
-"""
-
-
-def test_corr_sac_batch_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    want = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1] for ln in lines}
-    structs = {"r": ope.CorrSacBatchResult, "s": ope.CorrSacBatchStats}
-    got = {"sizeof_" + t: str(ctypes.sizeof(S)) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = str(getattr(S, name).offset)
-    got["status"] = f"{ope.CORRSAC_OK} {ope.CORRSAC_EMPTY_TARGET} {ope.CORRSAC_FEW_TARGET_FEATURES}"
+def test_corr_sac_batch_layouts_match_the_c_compiler(ope):
+    R, S = "ope_corr_sac_batch_result", "ope_corr_sac_batch_stats"
+    structs = {ope.CorrSacBatchResult: R, ope.CorrSacBatchStats: S}
+    got = {k: str(v) for k, v in ctypes_layout(structs).items()}
+    got["status.ok"], got["status.empty"], got["status.few"] = (str(v) for v in (ope.CORRSAC_OK, ope.CORRSAC_EMPTY_TARGET,
+                                                                                 ope.CORRSAC_FEW_TARGET_FEATURES))
     got["abi"] = "5"   # the change only adds to the ABI
-    assert got == want
-    assert (got["sizeof_r"], got["sizeof_s"]) == ("176", "48")
-    assert [got["r." + n] for n, _ in ope.CorrSacBatchResult._fields_] == ["0", "64", "128", "136", "144", "148", "152", "156", "160", "164",
-                                                                          "168", "172"]
+    want = c_layout(structs, extra={"status.ok": "OPE_CORRSAC_OK", "status.empty": "OPE_CORRSAC_EMPTY_TARGET",
+                                    "status.few": "OPE_CORRSAC_FEW_TARGET_FEATURES", "abi": "OPE_ABI_VERSION"})
+    assert got == {k: str(v) for k, v in want.items()}
+    assert (got[R, "sizeof"], got[S, "sizeof"]) == ("176", "48")
+    assert [got[R, n] for n, _ in ope.CorrSacBatchResult._fields_] == ["0", "64", "128", "136", "144", "148", "152", "156", "160", "164",
+                                                                       "168", "172"]
     assert [n for n, _ in ope.CorrSacBatchStats._fields_] == ["clusters", "active", "hypotheses", "draw_lists", "launches", "host_syncs"]
 
 

@@ -5,12 +5,12 @@ import ctypes
 import importlib
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import depth_ref as dr
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -39,38 +39,13 @@ def test_depth_entry_is_declared_exported_and_bound(ope, name):
         assert callable(getattr(ope.Context, method))
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_s %zu\n", sizeof(ope_depth_params), sizeof(ope_depth_stats));
-  O(ope_depth_params, "p", f_row); O(ope_depth_params, "p", c_row); O(ope_depth_params, "p", f_col); O(ope_depth_params, "p", c_col);
-  O(ope_depth_params, "p", scale); O(ope_depth_params, "p", z_max);
-  O(ope_depth_stats, "s", launches); O(ope_depth_stats, "s", host_syncs); O(ope_depth_stats, "s", pixels); O(ope_depth_stats, "s", valid);
-  O(ope_depth_stats, "s", kept);
-  printf("abi %d\nsensors %d %d %d\n", OPE_ABI_VERSION, OPE_SENSOR_KINECT, OPE_SENSOR_ASTRA, OPE_SENSOR_EUCLID);
-  return 0;
-}
-"""
-
-
-def test_depth_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    want = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1] for ln in lines}
-    structs = {"p": ope.DepthParams, "s": ope.DepthStats}
-    got = {"sizeof_" + t: str(ctypes.sizeof(S)) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = str(getattr(S, name).offset)
-    got["abi"] = "5"   # the change only adds to the ABI
-    got["sensors"] = "%d %d %d" % (ope.SENSOR_KINECT, ope.SENSOR_ASTRA, ope.SENSOR_EUCLID)
-    assert got == want
+def test_depth_layouts_match_the_c_compiler(ope):
+    structs = {ope.DepthParams: "ope_depth_params", ope.DepthStats: "ope_depth_stats"}
+    got = ctypes_layout(structs)
+    got["abi"] = 5   # the change only adds to the ABI
+    got["sensor.kinect"], got["sensor.astra"], got["sensor.euclid"] = ope.SENSOR_KINECT, ope.SENSOR_ASTRA, ope.SENSOR_EUCLID
+    assert got == c_layout(structs, extra={"abi": "OPE_ABI_VERSION", "sensor.kinect": "OPE_SENSOR_KINECT",
+                                           "sensor.astra": "OPE_SENSOR_ASTRA", "sensor.euclid": "OPE_SENSOR_EUCLID"})
     assert ope.lib().ope_abi_version() == 5
 
 

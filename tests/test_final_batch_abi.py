@@ -4,10 +4,10 @@ defaults are the reference's values."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -29,41 +29,15 @@ def test_final_entry_is_declared_exported_and_bound(ope, name):
     assert name in {n for n, _, _ in ope.ABI}
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define P(m) printf("p.%s %zu\n", #m, offsetof(ope_final_params, m))
-#define R(m) printf("r.%s %zu\n", #m, offsetof(ope_final_batch_result, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_r %zu\n", sizeof(ope_final_params), sizeof(ope_final_batch_result));
-  P(coarse); P(fine_leaf); P(fine_normals_k); P(min_fine_points); P(icp); P(fitness_max_range); P(accept_fitness); P(accept_strength);
-  R(coarse); R(seed); R(fine); R(n_fine_src); R(n_fine_tgt); R(status); R(accepted);
-  printf("status.ok %d\nstatus.empty %d\nstatus.few_features %d\nstatus.few_fine %d\n", OPE_FINAL_OK, OPE_FINAL_EMPTY_TARGET,
-         OPE_FINAL_FEW_TARGET_FEATURES, OPE_FINAL_FEW_FINE_POINTS);
-  printf("abi %d\n", OPE_ABI_VERSION);
-  return 0;
-}
-"""
-
-
-def test_final_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    want = dict(line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    want = {k: int(v) for k, v in want.items()}
-    P, R = ope.FinalParams, ope.FinalBatchResult
-    got = {"sizeof_p": ctypes.sizeof(P), "sizeof_r": ctypes.sizeof(R)}
-    for name, _ in P._fields_:
-        got["p." + name] = getattr(P, name).offset
-    for name, _ in R._fields_:
-        got["r." + name] = getattr(R, name).offset
+def test_final_layouts_match_the_c_compiler(ope):
+    structs = {ope.FinalParams: "ope_final_params", ope.FinalBatchResult: "ope_final_batch_result"}
+    got = ctypes_layout(structs)
     got["status.ok"], got["status.empty"] = ope.FINAL_OK, ope.FINAL_EMPTY_TARGET
     got["status.few_features"], got["status.few_fine"] = ope.FINAL_FEW_TARGET_FEATURES, ope.FINAL_FEW_FINE_POINTS
     got["abi"] = 5   # the change only adds to the ABI
-    assert got == want
+    assert got == c_layout(structs, extra={"status.ok": "OPE_FINAL_OK", "status.empty": "OPE_FINAL_EMPTY_TARGET",
+                                           "status.few_features": "OPE_FINAL_FEW_TARGET_FEATURES",
+                                           "status.few_fine": "OPE_FINAL_FEW_FINE_POINTS", "abi": "OPE_ABI_VERSION"})
 
 
 def test_final_defaults_are_the_reference_values(ope):

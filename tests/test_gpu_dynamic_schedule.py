@@ -194,7 +194,13 @@ def test_counters_stay_clean_across_runs_on_one_context(ctx):
     varies (before this queue as well), so the fp32 transform a later launch searches with may differ in a last bit.  The d2 of
     each run's last launch are therefore compared bit for bit with the oracle under that run's OWN transform — which is what
     "the same as a fresh run" means query by query — and with the fresh run's directly whenever the two transforms are the same
-    bits; the transforms at the run-to-run level of the atomic sums."""
+    bits; the transforms at the run-to-run level of the atomic sums.
+
+    Measured, not yet settled: 30 such pairs of 10-iteration runs (fresh context against a long-lived one, these inputs, one
+    MI355X) gave a handful of distinct distances, 0 to 1.1239e-6, 9 of the 30 above the 1e-6 below (1.0243e-6, 1.0344e-6, 1.0496e-6,
+    1.0931e-6, 1.1226e-6, 1.1239e-6); the same library under the Python binding as it was before its shared helpers and as it
+    is with them gave the same set of values (9 and 12 of 30 above).  So this test misses from time to time whatever else
+    changes; the bound is left as it was set."""
     ope = load_pkg()
     c, m = large(), model()
     src = c["src"]

@@ -4,10 +4,10 @@ pcl::MovingLeastSquares' own with ProcessingPcd::getSmooth's polynomial fit; the
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -31,37 +31,11 @@ def test_mls_entry_is_declared_exported_and_bound(ope, name):
         assert callable(getattr(ope.Context, method))
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_s %zu\n", sizeof(ope_mls_params), sizeof(ope_mls_stats));
-  O(ope_mls_params, "p", radius); O(ope_mls_params, "p", polynomial_fit); O(ope_mls_params, "p", order);
-  O(ope_mls_params, "p", sqr_gauss_param); O(ope_mls_params, "p", compute_normals);
-  O(ope_mls_stats, "s", n_in); O(ope_mls_stats, "s", n_out); O(ope_mls_stats, "s", n_plane_only); O(ope_mls_stats, "s", n_dropped);
-  O(ope_mls_stats, "s", neighbours_total);
-  printf("abi %d\n", OPE_ABI_VERSION);
-  return 0;
-}
-"""
-
-
-def test_mls_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    want = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1] for ln in lines}
-    structs = {"p": ope.MlsParams, "s": ope.MlsStats}
-    got = {"sizeof_" + t: str(ctypes.sizeof(S)) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = str(getattr(S, name).offset)
-    got["abi"] = "5"   # the change only adds to the ABI
-    assert got == want
+def test_mls_layouts_match_the_c_compiler(ope):
+    structs = {ope.MlsParams: "ope_mls_params", ope.MlsStats: "ope_mls_stats"}
+    got = ctypes_layout(structs)
+    got["abi"] = 5   # the change only adds to the ABI
+    assert got == c_layout(structs, extra={"abi": "OPE_ABI_VERSION"})
 
 
 def test_mls_defaults(ope):

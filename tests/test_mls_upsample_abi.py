@@ -4,10 +4,10 @@ pcl::MovingLeastSquares' own; the smoothing entries' structs are untouched and t
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -38,41 +38,12 @@ def test_every_upsample_symbol_of_the_header_is_in_the_binding_table(ope):
     assert declared <= {n for n, _, _ in ope.ABI}
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_s %zu\nsizeof_smooth %zu\n", sizeof(ope_mls_upsample_params), sizeof(ope_mls_upsample_stats), sizeof(ope_mls_params));
-  O(ope_mls_upsample_params, "p", radius); O(ope_mls_upsample_params, "p", polynomial_fit); O(ope_mls_upsample_params, "p", order);
-  O(ope_mls_upsample_params, "p", sqr_gauss_param); O(ope_mls_upsample_params, "p", compute_normals);
-  O(ope_mls_upsample_params, "p", voxel_size); O(ope_mls_upsample_params, "p", dilation_iterations);
-  O(ope_mls_upsample_stats, "s", n_in); O(ope_mls_upsample_stats, "s", n_valid); O(ope_mls_upsample_stats, "s", n_voxels);
-  O(ope_mls_upsample_stats, "s", n_invalid_nearest); O(ope_mls_upsample_stats, "s", n_polynomial);
-  O(ope_mls_upsample_stats, "s", n_rejected_farther); O(ope_mls_upsample_stats, "s", n_out); O(ope_mls_upsample_stats, "s", data_size);
-  O(ope_mls_upsample_stats, "s", launches); O(ope_mls_upsample_stats, "s", host_syncs);
-  printf("abi %d\n", OPE_ABI_VERSION);
-  return 0;
-}
-"""
-
-
-def test_upsample_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    want = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1] for ln in lines}
-    structs = {"p": ope.MlsUpsampleParams, "s": ope.MlsUpsampleStats}
-    got = {"sizeof_" + t: str(ctypes.sizeof(S)) for t, S in structs.items()}
-    got["sizeof_smooth"] = str(ctypes.sizeof(ope.MlsParams))   # untouched
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = str(getattr(S, name).offset)
-    got["abi"] = "5"   # the change only adds to the ABI
-    assert got == want
+def test_upsample_layouts_match_the_c_compiler(ope):
+    structs = {ope.MlsUpsampleParams: "ope_mls_upsample_params", ope.MlsUpsampleStats: "ope_mls_upsample_stats",
+               ope.MlsParams: "ope_mls_params"}   # the last one untouched
+    got = ctypes_layout(structs)
+    got["abi"] = 5   # the change only adds to the ABI
+    assert got == c_layout(structs, extra={"abi": "OPE_ABI_VERSION"})
 
 
 def test_upsample_defaults(ope):

@@ -4,10 +4,10 @@ the reference's literal (objectsegmentationplane.cpp:300)."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -31,37 +31,14 @@ def test_peel_entry_is_declared_exported_and_bound(ope, name):
         assert callable(getattr(ope.Context, method))
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_r %zu\n", sizeof(ope_peel_params), sizeof(ope_peel_result));
-  O(ope_peel_params, "p", keep_fraction); O(ope_peel_params, "p", max_planes);
-  O(ope_peel_result, "r", n_planes); O(ope_peel_result, "r", n_rest); O(ope_peel_result, "r", stop);
-  O(ope_peel_result, "r", launches); O(ope_peel_result, "r", host_syncs);
-  printf("abi %d\nstop %d %d %d\n", OPE_ABI_VERSION, OPE_PEEL_FRACTION, OPE_PEEL_NO_INLIERS, OPE_PEEL_MAX_PLANES);
-  return 0;
-}
-"""
-
-
-def test_peel_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    want = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1] for ln in lines}
-    structs = {"p": ope.PeelParams, "r": ope.PeelResult}
-    got = {"sizeof_" + t: str(ctypes.sizeof(S)) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = str(getattr(S, name).offset)
-    got["abi"] = "5"   # the change only adds to the ABI
-    got["stop"] = "%d %d %d" % (ope.PEEL_FRACTION, ope.PEEL_NO_INLIERS, ope.PEEL_MAX_PLANES)
-    assert got == want and got["stop"] == "0 1 2"
+def test_peel_layouts_match_the_c_compiler(ope):
+    structs = {ope.PeelParams: "ope_peel_params", ope.PeelResult: "ope_peel_result"}
+    got = ctypes_layout(structs)
+    got["abi"] = 5   # the change only adds to the ABI
+    got["stop.fraction"], got["stop.no_inliers"], got["stop.max_planes"] = stop = (ope.PEEL_FRACTION, ope.PEEL_NO_INLIERS, ope.PEEL_MAX_PLANES)
+    assert got == c_layout(structs, extra={"abi": "OPE_ABI_VERSION", "stop.fraction": "OPE_PEEL_FRACTION",
+                                           "stop.no_inliers": "OPE_PEEL_NO_INLIERS", "stop.max_planes": "OPE_PEEL_MAX_PLANES"})
+    assert stop == (0, 1, 2)
 
 
 def test_peel_defaults_are_the_reference_literals(ope):

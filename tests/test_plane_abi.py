@@ -5,10 +5,10 @@ pcl::SACSegmentation's own."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -33,44 +33,15 @@ def test_plane_entry_is_declared_exported_and_bound(ope, name):
         assert callable(getattr(ope.Context, method))
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_s %zu\nsizeof_t %zu\n", sizeof(ope_plane_params), sizeof(ope_plane_stats), sizeof(ope_tabletop_result));
-  O(ope_plane_params, "p", distance_threshold); O(ope_plane_params, "p", probability); O(ope_plane_params, "p", max_iterations);
-  O(ope_plane_params, "p", optimize_coefficients); O(ope_plane_params, "p", seed);
-  O(ope_plane_stats, "s", iterations); O(ope_plane_stats, "s", hypotheses); O(ope_plane_stats, "s", launches);
-  O(ope_plane_stats, "s", host_syncs); O(ope_plane_stats, "s", best); O(ope_plane_stats, "s", found);
-  O(ope_tabletop_result, "t", status); O(ope_tabletop_result, "t", n_prism); O(ope_tabletop_result, "t", n_plane);
-  O(ope_tabletop_result, "t", n_not_plane); O(ope_tabletop_result, "t", coeff_first); O(ope_tabletop_result, "t", coeff_second);
-  O(ope_tabletop_result, "t", corners); O(ope_tabletop_result, "t", iterations_first); O(ope_tabletop_result, "t", iterations_second);
-  O(ope_tabletop_result, "t", launches); O(ope_tabletop_result, "t", host_syncs);
-  printf("abi %d\nstatus %d %d %d\nmaxit %d\n", OPE_ABI_VERSION, OPE_TABLETOP_OK, OPE_TABLETOP_NO_PLANE_FIRST, OPE_TABLETOP_NO_PLANE_SECOND,
-         OPE_PLANE_MAX_ITERATIONS);
-  return 0;
-}
-"""
-
-
-def test_plane_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    want = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1] for ln in lines}
-    structs = {"p": ope.PlaneParams, "s": ope.PlaneStats, "t": ope.TabletopResult}
-    got = {"sizeof_" + t: str(ctypes.sizeof(S)) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = str(getattr(S, name).offset)
-    got["abi"] = "5"   # the change only adds to the ABI
-    got["status"] = "%d %d %d" % (ope.TABLETOP_OK, ope.TABLETOP_NO_PLANE_FIRST, ope.TABLETOP_NO_PLANE_SECOND)
-    got["maxit"] = "1023"
-    assert got == want
+def test_plane_layouts_match_the_c_compiler(ope):
+    structs = {ope.PlaneParams: "ope_plane_params", ope.PlaneStats: "ope_plane_stats", ope.TabletopResult: "ope_tabletop_result"}
+    got = ctypes_layout(structs)
+    got["abi"] = 5   # the change only adds to the ABI
+    got["status.ok"], got["status.first"], got["status.second"] = ope.TABLETOP_OK, ope.TABLETOP_NO_PLANE_FIRST, ope.TABLETOP_NO_PLANE_SECOND
+    got["maxit"] = 1023
+    assert got == c_layout(structs, extra={"abi": "OPE_ABI_VERSION", "status.ok": "OPE_TABLETOP_OK",
+                                           "status.first": "OPE_TABLETOP_NO_PLANE_FIRST", "status.second": "OPE_TABLETOP_NO_PLANE_SECOND",
+                                           "maxit": "OPE_PLANE_MAX_ITERATIONS"})
 
 
 def test_plane_defaults_are_the_reference_literals(ope):

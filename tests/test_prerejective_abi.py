@@ -4,10 +4,10 @@ compiler lays out ope_prerejective_params / _result / _stats; the defaults are t
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -31,47 +31,16 @@ def test_prerejective_entry_is_declared_exported_and_bound(ope, name):
         assert callable(getattr(ope.Context, method))
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  ope_prerejective_params p;
-  printf("sizeof_p %zu\nsizeof_r %zu\nsizeof_s %zu\n", sizeof(ope_prerejective_params), sizeof(ope_prerejective_result),
-         sizeof(ope_prerejective_stats));
-  O(ope_prerejective_params, "p", max_iterations); O(ope_prerejective_params, "p", nr_samples);
-  O(ope_prerejective_params, "p", k_correspondences); O(ope_prerejective_params, "p", similarity_threshold);
-  O(ope_prerejective_params, "p", max_corr_dist); O(ope_prerejective_params, "p", inlier_fraction); O(ope_prerejective_params, "p", seed);
-  O(ope_prerejective_result, "r", T); O(ope_prerejective_result, "r", error); O(ope_prerejective_result, "r", best_iteration);
-  O(ope_prerejective_result, "r", inliers); O(ope_prerejective_result, "r", converged);
-  O(ope_prerejective_stats, "s", iterations); O(ope_prerejective_stats, "s", survivors); O(ope_prerejective_stats, "s", launches);
-  O(ope_prerejective_stats, "s", host_syncs); O(ope_prerejective_stats, "s", nr_samples);
-  printf("abi %d\n", OPE_ABI_VERSION);
-  (void)p;
-  return 0;
-}
-"""
-
-
-def test_prerejective_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    want = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1] for ln in lines}
-    structs = {"p": ope.PrerejectiveParams, "r": ope.PrerejectiveResult, "s": ope.PrerejectiveStats}
-    got = {"sizeof_" + t: str(ctypes.sizeof(S)) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = str(getattr(S, name).offset)
+def test_prerejective_layouts_match_the_c_compiler(ope):
+    P, R, S = "ope_prerejective_params", "ope_prerejective_result", "ope_prerejective_stats"
+    structs = {ope.PrerejectiveParams: P, ope.PrerejectiveResult: R, ope.PrerejectiveStats: S}
+    got = {k: str(v) for k, v in ctypes_layout(structs).items()}
     got["abi"] = "5"   # the change only adds to the ABI
-    assert got == want
+    assert got == {k: str(v) for k, v in c_layout(structs, extra={"abi": "OPE_ABI_VERSION"}).items()}
     # the layout itself, pinned
-    assert (got["sizeof_p"], got["sizeof_r"], got["sizeof_s"]) == ("40", "88", "40")
-    assert [got["p." + n] for n, _ in ope.PrerejectiveParams._fields_] == ["0", "4", "8", "12", "16", "24", "32"]
-    assert [got["r." + n] for n, _ in ope.PrerejectiveResult._fields_] == ["0", "64", "72", "76", "80"]
+    assert (got[P, "sizeof"], got[R, "sizeof"], got[S, "sizeof"]) == ("40", "88", "40")
+    assert [got[P, n] for n, _ in ope.PrerejectiveParams._fields_] == ["0", "4", "8", "12", "16", "24", "32"]
+    assert [got[R, n] for n, _ in ope.PrerejectiveResult._fields_] == ["0", "64", "72", "76", "80"]
     assert [n for n, _ in ope.PrerejectiveStats._fields_] == ["iterations", "survivors", "launches", "host_syncs", "nr_samples"]
 
 

@@ -3,10 +3,10 @@ compiler lays out ope_prerejective_batch_result / _stats; the structs the new en
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -35,50 +35,22 @@ def test_batch_entry_is_declared_exported_and_bound(ope, name):
         assert callable(getattr(ope.Context, method))
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_r %zu\nsizeof_s %zu\n", sizeof(ope_prerejective_batch_result), sizeof(ope_prerejective_batch_stats));
-  printf("sizeof_params %zu\nsizeof_coarse %zu\nsizeof_final %zu\n", sizeof(ope_prerejective_params), sizeof(ope_coarse_params),
-         sizeof(ope_final_batch_result));
-  O(ope_prerejective_batch_result, "r", T); O(ope_prerejective_batch_result, "r", error); O(ope_prerejective_batch_result, "r", best_iteration);
-  O(ope_prerejective_batch_result, "r", inliers); O(ope_prerejective_batch_result, "r", converged); O(ope_prerejective_batch_result, "r", survivors);
-  O(ope_prerejective_batch_result, "r", n_src_keys); O(ope_prerejective_batch_result, "r", n_tgt_keys); O(ope_prerejective_batch_result, "r", status);
-  O(ope_prerejective_batch_result, "r", seed);
-  O(ope_prerejective_batch_stats, "s", clusters); O(ope_prerejective_batch_stats, "s", active); O(ope_prerejective_batch_stats, "s", iterations);
-  O(ope_prerejective_batch_stats, "s", survivors); O(ope_prerejective_batch_stats, "s", launches); O(ope_prerejective_batch_stats, "s", host_syncs);
-  O(ope_prerejective_batch_stats, "s", nr_samples);
-  printf("enum %d %d %d %d\n", OPE_PREREJ_OK, OPE_PREREJ_EMPTY_TARGET, OPE_PREREJ_FEW_TARGET_FEATURES, OPE_PREREJ_NAN_FEATURES);
-  printf("abi %d\n", OPE_ABI_VERSION);
-  return 0;
-}
-"""
-
-
-def test_batch_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).splitlines()
-    want = {ln.split(" ", 1)[0]: ln.split(" ", 1)[1] for ln in lines}
-    structs = {"r": ope.PrerejectiveBatchResult, "s": ope.PrerejectiveBatchStats}
-    got = {"sizeof_" + t: str(ctypes.sizeof(S)) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = str(getattr(S, name).offset)
-    got["sizeof_params"] = str(ctypes.sizeof(ope.PrerejectiveParams))
-    got["sizeof_coarse"] = str(ctypes.sizeof(ope.CoarseParams))
-    got["sizeof_final"] = str(ctypes.sizeof(ope.FinalBatchResult))
-    got["enum"] = " ".join(str(v) for v in (ope.PREREJ_OK, ope.PREREJ_EMPTY_TARGET, ope.PREREJ_FEW_TARGET_FEATURES, ope.PREREJ_NAN_FEATURES))
+def test_batch_layouts_match_the_c_compiler(ope):
+    R, S = "ope_prerejective_batch_result", "ope_prerejective_batch_stats"
+    structs = {ope.PrerejectiveBatchResult: R, ope.PrerejectiveBatchStats: S, ope.PrerejectiveParams: "ope_prerejective_params",
+               ope.CoarseParams: "ope_coarse_params", ope.FinalBatchResult: "ope_final_batch_result"}
+    got = {k: str(v) for k, v in ctypes_layout(structs).items()}
+    got["status.ok"], got["status.empty"], got["status.few"], got["status.nan"] = (
+        str(v) for v in (ope.PREREJ_OK, ope.PREREJ_EMPTY_TARGET, ope.PREREJ_FEW_TARGET_FEATURES, ope.PREREJ_NAN_FEATURES))
     got["abi"] = "5"   # the change only adds to the ABI
-    assert got == want
+    want = c_layout(structs, extra={"status.ok": "OPE_PREREJ_OK", "status.empty": "OPE_PREREJ_EMPTY_TARGET",
+                                    "status.few": "OPE_PREREJ_FEW_TARGET_FEATURES", "status.nan": "OPE_PREREJ_NAN_FEATURES",
+                                    "abi": "OPE_ABI_VERSION"})
+    assert got == {k: str(v) for k, v in want.items()}
     # the layouts, pinned; the three existing structs as they were before the batch
-    assert (got["sizeof_r"], got["sizeof_s"]) == ("112", "56")
-    assert [got["r." + n] for n, _ in ope.PrerejectiveBatchResult._fields_] == ["0", "64", "72", "76", "80", "84", "88", "92", "96", "104"]
+    assert (got[R, "sizeof"], got[S, "sizeof"]) == ("112", "56")
+    assert [got[R, n] for n, _ in ope.PrerejectiveBatchResult._fields_] == ["0", "64", "72", "76", "80", "84", "88", "92", "96", "104"]
     assert [n for n, _ in ope.PrerejectiveBatchStats._fields_] == ["clusters", "active", "iterations", "survivors", "launches", "host_syncs",
                                                                    "nr_samples"]
-    assert (got["sizeof_params"], got["sizeof_coarse"], got["sizeof_final"]) == ("40", "64", "232")
+    assert (got["ope_prerejective_params", "sizeof"], got["ope_coarse_params", "sizeof"], got["ope_final_batch_result", "sizeof"]) == (
+        "40", "64", "232")

@@ -5,10 +5,10 @@ import ctypes
 import math
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -30,35 +30,9 @@ def test_region_entry_is_declared_exported_and_bound(ope, name):
     assert name in {n for n, _, _ in ope.ABI}
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_s %zu\n", sizeof(ope_region_params), sizeof(ope_region_stats));
-  O(ope_region_params, "p", number_of_neighbours); O(ope_region_params, "p", normals_k); O(ope_region_params, "p", smoothness_threshold);
-  O(ope_region_params, "p", curvature_threshold); O(ope_region_params, "p", min_size); O(ope_region_params, "p", max_size);
-  O(ope_region_stats, "s", launches); O(ope_region_stats, "s", host_syncs); O(ope_region_stats, "s", sweeps);
-  O(ope_region_stats, "s", one_way_edges); O(ope_region_stats, "s", regions_before_size_filter); O(ope_region_stats, "s", refused_curvature);
-  return 0;
-}
-"""
-
-
-def test_region_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    want = dict(line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    want = {k: int(v) for k, v in want.items()}
-    structs = {"p": ope.RegionParams, "s": ope.RegionStats}
-    got = {"sizeof_" + t: ctypes.sizeof(S) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = getattr(S, name).offset
-    assert got == want
+def test_region_layouts_match_the_c_compiler(ope):
+    structs = {ope.RegionParams: "ope_region_params", ope.RegionStats: "ope_region_stats"}
+    assert ctypes_layout(structs) == c_layout(structs)
 
 
 def test_region_binding_has_the_header_s_argument_counts(ope):

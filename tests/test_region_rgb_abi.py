@@ -4,10 +4,10 @@ out ope_region_rgb_params / ope_region_rgb_stats; the defaults are the reference
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -30,38 +30,9 @@ def test_region_rgb_entry_is_declared_exported_and_bound(ope, name):
     assert name in {n for n, _, _ in ope.ABI}
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_s %zu\n", sizeof(ope_region_rgb_params), sizeof(ope_region_rgb_stats));
-  O(ope_region_rgb_params, "p", region_neighbour_number); O(ope_region_rgb_params, "p", distance_threshold);
-  O(ope_region_rgb_params, "p", point_color_threshold); O(ope_region_rgb_params, "p", region_color_threshold);
-  O(ope_region_rgb_params, "p", min_size); O(ope_region_rgb_params, "p", max_size);
-  O(ope_region_rgb_stats, "s", launches); O(ope_region_rgb_stats, "s", host_syncs); O(ope_region_rgb_stats, "s", sweeps);
-  O(ope_region_rgb_stats, "s", one_way_edges); O(ope_region_rgb_stats, "s", segments); O(ope_region_rgb_stats, "s", segment_pairs);
-  O(ope_region_rgb_stats, "s", homogeneous_regions); O(ope_region_rgb_stats, "s", regions_absorbed);
-  O(ope_region_rgb_stats, "s", regions_before_size_filter);
-  return 0;
-}
-"""
-
-
-def test_region_rgb_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    want = dict(line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    want = {k: int(v) for k, v in want.items()}
-    structs = {"p": ope.RegionRgbParams, "s": ope.RegionRgbStats}
-    got = {"sizeof_" + t: ctypes.sizeof(S) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = getattr(S, name).offset
-    assert got == want
+def test_region_rgb_layouts_match_the_c_compiler(ope):
+    structs = {ope.RegionRgbParams: "ope_region_rgb_params", ope.RegionRgbStats: "ope_region_rgb_stats"}
+    assert ctypes_layout(structs) == c_layout(structs)
 
 
 def test_region_rgb_binding_has_the_header_s_argument_counts(ope):

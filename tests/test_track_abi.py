@@ -4,10 +4,10 @@ defaults are the reference's literals (rosinterface.cpp:279,304, poseestimator.c
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
+from abi_probe import c_layout, ctypes_layout
 from conftest import ROOT, load_pkg
 
 HEADER = os.path.join(ROOT, "include", "ope.h")
@@ -29,46 +29,16 @@ def test_track_entry_is_declared_exported_and_bound(ope, name):
     assert name in {n for n, _, _ in ope.ABI}
 
 
-PROBE = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ope.h"
-#define O(t, tag, m) printf("%s.%s %zu\n", tag, #m, offsetof(t, m))
-int main(void) {
-  printf("sizeof_p %zu\nsizeof_c %zu\nsizeof_g %zu\nsizeof_r %zu\n", sizeof(ope_track_params), sizeof(ope_track_centroid),
-         sizeof(ope_track_gate_result), sizeof(ope_track_result));
-  O(ope_track_params, "p", gate_distance); O(ope_track_params, "p", coarse_fitness); O(ope_track_params, "p", final);
-  O(ope_track_centroid, "c", centroid); O(ope_track_centroid, "c", count); O(ope_track_centroid, "c", distance);
-  O(ope_track_gate_result, "g", branch); O(ope_track_gate_result, "g", selected); O(ope_track_gate_result, "g", source);
-  O(ope_track_result, "r", gate); O(ope_track_result, "r", selected); O(ope_track_result, "r", coarse_status);
-  O(ope_track_result, "r", seed); O(ope_track_result, "r", coarse); O(ope_track_result, "r", fine); O(ope_track_result, "r", rigid);
-  O(ope_track_result, "r", final_pose); O(ope_track_result, "r", icp); O(ope_track_result, "r", fitness);
-  O(ope_track_result, "r", fitness_n); O(ope_track_result, "r", n_fine_src); O(ope_track_result, "r", n_fine_tgt);
-  O(ope_track_result, "r", status); O(ope_track_result, "r", reserved);
-  printf("b.none %d\nb.gated %d\nb.all %d\nb.nothing %d\nb.loop %d\nskipped %d\n", OPE_TRACK_NO_CLUSTERS, OPE_TRACK_GATED,
-         OPE_TRACK_REALIGN_ALL, OPE_TRACK_NOTHING, OPE_TRACK_REALIGN_LOOP, OPE_TRACK_COARSE_SKIPPED);
-  printf("abi %d\n", OPE_ABI_VERSION);
-  return 0;
-}
-"""
-
-
-def test_track_layouts_match_the_c_compiler(ope, tmp_path):
-    c = tmp_path / "probe.c"
-    c.write_text(PROBE)
-    exe = tmp_path / "probe"
-    subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
-    want = dict(line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    want = {k: int(v) for k, v in want.items()}
-    structs = {"p": ope.TrackParams, "c": ope.TrackCentroid, "g": ope.TrackGateResult, "r": ope.TrackResult}
-    got = {"sizeof_" + t: ctypes.sizeof(S) for t, S in structs.items()}
-    for t, S in structs.items():
-        for name, _ in S._fields_:
-            got[t + "." + name] = getattr(S, name).offset
+def test_track_layouts_match_the_c_compiler(ope):
+    structs = {ope.TrackParams: "ope_track_params", ope.TrackCentroid: "ope_track_centroid", ope.TrackGateResult: "ope_track_gate_result",
+               ope.TrackResult: "ope_track_result"}
+    got = ctypes_layout(structs)
     got.update({"b.none": ope.TRACK_NO_CLUSTERS, "b.gated": ope.TRACK_GATED, "b.all": ope.TRACK_REALIGN_ALL, "b.nothing": ope.TRACK_NOTHING,
                 "b.loop": ope.TRACK_REALIGN_LOOP, "skipped": ope.TRACK_COARSE_SKIPPED})
     got["abi"] = 5   # the change only adds to the ABI
-    assert got == want
+    assert got == c_layout(structs, extra={"b.none": "OPE_TRACK_NO_CLUSTERS", "b.gated": "OPE_TRACK_GATED", "b.all": "OPE_TRACK_REALIGN_ALL",
+                                           "b.nothing": "OPE_TRACK_NOTHING", "b.loop": "OPE_TRACK_REALIGN_LOOP",
+                                           "skipped": "OPE_TRACK_COARSE_SKIPPED", "abi": "OPE_ABI_VERSION"})
 
 
 def test_track_defaults_are_the_reference_literals(ope):
