@@ -7,7 +7,7 @@
 // no communication between workgroups (no spin-wait, no co-residency requirement).  The update step is icp_update_lane
 // itself (icp_update.hpp), the same code ope_icp_run runs; the search, the rejectors and the terms of the sums follow
 // icp_accumulate_kernel operation for operation.  The sums of an iteration are added in a fixed order inside the workgroup
-// (16-lane DPP row sums, one LDS row per 16 lanes, one ordered pass over the rows), so a problem's result depends on its own
+// (the wave's reduce-scatter of icp_sums.hpp, one LDS row per wave, one ordered pass over the rows), so a problem's result depends on its own
 // inputs only: not on the run, the other problems of the batch or its position among them.
 #include <cfloat>
 #include <climits>
@@ -15,12 +15,13 @@
 #include <limits>
 
 #include "icp_update.hpp"
+#include "icp_sums.hpp"   // add_query_sums: the terms and the wave's reduce-scatter, shared with icp_kernels.hip
 
 namespace ope {
 
 // Threads per workgroup: 512 (eight waves, two per SIMD) was faster than 256 at C1 size, DESIGN.md 4.6.
 constexpr int kBatchBlock = 512;
-constexpr int kBatchRows = kBatchBlock / 16;   // 16-lane rows: one LDS row of partial sums each
+constexpr int kBatchRows = kBatchBlock / 64;   // one LDS row of partial sums per wave, each slot with one writing lane
 constexpr size_t kBatchMaxSrc = 65536;        // valid source points of one problem at most (larger runs belong to ope_icp_run)
 
 struct BatchProblem {
@@ -35,58 +36,6 @@ struct BatchOut {
   int iterations, converged, state, pad_;
   double fit_sum, fit_n;
 };
-
-typedef const __attribute__((address_space(3))) float *lds_cfloat_ptr_b;   // a pointer that stays an LDS pointer
-
-// One query's terms of the 17 (44) sums exactly as add_query_sums forms them (icp_kernels.hip), added into this lane's
-// 16-lane row of `rows` by the row's first lane: no atomics, one writer per row, so the order of every addition is fixed.
-template <bool NRM>
-__device__ __forceinline__ void batch_add_terms(double *row, lds_cfloat_ptr_b cs, uint32_t lane_id, bool ok, bool p2p, float x, float y,
-                                                float z, const float4 t, const float4 tn, float d2) {
-  asm volatile("" : "+v"(cs));
-  const float psx = cs[12], psy = cs[13], psz = cs[14];
-  const double sx = (double)x - (double)psx, sy = (double)y - (double)psy, sz = (double)z - (double)psz;
-  const double tx = (double)t.x - (double)psx, ty = (double)t.y - (double)psy, tz = (double)t.z - (double)psz;
-  const double w = ok ? 1.0 : 0.0;
-  const bool lead = (lane_id & 15u) == 0u;
-  double term[kNumSums];
-  term[0] = w;
-  term[1] = w * sx; term[2] = w * sy; term[3] = w * sz;
-  term[4] = w * tx; term[5] = w * ty; term[6] = w * tz;
-  term[7] = w * (tx * sx); term[8] = w * (tx * sy); term[9] = w * (tx * sz);
-  term[10] = w * (ty * sx); term[11] = w * (ty * sy); term[12] = w * (ty * sz);
-  term[13] = w * (tz * sx); term[14] = w * (tz * sy); term[15] = w * (tz * sz);
-  term[16] = ok ? (double)d2 : 0.0;
-#pragma unroll
-  for (int k = 0; k < kNumSums; ++k) {
-    const double r = row16_sum(term[k]);
-    if (lead) row[k] += r;
-  }
-  if (NRM && p2p) {
-    // TransformationEstimationPointToPlaneLLS (see add_query_sums): products in float, sums in double
-    const float v0 = __fsub_rn(__fmul_rn(tn.z, y), __fmul_rn(tn.y, z));
-    const float v1 = __fsub_rn(__fmul_rn(tn.x, z), __fmul_rn(tn.z, x));
-    const float v2 = __fsub_rn(__fmul_rn(tn.y, x), __fmul_rn(tn.x, y));
-    const float dd = __fsub_rn(__fsub_rn(__fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(tn.x, t.x), __fmul_rn(tn.y, t.y)), __fmul_rn(tn.z, t.z)),
-                                                     __fmul_rn(tn.x, x)), __fmul_rn(tn.y, y)), __fmul_rn(tn.z, z));
-    const double v[6] = {w * (double)v0, w * (double)v1, w * (double)v2, w * (double)tn.x, w * (double)tn.y, w * (double)tn.z};
-    int slot = kNumSums;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = r; c < 6; ++c) {
-        const double sum = row16_sum(v[r] * v[c]);
-        if (lead) row[slot] += sum;
-        ++slot;
-      }
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      const double sum = row16_sum(v[r] * (double)dd);
-      if (lead) row[slot] += sum;
-      ++slot;
-    }
-  }
-}
 
 // One workgroup per problem.  MODE 0: 1-NN; MODE 2: normal shooting over the k nearest, list in KREG registers (the sizes
 // launch_icp_accumulate uses).  NRM: normals are read (normal shooting, rejectors, point-to-plane).
@@ -124,7 +73,7 @@ __global__ __launch_bounds__(kBatchBlock, 4) void icp_batch_kernel(const BatchPr
   const int kk = st->k_normal_shooting;
   const uint32_t n_valid = pr.src.n_valid;
   const uint32_t lane_id = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  double *row = s_rows[threadIdx.x >> 4];
+  double *row = s_rows[wave];
   __syncthreads();
 
   for (int it = 0; it < max_it && s_st.done == 0; ++it) {
@@ -137,7 +86,7 @@ __global__ __launch_bounds__(kBatchBlock, 4) void icp_batch_kernel(const BatchPr
     for (uint32_t base = wave * 64u; base < n_valid; base += kBatchBlock) {
       const uint32_t i = base + lane_id;
       const bool active = i < n_valid;
-      lds_cfloat_ptr_b cst = (lds_cfloat_ptr_b)s_const;
+      lds_cfloat_ptr cst = (lds_cfloat_ptr)s_const;
       asm volatile("" : "+v"(cst));
       float F[12];
 #pragma unroll
@@ -202,8 +151,9 @@ __global__ __launch_bounds__(kBatchBlock, 4) void icp_batch_kernel(const BatchPr
         const double score = (double)nx * (-(double)x / sl) + (double)ny * (-(double)y / sl) + (double)nz * (-(double)z / sl);
         ok = score > thr_so;
       }
-      batch_add_terms<NRM>(row, (lds_cfloat_ptr_b)s_const, lane_id, ok, p2p, x, y, z, pr.tgt.pts[ok ? pos : 0],
-                           (NRM && p2p) ? pr.tgt.nrm[ok ? pos : 0] : make_float4(0.f, 0.f, 0.f, 0.f), d2);
+      // no atomics: the wave's reduce-scatter leaves one writing lane per slot of its row, so the order of every addition is fixed
+      add_query_sums<NRM, false>(row, (lds_cfloat_ptr)s_const, lane_id, ok, p2p, x, y, z, pr.tgt.pts[ok ? pos : 0],
+                                 (NRM && p2p) ? pr.tgt.nrm[ok ? pos : 0] : make_float4(0.f, 0.f, 0.f, 0.f), d2);
     }
     __syncthreads();
     if ((int)threadIdx.x < nsums) {   // rows in a fixed order
@@ -224,7 +174,7 @@ __global__ __launch_bounds__(kBatchBlock, 4) void icp_batch_kernel(const BatchPr
     for (uint32_t base = wave * 64u; base < n_valid; base += kBatchBlock) {
       const uint32_t i = base + lane_id;
       const bool active = i < n_valid;
-      lds_cfloat_ptr_b cst = (lds_cfloat_ptr_b)s_const;
+      lds_cfloat_ptr cst = (lds_cfloat_ptr)s_const;
       asm volatile("" : "+v"(cst));
       float F[12];
 #pragma unroll

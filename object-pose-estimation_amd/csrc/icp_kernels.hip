@@ -21,10 +21,10 @@
 #include "bvh_traverse.hpp"
 #include "lm_solve.hpp"
 #include "icp_update.hpp"
+#include "icp_sums.hpp"   // add_query_sums: one query per lane -> the wave's 17 (44) sums in LDS
 
 namespace ope {
 
-typedef const __attribute__((address_space(3))) float *lds_cfloat_ptr;   // a pointer that stays an LDS pointer
 static_assert(kCertCand >= 1 && kCertCand <= 8, "skip certificates: candidates per query");
 
 // ---- update launches overlapped with the accumulate launches (round 3; host side: api.hip, ope_icp_iterate) -------------
@@ -106,63 +106,6 @@ __device__ __forceinline__ uint32_t deal_next(uint32_t k, uint32_t stripe, uint3
 __device__ __forceinline__ void deal_clear_other_set(uint32_t *deal, uint32_t parity) {
   if (blockIdx.x == 0 && threadIdx.x < kDealStripes)
     __hip_atomic_store(deal + (size_t)(parity ^ 1u) * kDealStripes * kDealLineWords + threadIdx.x * kDealLineWords, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One query's contribution to the wave's running sums {n, Σs, Σt, Σ t sᵀ, Σd²} (+ 27 normal-equation sums with the
-// point-to-plane estimator): 16-lane row sums by DPP, then one ds_add_f64 per row and component into `acc` (LDS).
-// t: the matched target point, tn: its normal (point-to-plane only); lanes with ok == false contribute zeros.
-template <bool NRM>
-__device__ __forceinline__ void add_query_sums(double *acc, lds_cfloat_ptr cs2, uint32_t lane_id, bool ok, bool p2p, float x, float y, float z,
-                                               const float4 t, const float4 tn, float d2) {
-    {
-      // fp64 terms: differences and products of fp32 values are exact in fp64, so the 17 sums do not
-      // depend (beyond 1e-16) on how queries are grouped into lanes, chunks, waves or ranks
-      asm volatile("" : "+v"(cs2));
-      const float psx = cs2[12], psy = cs2[13], psz = cs2[14];
-      const double sx = (double)x - (double)psx, sy = (double)y - (double)psy, sz = (double)z - (double)psz;
-      const double tx = (double)t.x - (double)psx, ty = (double)t.y - (double)psy, tz = (double)t.z - (double)psz;
-      // 16-lane row sums by DPP (pure VALU), then one ds_add_f64 per row and component into the wave's
-      // 17 LDS slots (a full 64-lane fp64 butterfly cost ~200 dependent ds_bpermutes per chunk)
-      const double w = ok ? 1.0 : 0.0;
-      double term[kNumSums];
-      term[0] = w;
-      term[1] = w * sx; term[2] = w * sy; term[3] = w * sz;
-      term[4] = w * tx; term[5] = w * ty; term[6] = w * tz;
-      term[7] = w * (tx * sx); term[8] = w * (tx * sy); term[9] = w * (tx * sz);
-      term[10] = w * (ty * sx); term[11] = w * (ty * sy); term[12] = w * (ty * sz);
-      term[13] = w * (tz * sx); term[14] = w * (tz * sy); term[15] = w * (tz * sz);
-      term[16] = ok ? (double)d2 : 0.0;
-#pragma unroll
-      for (int k = 0; k < kNumSums; ++k) {
-        const double r = row16_sum(term[k]);
-        if ((lane_id & 15u) == 0u) unsafeAtomicAdd(acc + k, r);
-      }
-      if (NRM && p2p) {
-        // TransformationEstimationPointToPlaneLLS: row v = (s x n, n), right-hand side d = n . (t - s);
-        // the reference forms these products in float (operands are const float&), sums in double
-        const float v0 = __fsub_rn(__fmul_rn(tn.z, y), __fmul_rn(tn.y, z));
-        const float v1 = __fsub_rn(__fmul_rn(tn.x, z), __fmul_rn(tn.z, x));
-        const float v2 = __fsub_rn(__fmul_rn(tn.y, x), __fmul_rn(tn.x, y));
-        const float dd = __fsub_rn(__fsub_rn(__fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(tn.x, t.x), __fmul_rn(tn.y, t.y)), __fmul_rn(tn.z, t.z)),
-                                                         __fmul_rn(tn.x, x)), __fmul_rn(tn.y, y)), __fmul_rn(tn.z, z));
-        const double v[6] = {w * (double)v0, w * (double)v1, w * (double)v2, w * (double)tn.x, w * (double)tn.y, w * (double)tn.z};
-        int slot = kNumSums;
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-          for (int c = r; c < 6; ++c) {
-            const double sum = row16_sum(v[r] * v[c]);
-            if ((lane_id & 15u) == 0u) unsafeAtomicAdd(acc + slot, sum);
-            ++slot;
-          }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-          const double sum = row16_sum(v[r] * (double)dd);
-          if ((lane_id & 15u) == 0u) unsafeAtomicAdd(acc + slot, sum);
-          ++slot;
-        }
-      }
-    }
 }
 
 // ---- skip certificates: the two pieces the tree kernel and the grid kernel share (see icp_accumulate_kernel, "certified search")
@@ -618,8 +561,10 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
       __builtin_nontemporal_store(ok ? match : -1, corr_match + i);   // streamed out: nothing re-reads them in this launch
       __builtin_nontemporal_store(d2, corr_d2 + i);
     }
-    add_query_sums<NRM>(s_red[threadIdx.x >> 6], (lds_cfloat_ptr)s_const, lane_id, ok, p2p, x, y, z, tgt.pts[ok ? pos : 0],
-                        (NRM && p2p) ? tgt.nrm[ok ? pos : 0] : make_float4(0.f, 0.f, 0.f, 0.f), d2);
+    // (the wave's row through a scalar: its address then costs no vector register across the walks; the normal-shooting
+    // instantiations, at their register bound, keep every sum on 16-lane row sums: icp_sums.hpp, add_query_sums_by_rows)
+    add_query_sums<NRM, true, MODE != 2>(s_red[MODE != 2 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6], (lds_cfloat_ptr)s_const, lane_id, ok, p2p, x, y, z,
+                                         tgt.pts[ok ? pos : 0], (NRM && p2p) ? tgt.nrm[ok ? pos : 0] : make_float4(0.f, 0.f, 0.f, 0.f), d2);
     if (lane_id == 0 && !oct) chunk_cost[chunk] = (uint32_t)((__builtin_amdgcn_s_memtime() - t_begin) >> 4);
     if (dealt) {
       slot = deal_next((uint32_t)__builtin_amdgcn_readfirstlane((int)ticket_v), stripe, n_stripes, n_waves, n_slots);
@@ -909,8 +854,8 @@ __global__ __launch_bounds__(kAccBlock, CERT ? 4 : kAccWavesPerSimd) void icp_ac
       __builtin_nontemporal_store(ok ? match : -1, corr_match + i);
       __builtin_nontemporal_store(d2, corr_d2 + i);
     }
-    add_query_sums<NRM>(s_red[threadIdx.x >> 6], (lds_cfloat_ptr)s_const, lane_id, ok, p2p, x, y, z, make_float4(tm.x, tm.y, tm.z, tm.w),
-                        (NRM && p2p) ? (by_cert ? tgt.nrm[ok ? c_pos : 0u] : grid.gnrm[ok ? gpos : 0u]) : make_float4(0.f, 0.f, 0.f, 0.f), d2);
+    add_query_sums<NRM, true>(s_red[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)], (lds_cfloat_ptr)s_const, lane_id, ok, p2p, x, y, z, make_float4(tm.x, tm.y, tm.z, tm.w),
+                              (NRM && p2p) ? (by_cert ? tgt.nrm[ok ? c_pos : 0u] : grid.gnrm[ok ? gpos : 0u]) : make_float4(0.f, 0.f, 0.f, 0.f), d2);
     // tree chunks record their cost under their id, grid chunks behind them (the plan only needs their sum)
     if (lane_id == 0 && !oct) chunk_cost[tree_part ? chunk : n_tc + gchunk] = (uint32_t)((__builtin_amdgcn_s_memtime() - t_begin) >> 4);
   }
