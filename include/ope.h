@@ -418,6 +418,8 @@ int ope_reject_pairs(ope_ctx *ctx, int kind, const float *a, const float *b, siz
  * its launches per iteration depend on the list alone.  ope_icp_begin answers OPE_EINVAL, nothing launched, while a list is set
  * and the run asks for reciprocal correspondences, an estimator other than OPE_EST_SVD, fixed correspondences or a context with a
  * communicator; ope_icp_run_batch, the ope_final_pose_batch* family and ope_track_pose answer OPE_EINVAL while a list is set.
+ * The batched runs take a list as an ARGUMENT instead: ope_icp_run_batch_rejectors, ope_final_pose_batch_rejectors
+ * (ope_batch_rejectors.h, included at the end of this header).
  * OPE_EINVAL for a parameter out of range: factor not finite or < 0, a ratio outside [0, 1], min_ratio > max_ratio, an unknown
  * kind, more than OPE_GREJ_MAX rejectors. */
 enum { OPE_GREJ_MEDIAN_DISTANCE = 0, OPE_GREJ_ONE_TO_ONE = 1, OPE_GREJ_VAR_TRIMMED = 2 };
@@ -1492,6 +1494,9 @@ int ope_vfh_match(ope_ctx *ctx, const ope_vfh_db *db, const float *queries308, s
 /* ope_vfh_batch followed by ope_vfh_match with the signatures never leaving the device; out308_opt: the signatures as well. */
 int ope_vfh_recognise(ope_ctx *ctx, const ope_vfh_db *db, size_t n, ope_cloud *const *clusters, const ope_vfh_params *params, int k,
                       float *out308_opt, int32_t *out_idx, float *out_dist);
+
+/* The batched entry points that take a list of global rejectors as an argument. */
+#include "ope_batch_rejectors.h"
 
 #ifdef __cplusplus
 }

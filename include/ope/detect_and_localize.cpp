@@ -57,7 +57,11 @@
 // PoseEstimator::addFineRejector: the rejectors estimateFinePose's list keeps commented out (poseestimator.cpp:250-292; the reference's
 // literals are median:0.8 and trimmed:0.3), applied inside the fine ICP in the order given on the command line, behind the
 // surface-normal rejector.  With the flag the candidate loop and the tracker run one estimateFinalPose at a time (the batched and
-// tracked entry points have no such stage).  Exit status 2 for another name or a value that does not parse.
+// tracked entry points take no list from the context).  Exit status 2 for another name or a value that does not parse.
+//   ... --fine-rejector-batch   (with --fine-rejector; not with --track or --track-loop)
+// PoseEstimator::setFineRejectorBatch(true): --candidates (and --segment, --frame) with the SAC-IA coarse stage check all clusters
+// in one ope_final_pose_batch_rejectors call, the list applied inside the batched ICP kernel.  Exit status 2 without
+// --fine-rejector.  Without the flag every mode prints what it printed before.
 //
 //   ... --recognise <train_dir>   (with --candidates, --candidates-loop, --segment or --frame)
 // Before the pose stage, ope::ObjectDetection::getObjectNames over every cluster in one call against the table under <train_dir>
@@ -171,6 +175,7 @@ static int track_main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--fine-rejector") && i + 1 < argc) fine_rejectors.push_back(argv[++i]);
     else if (!std::strcmp(argv[i], "--coarse-batch")) { std::fprintf(stderr, "--coarse-batch does not go with --track or --track-loop\n"); return 2; }
     else if (!std::strcmp(argv[i], "--correspondences-batch")) { std::fprintf(stderr, "--correspondences-batch does not go with --track or --track-loop\n"); return 2; }
+    else if (!std::strcmp(argv[i], "--fine-rejector-batch")) { std::fprintf(stderr, "--fine-rejector-batch does not go with --track or --track-loop\n"); return 2; }
     else if (!std::strcmp(argv[i], "--time")) timed = true;
     else if (!frames.empty()) frames.back().push_back(argv[i]);
     else { std::fprintf(stderr, "unexpected argument %s\n", argv[i]); return 2; }
@@ -326,6 +331,7 @@ int main(int argc, char **argv) {
   bool coarse_batch = false;   // --coarse-batch
   bool correspondences_batch = false;   // --correspondences-batch
   std::vector<const char *> fine_rejectors;   // --fine-rejector, in the order given
+  bool fine_rejector_batch = false;           // --fine-rejector-batch
   float limits[6] = {-FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX, -FLT_MAX, FLT_MAX};
   for (int i = 1; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
@@ -333,6 +339,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--coarse-batch")) coarse_batch = true;
     else if (!std::strcmp(argv[i], "--correspondences-batch")) correspondences_batch = true;
     else if (!std::strcmp(argv[i], "--fine-rejector") && i + 1 < argc) fine_rejectors.push_back(argv[++i]);
+    else if (!std::strcmp(argv[i], "--fine-rejector-batch")) fine_rejector_batch = true;
     else if (!std::strcmp(argv[i], "--recognise") && i + 1 < argc) recognise = argv[++i];
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--candidates")) candidates = 1;
@@ -349,6 +356,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "--correspondences-batch goes with --coarse correspondences\n");
     return 2;
   }
+  if (fine_rejector_batch && fine_rejectors.empty()) { std::fprintf(stderr, "--fine-rejector-batch goes with --fine-rejector\n"); return 2; }
   if (except_plane && !frame) { std::fprintf(stderr, "--except-plane goes with --frame\n"); return 2; }
   if (region_grow && (!frame || except_plane)) { std::fprintf(stderr, "--region-grow goes with --frame and without --except-plane\n"); return 2; }
   if (region_grow_rgb && (!frame || except_plane || region_grow)) {
@@ -367,6 +375,7 @@ int main(int argc, char **argv) {
   poseEstimator.setCoarseBatch(coarse_batch);
   poseEstimator.setCorrespondencesBatch(correspondences_batch);
   poseEstimator.setUseSelfOccludedRejector(self_occluded);
+  poseEstimator.setFineRejectorBatch(fine_rejector_batch);
   for (const char *v : fine_rejectors)
     if (!parse_fine_rejector(v, poseEstimator)) return 2;
   auto print_frame = [&](size_t k, const pcl::Matrix4f &pose, double fitnessScore, double alignedStrength) {

@@ -53,12 +53,17 @@ class PoseEstimator {
   void setSacIaSeed(uint64_t seed) { sacia_seed_ = seed; }
   void setUseSelfOccludedRejector(bool on) { use_self_occluded_ = on; }
   // The rejectors estimateFinePose's list keeps commented out (:250-292, 3.1 median distance, 3.2 one to one, 3.5 var trimmed), in
-  // the order added, behind the surface-normal rejector.  They run inside the single-cluster estimateFinePose; the candidate batch
-  // and the tracked frame have no such stage (ope.h: the batched and tracked entry points refuse a list), so with rejectors set
-  // estimateFinalPoseCandidates and ope::ObjectTracker run the reference's loop, one estimateFinalPose at a time.
+  // the order added, behind the surface-normal rejector.  They run inside the single-cluster estimateFinePose.  With rejectors set
+  // estimateFinalPoseCandidates and ope::ObjectTracker run the reference's loop, one estimateFinalPose at a time, unless
+  // setFineRejectorBatch(true) sends the candidates through ope_final_pose_batch_rejectors (below); the tracked frame takes no list.
   void addFineRejector(const compat::registration::CorrespondenceRejector::Ptr &r) { if (r) fine_rejectors_.push_back(r); }
   void clearFineRejectors() { fine_rejectors_.clear(); }
   bool hasFineRejectors() const { return !fine_rejectors_.empty(); }
+  // estimateFinalPoseCandidates with fine rejectors: all clusters in one ope_final_pose_batch_rejectors call (the list applied inside
+  // the batched ICP kernel) instead of one estimateFinalPose at a time.  Off by default; needs COARSE_SAC_IA and every fine
+  // rejector being one of the three global ones (median distance, one to one, var trimmed), else the loop runs as without it.
+  void setFineRejectorBatch(bool on) { fine_rejector_batch_ = on; }
+  bool fineRejectorBatch() const { return fine_rejector_batch_; }
   // diagnostics of the last estimateFinalPose call
   Matrix4f lastCoarsePose() const { return last_coarse_; }
   Matrix4f lastFinePose() const { return last_fine_; }
@@ -215,7 +220,18 @@ class PoseEstimator {
     std::vector<ope_final_batch_result> res(clusters.size());
     int32_t sel = -1;
     // (ope_final_pose_batch's coarse stage is SAC-IA; the prerejective batch is opt-in: setCoarseBatch)
-    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() && fine_rejectors_.empty() &&
+    // (with fine rejectors the batch is opt-in too, SAC-IA only, and every rejector must be a global one: setFineRejectorBatch)
+    std::vector<ope_global_rejector> glist;
+    bool list_ok = fine_rejectors_.empty();
+    if (!list_ok && fine_rejector_batch_ && coarse_method_ == COARSE_SAC_IA && fine_rejectors_.size() <= (size_t)OPE_GREJ_MAX) {
+      list_ok = true;
+      for (const auto &r : fine_rejectors_) {
+        ope_global_rejector g;
+        if (r->global(g)) glist.push_back(g);
+        else list_ok = false;
+      }
+    }
+    bool batched = fitnessScoreFine > 0.0001 && !clusters.empty() && list_ok &&
                    (coarse_method_ == COARSE_SAC_IA || (coarse_method_ == COARSE_PREREJECTIVE && coarse_batch_) ||
                     (coarse_method_ == COARSE_CORRESPONDENCES && correspondences_batch_));
     if (batched) {
@@ -247,6 +263,9 @@ class PoseEstimator {
         q.inlier_threshold = 0.08;
         batched = ctx && model->h &&
                   ope_final_pose_batch_correspondences(ctx, model->h, hs.size(), hs.data(), &p, &q, nullptr, res.data(), &sel) == OPE_OK;
+      } else if (!glist.empty()) {
+        batched = ctx && model->h &&
+                  ope_final_pose_batch_rejectors(ctx, model->h, hs.size(), hs.data(), &p, glist.data(), glist.size(), nullptr, res.data(), &sel) == OPE_OK;
       } else {
         batched = ctx && model->h && ope_final_pose_batch(ctx, model->h, hs.size(), hs.data(), &p, nullptr, res.data(), &sel) == OPE_OK;
       }
@@ -451,7 +470,7 @@ class PoseEstimator {
   uint64_t sacia_seed_ = 1;
   CoarseMethod coarse_method_ = COARSE_SAC_IA;
   int coarse_calls_ = 0;
-  bool coarse_batch_ = false, correspondences_batch_ = false;
+  bool coarse_batch_ = false, correspondences_batch_ = false, fine_rejector_batch_ = false;
   bool use_self_occluded_ = false;
   std::vector<compat::registration::CorrespondenceRejector::Ptr> fine_rejectors_;   // addFineRejector, in the order added
   Matrix4f last_coarse_ = Matrix4f::Identity(), last_fine_ = Matrix4f::Identity(), last_rigid_ = Matrix4f::Identity();

@@ -741,6 +741,16 @@ ABI = [
     ("ope_mls_upsample_last_stats", C.c_int, [_vp, C.POINTER(MlsUpsampleStats)]),
 ]
 
+# every symbol include/ope_batch_rejectors.h declares (the header ope.h includes for the batched entry points that take a list of
+# global rejectors): bound by lib() like ABI
+ABI_BATCH_REJECTORS = [
+    ("ope_icp_run_batch_rejectors", C.c_int, [_vp, C.c_size_t, C.POINTER(_vp), C.POINTER(_vp), _fp, C.POINTER(IcpParams),
+                                               C.POINTER(GlobalRejector), C.c_size_t, C.c_double, C.POINTER(IcpBatchResult),
+                                               C.POINTER(GlobalRejectorStats), _ip, _fp]),
+    ("ope_final_pose_batch_rejectors", C.c_int, [_vp, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(FinalParams), C.POINTER(GlobalRejector),
+                                                  C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(FinalBatchResult), _ip]),
+]
+
 _lib = None
 
 
@@ -757,7 +767,7 @@ def lib() -> C.CDLL:
         except Exception:  # pragma: no cover - torch is optional for pure C-ABI use
             pass
         L = C.CDLL(LIB_PATH)
-        for name, res, args in ABI:
+        for name, res, args in ABI + ABI_BATCH_REJECTORS:
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -1010,6 +1020,11 @@ def _gate_out(g: "TrackGateResult", cent, n: int) -> GateOut:
                    np.array([c.count for c in cent[:n]], np.int32), np.array([c.distance for c in cent[:n]], np.float32))
 
 
+def _copy_struct(s):
+    """An element of a ctypes array as a structure of its own (the element itself is a view of the array's memory)."""
+    return type(s).from_buffer_copy(s)
+
+
 def _final_out(o) -> FinalOut:
     c = o.coarse
     co = CoarseOut(from_colmajor(np.frombuffer(c.T, np.float32)), c.best_error, c.best_iteration, c.n_src_keys, c.n_tgt_keys, c.status)
@@ -1212,6 +1227,12 @@ class Context:
     def icp_batch(self, srcs, indexes, params: IcpParams | None = None, guesses=None, fitness_max_range: float | None = None) -> list:
         """ope_icp_run_batch: problem i registers srcs[i] to indexes[i] (guesses[i] a (4,4) or None), all in one launch.
         One IcpBatchOut per problem; fitness / fitness_n are None without fitness_max_range."""
+        n, head, rng, out = self._icp_batch_args(srcs, indexes, params, guesses, fitness_max_range)
+        self._chk(lib().ope_icp_run_batch(self.h, n, *head, rng, out))
+        return self._icp_batch_out(out, n, fitness_max_range)
+
+    def _icp_batch_args(self, srcs, indexes, params, guesses, fitness_max_range):
+        """The arguments the batched ICP entries share: n, (sources, targets, guesses, params), the fitness range, the result array."""
         n = len(srcs)
         if len(indexes) != n:
             raise ValueError("one index per source cloud")
@@ -1225,7 +1246,10 @@ class Context:
             g = np.concatenate([colmajor(np.eye(4) if x is None else x) for x in guesses]) if n else np.zeros(16, np.float32)
         out = (IcpBatchResult * max(n, 1))()
         rng = -1.0 if fitness_max_range is None else float(fitness_max_range)
-        self._chk(lib().ope_icp_run_batch(self.h, n, hs, ht, _p(g, _fp), C.byref(p), rng, out))
+        return n, (hs, ht, _p(g, _fp), C.byref(p)), rng, out
+
+    @staticmethod
+    def _icp_batch_out(out, n, fitness_max_range):
         res = []
         for i in range(n):
             o = out[i]
@@ -1234,6 +1258,30 @@ class Context:
                                    r.n_corr, r.align_strength, o.fitness if fitness_max_range is not None else None,
                                    o.fitness_n if fitness_max_range is not None else None))
         return res
+
+    def icp_batch_rejectors(self, srcs, indexes, rejectors, params: IcpParams | None = None, guesses=None,
+                            fitness_max_range: float | None = None, pairs: bool = False):
+        """ope_icp_run_batch_rejectors: icp_batch with the global rejectors `rejectors` (GlobalRejector structures, applied in order)
+        inside every problem's workgroup.  Returns (results, stats, pairs): one IcpBatchOut per problem; stats[i][k] = rejector k
+        of problem i as the last iteration that searched applied it (launches 0); pairs (None unless asked for) = per problem
+        (index_match, distance), addressed by ORIGINAL source index: the surviving pair's original target index and distance
+        field, or -1 and 0.  An empty list without pairs is icp_batch; with pairs it runs the staged kernel with an empty list."""
+        n, head, rng, out = self._icp_batch_args(srcs, indexes, params, guesses, fitness_max_range)
+        rejectors = list(rejectors or [])
+        k = len(rejectors)
+        arr = (GlobalRejector * max(k, 1))(*rejectors)
+        st = (GlobalRejectorStats * max(n * k, 1))()
+        sizes = [s.n for s in srcs]
+        total = int(sum(sizes))
+        im = np.full(max(total, 1), -1, np.int32) if pairs else None
+        dist = np.zeros(max(total, 1), np.float32) if pairs else None
+        self._chk(lib().ope_icp_run_batch_rejectors(self.h, n, *head, arr, k, rng, out, st, _p(im, _ip), _p(dist, _fp)))
+        stats = [[_copy_struct(st[i * k + j]) for j in range(k)] for i in range(n)]
+        pr = None
+        if pairs:
+            off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+            pr = [(im[off[i]:off[i + 1]].copy(), dist[off[i]:off[i + 1]].copy()) for i in range(n)]
+        return self._icp_batch_out(out, n, fitness_max_range), stats, pr
 
     def coarse_pose_batch(self, model: "Cloud", clusters, params: CoarseParams | None = None, seeds=None) -> list:
         """ope_coarse_pose_batch: estimateCoarsePose(model, clusters[i]) for every cluster in one call; one CoarseOut each.
@@ -1250,19 +1298,27 @@ class Context:
         cloud, normals (m,3), FPFH (m,33)), in key-point order."""
         return tuple(self._read("ope_coarse_batch_features", (which,), [(np.int32, ()), (np.float32, (3,)), (np.float32, (33,))]))
 
-    def _final_pose_batch(self, entry: str, model, clusters, params, extra, seeds):
-        """One of the three ope_final_pose_batch* entries; extra: the coarse stage's own parameter struct, if it has one."""
+    def _final_pose_batch(self, entry: str, model, clusters, params, extra, seeds, lst=()):
+        """One of the ope_final_pose_batch* entries; extra: the coarse stage's own parameter struct, if it has one; lst: (array,
+        count) of the fine ICP's global rejectors, for the entry that takes them."""
         n, hc, sd = self._batch_args(clusters, seeds)
         p = params or default_final_params()
         out = (FinalBatchResult * max(n, 1))()
         sel = C.c_int32(-1)
-        self._chk(getattr(lib(), entry)(self.h, model.h, n, hc, C.byref(p), *[C.byref(q) for q in extra], sd, out, C.byref(sel)))
+        self._chk(getattr(lib(), entry)(self.h, model.h, n, hc, C.byref(p), *[C.byref(q) for q in extra], *lst, sd, out, C.byref(sel)))
         return [_final_out(o) for o in out[:n]], sel.value
 
     def final_pose_batch(self, model: "Cloud", clusters, params: FinalParams | None = None, seeds=None):
         """ope_final_pose_batch: estimateFinalPose(model, clusters[i]) of a fresh estimator for every cluster in one call.
         Returns ([FinalOut per cluster], selected): selected = the first accepted cluster, or -1."""
         return self._final_pose_batch("ope_final_pose_batch", model, clusters, params, (), seeds)
+
+    def final_pose_batch_rejectors(self, model: "Cloud", clusters, rejectors, params: FinalParams | None = None, seeds=None):
+        """ope_final_pose_batch_rejectors: final_pose_batch whose fine ICP applies the global rejectors `rejectors` (GlobalRejector
+        structures, in order) inside every cluster's workgroup; an empty list is final_pose_batch."""
+        rejectors = list(rejectors or [])
+        arr = (GlobalRejector * max(len(rejectors), 1))(*rejectors)
+        return self._final_pose_batch("ope_final_pose_batch_rejectors", model, clusters, params, (), seeds, (arr, len(rejectors)))
 
     def _batch_args(self, clusters, seeds):
         n = len(clusters)

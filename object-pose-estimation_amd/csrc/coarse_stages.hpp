@@ -122,9 +122,11 @@ struct FinePrep {
 };
 int final_batch_check(ope_ctx *ctx, size_t n, const ope_cloud *const *clusters, const ope_final_params &p);
 // everything of ope_final_pose_batch after its coarse stage (final_fine_prepare, icp_batch_core, the kept inputs, the results):
-// coarse[i] / seed_used[i] are what out[i].coarse / .seed report
+// coarse[i] / seed_used[i] are what out[i].coarse / .seed report; list (n_list > 0): the global rejectors of the fine ICP
+// (ope_final_pose_batch_rejectors)
 int final_batch_finish(ope_ctx *ctx, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_final_params &p,
-                       const ope_coarse_batch_result *coarse, const uint64_t *seed_used, ope_final_batch_result *out, int32_t *selected);
+                       const ope_coarse_batch_result *coarse, const uint64_t *seed_used, ope_final_batch_result *out, int32_t *selected,
+                       const ope_global_rejector *list = nullptr, size_t n_list = 0);
 int final_fine_prepare(ope_ctx *ctx, CallTmp &tmp, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                        const ope_final_params &p, const ope_coarse_batch_result *coarse, FinePrep &out);
 

@@ -440,11 +440,38 @@ int ope_final_pose_batch(ope_ctx *ctx, const ope_cloud *model, size_t n, const o
   return final_batch_finish(ctx, who, model, n, clusters, p, coarse.data(), seed_used.data(), out, selected);
 }
 
+int ope_final_pose_batch_rejectors(ope_ctx *ctx, const ope_cloud *model, size_t n, const ope_cloud *const *clusters, const ope_final_params *params,
+                                   const ope_global_rejector *list, size_t n_list, const uint64_t *seeds, ope_final_batch_result *out,
+                                   int32_t *selected) {
+  static const char *who = "ope_final_pose_batch_rejectors: ";
+  if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_final_pose_batch_rejectors: bad argument");
+  if (n_list == 0) return ope_final_pose_batch(ctx, model, n, clusters, params, seeds, out, selected);   // no list: that call
+  if (selected) *selected = -1;
+  ctx->final_off.clear();
+  ope_final_params p;
+  ope_final_default_params(&p);
+  if (params) p = *params;
+  { const int rc = icp_batch_check_list(ctx, "ope_final_pose_batch_rejectors", p.icp, list, n_list); if (rc != OPE_OK) return rc; }
+  if (n == 0) return OPE_OK;
+  if (!model || !clusters || !out) return set_err(ctx, OPE_EINVAL, std::string(who) + "bad argument");
+  if (n > 65535) return set_err(ctx, OPE_EINVAL, std::string(who) + "more than 65535 clusters (one grid row each)");
+  { const int rc = final_batch_check(ctx, n, clusters, p); if (rc != OPE_OK) return rc; }
+
+  // ---- 0. the coarse stage of ope_final_pose_batch
+  std::vector<ope_coarse_batch_result> coarse(n);
+  std::vector<uint64_t> seed_used(n, 0);
+  {
+    const int rc = coarse_pose_batch_impl(ctx, model, n, clusters, &p.coarse, seeds, seeds == nullptr, coarse.data(), seed_used.data());
+    if (rc != OPE_OK) return rc;
+  }
+  return final_batch_finish(ctx, who, model, n, clusters, p, coarse.data(), seed_used.data(), out, selected, list, n_list);
+}
+
 }  // extern "C"
 
 int ope::final_batch_finish(ope_ctx *ctx, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                             const ope_final_params &p, const ope_coarse_batch_result *coarse, const uint64_t *seed_used,
-                            ope_final_batch_result *out, int32_t *selected) {
+                            ope_final_batch_result *out, int32_t *selected, const ope_global_rejector *list, size_t n_list) {
   OPE_HIP(ctx, hipSetDevice(ctx->device));
   TraceRange r_all(ctx, "final_batch");
   const size_t nseg = 2 * n;
@@ -492,7 +519,8 @@ int ope::final_batch_finish(ope_ctx *ctx, const char *who, const ope_cloud *mode
       tgt_p[a] = &x;
     }
     TraceRange r(ctx, "final_icp");
-    const int rc = icp_batch_core(ctx, np, src_p.data(), tgt_p.data(), nullptr, p.icp, p.fitness_max_range, icp_out.data());
+    const BatchStageReq req{list, n_list, nullptr, nullptr, nullptr};
+    const int rc = icp_batch_core(ctx, np, src_p.data(), tgt_p.data(), nullptr, p.icp, p.fitness_max_range, icp_out.data(), n_list > 0 ? &req : nullptr);
     if (rc != OPE_OK) return rc;
   }
 

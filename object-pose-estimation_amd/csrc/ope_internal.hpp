@@ -648,8 +648,18 @@ struct BvhBatchTree {
 hipError_t build_bvh_batch_device(ope_ctx *ctx, const BvhBatchTree *d_trees, size_t n_trees, int max_depth);
 // icp_batch.hip: the parameter checks of ope_icp_run_batch, and its run once every problem has been checked
 int icp_batch_check_params(ope_ctx *ctx, const ope_icp_params &p);
+// a staged run (ope_icp_run_batch_rejectors): the list applied inside every problem's workgroup, and what the call reports of it
+struct BatchStageReq {
+  const ope_global_rejector *list;
+  size_t n_list;
+  ope_global_rejector_stats *stats;   // n x n_list, problem-major, or null
+  int32_t *index_match;               // sum of src[i]->n entries, or null
+  float *distance;                    // likewise
+};
+// what a batched entry point refuses of a list handed to it, and of the run's parameters under one
+int icp_batch_check_list(ope_ctx *ctx, const std::string &who, const ope_icp_params &p, const ope_global_rejector *list, size_t n_list);
 int icp_batch_core(ope_ctx *ctx, size_t n, const ope_cloud *const *src, const ope_index *const *tgt, const float *guesses,
-                   const ope_icp_params &p, double fitness_max_range, ope_icp_batch_result *out);
+                   const ope_icp_params &p, double fitness_max_range, ope_icp_batch_result *out, const BatchStageReq *stage = nullptr);
 // api.hip: the device state a run starts from, as ope_icp_begin fills it (thresholds per quirk Q1, the target index's pivot,
 // prev_mse, the inverse of the guess, the skip-certificate trigger) — one fill for ope_icp_begin and every problem of
 // ope_icp_run_batch.  guess: column-major, null = identity.  cert_run: the run may keep skip certificates; cluttered: it starts on
