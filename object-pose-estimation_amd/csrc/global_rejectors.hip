@@ -30,6 +30,8 @@
 #include <rocprim/rocprim.hpp>
 
 #include "bvh_traverse.hpp"
+#include "icp_pair.hpp"     // the moved query of the survivor sums
+#include "grej_rules.hpp"   // every rule of the three rejectors; here: their launches and reductions
 
 namespace ope {
 
@@ -39,8 +41,7 @@ constexpr int kGrejVtBlocks = 256;              // var trimmed: blocks of the he
 static_assert(kGrejVtBlocks == kGrejBlock, "the partials of the var-trimmed launches are reduced by one block, one lane each");
 
 struct GrejSlot {   // one per rejector of the list
-  unsigned long long n_in, n_out;
-  double threshold, ratio;
+  GrejStat stat;                    // (first: grej_read_stats copies the head of the slot)
   uint32_t hist[4][256];            // median distance: digit histograms, most significant digit first
   double vt_head[kGrejVtBlocks];    // var trimmed: partial head sums
   double vt_best[kGrejVtBlocks];    // ... the smallest FRMS of each block
@@ -57,8 +58,6 @@ struct GrejWork {
   double *d_partials = nullptr;                                  // [kNumSums][kAccMaxBlocks]
   GrejSlot *d_slots = nullptr;                                   // OPE_GREJ_MAX
 };
-
-__device__ __forceinline__ double grej_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // inclusive scan over the block's 256 lanes; s_scan[255] holds the total until the caller's next barrier
 __device__ __forceinline__ uint32_t grej_scan256(uint32_t v, uint32_t *s_scan) {
@@ -82,10 +81,12 @@ __device__ __forceinline__ void grej_median_select(const GrejSlot *slot, int upt
     const uint32_t incl = grej_scan256(h, s_scan);
     const uint32_t total = s_scan[kGrejBlock - 1];
     __syncthreads();
-    if (q == 0 && threadIdx.x == 0) { s_sel[2] = total; s_sel[1] = total / 2u; }   // position m / 2
+    if (q == 0 && threadIdx.x == 0) { s_sel[2] = total; s_sel[1] = grej_median_rank(total); }
     __syncthreads();
     const uint32_t rank = s_sel[1], excl = incl - h;
     __syncthreads();
+    // grej_digit_pick (grej_rules.hpp) for one digit per lane, on its own text: through the function grej_median_hist_kernel's
+    // registers are numbered differently
     if (h > 0u && excl <= rank && rank < incl) { s_sel[0] = (s_sel[0] << 8) | threadIdx.x; s_sel[1] = rank - excl; }   // one lane at most
     __syncthreads();
   }
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(kGrejBlock) void grej_init_kernel(const IcpState *_
     for (int s = 0; s < n_slots; ++s) {
 #pragma unroll
       for (int p = 0; p < 4; ++p) slots[s].hist[p][threadIdx.x] = 0u;
-      if (threadIdx.x == 0) { slots[s].n_in = 0ull; slots[s].n_out = 0ull; slots[s].threshold = grej_nan(); slots[s].ratio = grej_nan(); }
+      if (threadIdx.x == 0) slots[s].stat = grej_stat_none();
     }
   }
 }
@@ -122,14 +123,13 @@ __global__ __launch_bounds__(kGrejBlock) void grej_median_hist_kernel(const IcpS
   __shared__ uint32_t s_scan[kGrejBlock], s_hist[kGrejBlock], s_sel[3];
   grej_median_select(slot, pass, s_scan, s_sel);
   const uint32_t prefix = s_sel[0];
-  const int shift = 24 - 8 * pass;
   s_hist[threadIdx.x] = 0u;
   __syncthreads();
   const size_t stride = (size_t)gridDim.x * kGrejBlock;
   for (size_t i = (size_t)blockIdx.x * kGrejBlock + threadIdx.x; i < n; i += stride) {
     if (!keep[i]) continue;
-    const uint32_t key = __float_as_uint(d2[i]);
-    if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
+    uint32_t digit;
+    if (grej_median_digit(__float_as_uint(d2[i]), pass, prefix, digit)) atomicAdd(&s_hist[digit], 1u);
   }
   __syncthreads();
   if (s_hist[threadIdx.x] != 0u) atomicAdd(&slot->hist[pass][threadIdx.x], s_hist[threadIdx.x]);
@@ -141,28 +141,23 @@ __global__ __launch_bounds__(kGrejBlock) void grej_median_keep_kernel(const IcpS
   __shared__ uint32_t s_scan[kGrejBlock], s_sel[3];
   grej_median_select(slot, 4, s_scan, s_sel);
   const uint32_t m = s_sel[2];
-  const double median = (double)__uint_as_float(s_sel[0]);
-  const double thr = median * factor;
+  const GrejMedianRule rule(m, s_sel[0], factor);
   uint32_t kept = 0u;
   const size_t stride = (size_t)gridDim.x * kGrejBlock;
   for (size_t i = (size_t)blockIdx.x * kGrejBlock + threadIdx.x; i < n; i += stride) {
     if (!keep[i]) continue;
-    const bool k = m > 0u && (double)d2[i] <= thr;
+    const bool k = rule.keep(d2[i]);
     keep[i] = k ? 1 : 0;
     kept += k ? 1u : 0u;
   }
   const unsigned long long total = grej_block_count(kept, s_scan);
   if (threadIdx.x == 0) {
-    if (total) atomicAdd(&slot->n_out, total);
-    if (blockIdx.x == 0) { slot->n_in = (unsigned long long)m; slot->threshold = m > 0u ? median : grej_nan(); }
+    if (total) atomicAdd(&slot->stat.n_out, total);
+    if (blockIdx.x == 0) { slot->stat.n_in = (unsigned long long)m; slot->stat.threshold = rule.threshold(); }
   }
 }
 
 // ---- one to one
-__device__ __forceinline__ unsigned long long grej_word(float d, int32_t q) {
-  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(uint32_t)q;
-}
-
 template <bool KEEP_PASS>
 __global__ __launch_bounds__(kGrejBlock) void grej_one_to_one_kernel(const IcpState *__restrict__ st, uint32_t n, unsigned char *__restrict__ keep,
                                                                       const int32_t *__restrict__ match, const float *__restrict__ d2,
@@ -188,7 +183,7 @@ __global__ __launch_bounds__(kGrejBlock) void grej_one_to_one_kernel(const IcpSt
     }
   }
   const unsigned long long total = grej_block_count(cnt, s_scan);
-  if (threadIdx.x == 0 && total) atomicAdd(KEEP_PASS ? &slot->n_out : &slot->n_in, total);
+  if (threadIdx.x == 0 && total) atomicAdd(KEEP_PASS ? &slot->stat.n_out : &slot->stat.n_in, total);
 }
 
 // ---- var trimmed
@@ -204,7 +199,7 @@ __global__ __launch_bounds__(kGrejBlock) void grej_vt_keys_kernel(const IcpState
     cnt += k ? 1u : 0u;
   }
   const unsigned long long total = grej_block_count(cnt, s_scan);
-  if (threadIdx.x == 0 && total) atomicAdd(&slot->n_in, total);
+  if (threadIdx.x == 0 && total) atomicAdd(&slot->stat.n_in, total);
 }
 
 // fixed tree over the block's 256 values
@@ -227,27 +222,21 @@ __device__ __forceinline__ void grej_tree_argmin(double &v, uint32_t &j, double 
     if ((int)threadIdx.x < off) {
       const double v2 = s_d[threadIdx.x + off];
       const uint32_t j2 = s_j[threadIdx.x + off];
-      if (v2 < s_d[threadIdx.x] || (v2 == s_d[threadIdx.x] && j2 < s_j[threadIdx.x])) { s_d[threadIdx.x] = v2; s_j[threadIdx.x] = j2; }
+      if (grej_argmin_before(v2, j2, s_d[threadIdx.x], s_j[threadIdx.x])) { s_d[threadIdx.x] = v2; s_j[threadIdx.x] = j2; }
     }
     __syncthreads();
   }
   v = s_d[0]; j = s_j[0];
   __syncthreads();
 }
-__device__ __forceinline__ void grej_vt_range(const GrejSlot *slot, double min_ratio, double max_ratio, uint32_t &m, uint32_t &lo, uint32_t &hi) {
-  m = (uint32_t)slot->n_in;
-  lo = (uint32_t)floor(min_ratio * (double)m);
-  hi = (uint32_t)floor(max_ratio * (double)m);
-  if (hi > m) hi = m;
-  if (lo > m) lo = m;
-}
 
 __global__ __launch_bounds__(kGrejBlock) void grej_vt_head_kernel(const IcpState *__restrict__ st, const uint32_t *__restrict__ sorted, GrejSlot *slot,
                                                                    double min_ratio, double max_ratio) {
   if (st != nullptr && st->done) return;
   __shared__ double s_d[kGrejBlock];
-  uint32_t m, lo, hi;
-  grej_vt_range(slot, min_ratio, max_ratio, m, lo, hi);
+  const uint32_t m = (uint32_t)slot->stat.n_in;
+  uint32_t lo, hi;
+  grej_vt_range(m, min_ratio, max_ratio, lo, hi);
   double acc = 0.0;
   for (size_t j = (size_t)blockIdx.x * kGrejBlock + threadIdx.x; j < lo; j += (size_t)kGrejVtBlocks * kGrejBlock) acc += (double)__uint_as_float(sorted[j]);
   const double v = grej_tree_sum(acc, s_d);
@@ -259,16 +248,14 @@ __global__ __launch_bounds__(kGrejBlock) void grej_vt_frms_kernel(const IcpState
   if (st != nullptr && st->done) return;
   __shared__ double s_d[kGrejBlock];
   __shared__ uint32_t s_j[kGrejBlock];
-  uint32_t m, lo, hi;
-  grej_vt_range(slot, min_ratio, max_ratio, m, lo, hi);
+  const uint32_t m = (uint32_t)slot->stat.n_in;
+  uint32_t lo, hi;
+  grej_vt_range(m, min_ratio, max_ratio, lo, hi);
   const double L = grej_tree_sum(slot->vt_head[threadIdx.x], s_d);   // the same tree in every block: the same L
   double best = std::numeric_limits<double>::infinity();
   uint32_t best_j = 0xffffffffu;
   for (size_t j = (size_t)lo + (size_t)blockIdx.x * kGrejBlock + threadIdx.x; j < hi; j += (size_t)kGrejVtBlocks * kGrejBlock) {
-    const double id = (double)(j + 1);
-    const double r = id / (double)m;
-    const double inv = 1.0 / (r * r * r);
-    const double frms = inv * inv * (1.0 / id) * ((double)__uint_as_float(sorted[j]) + L);
+    const double frms = grej_vt_frms((uint32_t)j, m, sorted[j], L);
     if (frms < best) { best = frms; best_j = (uint32_t)j; }
   }
   grej_tree_argmin(best, best_j, s_d, s_j);
@@ -282,32 +269,25 @@ __global__ __launch_bounds__(kGrejBlock) void grej_vt_keep_kernel(const IcpState
   __shared__ double s_d[kGrejBlock];
   __shared__ uint32_t s_j[kGrejBlock];
   __shared__ uint32_t s_scan[kGrejBlock];
-  uint32_t m, lo, hi;
-  grej_vt_range(slot, min_ratio, max_ratio, m, lo, hi);
+  const uint32_t m = (uint32_t)slot->stat.n_in;
+  uint32_t lo, hi;
+  grej_vt_range(m, min_ratio, max_ratio, lo, hi);
   double best = slot->vt_best[threadIdx.x];
   uint32_t best_j = slot->vt_best_j[threadIdx.x];
   grej_tree_argmin(best, best_j, s_d, s_j);
-  const bool all = hi <= lo || best_j >= m;   // PCL: undefined; here every pair stays
-  float ratio = 1.0f;
-  double trimmed = grej_nan();
-  if (!all) {
-    ratio = __fdiv_rn((float)best_j, (float)m);
-    uint32_t idx = (uint32_t)(int)((double)m * (double)ratio);
-    if (idx >= m) idx = m - 1u;
-    trimmed = (double)__uint_as_float(sorted[idx]);
-  }
+  const GrejVtRule rule(m, lo, hi, best_j, sorted);
   uint32_t kept = 0u;
   const size_t stride = (size_t)gridDim.x * kGrejBlock;
   for (size_t i = (size_t)blockIdx.x * kGrejBlock + threadIdx.x; i < n; i += stride) {
     if (!keep[i]) continue;
-    const bool k = all || (double)d2[i] < trimmed;
+    const bool k = rule.all || (double)d2[i] < rule.trimmed;   // GrejVtRule::keep, on its own text: the call costs this kernel two SGPRs
     keep[i] = k ? 1 : 0;
     kept += k ? 1u : 0u;
   }
   const unsigned long long total = grej_block_count(kept, s_scan);
   if (threadIdx.x == 0) {
-    if (total) atomicAdd(&slot->n_out, total);
-    if (blockIdx.x == 0) { slot->threshold = trimmed; slot->ratio = (double)ratio; }
+    if (total) atomicAdd(&slot->stat.n_out, total);
+    if (blockIdx.x == 0) { slot->stat.threshold = rule.trimmed; slot->stat.ratio = (double)rule.ratio; }
   }
 }
 
@@ -337,8 +317,8 @@ __global__ __launch_bounds__(kGrejBlock) void grej_sums_kernel(CloudView src, Bv
     const int32_t mt = match[i];
     if (mt < 0) continue;
     if (!keep[i]) { match[i] = -1; continue; }
-    const float4 s = src.xyzw[i];
-    const float x = xform_row(F + 0, s.x, s.y, s.z), y = xform_row(F + 4, s.x, s.y, s.z), z = xform_row(F + 8, s.x, s.y, s.z);
+    float x, y, z;
+    pair_move_point((const float *)F, src.xyzw[i], x, y, z);
     const float4 t = tgt.pts[pos_of_orig[mt]];
     const double sx = (double)x - (double)psx, sy = (double)y - (double)psy, sz = (double)z - (double)psz;
     const double tx = (double)t.x - (double)psx, ty = (double)t.y - (double)psy, tz = (double)t.z - (double)psz;
@@ -517,14 +497,10 @@ int grej_sums(hipStream_t stream, GrejWork *w, const CloudView &src, const BvhVi
 const double *grej_partials(const GrejWork *w) { return w->d_partials; }
 
 static int grej_read_stats(ope_ctx *ctx, GrejWork *w, size_t which, int kind, ope_global_rejector_stats *out) {
-  struct { unsigned long long n_in, n_out; double threshold, ratio; } h;
-  OPE_HIP(ctx, hipMemcpyAsync(&h, w->d_slots + which, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  GrejStat h;
+  OPE_HIP(ctx, hipMemcpyAsync(&h, &w->d_slots[which].stat, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
   OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  out->n_in = (int64_t)h.n_in;
-  out->n_out = (int64_t)h.n_out;
-  out->threshold = h.threshold;
-  out->ratio = h.ratio;
-  out->launches = grej_launches(kind);
+  grej_stat_to_abi(h, grej_launches(kind), out);
   return OPE_OK;
 }
 

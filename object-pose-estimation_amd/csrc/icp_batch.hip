@@ -5,8 +5,8 @@
 // an update launch and, every check_every iterations, a host poll.  Here one workgroup owns one problem and runs its whole
 // loop: search -> rejectors -> sums -> update lane, then the next iteration, with no kernel boundary, no host round trip and
 // no communication between workgroups (no spin-wait, no co-residency requirement).  The update step is icp_update_lane
-// itself (icp_update.hpp), the same code ope_icp_run runs; the search, the rejectors and the terms of the sums follow
-// icp_accumulate_kernel operation for operation.  The sums of an iteration are added in a fixed order inside the workgroup
+// itself (icp_update.hpp), the same code ope_icp_run runs; the per-query rules of the search and the per-pair rejectors are those
+// of icp_pair.hpp, the terms of the sums those of icp_sums.hpp, as in icp_accumulate_kernel.  The sums of an iteration are added in a fixed order inside the workgroup
 // (the wave's reduce-scatter of icp_sums.hpp, one LDS row per wave, one ordered pass over the rows), so a problem's result depends on its own
 // inputs only: not on the run, the other problems of the batch or its position among them.
 // ope_icp_run_batch_rejectors runs the same body with a list of global rejectors between the search and the sums (the staged
@@ -18,6 +18,8 @@
 
 #include "icp_update.hpp"
 #include "icp_sums.hpp"   // add_query_sums: the terms and the wave's reduce-scatter, shared with icp_kernels.hip
+#include "icp_pair.hpp"   // the per-query rules, shared with icp_kernels.hip
+#include "grej_rules.hpp" // the rules of the global rejectors, shared with global_rejectors.hip
 
 namespace ope {
 
@@ -59,12 +61,11 @@ struct BatchStageProblem {   // offsets in 4-byte words into BatchStage::work
   size_t words_off;          // (even) the one-to-one words of a target too large for LDS
   size_t pair_off;           // first entry of this problem in the pair outputs (ORIGINAL source indices)
 };
-struct BatchStageStat { unsigned long long n_in, n_out; double threshold, ratio; };
 struct BatchStage {
   const BatchStageProblem *probs;
   uint32_t *work;
   const ope_global_rejector *list;
-  BatchStageStat *stats;   // n problems x OPE_GREJ_MAX
+  GrejStat *stats;   // n problems x OPE_GREJ_MAX
   int32_t *pair_match;     // or null
   float *pair_d2;          // or null
   int n_list;
@@ -77,11 +78,11 @@ struct BatchStageLds {
   float *d2;
   uint32_t *keys;
   unsigned long long *words;
-  BatchStageStat *stats;
+  GrejStat *stats;
   int32_t *pair_match;
   float *pair_d2;
   ope_global_rejector list[OPE_GREJ_MAX];
-  BatchStageStat stat[OPE_GREJ_MAX];   // as the last iteration that searched left them
+  GrejStat stat[OPE_GREJ_MAX];   // as the last iteration that searched left them
   double dred[2][kBatchRows];
   uint32_t jred[kBatchRows], cnt[kBatchRows], sel[4];
   int n_list, searched;
@@ -89,8 +90,6 @@ struct BatchStageLds {
 };
 typedef __attribute__((address_space(3))) BatchStageLds *lds_stage_ptr;
 typedef __attribute__((address_space(3))) uint32_t *lds_u32_ptr;
-
-__device__ __forceinline__ double stage_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // the sum of c over the workgroup (integers: any order gives it); s_cnt: one word per wave
 __device__ __forceinline__ uint32_t stage_count(uint32_t c, uint32_t *s_cnt) {
@@ -105,26 +104,24 @@ __device__ __forceinline__ uint32_t stage_count(uint32_t c, uint32_t *s_cnt) {
   return total;
 }
 
-// Median distance: position m / 2 of the alive pairs' fp32 bit patterns, exactly: four passes over 8-bit digits, most significant
-// first (grej_median_hist_kernel's), each histogram in LDS and scanned by wave 0.  s_sel = {prefix, rank within it, m}.
+// Median distance (grej_rules.hpp) over the alive pairs: each pass's histogram in LDS, scanned by wave 0.  s_sel = {prefix, rank within it, m}.
 __device__ __forceinline__ void stage_median(uint32_t *g_pos, const float *g_d2, uint32_t nv, double factor, uint32_t *hist, uint32_t *s_cnt,
-                                             uint32_t *s_sel, BatchStageStat *stat) {
+                                             uint32_t *s_sel, GrejStat *stat) {
   const uint32_t lane = threadIdx.x & 63u;
   if (threadIdx.x == 0) { s_sel[0] = 0u; s_sel[1] = 0u; s_sel[2] = 0u; }
   for (int pass = 0; pass < 4; ++pass) {
     if (threadIdx.x < 256) hist[threadIdx.x] = 0u;
     __syncthreads();
     const uint32_t prefix = s_sel[0];
-    const int shift = 24 - 8 * pass;
     for (uint32_t i = threadIdx.x; i < nv; i += kBatchBlock) {
       if (!(g_pos[i] & kStageAlive)) continue;
-      const uint32_t key = __float_as_uint(g_d2[i]);
-      if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+      uint32_t digit;
+      if (grej_median_digit(__float_as_uint(g_d2[i]), pass, prefix, digit)) atomicAdd(&hist[digit], 1u);
     }
     __syncthreads();
     if (threadIdx.x < 64) {   // lane l owns digits 4l .. 4l + 3
-      const uint32_t c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
-      const uint32_t tot = c0 + c1 + c2 + c3;
+      const uint32_t c[4] = {hist[4 * lane], hist[4 * lane + 1], hist[4 * lane + 2], hist[4 * lane + 3]};
+      const uint32_t tot = c[0] + c[1] + c[2] + c[3];
       uint32_t incl = tot;
 #pragma unroll
       for (int off = 1; off < 64; off <<= 1) {
@@ -132,12 +129,10 @@ __device__ __forceinline__ void stage_median(uint32_t *g_pos, const float *g_d2,
         if ((int)lane >= off) incl += v;
       }
       const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
-      const uint32_t rank = pass == 0 ? total / 2u : s_sel[1];   // position m / 2
-      const uint32_t excl = incl - tot;
-      if (tot > 0u && excl <= rank && rank < incl) {   // one lane at most
-        uint32_t r = rank - excl, d = 0u;
-        if (r >= c0) { r -= c0; d = 1u; if (r >= c1) { r -= c1; d = 2u; if (r >= c2) { r -= c2; d = 3u; } } }
-        s_sel[0] = (pass == 0 ? 0u : prefix << 8) | (4u * lane + d);
+      const uint32_t rank = pass == 0 ? grej_median_rank(total) : s_sel[1];
+      uint32_t d, r;
+      if (grej_digit_pick(c, incl, rank, d, r)) {   // one lane at most
+        s_sel[0] = (prefix << 8) | (4u * lane + d);
         s_sel[1] = r;
       }
       if (pass == 0 && lane == 0u) s_sel[2] = total;
@@ -145,25 +140,23 @@ __device__ __forceinline__ void stage_median(uint32_t *g_pos, const float *g_d2,
     __syncthreads();
   }
   const uint32_t m = s_sel[2];
-  const double median = (double)__uint_as_float(s_sel[0]);
-  const double thr = median * factor;
+  const GrejMedianRule rule(m, s_sel[0], factor);
   uint32_t kept = 0u;
   for (uint32_t i = threadIdx.x; i < nv; i += kBatchBlock) {
     const uint32_t p = g_pos[i];
     if (!(p & kStageAlive)) continue;
-    const bool k = m > 0u && (double)g_d2[i] <= thr;
+    const bool k = rule.keep(g_d2[i]);
     if (!k) g_pos[i] = p & ~kStageAlive;
     kept += k ? 1u : 0u;
   }
   const uint32_t n_out = stage_count(kept, s_cnt);
-  if (threadIdx.x == 0) { stat->n_in = m; stat->n_out = n_out; stat->threshold = m > 0u ? median : stage_nan(); stat->ratio = stage_nan(); }
+  if (threadIdx.x == 0) { stat->n_in = m; stat->n_out = n_out; stat->threshold = rule.threshold(); stat->ratio = grej_nan(); }
 }
 
-// One to one: per target point the smallest (distance bits << 32 | ORIGINAL query index) of its alive pairs, by 64-bit integer
-// minima (grej_one_to_one_kernel's word; the target point is named by its position in the index, which is one to one with its
-// original index); a pair stays iff the word is its own.
+// One to one (grej_rules.hpp: grej_word of the distance field and the ORIGINAL query index) over the alive pairs; the target point
+// is named by its position in the index, which is one to one with its original index.
 __device__ __forceinline__ void stage_one_to_one(uint32_t *g_pos, const float *g_d2, const float4 *__restrict__ src_xyzw, uint32_t nv, uint32_t n_tgt,
-                                                 unsigned long long *words, uint32_t *s_cnt, BatchStageStat *stat) {
+                                                 unsigned long long *words, uint32_t *s_cnt, GrejStat *stat) {
   for (uint32_t t = threadIdx.x; t < n_tgt; t += kBatchBlock) words[t] = ~0ull;
   __syncthreads();
   uint32_t cnt = 0u;
@@ -171,7 +164,7 @@ __device__ __forceinline__ void stage_one_to_one(uint32_t *g_pos, const float *g
     const uint32_t p = g_pos[i];
     if (!(p & kStageAlive)) continue;
     ++cnt;
-    const unsigned long long word = ((unsigned long long)__float_as_uint(g_d2[i]) << 32) | (unsigned long long)__float_as_uint(src_xyzw[i].w);
+    const unsigned long long word = grej_word(g_d2[i], __float_as_int(src_xyzw[i].w));
     atomicMin(words + (p & ~kStageAlive), word);
   }
   __syncthreads();
@@ -179,14 +172,14 @@ __device__ __forceinline__ void stage_one_to_one(uint32_t *g_pos, const float *g
   for (uint32_t i = threadIdx.x; i < nv; i += kBatchBlock) {
     const uint32_t p = g_pos[i];
     if (!(p & kStageAlive)) continue;
-    const unsigned long long word = ((unsigned long long)__float_as_uint(g_d2[i]) << 32) | (unsigned long long)__float_as_uint(src_xyzw[i].w);
+    const unsigned long long word = grej_word(g_d2[i], __float_as_int(src_xyzw[i].w));
     const bool k = words[p & ~kStageAlive] == word;
     if (!k) g_pos[i] = p & ~kStageAlive;
     kept += k ? 1u : 0u;
   }
   const uint32_t n_in = stage_count(cnt, s_cnt);
   const uint32_t n_out = stage_count(kept, s_cnt);
-  if (threadIdx.x == 0) { stat->n_in = n_in; stat->n_out = n_out; stat->threshold = stage_nan(); stat->ratio = stage_nan(); }
+  if (threadIdx.x == 0) { stat->n_in = n_in; stat->n_out = n_out; stat->threshold = grej_nan(); stat->ratio = grej_nan(); }
 }
 
 // keys[0 .. n) ascending, n a power of two >= 2: the bitonic network, one compare-exchange per thread and step
@@ -203,12 +196,11 @@ __device__ __forceinline__ void stage_bitonic(uint32_t *keys, uint32_t n) {
   }
 }
 
-// Var trimmed: the alive pairs' keys ascending (the others and the padding keyed to the top), then lo, hi, the head sum L, FRMS_j and
-// its first minimum, ratio in fp32, idx and the strict keep: grej_vt_range / grej_vt_frms_kernel / grej_vt_keep_kernel's
-// expressions, all fp64.  n2: the power of two the keys are padded to.
+// Var trimmed (grej_rules.hpp): the alive pairs' keys ascending (the others and the padding keyed to the top), then the head sum L,
+// FRMS_j and its first minimum over the lanes, then the waves, and the keep.  n2: the power of two the keys are padded to.
 __device__ __forceinline__ void stage_var_trimmed(uint32_t *g_pos, const float *g_d2, uint32_t nv, uint32_t n2, double min_ratio, double max_ratio,
                                                   uint32_t *keys, uint32_t *s_cnt, double (*s_dred)[kBatchRows], uint32_t *s_jred,
-                                                  BatchStageStat *stat) {
+                                                  GrejStat *stat) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint32_t cnt = 0u;
   for (uint32_t t = threadIdx.x; t < n2; t += kBatchBlock) {
@@ -218,10 +210,8 @@ __device__ __forceinline__ void stage_var_trimmed(uint32_t *g_pos, const float *
   }
   const uint32_t m = stage_count(cnt, s_cnt);   // (its barriers also publish the keys)
   stage_bitonic(keys, n2);
-  uint32_t lo = (uint32_t)floor(min_ratio * (double)m);
-  uint32_t hi = (uint32_t)floor(max_ratio * (double)m);
-  if (hi > m) hi = m;
-  if (lo > m) lo = m;
+  uint32_t lo, hi;
+  grej_vt_range(m, min_ratio, max_ratio, lo, hi);
   double acc = 0.0;
   for (uint32_t j = threadIdx.x; j < lo; j += kBatchBlock) acc += (double)__uint_as_float(keys[j]);
   acc = wave_sum(acc);
@@ -233,18 +223,15 @@ __device__ __forceinline__ void stage_var_trimmed(uint32_t *g_pos, const float *
 #pragma unroll
   for (int w = 0; w < kBatchRows; ++w) L += s_dred[0][w];
   for (uint32_t j = lo + threadIdx.x; j < hi; j += kBatchBlock) {
-    const double id = (double)(j + 1u);
-    const double r = id / (double)m;
-    const double inv = 1.0 / (r * r * r);
-    const double frms = inv * inv * (1.0 / id) * ((double)__uint_as_float(keys[j]) + L);
+    const double frms = grej_vt_frms(j, m, keys[j], L);
     if (frms < best) { best = frms; best_j = j; }
   }
-  // (smallest value, on equal values the smallest position): over the lanes, then over the waves
+  // grej_argmin_before over the lanes, then over the waves
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
     const double v2 = __shfl_xor(best, off, 64);
     const uint32_t j2 = (uint32_t)__shfl_xor((int)best_j, off, 64);
-    if (v2 < best || (v2 == best && j2 < best_j)) { best = v2; best_j = j2; }
+    if (grej_argmin_before(v2, j2, best, best_j)) { best = v2; best_j = j2; }
   }
   if (lane == 0u) { s_dred[1][wave] = best; s_jred[wave] = best_j; }
   __syncthreads();
@@ -254,27 +241,19 @@ __device__ __forceinline__ void stage_var_trimmed(uint32_t *g_pos, const float *
   for (int w = 1; w < kBatchRows; ++w) {
     const double v2 = s_dred[1][w];
     const uint32_t j2 = s_jred[w];
-    if (v2 < best || (v2 == best && j2 < best_j)) { best = v2; best_j = j2; }
+    if (grej_argmin_before(v2, j2, best, best_j)) { best = v2; best_j = j2; }
   }
-  const bool all = hi <= lo || best_j >= m;   // PCL: undefined; here every pair stays
-  float ratio = 1.0f;
-  double trimmed = stage_nan();
-  if (!all) {
-    ratio = __fdiv_rn((float)best_j, (float)m);
-    uint32_t idx = (uint32_t)(int)((double)m * (double)ratio);
-    if (idx >= m) idx = m - 1u;
-    trimmed = (double)__uint_as_float(keys[idx]);
-  }
+  const GrejVtRule rule(m, lo, hi, best_j, keys);
   uint32_t kept = 0u;
   for (uint32_t i = threadIdx.x; i < nv; i += kBatchBlock) {
     const uint32_t p = g_pos[i];
     if (!(p & kStageAlive)) continue;
-    const bool k = all || (double)g_d2[i] < trimmed;
+    const bool k = rule.keep(g_d2[i]);
     if (!k) g_pos[i] = p & ~kStageAlive;
     kept += k ? 1u : 0u;
   }
   const uint32_t n_out = stage_count(kept, s_cnt);   // (its barriers also end the reads of the keys)
-  if (threadIdx.x == 0) { stat->n_in = m; stat->n_out = n_out; stat->threshold = trimmed; stat->ratio = (double)ratio; }
+  if (threadIdx.x == 0) { stat->n_in = m; stat->n_out = n_out; stat->threshold = rule.trimmed; stat->ratio = (double)rule.ratio; }
 }
 
 // The list over the pairs the search pass stored, by the whole workgroup.  Out of line: the kernel's walks keep the registers they
@@ -325,12 +304,7 @@ __device__ __forceinline__ void icp_batch_body(const BatchProblem *__restrict__ 
   state_to_lds(&s_st, st);
 
   const double max_d2 = st->max_d2;
-  float best0 = INFINITY;   // the accumulate kernel's start bound with a finite max_corr_dist
-  if (max_d2 < 3.0e38) {
-    float f = (float)max_d2;
-    if ((double)f < max_d2) f = nextafterf(f, INFINITY);
-    best0 = nextafterf(f, INFINITY);
-  }
+  const float best0 = pair_start_bound(max_d2);
   const bool rej_sn = NRM && st->use_surface_normal_rej;
   const bool rej_so = NRM && st->use_self_occluded_rej;
   const bool p2p = NRM && st->estimator == OPE_EST_POINT_TO_PLANE_LLS;
@@ -343,7 +317,7 @@ __device__ __forceinline__ void icp_batch_body(const BatchProblem *__restrict__ 
   double *row = s_rows[wave];
   if constexpr (STAGED) {
     if ((int)threadIdx.x < OPE_GREJ_MAX) {
-      s_stg.stat[threadIdx.x] = BatchStageStat{0ull, 0ull, stage_nan(), stage_nan()};
+      s_stg.stat[threadIdx.x] = grej_stat_none();
       if ((int)threadIdx.x < stg.n_list) s_stg.list[threadIdx.x] = stg.list[threadIdx.x];
     }
     if (threadIdx.x == 0) {
@@ -373,22 +347,9 @@ __device__ __forceinline__ void icp_batch_body(const BatchProblem *__restrict__ 
     for (uint32_t base = wave * 64u; base < n_valid; base += kBatchBlock) {
       const uint32_t i = base + lane_id;
       const bool active = i < n_valid;
-      lds_cfloat_ptr cst = (lds_cfloat_ptr)s_const;
-      asm volatile("" : "+v"(cst));
-      float F[12];
-#pragma unroll
-      for (int k = 0; k < 12; ++k) F[k] = cst[k];
-      const float4 s = pr.src.xyzw[active ? i : base];
-      const float x = xform_row(F + 0, s.x, s.y, s.z);
-      const float y = xform_row(F + 4, s.x, s.y, s.z);
-      const float z = xform_row(F + 8, s.x, s.y, s.z);
-      float nx = 0.f, ny = 0.f, nz = 0.f;
-      if (NRM && pr.src.nrm != nullptr) {
-        const float4 n4 = pr.src.nrm[active ? i : base];
-        nx = rot_row(F + 0, n4.x, n4.y, n4.z);
-        ny = rot_row(F + 4, n4.x, n4.y, n4.z);
-        nz = rot_row(F + 8, n4.x, n4.y, n4.z);
-      }
+      const lds_cfloat_ptr cst = pair_consts(s_const);
+      const MovedQuery q = pair_moved_query<NRM>(cst, pr.src, active ? i : base);
+      const float x = q.x, y = q.y, z = q.z, nx = q.nx, ny = q.ny, nz = q.nz;
       // start at the leaf that held this query's nearest neighbour one iteration ago (0 = none yet): a start leaf never
       // changes what a walk finds
       const uint32_t h = active ? hint[i] : 0u;
@@ -408,36 +369,23 @@ __device__ __forceinline__ void icp_batch_body(const BatchProblem *__restrict__ 
         v.init(active);
         if (active) bvh_traverse(pr.tgt, x, y, z, v, stk, kBatchBlock, h);
         if (active) hint[i] = v.leaf;
-        // among the k nearest, the one with the smallest squared distance to the line (s, n)
-        // (…normal_shooting_weighted.hpp:115-135; cross product in double)
+        // among the k nearest, the one with the smallest squared distance to the line (s, n), the first on ties
+        // (…normal_shooting_weighted.hpp:115-135).  The same loop as icp_accumulate_kernel's: as one function it made every
+        // normal-shooting instantiation spill more scalar registers
         double min_dist = 1.79769313486231570815e308;
         d2 = INFINITY;
         pos = 0;
 #pragma unroll
         for (int j = 0; j < KREG; ++j) {
           if (j < v.count && j < kk) {
-            const float4 p = pr.tgt.pts[v.p[j]];
-            const double vx = (double)__fsub_rn(p.x, x), vy = (double)__fsub_rn(p.y, y), vz = (double)__fsub_rn(p.z, z);
-            const double cx = (double)ny * vz - (double)nz * vy;
-            const double cy = (double)nz * vx - (double)nx * vz;
-            const double cz = (double)nx * vy - (double)ny * vx;
-            const double dist = cx * cx + cy * cy + cz * cz;
+            const double dist = pair_line_dist2(pr.tgt.pts[v.p[j]], x, y, z, nx, ny, nz);
             if (dist < min_dist) { min_dist = dist; d2 = v.d[j]; pos = v.p[j]; }
           }
         }
-        // quirk Q2: squared line distance against the UNSQUARED max distance (:136)
-        ok = active && v.count > 0 && !(min_dist > max_dist_unsq);
+        ok = active && pair_ns_ok(v.count, min_dist, max_dist_unsq);
       }
-      if (NRM && ok && rej_sn) {
-        const float4 tn = pr.tgt.nrm[pos];
-        const float score = __fadd_rn(__fadd_rn(__fmul_rn(nx, tn.x), __fmul_rn(ny, tn.y)), __fmul_rn(nz, tn.z));
-        ok = (double)score > thr_sn;
-      }
-      if (NRM && ok && rej_so) {
-        const double sl = sqrt((double)__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
-        const double score = (double)nx * (-(double)x / sl) + (double)ny * (-(double)y / sl) + (double)nz * (-(double)z / sl);
-        ok = score > thr_so;
-      }
+      if (NRM && ok && rej_sn) ok = pair_passes_surface_normal(nx, ny, nz, pr.tgt.nrm[pos], thr_sn);
+      if (NRM && ok && rej_so) ok = pair_passes_self_occlusion(x, y, z, nx, ny, nz, thr_so);
       if constexpr (STAGED) {
         lds_stage_ptr sl = (lds_stage_ptr)&s_stg;
         asm volatile("" : "+v"(sl));
@@ -457,15 +405,8 @@ __device__ __forceinline__ void icp_batch_body(const BatchProblem *__restrict__ 
       for (uint32_t base = wave * 64u; base < n_valid; base += kBatchBlock) {
         const uint32_t i = base + lane_id;
         const bool active = i < n_valid;
-        lds_cfloat_ptr cst = (lds_cfloat_ptr)s_const;
-        asm volatile("" : "+v"(cst));
-        float F[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) F[k] = cst[k];
-        const float4 s = pr.src.xyzw[active ? i : base];
-        const float x = xform_row(F + 0, s.x, s.y, s.z);
-        const float y = xform_row(F + 4, s.x, s.y, s.z);
-        const float z = xform_row(F + 8, s.x, s.y, s.z);
+        const MovedQuery q = pair_moved_query<false>(pair_consts(s_const), pr.src, active ? i : base);
+        const float x = q.x, y = q.y, z = q.z;
         const uint32_t p = active ? g_pos[i] : 0u;
         const bool ok = (p & kStageAlive) != 0u;
         const float d2 = active ? g_d2[i] : INFINITY;
@@ -484,7 +425,8 @@ __device__ __forceinline__ void icp_batch_body(const BatchProblem *__restrict__ 
     __syncthreads();
   }
 
-  // getFitnessScore(max_range) of the final transform (fitness_kernel's semantics): 1-NN from +inf, d2 <= max_range counted
+  // getFitnessScore(max_range) of the final transform (fitness_kernel's semantics): 1-NN from +inf, d2 <= max_range counted.
+  // (The query is moved on this pass's own text: through pair_moved_query the large normal-shooting instantiations spill more.)
   double fsum = 0.0, fcnt = 0.0;
   if (do_fit) {
     if (threadIdx.x < 12) s_const[threadIdx.x] = s_st.Ff[threadIdx.x];
@@ -592,13 +534,18 @@ static void launch_icp_batch(hipStream_t stream, int n, int mode, bool nrm, int 
 
 using namespace ope;
 
-// the arguments and problems of ope_icp_run_batch (and of ope_icp_run_batch_rejectors, `who`): params into p, every refusal
-static int icp_batch_check_call(ope_ctx *ctx, const std::string &who, size_t n, const ope_cloud *const *src, const ope_index *const *tgt,
-                                const ope_icp_params *params, const void *out, ope_icp_params &p) {
-  if (!src || !tgt || !out) return set_err(ctx, OPE_EINVAL, who + ": bad argument");
-  if (n > (size_t)INT_MAX) return set_err(ctx, OPE_EINVAL, who + ": too many problems");
+// the caller's parameters, or the defaults
+static ope_icp_params icp_batch_params(const ope_icp_params *params) {
+  ope_icp_params p;
   ope_icp_default_params(&p);
   if (params) p = *params;
+  return p;
+}
+// the arguments and problems of ope_icp_run_batch (and of ope_icp_run_batch_rejectors, `who`) under p: every refusal
+static int icp_batch_check_call(ope_ctx *ctx, const std::string &who, size_t n, const ope_cloud *const *src, const ope_index *const *tgt,
+                                const ope_icp_params &p, const void *out) {
+  if (!src || !tgt || !out) return set_err(ctx, OPE_EINVAL, who + ": bad argument");
+  if (n > (size_t)INT_MAX) return set_err(ctx, OPE_EINVAL, who + ": too many problems");
   { const int rc = icp_batch_check_params(ctx, p); if (rc != OPE_OK) return rc; }
   const bool need_src_nrm = p.corr_mode == OPE_CORR_NORMAL_SHOOTING || p.use_surface_normal_rej || p.use_self_occluded_rej;
   const bool p2p = p.estimator == OPE_EST_POINT_TO_PLANE_LLS;
@@ -621,8 +568,8 @@ extern "C" int ope_icp_run_batch(ope_ctx *ctx, size_t n, const ope_cloud *const 
                                  const ope_icp_params *params, double fitness_max_range, ope_icp_batch_result *out) {
   if (!ctx) return set_err(ctx, OPE_EINVAL, "ope_icp_run_batch: bad argument");
   if (n == 0) return OPE_OK;
-  ope_icp_params p;
-  { const int rc = icp_batch_check_call(ctx, "ope_icp_run_batch", n, src, tgt, params, out, p); if (rc != OPE_OK) return rc; }
+  const ope_icp_params p = icp_batch_params(params);
+  { const int rc = icp_batch_check_call(ctx, "ope_icp_run_batch", n, src, tgt, p, out); if (rc != OPE_OK) return rc; }
   return icp_batch_core(ctx, n, src, tgt, guesses, p, fitness_max_range, out);
 }
 
@@ -648,16 +595,10 @@ extern "C" int ope_icp_run_batch_rejectors(ope_ctx *ctx, size_t n, const ope_clo
   if (!ctx) return set_err(ctx, OPE_EINVAL, std::string(who) + ": bad argument");
   if (n_list == 0 && index_match == nullptr && distance == nullptr)   // nothing asked of the stage: ope_icp_run_batch
     return ope_icp_run_batch(ctx, n, src, tgt, guesses, params, fitness_max_range, out);
-  {
-    ope_icp_params q;
-    ope_icp_default_params(&q);
-    if (params) q = *params;
-    const int rc = icp_batch_check_list(ctx, who, q, list, n_list);
-    if (rc != OPE_OK) return rc;
-  }
+  const ope_icp_params p = icp_batch_params(params);
+  { const int rc = icp_batch_check_list(ctx, who, p, list, n_list); if (rc != OPE_OK) return rc; }
   if (n == 0) return OPE_OK;
-  ope_icp_params p;
-  { const int rc = icp_batch_check_call(ctx, who, n, src, tgt, params, out, p); if (rc != OPE_OK) return rc; }
+  { const int rc = icp_batch_check_call(ctx, who, n, src, tgt, p, out); if (rc != OPE_OK) return rc; }
   const BatchStageReq req{list, n_list, stats, index_match, distance};
   return icp_batch_core(ctx, n, src, tgt, guesses, p, fitness_max_range, out, &req);
 }
@@ -732,7 +673,7 @@ int ope::icp_batch_core(ope_ctx *ctx, size_t n, const ope_cloud *const *src, con
       n_pairs += src[i]->n;
     }
   }
-  const size_t b_sstat = stage ? up8(sizeof(BatchStageStat) * OPE_GREJ_MAX * n) : 0, b_work = stage ? up8(4 * std::max<size_t>(n_work, 1)) : 0;
+  const size_t b_sstat = stage ? up8(sizeof(GrejStat) * OPE_GREJ_MAX * n) : 0, b_work = stage ? up8(4 * std::max<size_t>(n_work, 1)) : 0;
   const size_t b_pair = want_pairs ? up8(4 * std::max<size_t>(n_pairs, 1)) : 0;
   unsigned char *blk = nullptr;
   OPE_HIP(ctx, tmp_malloc(ctx->stream, (void **)&blk, host.size() + b_out + b_hint + b_sstat + b_work + 2 * b_pair));
@@ -748,7 +689,7 @@ int ope::icp_batch_core(ope_ctx *ctx, size_t n, const ope_cloud *const *src, con
     unsigned char *s0 = blk + host.size() + b_out + b_hint;
     stg.probs = reinterpret_cast<const BatchStageProblem *>(blk + b_prob + b_state);
     stg.list = reinterpret_cast<const ope_global_rejector *>(blk + b_prob + b_state + b_sprob);
-    stg.stats = reinterpret_cast<BatchStageStat *>(s0);
+    stg.stats = reinterpret_cast<GrejStat *>(s0);
     stg.work = reinterpret_cast<uint32_t *>(s0 + b_sstat);
     stg.n_list = (int)stage->n_list;
     if (want_pairs) {   // "no pair" everywhere: the kernel writes the survivors
@@ -764,24 +705,16 @@ int ope::icp_batch_core(ope_ctx *ctx, size_t n, const ope_cloud *const *src, con
                    do_fit ? fitness_max_range : 0.0, do_fit ? 1 : 0, d_out, stage ? &stg : nullptr);
   OPE_HIP(ctx, hipGetLastError());
   std::vector<BatchOut> ho(n);
-  std::vector<BatchStageStat> hstat(stage && stage->stats ? OPE_GREJ_MAX * n : 0);
+  std::vector<GrejStat> hstat(stage && stage->stats ? OPE_GREJ_MAX * n : 0);
   OPE_HIP(ctx, hipMemcpyAsync(ho.data(), d_out, sizeof(BatchOut) * n, hipMemcpyDeviceToHost, ctx->stream));
-  if (!hstat.empty()) OPE_HIP(ctx, hipMemcpyAsync(hstat.data(), stg.stats, sizeof(BatchStageStat) * hstat.size(), hipMemcpyDeviceToHost, ctx->stream));
+  if (!hstat.empty()) OPE_HIP(ctx, hipMemcpyAsync(hstat.data(), stg.stats, sizeof(GrejStat) * hstat.size(), hipMemcpyDeviceToHost, ctx->stream));
   if (want_pairs && n_pairs > 0) {
     if (stage->index_match) OPE_HIP(ctx, hipMemcpyAsync(stage->index_match, stg.pair_match, 4 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
     if (stage->distance) OPE_HIP(ctx, hipMemcpyAsync(stage->distance, stg.pair_d2, 4 * n_pairs, hipMemcpyDeviceToHost, ctx->stream));
   }
   OPE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (size_t i = 0; i < hstat.size() / OPE_GREJ_MAX; ++i)
-    for (size_t k = 0; k < stage->n_list; ++k) {
-      const BatchStageStat &h = hstat[i * OPE_GREJ_MAX + k];
-      ope_global_rejector_stats &s = stage->stats[i * stage->n_list + k];
-      s.n_in = (int64_t)h.n_in;
-      s.n_out = (int64_t)h.n_out;
-      s.threshold = h.threshold;
-      s.ratio = h.ratio;
-      s.launches = 0;   // the stage dispatches nothing of its own
-    }
+  for (size_t i = 0; i < hstat.size() / OPE_GREJ_MAX; ++i)   // (launches = 0: the stage dispatches nothing of its own)
+    for (size_t k = 0; k < stage->n_list; ++k) grej_stat_to_abi(hstat[i * OPE_GREJ_MAX + k], 0, &stage->stats[i * stage->n_list + k]);
   for (size_t i = 0; i < n; ++i) {
     const BatchOut &o = ho[i];
     ope_icp_batch_result &r = out[i];

@@ -22,6 +22,7 @@
 #include "lm_solve.hpp"
 #include "icp_update.hpp"
 #include "icp_sums.hpp"   // add_query_sums: one query per lane -> the wave's 17 (44) sums in LDS
+#include "icp_pair.hpp"   // the per-query rules: start bound, moved query, normal-shooting pick, per-pair rejectors
 
 namespace ope {
 
@@ -194,7 +195,7 @@ __device__ __forceinline__ bool cert_worth_building(float d2_prev, float cert_k,
 // MODE 0: 1-NN correspondences.  MODE 2: normal shooting over the k nearest, list in KREG >= k registers (every k <= 32:
 // KREG = k rounded up to a multiple of four, plus 10, the class default of vPCL
 // correspondence_estimation_normal_shooting_weighted.h:117; the reference uses 20, poseestimator.cpp:246,
-// regmeshpcd.cpp:144), walk started at last iteration's leaf.  (MODE 1, the LDS list of round 1, is no longer dispatched.)
+// regmeshpcd.cpp:144), walk started at last iteration's leaf.  (MODE 1, the LDS list of round 1, is gone.)
 // NRM: source/target normals present (rejectors and/or normal shooting).
 // RECIP: reciprocal correspondences (vPCL impl/correspondence_estimation_mod.hpp:216-303): keep (i, j) only
 // if the nearest SOURCE point of target point j is i again.  The reference searches a kd-tree rebuilt
@@ -229,18 +230,13 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
   __shared__ double s_red[BLOCK / 64][kNumSumsMax];
   __shared__ float s_stk[kMaxDepth + 2][BLOCK];  // pending-sibling bounds of the traversal (rows 1 .. D) and, above them, the deferred walk's leaf queue
   float *stk = &s_stk[0][threadIdx.x];
-  extern __shared__ unsigned char s_dyn[];  // MODE 1: k-NN lists
+  static_assert(MODE == 0 || MODE == 2, "1-NN, or normal shooting from a register list");
 
   const double max_d2 = st->max_d2;
   // With a finite setMaxCorrespondenceDistance the 1-NN search only has to see points that can survive the
   // threshold test (correspondence_estimation_mod.hpp:171 rejects d2 > max_d2 afterwards anyway): start from the
   // smallest float strictly above every admissible d2 instead of +inf, so far-off queries end at the first boxes.
-  float best0 = INFINITY;
-  if (max_d2 < 3.0e38) {
-    float f = (float)max_d2;
-    if ((double)f < max_d2) f = nextafterf(f, INFINITY);
-    best0 = nextafterf(f, INFINITY);
-  }
+  const float best0 = pair_start_bound(max_d2);
   if (threadIdx.x < 12) { if (chain == nullptr) s_const[threadIdx.x] = st->Ff[threadIdx.x]; }   // (overlapped: fetched by acc_launch_begin)
   else if (threadIdx.x < 15) s_const[threadIdx.x] = (float)st->pivot[threadIdx.x - 12];
   else if (threadIdx.x == 15) s_const[15] = best0;
@@ -352,8 +348,8 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
     const bool owner = active && (!oct || (lane_id & (GW - 1u)) == 0u);  // the one lane that reports a query
     // (the pointer keeps its LDS address space: through a generic pointer these became flat_loads, which take the
     // vector-memory path and wait on both counters)
-    lds_cfloat_ptr cst = (lds_cfloat_ptr)s_const;
-    asm volatile("" : "+v"(cst));   // keep the constants' loads here, inside the chunk loop
+    lds_cfloat_ptr cst = pair_consts(s_const);   // keep the constants' loads here, inside the chunk loop
+    // pair_moved_query (icp_pair.hpp), on its own text: through the function the certifying instantiations' VGPR counts move
     float F[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) F[k] = cst[k];
@@ -463,7 +459,7 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
         ok = ok && r.pos != kNoPos && !((double)r.best > max_d2) &&
              __float_as_int(srcix.pts[r.pos].w) == __float_as_int(s.w);
       }
-    } else if constexpr (MODE == 2) {
+    } else {
       // register list of KREG >= k entries: the k nearest are the first k of the KREG nearest
       constexpr int K = KREG;
       KnnRegVisitor<K> v;
@@ -501,61 +497,24 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
         hint[i] = v.leaf;
         if (knn_rk != nullptr) knn_rk[i] = v.count >= K ? v.d[K - 1] : INFINITY;
       }
-      // among the k nearest, the one with the smallest squared distance to the line (s, n)
-      // (…normal_shooting_weighted.hpp:115-135; cross product in double)
+      // among the k nearest, the one with the smallest squared distance to the line (s, n), the first on ties
+      // (…normal_shooting_weighted.hpp:115-135).  The same loop as icp_batch_body's: as one function it made every
+      // normal-shooting instantiation spill more scalar registers
       double min_dist = 1.79769313486231570815e308;
       d2 = INFINITY;
       pos = 0;
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         if (j < v.count && j < kk) {
-          const float4 p = tgt.pts[v.p[j]];
-          const double vx = (double)__fsub_rn(p.x, x), vy = (double)__fsub_rn(p.y, y), vz = (double)__fsub_rn(p.z, z);
-          const double cx = (double)ny * vz - (double)nz * vy;
-          const double cy = (double)nz * vx - (double)nx * vz;
-          const double cz = (double)nx * vy - (double)ny * vx;
-          const double dist = cx * cx + cy * cy + cz * cz;
+          const double dist = pair_line_dist2(tgt.pts[v.p[j]], x, y, z, nx, ny, nz);
           if (dist < min_dist) { min_dist = dist; d2 = v.d[j]; pos = v.p[j]; }
         }
       }
-      // quirk Q2: squared line distance against the UNSQUARED max distance (:136)
-      ok = active && v.count > 0 && !(min_dist > max_dist_unsq);
-      match = v.count > 0 ? (store_pos ? (int)pos : __float_as_int(tgt.pts[pos].w)) : -1;
-    } else {
-      if (dealt) ticket_v = deal_pop(deal_set, stripe, lane_id);
-      float *ld = reinterpret_cast<float *>(s_dyn) + threadIdx.x;
-      uint32_t *lp = reinterpret_cast<uint32_t *>(s_dyn + sizeof(float) * BLOCK * kKnnMaxK) + threadIdx.x;
-      KnnVisitor v{ld, lp, BLOCK, kk, 0, active ? INFINITY : -INFINITY};
-      bvh_traverse(tgt, x, y, z, v, stk, BLOCK);
-      // among the k nearest, the one with the smallest squared distance to the line (s, n)
-      // (…normal_shooting_weighted.hpp:115-135; cross product in double)
-      double min_dist = 1.79769313486231570815e308;
-      int min_j = 0;
-      for (int j = 0; j < v.count; ++j) {
-        const float4 p = tgt.pts[lp[j * BLOCK]];
-        const double vx = (double)__fsub_rn(p.x, x), vy = (double)__fsub_rn(p.y, y), vz = (double)__fsub_rn(p.z, z);
-        const double cx = (double)ny * vz - (double)nz * vy;
-        const double cy = (double)nz * vx - (double)nx * vz;
-        const double cz = (double)nx * vy - (double)ny * vx;
-        const double dist = cx * cx + cy * cy + cz * cz;
-        if (dist < min_dist) { min_dist = dist; min_j = j; }
-      }
-      // quirk Q2: squared line distance against the UNSQUARED max distance (:136)
-      ok = active && v.count > 0 && !(min_dist > max_dist_unsq);
-      d2 = v.count > 0 ? ld[min_j * BLOCK] : INFINITY;
-      pos = v.count > 0 ? lp[min_j * BLOCK] : 0;
+      ok = active && pair_ns_ok(v.count, min_dist, max_dist_unsq);
       match = v.count > 0 ? (store_pos ? (int)pos : __float_as_int(tgt.pts[pos].w)) : -1;
     }
-    if (NRM && ok && rej_sn) {
-      const float4 tn = tgt.nrm[pos];
-      const float score = __fadd_rn(__fadd_rn(__fmul_rn(nx, tn.x), __fmul_rn(ny, tn.y)), __fmul_rn(nz, tn.z));
-      ok = (double)score > thr_sn;
-    }
-    if (NRM && ok && rej_so) {
-      const double sl = sqrt((double)__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
-      const double score = (double)nx * (-(double)x / sl) + (double)ny * (-(double)y / sl) + (double)nz * (-(double)z / sl);
-      ok = score > thr_so;
-    }
+    if (NRM && ok && rej_sn) ok = pair_passes_surface_normal(nx, ny, nz, tgt.nrm[pos], thr_sn);
+    if (NRM && ok && rej_so) ok = pair_passes_self_occlusion(x, y, z, nx, ny, nz, thr_so);
     ok = ok && owner;
     if (owner) {
       __builtin_nontemporal_store(ok ? match : -1, corr_match + i);   // streamed out: nothing re-reads them in this launch
@@ -573,18 +532,8 @@ __global__ __launch_bounds__(MODE == 0 ? kAccBlock : kKnnBlock, (MODE == 0 && !R
     }
   }
 
-  // wave slots -> block partial, fixed order
   __syncthreads();
-  if (threadIdx.x < (p2p ? kNumSumsMax : kNumSums)) {
-    double v = 0.0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) v += s_red[w][threadIdx.x];
-    // One-GPU runs keep one row per block and reduce the rows in a fixed tree (bit-reproducible for a launch
-    // geometry).  Sharded runs add straight into the 17 (44) sums that the all-reduce takes next: one launch and one
-    // kernel boundary less per iteration, at the price of an addition order that varies from run to run (1e-16).
-    if (S_atomic != nullptr) unsafeAtomicAdd(S_atomic + threadIdx.x, v);
-    else partials[threadIdx.x * kAccMaxBlocks + blockIdx.x] = v;
-  }
+  pair_write_block_partial<BLOCK / 64>(s_red, p2p ? kNumSumsMax : kNumSums, S_atomic, partials);
   if (CERT && threadIdx.x == 64 && s_ncert != 0u)
     atomicAdd(reinterpret_cast<unsigned long long *>(work_counter + 40), (unsigned long long)s_ncert);   // ope_icp_certificate_stats
   acc_launch_end(chain);
@@ -686,12 +635,7 @@ __global__ __launch_bounds__(kAccBlock, CERT ? 4 : kAccWavesPerSimd) void icp_ac
   __shared__ float s_stk[kMaxDepth + 1][BLOCK];
   float *stk = &s_stk[0][threadIdx.x];
   const double max_d2 = st->max_d2;
-  float best0 = INFINITY;
-  if (max_d2 < 3.0e38) {
-    float f = (float)max_d2;
-    if ((double)f < max_d2) f = nextafterf(f, INFINITY);
-    best0 = nextafterf(f, INFINITY);
-  }
+  const float best0 = pair_start_bound(max_d2);
   if (threadIdx.x < 12) { if (chain == nullptr) s_const[threadIdx.x] = st->Ff[threadIdx.x]; }   // (overlapped: fetched by acc_launch_begin)
   else if (threadIdx.x < 15) s_const[threadIdx.x] = (float)st->pivot[threadIdx.x - 12];
   else if (threadIdx.x == 15) s_const[15] = best0;
@@ -754,22 +698,9 @@ __global__ __launch_bounds__(kAccBlock, CERT ? 4 : kAccWavesPerSimd) void icp_ac
     const bool active = qpos < pos_end;
     const uint32_t i = active ? qorder[qpos] : qorder[pos0];
     const bool owner = active && (!oct || (lane_id & 7u) == 0u);
-    lds_cfloat_ptr cst = (lds_cfloat_ptr)s_const;
-    asm volatile("" : "+v"(cst));
-    float F[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) F[k] = cst[k];
-    const float4 s = src.xyzw[i];
-    const float x = xform_row(F + 0, s.x, s.y, s.z);
-    const float y = xform_row(F + 4, s.x, s.y, s.z);
-    const float z = xform_row(F + 8, s.x, s.y, s.z);
-    float nx = 0.f, ny = 0.f, nz = 0.f;
-    if (NRM && src.nrm != nullptr) {
-      const float4 n4 = src.nrm[i];
-      nx = rot_row(F + 0, n4.x, n4.y, n4.z);
-      ny = rot_row(F + 4, n4.x, n4.y, n4.z);
-      nz = rot_row(F + 8, n4.x, n4.y, n4.z);
-    }
+    const lds_cfloat_ptr cst = pair_consts(s_const);
+    const MovedQuery q = pair_moved_query<NRM>(cst, src, i);
+    const float x = q.x, y = q.y, z = q.z, nx = q.nx, ny = q.ny, nz = q.nz;
     // ---- skip certificates (CERT instantiation; see icp_accumulate_kernel): a query answered by its certificate neither scans
     // nor walks; one that has to search and whose certificate would be worth it builds one (a 6-nearest TREE walk: candidates are
     // positions in the tree's point order, which this kernel reads its matches from as well in that case); everybody else — `live`
@@ -839,16 +770,8 @@ __global__ __launch_bounds__(kAccBlock, CERT ? 4 : kAccWavesPerSimd) void icp_ac
       if (cls != (tree_part ? 0 : 1) || !chunk_order) qclass[i] = cls;   // the partition's expectation is written at the plan step
     }
     if (CERT && owner && build && found) ghint[i] = grid.gpos_of_bvhpos[c_pos] + 1u;   // (the scans of later launches start from it)
-    if (NRM && ok && rej_sn) {
-      const float4 tn = by_cert ? tgt.nrm[c_pos] : grid.gnrm[gpos];
-      const float score = __fadd_rn(__fadd_rn(__fmul_rn(nx, tn.x), __fmul_rn(ny, tn.y)), __fmul_rn(nz, tn.z));
-      ok = (double)score > thr_sn;
-    }
-    if (NRM && ok && rej_so) {
-      const double sl = sqrt((double)__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
-      const double score = (double)nx * (-(double)x / sl) + (double)ny * (-(double)y / sl) + (double)nz * (-(double)z / sl);
-      ok = score > thr_so;
-    }
+    if (NRM && ok && rej_sn) ok = pair_passes_surface_normal(nx, ny, nz, by_cert ? tgt.nrm[c_pos] : grid.gnrm[gpos], thr_sn);
+    if (NRM && ok && rej_so) ok = pair_passes_self_occlusion(x, y, z, nx, ny, nz, thr_so);
     ok = ok && owner;
     if (owner) {
       __builtin_nontemporal_store(ok ? match : -1, corr_match + i);
@@ -860,13 +783,7 @@ __global__ __launch_bounds__(kAccBlock, CERT ? 4 : kAccWavesPerSimd) void icp_ac
     if (lane_id == 0 && !oct) chunk_cost[tree_part ? chunk : n_tc + gchunk] = (uint32_t)((__builtin_amdgcn_s_memtime() - t_begin) >> 4);
   }
   __syncthreads();
-  if (threadIdx.x < (p2p ? kNumSumsMax : kNumSums)) {
-    double v = 0.0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) v += s_red[w][threadIdx.x];
-    if (S_atomic != nullptr) unsafeAtomicAdd(S_atomic + threadIdx.x, v);
-    else partials[threadIdx.x * kAccMaxBlocks + blockIdx.x] = v;
-  }
+  pair_write_block_partial<BLOCK / 64>(s_red, p2p ? kNumSumsMax : kNumSums, S_atomic, partials);
   if (CERT && threadIdx.x == 64 && s_ncert != 0u) atomicAdd(reinterpret_cast<unsigned long long *>(cert_stats), (unsigned long long)s_ncert);
   acc_launch_end(chain);
 }
@@ -1133,6 +1050,8 @@ __global__ __launch_bounds__(64) void icp_fixed_pairs_kernel(const IcpState *__r
   const double px = st->pivot[0], py = st->pivot[1], pz = st->pivot[2];
   for (uint32_t f = threadIdx.x; f < n; f += 64u) {
     const float4 s = fix[4 * f], sn = fix[4 * f + 1], t = fix[4 * f + 2], tn = fix[4 * f + 3];
+    // (the moved point and normal of pair_moved_query and pair_passes_surface_normal, on their own text here: with them as calls
+    // as well this kernel's SGPR count moves)
     const float x = xform_row(st->Ff + 0, s.x, s.y, s.z), y = xform_row(st->Ff + 4, s.x, s.y, s.z), z = xform_row(st->Ff + 8, s.x, s.y, s.z);
     const float nx = rot_row(st->Ff + 0, sn.x, sn.y, sn.z), ny = rot_row(st->Ff + 4, sn.x, sn.y, sn.z), nz = rot_row(st->Ff + 8, sn.x, sn.y, sn.z);
     const float vx = __fsub_rn(t.x, x), vy = __fsub_rn(t.y, y), vz = __fsub_rn(t.z, z);
@@ -1141,15 +1060,11 @@ __global__ __launch_bounds__(64) void icp_fixed_pairs_kernel(const IcpState *__r
       const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(vx, vx), __fmul_rn(vy, vy)), __fmul_rn(vz, vz));
       dist = (float)((double)d2 * 1e10);
     } else {
-      const double cx = (double)ny * vz - (double)nz * vy, cy = (double)nz * vx - (double)nx * vz, cz = (double)nx * vy - (double)ny * vx;
-      dist = (float)(cx * cx + cy * cy + cz * cz);
+      dist = (float)pair_line_dist2(t, x, y, z, nx, ny, nz);
     }
     bool pass_sn = true, pass_so = true;
     if (rej_sn) pass_sn = (double)__fadd_rn(__fadd_rn(__fmul_rn(nx, tn.x), __fmul_rn(ny, tn.y)), __fmul_rn(nz, tn.z)) > thr_sn;
-    if (rej_so) {
-      const double sl = sqrt((double)__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
-      pass_so = (double)nx * (-(double)x / sl) + (double)ny * (-(double)y / sl) + (double)nz * (-(double)z / sl) > thr_so;
-    }
+    if (rej_so) pass_so = pair_passes_self_occlusion(x, y, z, nx, ny, nz, thr_so);
     const int listed = (!ns_mode && pass_sn && pass_so) ? 1 : 0;                            // listed by the estimation, through every rejector
     const int appended = ((rej_sn || rej_so) && (rej_sn ? pass_sn : pass_so)) ? 1 : 0;      // the first rejector alone, appended
     seen[f] = make_float2(dist, __int_as_float(listed | (appended << 1)));
@@ -1281,10 +1196,8 @@ __global__ __launch_bounds__(256) void fitness_kernel(CloudView q, BvhView tgt, 
   for (uint32_t base = blockIdx.x * 256 + (threadIdx.x & ~63u); base < q.n_valid; base += gridDim.x * 256) {
     const uint32_t i = base + lane_id;
     const bool active = i < q.n_valid;
-    const float4 s = q.xyzw[active ? i : base];
-    const float x = xform_row(F + 0, s.x, s.y, s.z);
-    const float y = xform_row(F + 4, s.x, s.y, s.z);
-    const float z = xform_row(F + 8, s.x, s.y, s.z);
+    float x, y, z;
+    pair_move_point((const float *)F, q.xyzw[active ? i : base], x, y, z);
     NearestVisitor v{active ? INFINITY : -INFINITY, kNoPos, 0};
     if (active) bvh_traverse(tgt, x, y, z, v, stk, 256, hint ? hint[i] : 0u);
     if (active && v.pos != kNoPos && (double)v.best <= max_range) { sum += (double)v.best; cnt += 1.0; }

@@ -853,6 +853,63 @@ def test_fixed_correspondences_with_a_rejector_are_counted_as_the_reference_coun
     assert frob(out.T, ref.T) < (5e-4 if ns_mode else 1e-4)
 
 
+def _fixed_self_occlusion_inputs():
+    """How the inputs stored in tests/golden/fixed_pairs_self_occlusion.npz were made (the test reads them from the file): one
+    chunk of 64 source points with random unit normals against 300 target points, eight given pairs."""
+    rng = np.random.default_rng(11)
+    tgt = synth.model_surface(300, 1)
+    src = (tgt[rng.choice(len(tgt), 64, replace=False)] + rng.normal(0.0, 2e-3, (64, 3))).astype(np.float32)
+    sn = rng.normal(size=(64, 3))
+    sn = (sn / np.linalg.norm(sn, axis=1, keepdims=True)).astype(np.float32)
+    tn = np.asarray(oracle.normals_knn(tgt, 8)[0], np.float32)
+    fq = np.arange(8, dtype=np.int32)
+    fm = rng.choice(len(tgt), 8, replace=False).astype(np.int32)
+    return dict(src=src, sn=sn, tgt=np.asarray(tgt, np.float32), tn=tn, fq=fq, fm=fm)
+
+
+def _fixed_self_occlusion_run(ctx, mode, inp):
+    """Two iterations over the given pairs under the self-occlusion rejector.  Returns everything the run reports, as arrays."""
+    ope = load_pkg()
+    kw = dict(max_iterations=2, transformation_epsilon=0.0, euclidean_fitness_epsilon=0.0, mse_threshold_absolute=-1.0,
+              deterministic_sums=1, use_self_occluded_rej=1, self_occluded_thr=0.0,
+              corr_mode=1 if mode == "normal_shooting" else 0, k_normal_shooting=10)
+    cs, ct = ctx.upload(inp["src"], normals=inp["sn"]), ctx.upload(inp["tgt"], normals=inp["tn"])
+    ix = ctx.build_index(ct)
+    ctx.icp_set_fixed_correspondences(cs, ct, inp["fq"], inp["fm"])
+    try:
+        out = ctx.icp(cs, ix, ope.default_icp_params(**kw))
+        dist, listed, appended = ctx.icp_fixed_correspondences()
+        q, m, d2 = ctx.icp_correspondences(len(inp["src"]))
+    finally:
+        ctx.icp_set_fixed_correspondences(None, None)
+    order = np.argsort(q, kind="stable")
+    return dict(T=np.asarray(out.T, np.float32), n_corr=np.int64(out.n_corr), last_mse=np.float64(out.last_mse),
+                dist=np.asarray(dist, np.float32), listed=np.asarray(listed, np.uint8), appended=np.asarray(appended, np.uint8),
+                q=np.asarray(q, np.int32)[order], m=np.asarray(m, np.int32)[order], d2=np.asarray(d2, np.float32)[order])
+
+
+@pytest.mark.parametrize("mode", ["nn", "normal_shooting"])
+def test_fixed_correspondences_under_the_self_occlusion_rejector_keep_their_recorded_bits(ctx, mode):
+    """icp_fixed_pairs_kernel under the self-occlusion rejector (the other rejector has the test above), 1-NN and normal
+    shooting: the distance fields, the listed / appended flags, the searched pairs, the transform, the count and the MSE are
+    what the commit before the per-query rules moved into csrc/icp_pair.hpp returned for the same inputs, bit for bit.  Inputs
+    and outputs both come from tests/golden/fixed_pairs_self_occlusion.npz (deterministic_sums, so the bits do not depend on
+    the run).  The rejector decides every one of the eight pairs by its normal: their scores n . (-p / |p|) at the first
+    iteration are 0.68, -0.77, 0.52, -0.03, 0.99, -0.46, 0.31, -0.38 against the threshold 0, checked below in fp64."""
+    import os
+    rec = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fixed_pairs_self_occlusion.npz"))
+    inp = {k: rec["in/" + k] for k in ("src", "sn", "tgt", "tn", "fq", "fm")}
+    p, n = inp["src"][inp["fq"]].astype(np.float64), inp["sn"][inp["fq"]].astype(np.float64)
+    score = -(n * p).sum(1) / np.linalg.norm(p, axis=1)
+    assert (score > 0).sum() == 4 and np.abs(score).min() > 0.02      # a pair per outcome, none decided by rounding
+    np.testing.assert_array_equal(rec[mode + "/appended"], (score > 0).astype(np.uint8))
+    got = _fixed_self_occlusion_run(ctx, mode, inp)
+    for k, v in got.items():
+        want = rec[mode + "/" + k]
+        assert v.dtype == want.dtype and v.shape == want.shape, k
+        assert v.tobytes() == want.tobytes(), (k, v, want)
+
+
 def test_fixed_correspondences_are_refused_where_the_reference_has_none(ctx):
     ope = load_pkg()
     src, tgt, fq, fm = _fixed_case()
