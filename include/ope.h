@@ -1497,6 +1497,8 @@ int ope_vfh_recognise(ope_ctx *ctx, const ope_vfh_db *db, size_t n, ope_cloud *c
 
 /* The batched entry points that take a list of global rejectors as an argument. */
 #include "ope_batch_rejectors.h"
+/* The draws of the batched prerejective aligner made on the device. */
+#include "ope_device_draws.h"
 
 #ifdef __cplusplus
 }

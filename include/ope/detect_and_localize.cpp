@@ -48,6 +48,9 @@
 //   ... --coarse-batch   (every mode but --depth, --track and --track-loop)
 // is given: PoseEstimator::setCoarseBatch(true), so --candidates (and --segment, --frame) with --coarse prerejective check all
 // clusters in one ope_final_pose_batch_prerejective call.  Without the flag every mode prints what it printed before.
+//   ... --device-draws   (with --coarse prerejective --coarse-batch)
+// PoseEstimator::setCoarseDeviceDraws(true): that call makes its draws on the device; it prints the same lines.  Exit status 2
+// without --coarse prerejective --coarse-batch.
 //   ... --correspondences-batch   (with --coarse correspondences; not with --track or --track-loop)
 // PoseEstimator::setCorrespondencesBatch(true): --candidates (and --segment, --frame) with --coarse correspondences check all clusters
 // in one ope_final_pose_batch_correspondences call.  Exit status 2 without --coarse correspondences.  --coarse-batch does not touch
@@ -174,6 +177,7 @@ static int track_main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--self-occluded")) self_occluded = true;
     else if (!std::strcmp(argv[i], "--fine-rejector") && i + 1 < argc) fine_rejectors.push_back(argv[++i]);
     else if (!std::strcmp(argv[i], "--coarse-batch")) { std::fprintf(stderr, "--coarse-batch does not go with --track or --track-loop\n"); return 2; }
+    else if (!std::strcmp(argv[i], "--device-draws")) { std::fprintf(stderr, "--device-draws does not go with --track or --track-loop\n"); return 2; }
     else if (!std::strcmp(argv[i], "--correspondences-batch")) { std::fprintf(stderr, "--correspondences-batch does not go with --track or --track-loop\n"); return 2; }
     else if (!std::strcmp(argv[i], "--fine-rejector-batch")) { std::fprintf(stderr, "--fine-rejector-batch does not go with --track or --track-loop\n"); return 2; }
     else if (!std::strcmp(argv[i], "--time")) timed = true;
@@ -329,6 +333,7 @@ int main(int argc, char **argv) {
   std::string recognise;       // --recognise <train_dir>: name every cluster before the pose stage
   ope::PoseEstimator::CoarseMethod coarse = ope::PoseEstimator::COARSE_SAC_IA;   // --coarse
   bool coarse_batch = false;   // --coarse-batch
+  bool device_draws = false;   // --device-draws
   bool correspondences_batch = false;   // --correspondences-batch
   std::vector<const char *> fine_rejectors;   // --fine-rejector, in the order given
   bool fine_rejector_batch = false;           // --fine-rejector-batch
@@ -337,6 +342,7 @@ int main(int argc, char **argv) {
     if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--coarse") && i + 1 < argc) { if (!parse_coarse(argv[++i], coarse)) return 2; }
     else if (!std::strcmp(argv[i], "--coarse-batch")) coarse_batch = true;
+    else if (!std::strcmp(argv[i], "--device-draws")) device_draws = true;
     else if (!std::strcmp(argv[i], "--correspondences-batch")) correspondences_batch = true;
     else if (!std::strcmp(argv[i], "--fine-rejector") && i + 1 < argc) fine_rejectors.push_back(argv[++i]);
     else if (!std::strcmp(argv[i], "--fine-rejector-batch")) fine_rejector_batch = true;
@@ -356,6 +362,10 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "--correspondences-batch goes with --coarse correspondences\n");
     return 2;
   }
+  if (device_draws && !(coarse == ope::PoseEstimator::COARSE_PREREJECTIVE && coarse_batch)) {
+    std::fprintf(stderr, "--device-draws goes with --coarse prerejective --coarse-batch\n");
+    return 2;
+  }
   if (fine_rejector_batch && fine_rejectors.empty()) { std::fprintf(stderr, "--fine-rejector-batch goes with --fine-rejector\n"); return 2; }
   if (except_plane && !frame) { std::fprintf(stderr, "--except-plane goes with --frame\n"); return 2; }
   if (region_grow && (!frame || except_plane)) { std::fprintf(stderr, "--region-grow goes with --frame and without --except-plane\n"); return 2; }
@@ -373,6 +383,7 @@ int main(int argc, char **argv) {
   poseEstimator.setSacIaSeed(seed);
   poseEstimator.setCoarseMethod(coarse);
   poseEstimator.setCoarseBatch(coarse_batch);
+  poseEstimator.setCoarseDeviceDraws(device_draws);
   poseEstimator.setCorrespondencesBatch(correspondences_batch);
   poseEstimator.setUseSelfOccludedRejector(self_occluded);
   poseEstimator.setFineRejectorBatch(fine_rejector_batch);

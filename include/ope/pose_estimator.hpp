@@ -46,6 +46,11 @@ class PoseEstimator {
   // setCorrespondencesBatch)
   void setCoarseBatch(bool on) { coarse_batch_ = on; }
   bool coarseBatch() const { return coarse_batch_; }
+  // that one call makes its draws on the device (ope_prerejective_set_draws, OPE_DRAWS_DEVICE) instead of in a host loop; the poses
+  // are the same.  Off by default; takes effect only together with COARSE_PREREJECTIVE and setCoarseBatch(true).  Off, the estimator
+  // does not touch the context's mode.
+  void setCoarseDeviceDraws(bool on) { coarse_device_draws_ = on; }
+  bool coarseDeviceDraws() const { return coarse_device_draws_; }
   // estimateFinalPoseCandidates with COARSE_CORRESPONDENCES: all clusters in one ope_final_pose_batch_correspondences call instead of
   // one estimateFinalPose at a time (off by default)
   void setCorrespondencesBatch(bool on) { correspondences_batch_ = on; }
@@ -254,8 +259,14 @@ class PoseEstimator {
         q.max_corr_dist = 0.15;
         q.inlier_fraction = 0.25f;
         q.seed = sacia_seed_ + (uint64_t)coarse_calls_;   // the k-th coarse call draws with seed + k
+        // (the context is shared: with the switch on, the mode it had comes back after the call; with the switch off the context
+        // is left alone, so a mode set directly with ope_prerejective_set_draws holds)
+        int draws_before = OPE_DRAWS_HOST;
+        const bool set_draws = ctx && coarse_device_draws_;
+        if (set_draws) { ope_prerejective_get_draws(ctx, &draws_before); ope_prerejective_set_draws(ctx, OPE_DRAWS_DEVICE); }
         batched = ctx && model->h &&
                   ope_final_pose_batch_prerejective(ctx, model->h, hs.size(), hs.data(), &p, &q, nullptr, res.data(), &sel) == OPE_OK;
+        if (set_draws) ope_prerejective_set_draws(ctx, draws_before);
       } else if (coarse_method_ == COARSE_CORRESPONDENCES) {
         ope_corr_sac_params q;
         ope_corr_sac_default_params(&q);   // (PCL's fixed seed: every rejector of the loop is a fresh object)
@@ -470,7 +481,7 @@ class PoseEstimator {
   uint64_t sacia_seed_ = 1;
   CoarseMethod coarse_method_ = COARSE_SAC_IA;
   int coarse_calls_ = 0;
-  bool coarse_batch_ = false, correspondences_batch_ = false, fine_rejector_batch_ = false;
+  bool coarse_batch_ = false, correspondences_batch_ = false, fine_rejector_batch_ = false, coarse_device_draws_ = false;
   bool use_self_occluded_ = false;
   std::vector<compat::registration::CorrespondenceRejector::Ptr> fine_rejectors_;   // addFineRejector, in the order added
   Matrix4f last_coarse_ = Matrix4f::Identity(), last_fine_ = Matrix4f::Identity(), last_rigid_ = Matrix4f::Identity();

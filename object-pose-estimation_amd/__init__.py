@@ -751,6 +751,19 @@ ABI_BATCH_REJECTORS = [
                                                   C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(FinalBatchResult), _ip]),
 ]
 
+# every symbol include/ope_device_draws.h declares (the draws of the batched prerejective aligner made on the device): bound by
+# lib() like ABI.  The header has no struct: its statistics are eight int64.
+ABI_DEVICE_DRAWS = [
+    ("ope_prerejective_set_draws", C.c_int, [_vp, C.c_int]),
+    ("ope_prerejective_get_draws", C.c_int, [_vp, _ip]),
+    ("ope_prerejective_set_draws_limits", C.c_int, [_vp, C.c_int, C.c_int64]),
+    ("ope_prerejective_draws_device", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_size_t, C.c_int,
+                                                 C.c_int64, _ip, _ip, C.POINTER(C.c_int64)]),
+    ("ope_prerejective_draws_last_stats", C.c_int, [_vp, C.POINTER(C.c_int64)]),
+]
+DRAWS_HOST, DRAWS_DEVICE = 0, 1
+DRAWS_STATS_FIELDS = ("mode", "device", "overflow", "short", "host_for_size", "positions", "tile", "launches")
+
 _lib = None
 
 
@@ -767,7 +780,7 @@ def lib() -> C.CDLL:
         except Exception:  # pragma: no cover - torch is optional for pure C-ABI use
             pass
         L = C.CDLL(LIB_PATH)
-        for name, res, args in ABI + ABI_BATCH_REJECTORS:
+        for name, res, args in ABI + ABI_BATCH_REJECTORS + ABI_DEVICE_DRAWS:
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -1354,6 +1367,40 @@ class Context:
         smp, tg, sv, T, inl, err = self._read("ope_prerejective_batch_hypotheses", (which,), [
             (np.int32, (S,)), (np.int32, (S,)), (np.uint8, ()), (np.float32, (16,)), (np.int32, ()), (np.float64, ())])
         return dict(samples=smp, targets=tg, survived=sv.astype(bool), T=_T_stack(T), inliers=inl, error=err)
+
+    def prerejective_set_draws(self, mode: int):
+        """ope_prerejective_set_draws: DRAWS_HOST (the default) or DRAWS_DEVICE for prerejective_pose_batch and
+        final_pose_batch_prerejective from now on; the single prerejective ignores it."""
+        self._chk(lib().ope_prerejective_set_draws(self.h, int(mode)))
+
+    def prerejective_set_draws_limits(self, window: int = 0, budget: int = 0):
+        """ope_prerejective_set_draws_limits: the window and the stream budget of the batched calls' device draws (0 = the
+        defaults); smaller values only send more problems back to the host loop."""
+        self._chk(lib().ope_prerejective_set_draws_limits(self.h, int(window), int(budget)))
+
+    def prerejective_get_draws(self) -> int:
+        mode = C.c_int(0)
+        self._chk(lib().ope_prerejective_get_draws(self.h, C.byref(mode)))
+        return mode.value
+
+    def prerejective_draws_device(self, ns: int, S: int, K: int, H: int, seeds, window: int = 0, budget: int = 0):
+        """ope_prerejective_draws_device: the draws of one problem per seed, made on the device.  Returns (samples, picks), each
+        (len(seeds), H, S) int32, and the stats dict of prerejective_draws_stats."""
+        sd = np.ascontiguousarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64)
+        n = len(sd)
+        shape = (n, max(int(H), 0), max(int(S), 0))
+        samples, picks = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+        st = (C.c_int64 * 8)()
+        self._chk(lib().ope_prerejective_draws_device(self.h, int(ns), int(S), int(K), int(H), _p(sd, C.POINTER(C.c_uint64)), n, int(window),
+                                                      int(budget), _p(samples, _ip), _p(picks, _ip), st))
+        return samples, picks, (dict(zip(DRAWS_STATS_FIELDS, (int(v) for v in st))) if n else self.prerejective_draws_stats())
+
+    def prerejective_draws_stats(self) -> dict:
+        """ope_prerejective_draws_last_stats: mode, device (problems drawn there), overflow / short (problems that fell back),
+        host_for_size, positions (P), tile (T), launches of the draw stage of the last call that had one."""
+        st = (C.c_int64 * 8)()
+        self._chk(lib().ope_prerejective_draws_last_stats(self.h, st))
+        return dict(zip(DRAWS_STATS_FIELDS, (int(v) for v in st)))
 
     def final_pose_batch_prerejective(self, model: "Cloud", clusters, params: FinalParams | None = None,
                                       prerejective: PrerejectiveParams | None = None, seeds=None):

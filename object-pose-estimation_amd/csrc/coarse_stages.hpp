@@ -101,6 +101,13 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
                                  const ope_coarse_params *front, const ope_prerejective_params *params, const uint64_t *seeds,
                                  bool seed_by_rank, int keep_hypotheses, ope_prerejective_batch_result *out);
 
+// prerejective_draws.hip: the draws of n problems (common ns, S, K, H; host seeds) written packed (sample | pick << 12) to d_draws
+// (n * H * S) by one seed upload and three launches on the context's stream; plan.fits is the caller's to check.  *d_words
+// (n, from tmp): per problem kDrawOverflow / kDrawShort once the stream has run, for the caller to fetch with its next download.
+struct DrawPlan;
+hipError_t draws_device_launch(ope_ctx *ctx, CallTmp &tmp, const DrawPlan &plan, int ns, int S, int K, int H, const uint64_t *seeds, size_t n,
+                               uint16_t *d_draws, uint32_t **d_words, int64_t *launches, int64_t *host_syncs);
+
 // corr_sac_batch.hip: ope_corr_sac_pose_batch; who: the entry point its errors name
 int corr_sac_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud *model, size_t n, const ope_cloud *const *clusters,
                              const ope_coarse_params *front, const ope_corr_sac_params *params, const uint64_t *seeds, int keep_hypotheses,

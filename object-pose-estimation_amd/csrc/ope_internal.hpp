@@ -325,6 +325,13 @@ struct ope_ctx {
   std::vector<float> pb_surv_T;
   std::vector<double> pb_surv_err;
 
+  // where the prerejective batch draws (ope_prerejective_set_draws) and the draw stage of the last call that had one
+  // (ope_prerejective_draws_last_stats; prerejective_draws.hip)
+  int draws_mode = 0;
+  int draws_window = 0;        // ope_prerejective_set_draws_limits: 0 = the defaults
+  int64_t draws_budget = 0;
+  int64_t draws_stats[8] = {};
+
   ope_depth_stats depth_stats{};   // what the last ope_depth_to_cloud did (depth.hip)
 
   ope_mls_stats mls_stats{};   // what the last ope_mls_smooth* call did (mls.hip)

@@ -5,7 +5,10 @@
 // 3 synchronisations, 8 bytes per draw uploaded).  Here every stage runs once for all clusters:
 //   a. the front end of ope_coarse_pose_batch (coarse_front_launch: key points, normals, FPFH of the model and every cluster);
 //   b. the host draws every active cluster's iterations by ope_prerejective's loop (prerej_draws) while the device computes the
-//      features; they go up packed, 16 bits per draw (sample | pick << 12), in one copy;
+//      features; they go up packed, 16 bits per draw (sample | pick << 12), in one copy.  With ope_prerejective_set_draws(ctx,
+//      OPE_DRAWS_DEVICE) the same words are written in place by prerejective_draws.hip (a seed upload and three launches: 12
+//      launches for the call instead of 9); a problem the device could not finish comes back with the second synchronisation, is
+//      drawn here and uploaded, and d, e run again;
 //   c. one launch finds the k nearest descriptors of every model key point in every active cluster (feature_knn_block); the rows
 //      stay on the device;
 //   d. one lane per (cluster, iteration) turns picks into targets and runs the polygon test (polygon_ok); a sampled row without a
@@ -29,6 +32,7 @@
 
 #include "coarse_stages.hpp"
 #include "feature_math.hpp"
+#include "prerejective_draws_plan.hpp"
 #include "prerejective_math.hpp"
 #include "stage_host.hpp"
 
@@ -164,6 +168,8 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
   if ((unsigned long long)n * (unsigned long long)H > 0x7fffffffull)
     return set_err(ctx, OPE_EINVAL, std::string(who) + "clusters x max_iterations above 2^31 - 1");
   if (const int rc = refuse_communicator(ctx, who)) return rc;
+  if (ctx->draws_mode == OPE_DRAWS_DEVICE && ctx->draws_window && ctx->draws_window < 2 * S)
+    return set_err(ctx, OPE_EINVAL, std::string(who) + "the draws' window (ope_prerejective_set_draws_limits) is below 2 * nr_samples");
   // the front end's refusals (sizes, key points; the model needs nr_samples key points)
   fp.sacia.nr_samples = S; fp.sacia.k_correspondences = K; fp.sacia.max_iterations = H;
   long long model_keys = -2;
@@ -218,17 +224,27 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
   TraceRange r_al(ctx, "prerejective_batch_align");
   const size_t HS = (size_t)H * S, total = na * (size_t)H;
   std::vector<uint64_t> seed_of(na);
-  std::vector<uint16_t> draws(na * HS);
-  std::vector<int32_t> samp(HS), pick(HS);
+  for (size_t a = 0; a < na; ++a) seed_of[a] = seeds ? seeds[active_cluster[a]] : p.seed + (uint64_t)(seed_by_rank ? a : active_cluster[a]);
+  // with OPE_DRAWS_DEVICE the draws are made in place by prerejective_draws.hip, unless their tile tables are too large for one call
+  const bool want_device = ctx->draws_mode == OPE_DRAWS_DEVICE;
+  const DrawPlan plan = draw_plan((int)nsk, S, H, na, want_device ? ctx->draws_window : 0, want_device ? ctx->draws_budget : 0);
+  const bool device_draws = want_device && plan.fits;
+  draw_stats_begin(ctx->draws_stats, ctx->draws_mode, plan, device_draws);
+  // the host's copies of the draws: all of them with host draws; with device draws only for a fallback or the kept hypotheses
+  std::vector<uint16_t> draws;
+  std::vector<int32_t> samp, pick;
+  if (!device_draws) draws.resize(na * HS);
   if (keep_hypotheses) ctx->pb_samples.resize(na * HS);
-  for (size_t a = 0; a < na; ++a) {
-    const size_t i = active_cluster[a];
-    seed_of[a] = seeds ? seeds[i] : p.seed + (uint64_t)(seed_by_rank ? a : i);
+  auto host_draws = [&](size_t a) {
+    draws.resize(na * HS);
+    samp.resize(HS); pick.resize(HS);
     prerej_draws((int)nsk, S, K, H, seed_of[a], samp.data(), pick.data());
     uint16_t *w = &draws[a * HS];
     for (size_t j = 0; j < HS; ++j) w[j] = (uint16_t)((uint32_t)samp[j] | ((uint32_t)pick[j] << 12));
     if (keep_hypotheses) std::memcpy(&ctx->pb_samples[a * HS], samp.data(), 4 * HS);
-  }
+  };
+  if (!device_draws)
+    for (size_t a = 0; a < na; ++a) host_draws(a);
 
   const size_t draw_bytes = 2 * na * HS;
   auto *d_active = (int2 *)tmp.get(sizeof(int2) * na, e);
@@ -243,7 +259,14 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
   if (e == hipSuccess) e = h2d_copy(st, d_active, active.data(), sizeof(int2) * na);
   if (e != hipSuccess) return fail("buffers");
   uint32_t *d_nsurv = d_words, *d_off = d_words + 1, *d_nan = d_words + 2 + na;
-  e = upload_staged(st, d_draws, draws.data(), draw_bytes, &St.launches, &St.host_syncs);   // (nothing stages again before the next synchronisation)
+  uint32_t *d_draw_words = nullptr;   // device draws: per problem, whether the host has to draw it after all
+  if (device_draws) {
+    const int64_t before = St.launches;
+    e = draws_device_launch(ctx, tmp, plan, (int)nsk, S, K, H, seed_of.data(), na, d_draws, &d_draw_words, &St.launches, &St.host_syncs);
+    ctx->draws_stats[kDsLaunches] = St.launches - before;
+  } else {
+    e = upload_staged(st, d_draws, draws.data(), draw_bytes, &St.launches, &St.host_syncs);   // (nothing stages again before the next synchronisation)
+  }
   if (e == hipSuccess) { e = hipMemsetAsync(d_nan, 0, 4 * na, st); ++St.launches; }
   if (e != hipSuccess) return fail("upload");
 
@@ -252,19 +275,42 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
   STAGE_LAUNCH(ctx, St.launches, prerej_batch_knn_kernel, 132.0 * (double)na * (double)nsk * (double)fr.max_keys, dim3(nsk, (unsigned)na), dim3(256), 0, st,
                (const float *)fr.d_fpfh, (const uint32_t *)fr.d_key_off, (const int2 *)d_active, K, d_nn);
   const float thr2 = p.similarity_threshold * p.similarity_threshold;
-  STAGE_LAUNCH(ctx, St.launches, prerej_batch_polygon_kernel, (double)total * (38.0 * S + 1.0), dim3(grid_of(total, kPrBlock)), dim3(kPrBlock), 0, st, v,
-               (uint32_t)total, thr2, d_flags, d_nan);
-  e = select_flagged(ctx, "prerej_batch_select", 5.0 * (double)total, &St.launches, d_sel, tb, d_flags, d_surv, d_nsurv, total);
-  if (e != hipSuccess) return fail("select");
-  STAGE_LAUNCH(ctx, St.launches, prerej_batch_offsets_kernel, 8.0 * (double)na, dim3(grid_of(na + 1, kPrBlock)), dim3(kPrBlock), 0, st,
-               (const uint32_t *)d_surv, (const uint32_t *)d_nsurv, (uint32_t)na, (uint32_t)H, d_off);
-  std::vector<uint32_t> words(2 * na + 2);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = coarse_front_download(ctx, fr);
-  if (e == hipSuccess) e = hipMemcpyAsync(words.data(), d_words, 4 * words.size(), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  ++St.host_syncs;
-  if (e != hipSuccess) return fail("prerejection");
+  std::vector<uint32_t> words(2 * na + 2), draw_words(device_draws ? na : 0);
+  // d, e and the second synchronisation; first: the features and the draws' words come back with it
+  auto prereject = [&](bool first) -> int {
+    STAGE_LAUNCH(ctx, St.launches, prerej_batch_polygon_kernel, (double)total * (38.0 * S + 1.0), dim3(grid_of(total, kPrBlock)), dim3(kPrBlock), 0, st, v,
+                 (uint32_t)total, thr2, d_flags, d_nan);
+    e = select_flagged(ctx, "prerej_batch_select", 5.0 * (double)total, &St.launches, d_sel, tb, d_flags, d_surv, d_nsurv, total);
+    if (e != hipSuccess) return fail("select");
+    STAGE_LAUNCH(ctx, St.launches, prerej_batch_offsets_kernel, 8.0 * (double)na, dim3(grid_of(na + 1, kPrBlock)), dim3(kPrBlock), 0, st,
+                 (const uint32_t *)d_surv, (const uint32_t *)d_nsurv, (uint32_t)na, (uint32_t)H, d_off);
+    e = hipGetLastError();
+    if (e == hipSuccess && first) e = coarse_front_download(ctx, fr);
+    if (e == hipSuccess) e = hipMemcpyAsync(words.data(), d_words, 4 * words.size(), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && first && device_draws) e = hipMemcpyAsync(draw_words.data(), d_draw_words, 4 * na, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    ++St.host_syncs;
+    if (e != hipSuccess) return fail("prerejection");
+    return OPE_OK;
+  };
+  if (const int rc = prereject(true)) return rc;
+  if (device_draws) {
+    // a problem the device could not finish is drawn here, goes up into its slice, and the prerejection runs again
+    const std::vector<size_t> again = draw_fallbacks(draw_words.data(), na, ctx->draws_stats);
+    for (const size_t a : again) {
+      host_draws(a);
+      e = upload_staged(st, d_draws + a * HS, &draws[a * HS], 2 * HS, &St.launches, &St.host_syncs);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);   // (the staging block is filled again by the next problem)
+      ++St.host_syncs;
+      if (e != hipSuccess) return fail("upload");
+    }
+    if (!again.empty()) {
+      e = hipMemsetAsync(d_nan, 0, 4 * na, st);
+      ++St.launches;
+      if (e != hipSuccess) return fail("upload");
+      if (const int rc = prereject(false)) return rc;
+    }
+  }
   coarse_front_keep(ctx, fr);
   const uint32_t nsurv = std::min<uint32_t>(words[0], (uint32_t)total);
   const uint32_t *off = &words[1], *nan_word = &words[2 + na];
@@ -306,10 +352,14 @@ int prerejective_pose_batch_impl(ope_ctx *ctx, const char *who, const ope_cloud 
     nn.resize(na * (size_t)nsk * K);
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->pb_survived.data(), d_flags, total, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(nn.data(), d_nn, 4 * nn.size(), hipMemcpyDeviceToHost, st);
+    if (device_draws) draws.resize(na * HS);
+    if (e == hipSuccess && device_draws) e = hipMemcpyAsync(draws.data(), d_draws, draw_bytes, hipMemcpyDeviceToHost, st);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   ++St.host_syncs;
   if (e != hipSuccess) return fail("fitness");
+  if (keep_hypotheses && device_draws)
+    for (size_t j = 0; j < na * HS; ++j) ctx->pb_samples[j] = (int32_t)(draws[j] & 0xfffu);
 
   // ---- h. the accept loop per cluster, over its survivors in iteration order
   for (size_t a = 0; a < na; ++a) {
